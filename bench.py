@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Throughput bench of the Quadtree-MPNNLSTM training hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = one full training step (forward + masked MSE + backward + [all-reduce] + clip_grad_norm_(10)
 + Adam) over one per-GPU batch of synthetic Moving-MNIST-like clips that is already resident in HBM.
@@ -14,9 +14,14 @@ events around every launch of one extra, untimed training step; `cpu_baseline` t
 Arithmetic: fp32 everywhere (fp32 MFMA for every GEMM, forward and backward) -- `dtype` "f32" means that.  The opt-in
 split-bf16 data gradient of the gate GEMM (ops.DGRAD_SPLIT_BF16) is NOT part of `value`; the same captured step is timed
 with it as well and reported beside the headline as `split_bf16_dgrad` (frozen model, same invocation).
-Order: frozen phase -> warm-up -> the timed window (`value`) -> `--repeats` further windows (median / spread) -> then, on
-rank 0 alone while the other ranks wait at a host-side store barrier (not inside an RCCL collective): the kernel probes on
-a freshly initialised model, the split-bf16 variant, the CPU baseline.
+A plain run does what `value` needs and nothing else: set-up (capture, then the frozen phase's steps at learning rate 0,
+untimed) -> warm-up -> the K timed steps (`value`, `ms_per_step`) -> --dump-outputs -> the line.  --full times the frozen
+phase (`frozen_ms_per_step`) and adds `--repeats` further windows (median / spread) after the timed one, then, on rank 0
+alone while the other ranks wait at a host-side store barrier (not inside an RCCL collective): the kernel probes on a
+freshly initialised model, the split-bf16 variant, the CPU baseline.  Both compute the same timed steps.
+--dump-outputs DIR writes what the last timed step hands its caller (loss.npy; params.npy and grad.npy: the parameters after
+its update and the clipped gradient the update used, flat in model.parameters() order; float32) -- inputs and initial weights
+come from fixed seeds, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -42,21 +47,31 @@ def parse():
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--batch', type=int, default=32, help='clips per GPU')
     ap.add_argument('--noise', type=float, default=NOISE)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-roofline', action='store_true')
-    ap.add_argument('--cpu-clips', type=int, default=10)
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write the last timed step\'s loss, updated parameters and clipped gradient to DIR/<name>.npy')
+    ap.add_argument('--full', action='store_true',
+                    help='also time the frozen phase, and run the repeat windows, the kernel probes, the split-bf16 variant and '
+                         'the CPU baseline (the options below marked --full tune them)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='(--full) skip the CPU baseline')
+    ap.add_argument('--no-roofline', action='store_true', help='(--full) skip the kernel probes')
+    ap.add_argument('--cpu-clips', type=int, default=10, help='(--full) clips the CPU baseline times')
     ap.add_argument('--frozen-steps', type=int, default=10,
-                    help='steps timed with the learning rate at 0 before training starts (frozen_ms_per_step; 0 = skip)')
+                    help='steps with the learning rate at 0 before training starts, after 3 more (0 = none); --full times them '
+                         '(frozen_ms_per_step)')
     ap.add_argument('--repeats', type=int, default=4,
-                    help='further timed windows of --steps steps after the one `value` comes from (median / spread; 0 = none)')
-    ap.add_argument('--no-split-variant', action='store_true', help='skip the split-bf16 data-gradient comparison')
+                    help='(--full) further timed windows of --steps steps after the one `value` comes from (median / spread; '
+                         '0 = none)')
+    ap.add_argument('--no-split-variant', action='store_true', help='(--full) skip the split-bf16 data-gradient comparison')
     ap.add_argument('--eager', action='store_true', help='Python-driven launches instead of hipGraph replay')
     ap.add_argument('--host-inputs', action='store_true',
                     help='keep the batches in pinned host memory and copy them in every step (PCIe-inclusive rate; informational)')
     ap.add_argument('--force-multi', action='store_true',
                     help='--gpus 1 only: a process group of ONE rank over RCCL and the multi-rank step structure (graph 1, flat '
                          'all-reduce, graph 2) -- what a rank of an N-GPU run does per step, measured on one GPU (informational)')
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    return args
 
 
 def make_predictor(device, capturable=False):
@@ -439,6 +454,23 @@ def cpu_baseline(n_clips, n_warm=3):
                                       f'median of {n_clips} clips after {n_warm} warm-up clips ({sum(times):.1f} s in all)'}
 
 
+def dump_outputs(out_dir, nfp, loss):
+    """What the last training step hands its caller, as float32 DIR/<name>.npy: `loss` (the step's return value), `params` (every
+    parameter after the step's update) and `grad` (the gradient that update used, after clipping to norm 10; zero for a parameter
+    without one), both flat in model.parameters() order -- 34 513 values each for the bench model."""
+    import numpy as np
+    import torch
+    params = list(nfp.model.parameters())
+    with torch.no_grad():
+        out = {'loss': loss.detach().reshape(()),
+               'params': torch.cat([p.detach().reshape(-1) for p in params]),
+               'grad': torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1) for p in params])}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in out.items():
+        np.save(os.path.join(out_dir, name + '.npy'), t.float().cpu().numpy())
+    log(f'outputs of the last timed step written to {out_dir}: {", ".join(sorted(out))}')
+
+
 def log(msg):
     print(f'[bench {time.strftime("%H:%M:%S")}] {msg}', file=sys.stderr, flush=True)
 
@@ -537,25 +569,33 @@ def main():
             per_rank = [float(o.item()) for o in owns]
         return dt, loss, per_rank
 
-    def frozen_ms(p, step, n):
+    def frozen_ms(p, step, n, measure=True):
         """ms per step of `step` with the learning rate at 0 (three untimed steps first); Adam's state is zeroed afterwards.
         The caller sets the learning rate to 0 BEFORE make_graphed_step, whose two eager warm-up steps are real optimizer steps:
         the frozen model is then the model as initialised, the same for every build and every gradient arithmetic (two real
-        steps with another rounding of the gradients end in another model, other meshes and another step time)."""
+        steps with another rounding of the gradients end in another model, other meshes and another step time).
+        measure=False runs the same steps untimed and returns None."""
         lr = float(os.environ.get('QT_BENCH_LR', LR))
         set_lr(p.optimizer, 0.0)
         for i in range(3):
             step(*pool[i % n_pool])
-        dtf, _, _ = timed(step, n)
+        if measure:
+            dtf, _, _ = timed(step, n)
+        else:
+            for i in range(n):
+                step(*pool[i % n_pool])
         set_lr(p.optimizer, lr)
         for st in p.optimizer.state.values():         # the frozen steps leave no trace in Adam's moments / step counts
             for v in st.values():
                 if torch.is_tensor(v):
                     v.zero_()
-        return dtf / n * 1e3
+        return dtf / n * 1e3 if measure else None
 
     # Phase 0 (untimed for `value`): the same step with the learning rate at 0.  The decoder's meshes follow the model's own
     # output, so the trained number below moves with the training trajectory; the frozen one is comparable between builds.
+    # A plain run takes these steps too, untimed: they draw from the dropout generator, so without them the warm-up and the
+    # timed window would train on other dropout masks than the ones `value` has always been measured on -- another trajectory
+    # with other meshes and another step time (7.24 instead of 7.07 ms on the default workload), and other outputs than --full.
     if args.eager:
         step = lambda x, y, c: nfp.train_step(x, y, c, mask)
     else:
@@ -569,8 +609,9 @@ def main():
     if args.frozen_steps > 0 and args.eager:
         set_lr(nfp.optimizer, 0.0)
     if args.frozen_steps > 0:
-        frozen = frozen_ms(nfp, step, args.frozen_steps)
-        log(f'frozen model (lr = 0): {frozen:.3f} ms per step over {args.frozen_steps} steps')
+        frozen = frozen_ms(nfp, step, args.frozen_steps, measure=args.full)
+        if frozen is not None:
+            log(f'frozen model (lr = 0): {frozen:.3f} ms per step over {args.frozen_steps} steps')
 
     for i in range(args.warmup):
         l = step(*pool[i % n_pool])
@@ -580,17 +621,19 @@ def main():
     assert torch.isfinite(loss).item(), 'non-finite loss in the timed region'
     final_loss = float(loss)
     log(f'timed {args.steps} steps in {dt:.3f} s')
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, nfp, loss)          # (before any further step overwrites the graph's static outputs)
     # further windows of the same length (training goes on, so they are not the same steps: the spread shows how much of a
     # difference between two runs is the box / the trajectory and how much is the build)
     windows = [dt / args.steps * 1e3]
-    for _ in range(max(args.repeats, 0)):
+    for _ in range(max(args.repeats, 0) if args.full else 0):
         dtr, lr_, _ = timed(step, args.steps)
         assert torch.isfinite(lr_).item(), 'non-finite loss in a repeat window'
         windows.append(dtr / args.steps * 1e3)
 
     # ---- single-rank work AFTER every timed window.  The other ranks wait on the host (store barrier), not in a collective.
     probes = {}
-    if rank == 0:
+    if rank == 0 and args.full:
         if not args.no_roofline or (not args.no_split_variant and not args.eager):
             del step
             nfp._graph = None
@@ -656,10 +699,10 @@ def main():
             'rank_ms_per_step': {'min': round(min(per_rank) / args.steps * 1e3, 3), 'max': round(max(per_rank) / args.steps * 1e3, 3)},
         }
         line.update(probes)
-        st = step_record(dt / args.steps * 1e3)
+        st = step_record(dt / args.steps * 1e3) if args.full else None
         if st is not None:
             line['step'] = st
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 line['cpu_baseline'] = cpu_baseline(args.cpu_clips)
             except Exception as e:                                            # pragma: no cover

@@ -139,7 +139,7 @@ def test_rccl_runs_the_multi_rank_step_structure_in_a_world_of_one():
 
 
 def test_bench_two_ranks_prints_one_line_with_probes():
-    """bench.py --gpus 2 (spawned through torchrun as the driver does): rank 0 runs the roofline probes alone after the
+    """bench.py --gpus 2 --full (spawned through torchrun as the driver does): rank 0 runs the roofline probes alone after the
     timed region, so they must be collective-free -- the run has to end with ONE JSON line carrying `roofline`."""
     import json
     import subprocess
@@ -152,7 +152,7 @@ def test_bench_two_ranks_prints_one_line_with_probes():
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK'):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--batch', '4',
-           '--frozen-steps', '2']
+           '--full', '--frozen-steps', '2']
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith('{')]

@@ -218,3 +218,41 @@ def test_baseline_mnist64_configs_train(cfg):
         nv = ms.n_valid
         assert float(ms.npix[:nv].sum()) == nb * 64 * 64
         assert int(ms.labels.max()) == nv - 1 and int(ms.labels.min()) >= 0
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_one(tmp_path):
+    """bench.py without --full: exactly --steps timed steps behind `ms_per_step` / `value`, none of the --full records, and
+    --dump-outputs holds the last timed step's loss (the line's final_loss), its updated parameters and its clipped gradient.
+    --full computes the same timed steps (its frozen phase is the plain run's untimed one): the same outputs."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+    def run(out, *extra):
+        cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--batch', '4',
+               '--dump-outputs', str(out), *extra]
+        res = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+        assert res.returncode == 0, res.stderr[-2000:]
+        lines = [l for l in res.stdout.splitlines() if l.startswith('{')]
+        assert len(lines) == 1, res.stdout[-2000:]
+        return json.loads(lines[0]), [np.load(out / f) for f in ('loss.npy', 'params.npy', 'grad.npy')]
+
+    rec, (loss, params, grad) = run(tmp_path / 'plain')
+    assert rec['steps'] == 3 and rec['warmup'] == 1 and rec['unit'] == 'frames/s' and rec['dtype'] == 'f32'
+    assert rec['higher_is_better'] is True and rec['ms_per_step'] > 0
+    assert abs(rec['value'] - 4 * (T_IN + T_OUT) * 1e3 / rec['ms_per_step']) <= 1e-3 * rec['value']
+    assert rec['window_ms_per_step'] == [rec['ms_per_step']] and rec['frozen_ms_per_step'] is None
+    assert not {'roofline', 'mfma', 'rollout_sizes', 'split_bf16_dgrad', 'step', 'cpu_baseline'} & set(rec)
+    assert sorted(os.listdir(tmp_path / 'plain')) == ['grad.npy', 'loss.npy', 'params.npy']
+    assert loss.dtype == params.dtype == grad.dtype == np.float32
+    assert loss.shape == () and params.shape == grad.shape == (34513,)
+    assert np.isfinite(params).all() and np.isfinite(grad).all()
+    assert abs(float(loss) - rec['config']['final_loss']) <= 1e-6 * max(1.0, abs(float(loss)))
+    assert 0 < np.linalg.norm(grad.astype(np.float64)) <= 10.0 * (1 + 1e-4)          # clip_grad_norm_(10) before Adam
+
+    full, outs = run(tmp_path / 'full', '--full', '--repeats', '0', '--no-roofline', '--no-split-variant', '--no-cpu-baseline')
+    assert full['frozen_ms_per_step'] > 0
+    for a, b in zip(outs, (loss, params, grad)):
+        np.testing.assert_allclose(a, b, rtol=1e-5, atol=1e-7)

@@ -1,4 +1,4 @@
-run() { echo "== $*"; env "$@" python bench.py --steps 20 --warmup 5 --repeats 2 --no-split-variant --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['ms_per_step'], d.get('windows_ms'), d.get('frozen_ms_per_step'))"; }
+run() { echo "== $*"; env "$@" python bench.py --full --steps 20 --warmup 5 --repeats 2 --no-split-variant --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['ms_per_step'], d.get('windows_ms'), d.get('frozen_ms_per_step'))"; }
 run A=1
 run HIP_FORCE_DEV_KERNARG=1
 run HIP_FORCE_DEV_KERNARG=0

@@ -3,7 +3,7 @@
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 R=${1:-r5}
 F="--steps 2 --warmup 3 --frozen-steps 0 --repeats 0 --no-split-variant --no-cpu-baseline --no-roofline"
-CMD="python3 bench.py --steps 20 --warmup 5 --repeats 0 --no-split-variant --no-cpu-baseline"
+CMD="python3 bench.py --full --steps 20 --warmup 5 --repeats 0 --no-split-variant --no-cpu-baseline"
 rocprofv3 --kernel-trace --stats -d gpurun_out/${R}_prof -o r --output-format csv -- $CMD > gpurun_out/${R}_bench_under_rocprof.json 2> gpurun_out/${R}_prof.log
 echo "stats done"
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d gpurun_out/${R}_pmc_f -o r -- python3 bench.py $F > /dev/null 2> gpurun_out/${R}_pmc_f.log
