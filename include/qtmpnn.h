@@ -567,6 +567,23 @@ int qt_attn_bwd(const int32_t* rowptr, const int32_t* col, const float* xy, cons
  * the heads of out / g.  One dense (N, C) plane per block and head is ld = C, ps = N C, hs = 4 N C (what qt_proj_group writes with
  * Kb = 4): a gathered k or v row is then one whole 128-byte line of a contiguous array. */
 
+/* ---------------------------------------------------------------- multi-head attention with a fused head merge (MHTransformerConv)
+ * The reference's MHTransformerConv (model/model.py:26-37): TransformerConv(heads = H, concat = True, beta = False, edge_dim = 2,
+ * root_weight = True) followed by lin (H C -> C):  cat_i = [out_i^0 | ... | out_i^{H-1}] (+ skip, per head as in qt_attn_fwd),
+ * y_i = Wlin cat_i + blin.  proj (N, H 4C): [q | k | v | skip] per head, head-major (the rows qt_attn_fwd reads with G = H);
+ * We (H, C, 2); Wt (H C, C) = Wlin^T with zero rows / columns for the padding channels above c_real; blin (C).  C = 4, 8, 16 or 32,
+ * 1 <= H <= 4.  qt_mhattn_fwd writes y (N, C), stats (H, N, 2) and, when cat != NULL, the plane cat (N, H C) the backward needs; it
+ * draws the dropout masks of qt_attn_fwd with G = H for the same seed / seed_dev.
+ * qt_mhattn_bwd_merge: g (N, ld_g) -> gcat (N, H C) = g Wlin, and part (qt_mhattn_blocks(N, C, H), H C C + C) per-block partials of
+ * [dWt (H C, C) | dblin (C)] (summed with qt_colsum; accumulate bit 0: add into part).  The attention gradient is then qt_attn_bwd
+ * with G = H, g = gcat and out = cat. */
+int qt_mhattn_blocks(int N, int C, int heads);
+int qt_mhattn_fwd(const int32_t* rowptr, const int32_t* col, const float* eattr, const float* selfloop, const float* proj,
+                  const float* We, const float* Wt, const float* blin, int C, int c_real, int heads, int N, const int32_t* n_dev,
+                  float keep, uint32_t seed, const uint32_t* seed_dev, float* y, float* stats, float* cat, void* stream);
+int qt_mhattn_bwd_merge(const float* g, int ld_g, const float* Wt, const float* cat, int C, int heads, int N, const int32_t* n_dev,
+                        float* gcat, float* part, int accumulate, void* stream);
+
 /* ---------------------------------------------------------------- gate-weight packing of stacked ChebConvs
  * A GraphConv stack applies its ChebConvs with no nonlinearity in between (model/model.py:59-97, :95-96), so the eight
  * stacks of a GConvLSTM (model/model.py:263-463) are Chebyshev series in weight space, composed layer by layer:

@@ -191,6 +191,93 @@ class PackedConv:
         self.W, self.We, self.acc, self.acc_e = W, We, acc, acc_e
 
 
+class MHTransformerConv(nn.Module):
+    """The reference's MHTransformerConv (model/model.py:26-37): torch_geometric TransformerConv(in, out, heads, concat=True,
+    beta=False, dropout, edge_dim=2, bias=True, root_weight=True) followed by lin = Linear(heads * out, out).  Parameters, in the
+    reference's creation order: lin_key / lin_query / lin_value (.weight (heads out, in), .bias), lin_edge.weight (heads out, 2),
+    lin_skip (.weight, .bias), lin (.weight (out, heads out), .bias).  One projection GEMM produces [q | k | v | skip] per head;
+    the attention of all heads and the head merge run in one launch (ops.mh_attention)."""
+
+    def __init__(self, in_channels, out_channels, heads=1, concat=True, beta=False, dropout=0.0, edge_dim=None, bias=True,
+                 root_weight=True):
+        super().__init__()
+        assert concat and not beta and edge_dim == 2 and bias and root_weight, \
+            'the reference uses concat=True, beta=False, edge_dim=2, bias=True, root_weight=True'
+        if not (1 <= heads <= 4 and 1 <= out_channels <= 32):
+            raise ValueError(f'MHTransformerConv(heads={heads}, out_channels={out_channels}): the HIP kernels take 1 .. 4 heads of '
+                             'at most 32 channels')
+        self.in_channels, self.out_channels, self.heads, self.dropout = in_channels, out_channels, heads, dropout
+        hc = heads * out_channels
+        self.lin_key = nn.Linear(in_channels, hc)
+        self.lin_query = nn.Linear(in_channels, hc)
+        self.lin_value = nn.Linear(in_channels, hc)
+        self.lin_edge = nn.Linear(edge_dim, hc, bias=False)
+        self.lin_skip = nn.Linear(in_channels, hc)
+        self.lin = nn.Linear(hc, out_channels)
+        for lin in (self.lin_key, self.lin_query, self.lin_value, self.lin_edge, self.lin_skip, self.lin):
+            nn.init.xavier_uniform_(lin.weight)
+            if lin.bias is not None:
+                nn.init.zeros_(lin.bias)
+
+    @staticmethod
+    def _layout(convs):
+        """(W (n, cin_p + 4, H 4 cp), We (n, H, cp, 2), Wt (n, H cp, cp), blin (n, cp)) of n convolutions of one shape: W[i] =
+        [q | k | v | skip] of every head, head-major, with the bias row + 3 zero rows; Wt = lin.weight^T split by head.  Channels
+        above out_channels (cp = out rounded up to 4) are zero everywhere, so the padding columns of cat and y stay zero."""
+        c0 = convs[0]
+        n, H, cin, cout = len(convs), c0.heads, c0.in_channels, c0.out_channels
+        cin_p, cp = cin + (-cin) % 4, cout + (-cout) % 4
+        blocks = [[c.lin_query, c.lin_key, c.lin_value, c.lin_skip] for c in convs]
+        w = torch.stack([l.weight for b4 in blocks for l in b4]).view(n, 4, H, cout, cin)
+        w = nn.functional.pad(w.permute(0, 4, 2, 1, 3), (0, cp - cout, 0, 0, 0, 0, 0, cin_p - cin))        # (n, cin_p, H, 4, cp)
+        b = torch.stack([l.bias for b4 in blocks for l in b4]).view(n, 4, H, cout).transpose(1, 2)
+        b = nn.functional.pad(b, (0, cp - cout)).reshape(n, 1, H * 4 * cp)
+        W = torch.cat([w.reshape(n, cin_p, H * 4 * cp), nn.functional.pad(b, (0, 0, 0, 3))], dim=1)
+        We = nn.functional.pad(torch.stack([c.lin_edge.weight for c in convs]).view(n, H, cout, 2), (0, 0, 0, cp - cout))
+        Wt = torch.stack([c.lin.weight for c in convs]).view(n, cout, H, cout).permute(0, 2, 3, 1)             # (n, H, c, o)
+        Wt = nn.functional.pad(Wt, (0, cp - cout, 0, cp - cout)).reshape(n, H * cp, cp)
+        bl = nn.functional.pad(torch.stack([c.lin.bias for c in convs]), (0, cp - cout))
+        return W, We, Wt, bl
+
+    def pack(self):
+        """The packed weights of one forward pass (see _layout) with the gradient accumulators all uses in the pass share."""
+        return MHTransformerConv.pack_many([self])[0]
+
+    @staticmethod
+    def pack_many(convs):
+        """[PackedMHConv] for a list of convolutions, one batched packing per (in, out, heads) shape: the same matrices as pack()."""
+        out = [None] * len(convs)
+        groups = {}
+        for i, c in enumerate(convs):
+            groups.setdefault((c.in_channels, c.out_channels, c.heads), []).append(i)
+        for idxs in groups.values():
+            W, We, Wt, bl = MHTransformerConv._layout([convs[i] for i in idxs])
+            for i, *t in zip(idxs, W.unbind(0), We.unbind(0), Wt.unbind(0), bl.unbind(0)):
+                out[i] = PackedMHConv(*t, ops.GradAcc(), ops.GradAcc(), ops.GradAcc())
+        return out
+
+    def forward(self, x, edge_index, edge_weight=None, packed=None):
+        mesh = _need_mesh(edge_index, x)
+        cin, cout = self.in_channels, self.out_channels
+        cin_p, cp = cin + (-cin) % 4, cout + (-cout) % 4
+        x = x[:, :cin] if x.shape[1] > cin_p else x
+        if x.shape[1] < cin_p:
+            x = nn.functional.pad(x, (0, cin_p - x.shape[1]))
+        pc = packed if packed is not None else self.pack()
+        proj = ops.cheb_poly(x, pc.W, mesh, 1, 1, acc=pc.acc if packed is not None else None)      # one GEMM: [q | k | v | skip] x H
+        y = ops.mh_attention(proj, pc.We, pc.Wt, pc.bl, mesh, cout, self.heads, self.dropout, self.training,
+                             pc.acc_e if packed is not None else None, pc.acc_l if packed is not None else None)
+        return y[:, :cout] if cp != cout else y
+
+
+class PackedMHConv:
+    """Packed weights of one MHTransformerConv for one forward pass."""
+    __slots__ = ('W', 'We', 'Wt', 'bl', 'acc', 'acc_e', 'acc_l')
+
+    def __init__(self, W, We, Wt, bl, acc, acc_e, acc_l):
+        self.W, self.We, self.Wt, self.bl, self.acc, self.acc_e, self.acc_l = W, We, Wt, bl, acc, acc_e, acc_l
+
+
 def _need_mesh(edge_index, *node_tensors):
     """The Mesh a module received in the reference's edge_index slot; node_tensors: (N, c) operands whose rows must be the mesh's
     nodes -- the kernels walk the mesh's rows and read these buffers unchecked."""
@@ -207,7 +294,7 @@ CONVOLUTIONS = {
     'ChebConv': ChebConv,
     'GCNConv': GCNConv,
     'TransformerConv': TransformerConv,
-    'MHTransformerConv': None,
+    'MHTransformerConv': MHTransformerConv,
     'GATConv': None,
     'GATv2Conv': None,
     'Dummy': None,
@@ -293,7 +380,7 @@ class GConvLSTM(nn.Module):
         tensors and their gradient accumulator.  W: ((K*C + Ks_padded), 4h) for Z = [X (padded to in_pad) | H]."""
         h = self.out_channels
         if not self.is_series:          # attention convolutions are nonlinear: no weight-space composition; TransformerConv stacks run
-                                        # layer by layer (_pack_multi), other kinds one convolution after another
+                                        # layer by layer (_pack_multi), MHTransformerConv ones one convolution after another
             wc = torch.cat([self.w_c_i, self.w_c_f, self.w_c_o], dim=0)
             b = torch.cat([self.b_i, self.b_f, self.b_c, self.b_o], dim=0)
             acc_p = ops.GradAcc()
@@ -304,11 +391,11 @@ class GConvLSTM(nn.Module):
                 for c in cells:
                     c.multi = multi
                 return cells
-            if isinstance(self.conv_x_i.convolutions[0], TransformerConv):
+            if isinstance(self.conv_x_i.convolutions[0], (TransformerConv, MHTransformerConv)):
                 # all convolutions of one shape are packed together: a handful of stack / pad / cat launches per shape
                 # instead of a dozen per convolution (24+ convolutions per cell)
                 flat = [(n, l, c) for n in names for l, c in enumerate(getattr(self, n).convolutions)]
-                packed = TransformerConv.pack_many([c for _, _, c in flat])
+                packed = type(self.conv_x_i.convolutions[0]).pack_many([c for _, _, c in flat])
                 convs = {n: [None] * self.n_conv_layers for n in names}
                 for (n, l, _), pc in zip(flat, packed):
                     convs[n][l] = pc
@@ -524,4 +611,3 @@ SplitGConvLSTM = _not_built('SplitGConvLSTM')
 DummyLSTM = _not_built('DummyLSTM')
 MPNNLSTM = _not_built('MPNNLSTM')
 MPNNLSTMI = _not_built('MPNNLSTMI')
-MHTransformerConv = _not_built('MHTransformerConv')

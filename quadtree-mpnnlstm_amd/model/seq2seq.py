@@ -257,7 +257,7 @@ class Decoder(_NoCachesInPickle, nn.Module):
         z = ops.head_input(out, pk['ln_o'], concat_layers, self.head_width, mesh, pk['acc_o'])    # (N, h), (N, 4)
         if drop is None and self.training and self.dropout.p > 0:
             drop = self.dropout_masks(1, z[0].shape[0], z[0].device)[0]
-        if pk['fc1'] is None:           # attention head (TransformerConv): activations as plain tensor ops
+        if pk['fc1'] is None:           # attention head (TransformerConv, MHTransformerConv): activations as plain tensor ops
             p1, p2 = pk.get('heads') or (None, None)
             y = self.fc_out2(torch.relu(self.fc_out1(torch.cat(z, dim=1), mesh, packed=p1)), mesh, packed=p2)
             y = torch.tanh(y if drop is None else y * drop.unsqueeze(1)) + X[:, :1]
@@ -297,8 +297,8 @@ class Seq2Seq(_NoCachesInPickle, nn.Module):
                  convolution_type='ChebConv', rnn_type='LSTM', binary=False, dummy=False, device=None, debug=False):
         super().__init__()
         # a node's row is spread over hidden / 4 lanes of a 64-lane wave (float4 each): the cell kernels are built for the powers of
-        # two 8 .. 128, the attention kernels for 8, 16 and 32; said here, not by the first launch
-        sizes = (8, 16, 32) if convolution_type == 'TransformerConv' else (8, 16, 32, 64, 128)
+        # two 8 .. 128, the attention kernels (one and several heads) for 8, 16 and 32; said here, not by the first launch
+        sizes = (8, 16, 32) if convolution_type in ('TransformerConv', 'MHTransformerConv') else (8, 16, 32, 64, 128)
         if hidden_size not in sizes:
             raise ValueError(f'hidden_size={hidden_size}: the HIP kernels for convolution_type={convolution_type!r} are built for '
                              f'hidden sizes {sizes} (the reference scripts use 16 and 32)')

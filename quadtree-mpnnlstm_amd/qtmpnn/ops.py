@@ -948,6 +948,84 @@ def attention(proj, We, mesh, c_real, dropout_p=0.0, training=False, acc=None, h
     return _Attention.apply(proj, We, mesh, c_real, keep, seed, acc, heads, gmod)
 
 
+class _MHAttention(Function):
+    """y = Wlin concat_g(attention_g) + blin: MHTransformerConv (model/model.py:26-37, heads H, concat) from the fused projection
+    proj (N, H 4C) = [q | k | v | skip] per head (the rows of _Attention with heads = H), We (H, C, 2), Wt (H C, C) = Wlin^T and blin
+    (C), both zero padded above c_real.  Forward: one launch (qt_mhattn_fwd: attention of all heads + head merge).  Backward: the
+    merge (qt_mhattn_bwd_merge: gcat = g Wlin, dWt / dblin partials), then the attention of H heads (qt_attn_bwd) on gcat.
+    acc_e / acc_l: GradAcc of We / of [Wt | blin] shared by all uses of the convolution in a forward pass, or None."""
+
+    @staticmethod
+    def forward(ctx, proj, We, Wt, blin, mesh, c_real, keep, seed, acc_e, acc_l, heads):
+        proj, We, Wt, blin = _c(proj.float()), _c(We.float()), _c(Wt.float()), _c(blin.float())
+        ctx.epoch = dropout_epoch(proj.device) if keep < 1.0 else None
+        H = heads
+        N, C = proj.shape[0], proj.shape[1] // (4 * H)
+        assert We.shape == (H, C, 2) and Wt.shape == (H * C, C) and blin.shape == (C,), (We.shape, Wt.shape, blin.shape)
+        xy, selfpair, eattr, _ = mesh.attn_geometry()
+        y = proj.new_empty(N, C)
+        stats = proj.new_empty(H, N, 2)
+        cat = proj.new_empty(N, H * C) if any(ctx.needs_input_grad[:4]) else None
+        _lib.call('qt_mhattn_fwd', ptr(mesh.rowptr), ptr(mesh.col), ptr(eattr), ptr(selfpair), ptr(proj), ptr(We), ptr(Wt), ptr(blin),
+                  C, c_real, H, N, ptr(mesh.n_dev), keep, seed, ptr(ctx.epoch), ptr(y), ptr(stats), ptr(cat))
+        ctx.save_for_backward(proj, We, Wt, stats, cat)
+        ctx.mesh, ctx.c_real, ctx.keep, ctx.seed, ctx.acc_e, ctx.acc_l, ctx.H = mesh, c_real, keep, seed, acc_e, acc_l, H
+        ctx.use_e = acc_e.enter() if acc_e is not None else 0
+        ctx.use_l = acc_l.enter() if acc_l is not None else 0
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        proj, We, Wt, stats, cat = ctx.saved_tensors
+        mesh, acc_e, acc_l, H = ctx.mesh, ctx.acc_e, ctx.acc_l, ctx.H
+        N, C = proj.shape[0], proj.shape[1] // (4 * H)
+        xy, selfpair, eattr, rev = mesh.attn_geometry()
+        g, ld_g = _rows(g.float())
+        nl = H * C * C + C                          # [dWt | dblin] per block
+        if acc_l is None:
+            nblk_l = max(_lib.value('qt_mhattn_blocks', N, C, H), 1)
+            part_l = proj.new_empty(nblk_l, nl) if N > 0 else proj.new_zeros(nblk_l, nl)
+        else:
+            nblk_l = max(_lib.value('qt_mhattn_blocks', max(mesh.B * mesh.P, N), C, H), 1)
+            part_l = acc_l.slab(proj, nblk_l, nl)
+        gcat = proj.new_empty(N, H * C)
+        if acc_e is None:
+            nblk = max(_lib.value('qt_attn_blocks', N, C), 1)
+            part = proj.new_empty(nblk, H * 2 * C) if N > 0 else proj.new_zeros(nblk, H * 2 * C)
+        else:
+            nblk = max(_lib.value('qt_attn_blocks', max(mesh.B * mesh.P, N), C), 1)
+            part = acc_e.slab(proj, nblk, H * 2 * C)
+        coef = proj.new_empty(H, rev.numel() + N, 2)
+        gproj = torch.empty_like(proj)
+        if N > 0:
+            _lib.call('qt_mhattn_bwd_merge', ptr(g), ld_g, ptr(Wt), ptr(cat), C, H, N, ptr(mesh.n_dev), ptr(gcat), ptr(part_l),
+                      0 if acc_l is None else 1)
+            _lib.call('qt_attn_bwd', ptr(mesh.rowptr), ptr(mesh.col), ptr(xy), ptr(eattr), ptr(selfpair), ptr(proj), 4 * C * H, ptr(We), C,
+                      ctx.c_real, N, ptr(mesh.n_dev), ctx.keep, ctx.seed, ptr(ctx.epoch), ptr(gcat), H * C, ptr(stats), ptr(cat), 0,
+                      ptr(gproj), ptr(part), 0 if acc_e is None else 1, ptr(rev), ptr(coef), rev.numel(), H, H, 0, 0, 0, 0)
+        else:
+            gproj.zero_()
+        gWe = gWt = gb = None
+        if acc_e is None or acc_e.leave(ctx.use_e):
+            psum = proj.new_empty(H * 2 * C)
+            _lib.call('qt_colsum', ptr(part), nblk, H * 2 * C, ptr(psum))           # part (block, head, 2C)
+            gWe = psum.view(H, 2, C).transpose(1, 2).contiguous()
+        if acc_l is None or acc_l.leave(ctx.use_l):
+            lsum = proj.new_empty(nl)
+            _lib.call('qt_colsum', ptr(part_l), nblk_l, nl, ptr(lsum))
+            gWt, gb = lsum[:H * C * C].view(H * C, C), lsum[H * C * C:]
+        return (gproj, gWe, gWt, gb) + (None,) * 7
+
+
+def mh_attention(proj, We, Wt, blin, mesh, c_real, heads, dropout_p=0.0, training=False, acc_e=None, acc_l=None):
+    """MHTransformerConv from its fused projection (see _MHAttention); the dropout seed is drawn like attention()'s, and the device
+    step counter (dropout_epoch) makes captured replays draw new masks."""
+    keep = 1.0 - dropout_p if (training and dropout_p > 0) else 1.0
+    _ATTN_CALLS[0] += 1
+    seed = (_ATTN_CALLS[0] * 2654435761 + int(torch.initial_seed())) & 0xFFFFFFFF
+    return _MHAttention.apply(proj, We, Wt, blin, mesh, c_real, keep, seed, acc_e, acc_l, heads)
+
+
 _PROJ_BWD_FUSED = os.environ.get('QT_NO_PROJ_BWD_FUSED') != '1'      # (A/B switch)
 _PROJ_BWD_SHARED = os.environ.get('QT_NO_PROJ_BWD_SHARED') != '1'    # (A/B switch: the first-layer segments too)
 _STATS = {'skip_alias': 0}      # (how often a layer's gradient array was completed in place: tests look at it)

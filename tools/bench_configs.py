@@ -4,6 +4,7 @@
 cfg3: Moving-MNIST-like 128x128, 2 digits, in=10/out=20, 8 clips per GPU (the per-GPU share of the 8-GPU config).
 cfg4: ice-like 128x128 patches, 5 channels, in=12/out=6, 16 clips, land mask, transform_func, hidden 32, 1 layer, 3 conv layers.
 cfg4t: cfg4 with convolution_type='TransformerConv' (what ice_exp.py hard-codes).
+cfg4m: cfg4 with convolution_type='MHTransformerConv' (three heads per convolution, fused head merge).
 cfg4tp: cfg4t on the pixelwise mesh (thresh=-inf: what ice_exp.py:145 really runs -- no quadtree, one node per unmasked pixel).
 cfg5: ice-like 256x256, 5 channels, in=12/out=12, 4 clips per GPU (the per-GPU share of BASELINE configs[4]: 32 clips over 8 GPUs),
       quadtree rebuilt at every step (ice_exp_nwt.py:46,80,89-96 with a finite threshold); cfg5t: the same with TransformerConv.
@@ -32,6 +33,8 @@ else:
     kw, thresh, feat = dict(hidden_size=32, dropout=0.1, n_layers=1, n_conv_layers=3), 0.15, 5
     if cfg in ('cfg4t', 'cfg4tp', 'cfg5t'):
         kw['convolution_type'] = 'TransformerConv'
+    if cfg == 'cfg4m':
+        kw['convolution_type'] = 'MHTransformerConv'
     if cfg == 'cfg4tp':
         thresh = -np.inf
     tf = lambda a: abs(abs(a - 0.5) - 0.5)
