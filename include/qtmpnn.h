@@ -192,6 +192,13 @@ int qt_edges_norm_tiles(const int32_t* rowptr, const int32_t* col, const float* 
  */
 int qt_gather(const float* val, int C, const int32_t* labels, const float* inv_npix,
               int64_t npixels_total, float* img, void* stream);
+/* qt_gather_frame: one output step of an inference rollout written into its slot of a caller-owned stack (B, T, P, C):
+ *   out[b * clip_stride + out_off + p * C + c] = val[labels[b,p] * ld_val + c], or `fill` where labels[b,p] < 0 or >= the node
+ *   count (read from n_dev when given: capturable); fill = NaN if nan_fill (unflatten_pixelwise, graph_functions.py:460-468,
+ *   pixelwise meshes with a mask) else 0 (unflatten, :451-458).  Serves the predict loop of model/mpnnlstm.py:402-440 without the
+ *   per-step image, masked fill, permute copy and host stack.  out_off = t * P * C, clip_stride = T * P * C for slot t. */
+int qt_gather_frame(const float* val, int ld_val, int C, const int32_t* labels, int B, int64_t P, int N,
+                    const int32_t* n_dev, int nan_fill, float* out, int64_t out_off, int64_t clip_stride, void* stream);
 int qt_pool(const float* img, int S, int64_t img_clip_stride /* floats between clips, 0 = dense */, const float* src_val, const int32_t* src_labels, const float* src_npix, int src_inv,
             int C, const int32_t* labels, const uint8_t* level, const float* npix, int mean,
             int B, int n, int m, int N, const int32_t* cell /* or NULL */, const int32_t* n_dev,
@@ -448,6 +455,11 @@ int qt_dense_lstm(const float* a0, int lda0, const float* a_rest, const float* a
                   const float* Ws, int h, int N, const int32_t* n_dev, const float* Cprev, int ld_c,
                   const float* wc, const float* b, const float* ln, float* O, float* Hn, float* Cn,
                   float* gates, int planes_sm /* as in qt_dense2 */, void* stream);
+/* Forward-only twin of qt_lstm_fwd for passes without a backward (inference, model/mpnnlstm.py:402-440, and any forward under
+ * torch.no_grad): the same launch with the same arithmetic -- O, Hn and Cn bit for bit as its -- that skips the store of the
+ * (N, 4h) gate activations only the backward reads; O is required (the decoder head reads it). */
+int qt_lstm_infer(const float* G, const float* G2, int ld_g, const float* Cprev, int ld_c, const float* wc, const float* b,
+                  const float* ln, int N, const int32_t* n_dev, int h, float* O, float* Hn, float* Cn, void* stream);
 /* gO, gHn, gCn may each be NULL (that output was not used: zero gradient).  part: (nblk, 11*h) partial sums [g_wc(3h) | g_b(4h) | g_ln(4h)], nblk = qt_lstm_bwd_blocks(N, h) */
 int qt_lstm_bwd_blocks(int N, int h);
 int qt_lstm_bwd(const float* gO, int ld_go, const float* gHn, int ld_gh, const float* gCn, int ld_gc,   /* row strides */

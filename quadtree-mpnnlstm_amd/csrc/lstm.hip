@@ -42,11 +42,13 @@ __global__ __launch_bounds__(256) void k_lstm_fwd(const float* __restrict__ G, c
     st4(O + node * h + j0, Og);
     st4(Hn + node * h + j0, hn);
     st4(Cn + node * h + j0, cn);
-    float* gs = gates + node * 4 * h + j0;
-    st4(gs, I);
-    st4(gs + h, F);
-    st4(gs + 2 * h, T);
-    st4(gs + 3 * h, Og);
+    if (gates) {                // (NULL: a forward-only launch, qt_lstm_infer -- nothing will read the gates back)
+        float* gs = gates + node * 4 * h + j0;
+        st4(gs, I);
+        st4(gs + h, F);
+        st4(gs + 2 * h, T);
+        st4(gs + 3 * h, Og);
+    }
 }
 
 template <int LPN>
@@ -236,6 +238,21 @@ extern "C" int qt_lstm_fwd(const float* G, const float* G2, int ld_g, const floa
     const int grid = qt_cdiv((int64_t)N * lanes_per_node(h), 256);
     QT_ARG(!Cprev || (ld_c >= h && ld_c % 4 == 0), "bad Cprev row stride");
     QT_DISPATCH_LPN(h, k_lstm_fwd, grid, stream, G, G2, ld_g, Cprev, wc, b, ln, N, n_dev, h, ld_c, O, Hn, Cn, gates);
+    QT_LAUNCHED();
+    return QT_OK;
+}
+
+extern "C" int qt_lstm_infer(const float* G, const float* G2, int ld_g, const float* Cprev, int ld_c, const float* wc, const float* b,
+                             const float* ln, int N, const int32_t* n_dev, int h, float* O, float* Hn, float* Cn, void* stream) {
+    QT_ARG(G && wc && b && O && Hn && Cn, "null pointer");
+    if (ld_g == 0) ld_g = 4 * h;
+    QT_ARG(ld_g >= 4 * h && ld_g % 4 == 0 && (((uintptr_t)G | (uintptr_t)G2) & 15) == 0, "bad gate row stride / alignment");
+    QT_ARG(h_ok(h), "hidden size must be 8, 16, 32, 64 or 128");
+    if (N <= 0) return QT_OK;
+    const int grid = qt_cdiv((int64_t)N * lanes_per_node(h), 256);
+    QT_ARG(!Cprev || (ld_c >= h && ld_c % 4 == 0), "bad Cprev row stride");
+    float* no_gates = nullptr;
+    QT_DISPATCH_LPN(h, k_lstm_fwd, grid, stream, G, G2, ld_g, Cprev, wc, b, ln, N, n_dev, h, ld_c, O, Hn, Cn, no_gates);
     QT_LAUNCHED();
     return QT_OK;
 }

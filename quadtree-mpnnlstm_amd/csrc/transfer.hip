@@ -467,6 +467,21 @@ __global__ void k_gather(const float* __restrict__ val, int C, const int32_t* __
     vstore<VEC>(img + p * C + ch * VEC, x, sc);
 }
 
+// one output frame of a rollout straight into its slot of the caller's (B, T, P, C) stack: out[b * clip_stride + out_off + p C + c]
+__global__ __launch_bounds__(256) void k_gather_frame(const float* __restrict__ val, int ld_val, int C,
+                                                      const int32_t* __restrict__ labels, int64_t P, int64_t total, int Ncap,
+                                                      const int32_t* __restrict__ n_dev, float fill, float* __restrict__ out,
+                                                      int64_t out_off, int64_t clip_stride) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int64_t bp = idx / C;
+    const int c = (int)(idx - bp * C);
+    const int64_t b = bp / P, p = bp - b * P;
+    const int lab = labels[bp];
+    const float v = (lab >= 0 && lab < qt_rows(n_dev, Ncap)) ? val[(int64_t)lab * ld_val + c] : fill;
+    out[b * clip_stride + out_off + p * C + c] = v;
+}
+
 __global__ __launch_bounds__(256) void k_sse(const float* __restrict__ out, int out_stride, const int32_t* __restrict__ labels,
                                              const float* __restrict__ y, int64_t y_clip_stride, int64_t P,
                                              float* __restrict__ partial) {
@@ -635,6 +650,19 @@ extern "C" int qt_gather(const float* val, int C, const int32_t* labels, const f
         hipLaunchKernelGGL(k_gather<4>, dim3(grid), dim3(256), 0, (hipStream_t)stream, val, C, labels, inv_npix, npixels_total, img);
     else
         hipLaunchKernelGGL(k_gather<1>, dim3(grid), dim3(256), 0, (hipStream_t)stream, val, C, labels, inv_npix, npixels_total, img);
+    QT_LAUNCHED();
+    return QT_OK;
+}
+
+extern "C" int qt_gather_frame(const float* val, int ld_val, int C, const int32_t* labels, int B, int64_t P, int N,
+                               const int32_t* n_dev, int nan_fill, float* out, int64_t out_off, int64_t clip_stride, void* stream) {
+    QT_ARG(val && labels && out, "null pointer");
+    QT_ARG(C > 0 && ld_val >= C && B > 0 && P > 0 && N >= 0, "bad sizes");
+    QT_ARG(out_off >= 0 && (B == 1 || clip_stride >= out_off + P * C), "output slot outside its clip's row");
+    const int64_t total = (int64_t)B * P * C;
+    const float fill = nan_fill ? __builtin_nanf("") : 0.0f;
+    hipLaunchKernelGGL(k_gather_frame, dim3(qt_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, val, ld_val, C, labels, P, total,
+                       N, n_dev, fill, out, out_off, clip_stride);
     QT_LAUNCHED();
     return QT_OK;
 }

@@ -355,6 +355,66 @@ class NextFramePredictorS2S(NextFramePredictor):
         return step
 
     @on_device(lambda self, *a, **k: self.device)
+    def make_graphed_rollout(self, x, concat_layers=None, mask=None, high_interest_region=None, graph_structure=None):
+        """Capture one no-grad inference rollout (predict's loop body for one batch) in a hipGraph and return
+        `rollout(x, concat) -> (B, T_out, W, H, 1)` device stack; `rollout.warmup` holds the eager result of the given batch.
+
+        As make_graphed_step: static mode (worst-case capacities, node counts read on the device; the caller restores
+        `static_shapes`), one eager warm-up rollout on a side stream -- a real prediction of this batch -- then the capture there.
+        Every step's frame is written by one gather launch into its slot of the stack, so a replay ends in ONE host copy.  Host
+        state an eager rollout advances is advanced by a replay too: Python's `random` (unroll_output draws once per output step)
+        and the attention-dropout seed counter.  In train() mode every replay draws new dropout masks (torch's graph-safe RNG
+        for the decoder, the device counter ops.dropout_epoch for attention)."""
+        import random
+        model = self.model
+        model.static_shapes = True
+        T_out = self.output_timesteps
+        B = 1 if x.dim() == 4 else x.shape[0]
+        sx = x.clone()
+        sc = concat_layers.clone() if concat_layers is not None else None
+        out = torch.empty(B, T_out, x.shape[-3], x.shape[-2], 1, device=x.device)
+
+        def rollout():
+            with torch.no_grad():
+                y_hat, meshes = model(sx, concat_layers=sc, teacher_forcing_ratio=0, mask=mask,
+                                      high_interest_region=high_interest_region, graph_structure=graph_structure)
+                for t, (o, ms) in enumerate(zip(y_hat, meshes)):
+                    ops.gather_frame_into(o, ms, out, t)
+            return out
+
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        calls0 = ops._ATTN_CALLS[0]
+        with torch.cuda.stream(side):
+            warm = rollout().clone()
+        torch.cuda.current_stream().wait_stream(side)
+        calls1 = ops._ATTN_CALLS[0]
+        # the capture records launches without running them: whatever host state it advances is put back, and every replay
+        # advances it as an eager rollout would
+        rstate = random.getstate()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=side, capture_error_mode='thread_local'):
+            rollout()
+        random.setstate(rstate)
+        ops._ATTN_CALLS[0] = calls1
+        from qtmpnn import mesh as _mesh
+        uses_tiles = bool(_mesh._TILE_USED)
+        check_tile_errors(always=uses_tiles)
+
+        @on_device(lambda *a, **k: self.device)
+        def replay(x, concat_layers=None):
+            sx.copy_(x)
+            if sc is not None:
+                sc.copy_(concat_layers)
+            graph.replay()
+            for _ in range(T_out):
+                random.random()
+            ops._ATTN_CALLS[0] += calls1 - calls0
+            return out
+        replay.warmup = warm
+        return replay
+
+    @on_device(lambda self, *a, **k: self.device)
     def train(self, loader_train, loader_test, climatology=None, n_epochs=200, lr=0.01, lr_decay=0.95, mask=None,
               high_interest_region=None, truncated_backprop=45, graph_structure=None, use_graph=False):
         """The reference's training loop (mpnnlstm.py:186-387).  use_graph=True (beyond the reference) replays the whole training
@@ -444,20 +504,40 @@ class NextFramePredictorS2S(NextFramePredictor):
         return torch.moveaxis(climatology[:, doys], 0, -1)
 
     @on_device(lambda self, *a, **k: self.device)
-    def predict(self, loader, climatology=None, mask=None, high_interest_region=None, graph_structure=None):
-        """Inference over a loader -> (n_clips, T_out, W, H, 1) array (mpnnlstm.py:402-440)."""
+    def predict(self, loader, climatology=None, mask=None, high_interest_region=None, graph_structure=None, use_graph=False):
+        """Inference over a loader -> (n_clips, T_out, W, H, 1) array (mpnnlstm.py:402-440).
+
+        use_graph=True (beyond the reference) replays every rollout as a hipGraph: each distinct (input shape, climatology shape,
+        train / eval mode) is captured once per call (make_graphed_rollout; the first batch of that key is predicted eagerly in
+        static mode as the warm-up, and its result is the one returned), later batches copy into the captured inputs, replay and
+        make one host copy.  The graphs are dropped and `static_shapes` is restored when the call returns."""
         image_shape = loader.dataset.image_shape
         self.model.to(self.device)
         preds = []
-        for x, y, launch_date in loader:
-            x = self._clip(x)
-            concat = self.get_climatology_array(climatology, launch_date) if climatology is not None else None
-            with torch.no_grad():
-                y_hat, meshes = self.model(x, concat_layers=concat, teacher_forcing_ratio=0, mask=mask,
-                                           high_interest_region=high_interest_region, graph_structure=graph_structure)
-                frames = [unflatten(o, ms, image_shape, mask).cpu().numpy() for o, ms in zip(y_hat, meshes)]
-            frames = np.stack(frames, axis=0 if x.dim() == 4 else 1)
-            preds.extend([frames] if x.dim() == 4 else list(frames))
+        graphed, static0 = {}, self.model.static_shapes
+        try:
+            for x, y, launch_date in loader:
+                x = self._clip(x)
+                concat = self.get_climatology_array(climatology, launch_date) if climatology is not None else None
+                if use_graph:
+                    key = (tuple(x.shape), None if concat is None else tuple(concat.shape), self.model.training)
+                    if key not in graphed:
+                        graphed[key] = self.make_graphed_rollout(x, concat, mask=mask, high_interest_region=high_interest_region,
+                                                                 graph_structure=graph_structure)
+                        stack = graphed[key].warmup
+                    else:
+                        stack = graphed[key](x, concat)
+                    preds.extend(list(stack.cpu().numpy()))
+                    continue
+                with torch.no_grad():
+                    y_hat, meshes = self.model(x, concat_layers=concat, teacher_forcing_ratio=0, mask=mask,
+                                               high_interest_region=high_interest_region, graph_structure=graph_structure)
+                    frames = [unflatten(o, ms, image_shape, mask).cpu().numpy() for o, ms in zip(y_hat, meshes)]
+                frames = np.stack(frames, axis=0 if x.dim() == 4 else 1)
+                preds.extend([frames] if x.dim() == 4 else list(frames))
+        finally:
+            graphed.clear()
+            self.model.static_shapes = static0
         check_tile_errors(always=True)
         return np.stack(preds, 0)
 

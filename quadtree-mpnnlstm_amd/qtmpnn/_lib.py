@@ -60,6 +60,8 @@ _SIGNATURES = {
     'qt_sse_bwd': [_P, _I, _P, _P, _P, _I, _P, _I, _P, _P],
     'qt_wgrad_group_blocks': [_I, _P],
     'qt_wgrad_group': [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P],
+    'qt_lstm_infer': [_P, _P, _I, _P, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P],
+    'qt_gather_frame': [_P, _I, _I, _P, _I, _L, _I, _P, _I, _P, _L, _L, _P],
     'qt_dense_lstm': [_P, _I, _P, _P, _I, _P, _I, _I, _I, _P, _P, _P, _I, _P, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P],
     'qt_decoder_input': [_P, _I, _P, _I, _P, _P, _P],
     'qt_concat': [_P, _P, _P, _I, _I, _P, _P, _P],

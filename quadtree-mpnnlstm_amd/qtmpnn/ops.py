@@ -1407,6 +1407,32 @@ class _GateCell(Function):
         return gZa, gZb, gW, gCp, gwc, gb, gln, None, None, None, None, None, None, None
 
 
+_FORWARD_ONLY = os.environ.get('QT_NO_FORWARD_ONLY') != '1'      # (A/B switch: 1 = the training launches also without autograd)
+
+
+def _forward_only(*ts):
+    """True when no backward can follow: autograd is off, or none of the tensors needs a gradient.  lstm_cell then takes the
+    forward-only launch (qt_lstm_infer), which skips the store of the (N, 4h) gate activations.  (The gate GEMM with the cell
+    as its epilogue, qt_dense_lstm, keeps its store: skipping it there measured no gain, 28.40 vs 28.66 us per launch at
+    hidden 32 and none at hidden 16 -- the launch is bound by its GEMM, not by those bytes.)"""
+    return _FORWARD_ONLY and (not torch.is_grad_enabled() or not any(t is not None and t.requires_grad for t in ts))
+
+
+def _lstm_cell_infer(G, Cprev, wc, b, ln, mesh):
+    """_LstmCell.forward without the saved gates."""
+    G = _c(G)
+    pair = G.dim() == 3
+    assert not pair or G.shape[1] == 2
+    N, h4 = G.shape[0], G.shape[-1]
+    h = h4 // 4
+    wc, b, ln = _c(wc), _c(b), _c(ln)
+    Cprev, ld_c = _rows(Cprev)
+    O, Hn, Cn = (G.new_empty(N, h) for _ in range(3))
+    _lib.call('qt_lstm_infer', ptr(G), G.data_ptr() + 4 * h4 if pair else None, 2 * h4 if pair else h4, ptr(Cprev), ld_c, ptr(wc),
+              ptr(b), ptr(ln), N, ptr(mesh.n_dev), h, ptr(O), ptr(Hn), ptr(Cn))
+    return O, Hn, Cn
+
+
 def gate_cell(X, H, W, Cprev, wc, b, ln, mesh, K, Ks, acc_w=None, acc_p=None, alias_h=False, pass_x=False):
     """(O, LayerNorm_h(H'), LayerNorm_c(C')) of one GConvLSTM update from Z = [X | H] (H may be None) and the packed
     gate weights W; X and H are passed as they are (column views of wider matrices included), never concatenated.
@@ -1423,6 +1449,8 @@ def gate_cell(X, H, W, Cprev, wc, b, ln, mesh, K, Ks, acc_w=None, acc_p=None, al
 
 
 def lstm_cell(G, Cprev, wc, b, ln, mesh, acc=None):
+    if G.is_cuda and _forward_only(G, Cprev, wc, b, ln):
+        return _lstm_cell_infer(G, Cprev, wc, b, ln, mesh)
     return _LstmCell.apply(G, Cprev, wc, b, ln, mesh, acc)
 
 
@@ -1571,6 +1599,23 @@ class _Gather(Function):
 
 def gather_pixels(val, mesh):
     return _Gather.apply(val, mesh)
+
+
+def gather_frame_into(val, mesh, out, t):
+    """unflatten of one output step straight into slot t of out (B, T, n, m, C) -- data only (no autograd): node values val
+    (N, C) (a column view of a wider matrix is read in place) go to their pixels; pixels without a node get NaN on pixelwise
+    meshes with a mask (unflatten_pixelwise) and 0 otherwise (unflatten).  Capturable: the node count is read on the device."""
+    assert not val.requires_grad and out.is_contiguous() and out.dim() == 5 and out.dtype == torch.float32
+    B, T, n, m, C = out.shape
+    assert (B, n, m) == (mesh.B, mesh.n, mesh.m) and 0 <= t < T and val.shape[1] == C, 'frame does not match the output stack'
+    val = val.float()
+    if not (val.dim() == 2 and (C == 1 or val.stride(1) == 1)):
+        val = val.contiguous()
+    ld = val.stride(0) if val.shape[0] > 1 else C
+    P = mesh.P
+    _lib.call('qt_gather_frame', ptr(val), ld, C, ptr(mesh.labels), mesh.B, P, val.shape[0], ptr(mesh.n_dev),
+              int(bool(mesh.pixelwise and mesh.mask is not None)), ptr(out), t * P * C, T * P * C)
+    return out
 
 
 _CLIP_REMESH = os.environ.get('QT_NO_CLIP_REMESH') != '1'      # (A/B switch: 1 = the general node / tile kernels everywhere)
