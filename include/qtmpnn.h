@@ -596,6 +596,17 @@ int qt_mhattn_fwd(const int32_t* rowptr, const int32_t* col, const float* eattr,
 int qt_mhattn_bwd_merge(const float* g, int ld_g, const float* Wt, const float* cat, int C, int heads, int N, const int32_t* n_dev,
                         float* gcat, float* part, int accumulate, void* stream);
 
+/* ---------------------------------------------------------------- attention coefficients (return_attention_weights)
+ * The softmax coefficients qt_attn_fwd uses, before dropout, for G groups on one mesh (a convolution, a head, or a convolution x
+ * head): alpha_ij = exp(s_ij - max) / (sum + 1e-16), s_ij = q_i . (k_j + e_ij) / sqrt(c_real), self pair with attributes (0, 0).
+ * Operands as in qt_attn_fwd: group g reads proj + g hs, q / k blocks ps apart, rows ld apart (0 = C, 4C: rows side by side), and
+ * We[g] of (G, C, 2); rev (E) from qt_attn_edge_attrs.  alpha_e (G, E): the coefficient of the message col[e] -> row(e) at
+ * rev[e], i.e. in the CSR order of the pairs (src = row, dst = col); alpha_s (G, N): that of node i's self pair (0 without one).
+ * Two passes per node (max and sum, then the coefficients): the forward's stats are not needed.  C = 4, 8, 16 or 32. */
+int qt_attn_weights(const int32_t* rowptr, const int32_t* col, const float* eattr, const float* selfloop, const float* proj, int ld,
+                    int64_t ps, int64_t hs, const float* We, int C, int c_real, int G, int N, const int32_t* n_dev, const int32_t* rev,
+                    int E, float* alpha_e, float* alpha_s, void* stream);
+
 /* ---------------------------------------------------------------- gate-weight packing of stacked ChebConvs
  * A GraphConv stack applies its ChebConvs with no nonlinearity in between (model/model.py:59-97, :95-96), so the eight
  * stacks of a GConvLSTM (model/model.py:263-463) are Chebyshev series in weight space, composed layer by layer:

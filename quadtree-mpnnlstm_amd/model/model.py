@@ -170,7 +170,11 @@ class TransformerConv(nn.Module):
                 out[i] = PackedConv(Wk, Wek, ops.GradAcc(), ops.GradAcc())
         return out
 
-    def forward(self, x, edge_index, edge_weight=None, packed=None):
+    def forward(self, x, edge_index, edge_weight=None, packed=None, return_attention_weights=None):
+        """return_attention_weights=True (or PyG's positional flag in the `packed` slot): (out, (edge_index, alpha)) as PyG returns
+        them, alpha (E', 1) over mesh.edge_index(self_loops=True), before dropout and DETACHED (PyG's alpha carries autograd).
+        `out` is the same as without the flag."""
+        packed, want = _attention_flag(packed, return_attention_weights)
         mesh = _need_mesh(edge_index, x)
         cin, cout = self.in_channels, self.out_channels
         cin_p, cp = cin + (-cin) % 4, cout + (-cout) % 4
@@ -180,7 +184,8 @@ class TransformerConv(nn.Module):
         pc = packed if packed is not None else self.pack()
         proj = ops.cheb_poly(x, pc.W, mesh, 1, 1, acc=pc.acc if packed is not None else None)     # one GEMM: [q | k | v | skip]
         out = ops.attention(proj, pc.We, mesh, cout, self.dropout, self.training, pc.acc_e if packed is not None else None)
-        return out[:, :cout] if cp != cout else out
+        out = out[:, :cout] if cp != cout else out
+        return _attention_result(self, out, want, mesh, lambda: ops.attention_weights(proj, pc.We, mesh, cout))
 
 
 class PackedConv:
@@ -256,7 +261,10 @@ class MHTransformerConv(nn.Module):
                 out[i] = PackedMHConv(*t, ops.GradAcc(), ops.GradAcc(), ops.GradAcc())
         return out
 
-    def forward(self, x, edge_index, edge_weight=None, packed=None):
+    def forward(self, x, edge_index, edge_weight=None, packed=None, return_attention_weights=None):
+        """return_attention_weights=True (or PyG's positional flag in the `packed` slot): (y, (edge_index, alpha)), alpha (E', heads)
+        over mesh.edge_index(self_loops=True), before dropout and detached (see TransformerConv.forward)."""
+        packed, want = _attention_flag(packed, return_attention_weights)
         mesh = _need_mesh(edge_index, x)
         cin, cout = self.in_channels, self.out_channels
         cin_p, cp = cin + (-cin) % 4, cout + (-cout) % 4
@@ -267,7 +275,10 @@ class MHTransformerConv(nn.Module):
         proj = ops.cheb_poly(x, pc.W, mesh, 1, 1, acc=pc.acc if packed is not None else None)      # one GEMM: [q | k | v | skip] x H
         y = ops.mh_attention(proj, pc.We, pc.Wt, pc.bl, mesh, cout, self.heads, self.dropout, self.training,
                              pc.acc_e if packed is not None else None, pc.acc_l if packed is not None else None)
-        return y[:, :cout] if cp != cout else y
+        y = y[:, :cout] if cp != cout else y
+        # the H heads' rows side by side (head-major [q | k | v | skip]): groups 4 cp apart, blocks cp apart
+        return _attention_result(self, y, want, mesh,
+                                 lambda: ops.attention_weights(proj, pc.We, mesh, cout, self.heads, ps=cp, hs=4 * cp))
 
 
 class PackedMHConv:
@@ -276,6 +287,70 @@ class PackedMHConv:
 
     def __init__(self, W, We, Wt, bl, acc, acc_e, acc_l):
         self.W, self.We, self.Wt, self.bl, self.acc, self.acc_e, self.acc_l = W, We, Wt, bl, acc, acc_e, acc_l
+
+
+def _attention_flag(packed, flag):
+    """(packed, return_attention_weights) of an attention convolution's call: a bool in the `packed` slot is PyG's positional
+    return_attention_weights flag (conv(x, edge_index, edge_attr, True)), never packed weights."""
+    if isinstance(packed, bool):
+        if flag is not None:
+            raise TypeError('return_attention_weights given twice: positionally (in the `packed` slot) and by keyword')
+        return None, packed
+    if flag is not None and not isinstance(flag, bool):
+        raise TypeError(f'return_attention_weights must be a bool or None, not {type(flag).__name__}')
+    return packed, bool(flag)
+
+
+def _attention_result(conv, out, want, mesh, weights):
+    """The return value of an attention convolution: `out`, or with the flag (out, (edge_index, alpha)).  weights() launches
+    qt_attn_weights on the operands the forward just used; it also runs when a recording (Seq2Seq.record_attention) selects `conv`."""
+    rec = _RECORDER[0]
+    name = rec.name_of(conv) if rec is not None else None
+    if not (want or name is not None):
+        return out
+    if name is not None:
+        rec.check()
+    pairs = ops.pyg_attention(mesh, *weights())
+    if name is not None:
+        rec.add(name, mesh, pairs)
+    return (out, pairs) if want else out
+
+
+class AttentionRecorder:
+    """The state of one Seq2Seq.record_attention block: which convolutions to record (qualified module names, a predicate or all),
+    and the records so far -- dicts with name, phase ('encoder' | 'decoder'), t (the step within the phase: the convolution's
+    call count so far), mesh, edge_index (2, E') int64 and alpha (E', heads) float32, detached, in PyG's layout."""
+
+    def __init__(self, model, select=None):
+        self.model, self.records, self._calls = model, [], {}
+        if select is None:
+            pred = lambda n: True
+        elif callable(select):
+            pred = select
+        else:
+            names = set([select] if isinstance(select, str) else select)
+            pred = names.__contains__
+        self._names = {id(m): n for n, m in model.named_modules() if isinstance(m, (TransformerConv, MHTransformerConv)) and pred(n)}
+
+    def name_of(self, conv):
+        return self._names.get(id(conv))
+
+    def names_of(self, convs):
+        return [self._names.get(id(c)) for c in convs]
+
+    def check(self):
+        if getattr(self.model, 'static_shapes', False) or (torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()):
+            raise RuntimeError('attention weights cannot be recorded in static mode or inside a graph capture (make_graphed_step, '
+                               'make_graphed_rollout, predict(use_graph=True)): the edge list needs a host read')
+
+    def add(self, name, mesh, pairs):
+        self.check()
+        t = self._calls.get(name, 0)
+        self._calls[name] = t + 1
+        self.records.append(dict(name=name, phase=name.split('.')[0], t=t, mesh=mesh, edge_index=pairs[0], alpha=pairs[1]))
+
+
+_RECORDER = [None]      # the open AttentionRecorder, or None: then no convolution launches anything for it
 
 
 def _need_mesh(edge_index, *node_tensors):
@@ -566,7 +641,8 @@ class GConvLSTM(nn.Module):
             y, L = None, len(pk.multi)
             for l, (Ws, We, acc) in enumerate(pk.multi):
                 segs = [(X, Ws[0]), (Hz, Ws[1])] if l == 0 else [(y, Ws[0])]
-                y = ops.multi_conv(segs, We, mesh, self.out_channels, c0.dropout, self.training, acc, gmod=4 if l == L - 1 else 0)
+                y = ops.multi_conv(segs, We, mesh, self.out_channels, c0.dropout, self.training, acc, gmod=4 if l == L - 1 else 0,
+                                   record=self._multi_record(l, mesh))
             return ops.lstm_cell(y, C, pk.wc, pk.b, pk.ln, mesh, pk.acc_p)
         if pk.W is None:
             Hz = H if H is not None else X.new_zeros(X.shape[0], self.out_channels)     # conv_h(0) is not 0 (biases)
@@ -578,6 +654,31 @@ class GConvLSTM(nn.Module):
             G = torch.cat([stack(f'conv_x_{g}', X) + stack(f'conv_h_{g}', Hz) for g in self.GATES], dim=1)
             return ops.lstm_cell(G, C, pk.wc, pk.b, pk.ln, mesh, pk.acc_p)
         return ops.gate_cell(X, H, pk.W, C, pk.wc, pk.b, pk.ln, mesh, pk.K, pk.Ks, pk.acc_w, pk.acc_p, alias_h, pass_x)
+
+    def _multi_record(self, l, mesh):
+        """The record(P, We) hook of ops.multi_conv for layer l while a recording selects any of its eight convolutions, else None:
+        the weights launch reads the layer's projections P (G, 4, N, C) in place -- one launch for all eight stacks, or one per
+        selected stack."""
+        rec = _RECORDER[0]
+        if rec is None:
+            return None
+        convs = [getattr(self, f'{br}_{g}').convolutions[l] for br in ('conv_x', 'conv_h') for g in self.GATES]
+        names = rec.names_of(convs)
+        if not any(names):
+            return None
+        h = self.out_channels
+
+        def record(P, We):
+            rec.check()
+            G, _, N, C = P.shape
+            if all(names):
+                ae, as_ = ops.attention_weights(P, We, mesh, h, G, ld=C, ps=N * C, hs=4 * N * C)
+                parts = [(n, ae[g:g + 1], as_[g:g + 1]) for g, n in enumerate(names)]
+            else:
+                parts = [(n, *ops.attention_weights(P[g], We[g], mesh, h, 1, ld=C, ps=N * C, hs=4 * N * C)) for g, n in enumerate(names) if n]
+            for n, ae, as_ in parts:
+                rec.add(n, mesh, ops.pyg_attention(mesh, ae, as_))
+        return record
 
     def forward(self, X, edge_index, edge_weight=None, H=None, C=None):
         pad = (-X.shape[1]) % 4

@@ -541,5 +541,17 @@ class NextFramePredictorS2S(NextFramePredictor):
         check_tile_errors(always=True)
         return np.stack(preds, 0)
 
+    @on_device(lambda self, *a, **k: self.device)
+    def attention_weights(self, x, concat_layers=None, mask=None, high_interest_region=None, graph_structure=None, select=None):
+        """The attention coefficients of one no-grad rollout of x (predict's eager forward, teacher forcing 0): the records of
+        Seq2Seq.record_attention(select), one per attention convolution call, with PyG's (edge_index, alpha) per record."""
+        self.model.to(self.device)
+        x = x.to(self.device)
+        concat = concat_layers.to(self.device) if concat_layers is not None else None
+        with torch.no_grad(), self.model.record_attention(select) as records:
+            self.model(x, concat_layers=concat, teacher_forcing_ratio=0, mask=mask, high_interest_region=high_interest_region,
+                       graph_structure=graph_structure)
+        return records
+
     def score(self, x, y, rollout=None):
         pass

@@ -3,6 +3,7 @@ and running on the GPU mesh pipeline (qtmpnn).  Constructor kwargs, forward() ar
 (outputs, output_mappings) and state-dict keys follow the reference; `x` may carry a leading clip
 axis (B, T_in, W, H, C) -- the reference processes one clip per call (ice_exp.py:137-139).
 """
+import contextlib
 import random
 
 import numpy as np
@@ -324,6 +325,27 @@ class Seq2Seq(_NoCachesInPickle, nn.Module):
         self.thresh, self.transform_func, self.graph, self.device = thresh, transform_func, None, device
         self.max_grid_size = 64                      # image_to_graph default, never overridden (graph_functions.py:590)
         self.static_shapes = False                   # True: worst-case capacities + device-side node counts (hipGraph)
+
+    # -- attention weights -----------------------------------------------------------------
+    @contextlib.contextmanager
+    def record_attention(self, select=None):
+        """Record the attention coefficients of every TransformerConv / MHTransformerConv evaluated while the block is open.  Yields
+        a list that fills with one dict per convolution call: name (qualified, as in named_modules(), e.g.
+        'encoder.rnns.0.conv_x_i.convolutions.1' or 'decoder.fc_out2'), phase ('encoder' | 'decoder'), t (the step within the
+        phase), mesh, edge_index = mesh.edge_index(self_loops=True) and alpha (E', heads): PyG's return_attention_weights pair, before
+        dropout, detached.  select: a collection of names or a predicate on the name; unselected convolutions cost no launch.
+        The forward's results, and the dropout masks it and later steps draw, are the same as without recording.  Not in static
+        mode or inside a graph capture (RuntimeError): the edge lists need host reads."""
+        from model import model as _model
+        if _model._RECORDER[0] is not None:
+            raise RuntimeError('record_attention blocks do not nest')
+        rec = _model.AttentionRecorder(self, select)
+        rec.check()
+        _model._RECORDER[0] = rec
+        try:
+            yield rec.records
+        finally:
+            _model._RECORDER[0] = None
 
     # -- weight packing -----------------------------------------------------------------
     def _packs(self, enc_in_pad):

@@ -93,6 +93,7 @@ _SIGNATURES = {
     'qt_mhattn_blocks': [_I, _I, _I],
     'qt_mhattn_fwd': [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _F, ctypes.c_uint32, _P, _P, _P, _P, _P],
     'qt_mhattn_bwd_merge': [_P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _I, _P],
+    'qt_attn_weights': [_P, _P, _P, _P, _P, _I, _L, _L, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P],
 }
 _PLAIN = {'qt_proj_bwd_blocks', 'qt_abi_version', 'qt_cheb_clip_rows', 'qt_cheb_tile_sync_words', 'qt_cheb_tile_xbuf_words', 'qt_tile_cap', 'qt_remesh_clip_rows', 'qt_tail_cap', 'qt_num_cus', 'qt_lstm_fused_blocks', 'qt_wgrad_blocks', 'qt_lstm_bwd_blocks', 'qt_lstm_dgrad_blocks', 'qt_attn_blocks', 'qt_mhattn_blocks'}  # return a value, not an error code
 

@@ -1026,6 +1026,50 @@ def mh_attention(proj, We, Wt, blin, mesh, c_real, heads, dropout_p=0.0, trainin
     return _MHAttention.apply(proj, We, Wt, blin, mesh, c_real, keep, seed, acc_e, acc_l, heads)
 
 
+def attention_weights(proj, We, mesh, c_real, G=1, ld=0, ps=0, hs=0):
+    """(alpha_e (G, E), alpha_s (G, N)): the softmax coefficients of G attention groups on `mesh` before dropout (qt_attn_weights),
+    from the operands the forward launch read -- proj with row stride ld (0: proj's own) and q / k blocks ps apart, groups hs apart
+    (0, 0: rows side by side, C and 4C), We (G, C, 2).  alpha_e[g, rev[e]] is the coefficient of the message col[e] -> row(e), i.e.
+    alpha_e follows the CSR order of the pairs (src = row, dst = col); alpha_s that of each node's self pair (0 without one).
+    No autograd, and neither the dropout seed counter nor the device epoch moves: recording never changes the masks of a step."""
+    proj, We = proj.detach(), _c(We.detach().float())
+    assert proj.dtype == torch.float32 and proj.stride(-1) == 1, 'proj: float32 rows'
+    We = We.view(G, -1, 2)
+    C, N = We.shape[1], mesh.N
+    ld = ld or proj.stride(0)
+    _, selfpair, eattr, rev = mesh.attn_geometry()
+    E = rev.numel()
+    alpha_e, alpha_s = proj.new_empty(G, E), proj.new_empty(G, N)
+    _lib.call('qt_attn_weights', ptr(mesh.rowptr), ptr(mesh.col), ptr(eattr), ptr(selfpair), ptr(proj), ld, ps, hs, ptr(We), C, c_real,
+              G, N, ptr(mesh.n_dev), ptr(rev), E, ptr(alpha_e), ptr(alpha_s))
+    return alpha_e, alpha_s
+
+
+def pyg_attention(mesh, alpha_e, alpha_s):
+    """PyG's (edge_index, alpha) from attention_weights' output: edge_index is mesh.edge_index(self_loops=True) (sorted int64, the
+    self pairs of multi-pixel cells included) over the valid nodes only, alpha (E', G) float32 in the same order.  Needs host reads
+    (the edge count), so it refuses to run inside a graph capture."""
+    if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError('attention weights cannot be returned inside a graph capture: the edge list needs a host read')
+    nv = mesh.n_valid
+    key = ('pyg_pairs', nv)
+    pairs = mesh._ones.get(key) if mesh.n_dev is None else None
+    if pairs is None:
+        rp = mesh.rowptr[:nv + 1].long()
+        ev = int(rp[-1]) if nv > 0 else 0
+        src = torch.repeat_interleave(torch.arange(nv, device=rp.device), rp[1:] - rp[:-1])
+        dst = mesh.col[:ev].long()
+        multi = torch.nonzero(mesh.npix[:nv] > 1).flatten()
+        src, dst = torch.cat([src, multi]), torch.cat([dst, multi])
+        order = torch.argsort(src * max(nv, 1) + dst)          # (the permutation Mesh.edge_index applies)
+        pairs = (torch.stack([src[order], dst[order]]), order, ev, multi)
+        if mesh.n_dev is None:
+            mesh._ones[key] = pairs
+    edge_index, order, ev, multi = pairs
+    alpha = torch.cat([alpha_e[:, :ev], alpha_s[:, multi]], dim=1)[:, order]
+    return edge_index, alpha.t().contiguous()
+
+
 _PROJ_BWD_FUSED = os.environ.get('QT_NO_PROJ_BWD_FUSED') != '1'      # (A/B switch)
 _PROJ_BWD_SHARED = os.environ.get('QT_NO_PROJ_BWD_SHARED') != '1'    # (A/B switch: the first-layer segments too)
 _STATS = {'skip_alias': 0}      # (how often a layer's gradient array was completed in place: tests look at it)
@@ -1046,7 +1090,7 @@ class _MultiConv(Function):
     gate: ops.lstm_cell adds them inside its kernel and hands back ONE gradient for both, as a stride-0 view).  acc: GradAcc of this layer's weights for the pass (dWe slab + deferred grouped weight gradients), or None."""
 
     @staticmethod
-    def forward(ctx, mesh, c_real, keep, seed, acc, gmod, nseg, *args):
+    def forward(ctx, mesh, c_real, keep, seed, acc, gmod, record, nseg, *args):
         As = [_c(a.float()) if a.dim() == 3 else _rows(a.float())[0] for a in args[:nseg]]
         Ws = [_c(w.float()) for w in args[nseg:2 * nseg]]
         We = _c(args[2 * nseg].float())
@@ -1067,6 +1111,8 @@ class _MultiConv(Function):
             segs.append((hoff, gin, cin, co, lda, gsa))
             hoff += gin * co // (4 * C)
         assert hoff == G, (hoff, G)
+        if record is not None:      # attention weights of (some of) the G stacks, read from P before the attention launch
+            record(P, We)
         xy, selfpair, eattr, _ = mesh.attn_geometry()
         gmod = gmod or G
         summed = gmod < G
@@ -1127,11 +1173,11 @@ class _MultiConv(Function):
         pslab = acc.pslab if acc is not None else {}
         fused = set()
         for s, ((hoff, gin, cin, co, lda, gsa), A, W) in enumerate(zip(ctx.segs, As, Ws)):
-            if not ctx.needs_input_grad[7 + s]:
+            if not ctx.needs_input_grad[8 + s]:
                 gAs.append(None)
                 continue
             heads = co // (4 * C)
-            if (_PROJ_BWD_FUSED and N > 0 and cin == 32 and C == 32 and ctx.needs_input_grad[7 + nseg + s] and W.is_contiguous()
+            if (_PROJ_BWD_FUSED and N > 0 and cin == 32 and C == 32 and ctx.needs_input_grad[8 + nseg + s] and W.is_contiguous()
                     and ((gin > 1 and heads == 1 and A.is_contiguous()) or (_PROJ_BWD_SHARED and gin == 1 and heads > 1 and lda % 4 == 0 and A.data_ptr() % 16 == 0))):
                 # data gradient AND this use's weight gradient in one pass over the gradient planes (csrc/projbwd.hip): the planes are
                 # read once and need not be kept for the deferred grouped weight gradient
@@ -1168,12 +1214,12 @@ class _MultiConv(Function):
                 gA.zero_()
             gAs.append(gA)
         last = acc is None or acc.leave(ctx.use_idx)
-        need_w = any(ctx.needs_input_grad[7 + nseg:7 + 2 * nseg])
+        need_w = any(ctx.needs_input_grad[8 + nseg:8 + 2 * nseg])
         pending = acc.pending if acc is not None else []
         if need_w and N > 0 and len(fused) < nseg:          # (the segments in `fused` have their share in the slabs already)
             pending.append((As, gP, N, mesh.n_dev, mesh.cheb_ones(1), fused))
         if not last:
-            return (None,) * 7 + tuple(gAs) + (None,) * (nseg + 1)
+            return (None,) * 8 + tuple(gAs) + (None,) * (nseg + 1)
         gWs = [None] * nseg
         if need_w:
             for s, (seg, W) in enumerate(zip(ctx.segs, Ws)):
@@ -1190,7 +1236,7 @@ class _MultiConv(Function):
         psum = P.new_empty(G * 2 * C)
         _lib.call('qt_colsum', ptr(part), nblk, G * 2 * C, ptr(psum))
         gWe = psum.view(G, 2, C).transpose(1, 2).contiguous()
-        return (None,) * 7 + tuple(gAs) + tuple(gWs) + (gWe,)
+        return (None,) * 8 + tuple(gAs) + tuple(gWs) + (gWe,)
 
 
 def _wgrad_groups(uses, s, seg, C, W):
@@ -1218,13 +1264,15 @@ def _wgrad_groups(uses, s, seg, C, W):
     return gW
 
 
-def multi_conv(segments, We, mesh, c_real, dropout_p=0.0, training=False, acc=None, gmod=0):
+def multi_conv(segments, We, mesh, c_real, dropout_p=0.0, training=False, acc=None, gmod=0, record=None):
     """segments: [(A, W)] as in _MultiConv; We (G, C, 2).  Returns (G, N, C), or with gmod < G the rows (N, G / gmod, gmod C)
-    whose head groups the consumer adds (ops.lstm_cell does, inside its kernel)."""
+    whose head groups the consumer adds (ops.lstm_cell does, inside its kernel).  record: None, or record(P, We) called with the
+    projections P (G, 4, N, C) right after they are computed (attention_weights reads them with ld = C, ps = N C, hs = 4 N C)."""
     keep = 1.0 - dropout_p if (training and dropout_p > 0) else 1.0
     _ATTN_CALLS[0] += 1
     seed = (_ATTN_CALLS[0] * 2654435761 + int(torch.initial_seed())) & 0xFFFFFFFF
-    return _MultiConv.apply(mesh, c_real, keep, seed, acc, gmod, len(segments), *[a for a, _ in segments], *[w for _, w in segments], We)
+    return _MultiConv.apply(mesh, c_real, keep, seed, acc, gmod, record, len(segments), *[a for a, _ in segments], *[w for _, w in segments],
+                            We)
 
 
 # ------------------------------------------------------------------------------ LSTM cell
