@@ -263,35 +263,51 @@ def test_encoder_decoder_step_golden():
     close(cel, g['dec_cell'])
 
 
-@pytest.mark.parametrize('h', [8, 16, 32])
+@pytest.mark.parametrize('h', [8, 16, 32, 64, 128])
 def test_lstm_kernel_vs_torch(h):
-    """Cell + fused LayerNorm against a plain fp32 torch reference (forward and every gradient)."""
+    """Cell + fused LayerNorm against a plain float64 torch reference (forward and every gradient), at every hidden size (a node's
+    row spans h / 4 lanes) and ragged node counts: 70 001 rows take more than one grid-stride sweep of k_lstm_bwd (512 blocks of
+    256 / LPN nodes).  Also the first step (Cprev = None: a zero cell state) and the cell without LayerNorm (ln = None)."""
     from qtmpnn import ops
-    torch.manual_seed(h)
-    N = 1000
-    mk = lambda *s: torch.randn(*s, device=dev(), requires_grad=True)
-    G, Cp, wc, b, ln = mk(N, 4 * h), mk(N, h), mk(3, h), mk(4, h), mk(4, h)
+    from qtmpnn.mesh import Mesh
 
     def ref(G, Cp, wc, b, ln):
         gi, gf, gc, go = G.split(h, dim=1)
+        Cp = torch.zeros_like(gi) if Cp is None else Cp
         I = torch.sigmoid(gi + wc[0] * Cp + b[0])
         F = torch.sigmoid(gf + wc[1] * Cp + b[1])
         T = torch.tanh(gc + b[2])
         Cr = F * Cp + I * T
         Og = torch.sigmoid(go + wc[2] * Cr + b[3])
         Hr = Og * torch.tanh(Cr)
+        if ln is None:
+            return Og, Hr, Cr
         return (Og, torch.nn.functional.layer_norm(Hr, (h,), ln[0], ln[1], 1e-5),
                 torch.nn.functional.layer_norm(Cr, (h,), ln[2], ln[3], 1e-5))
-    from qtmpnn.mesh import Mesh
-    outs = ops.lstm_cell(G, Cp, wc, b, ln, Mesh())
-    refs = ref(G, Cp, wc, b, ln)
-    for a, r in zip(outs, refs):
-        close(a, r, atol=2e-5)
-    gs = [torch.randn_like(o) for o in refs]
-    ga = torch.autograd.grad(outs, [G, Cp, wc, b, ln], gs)
-    gr = torch.autograd.grad(refs, [G, Cp, wc, b, ln], gs)
-    for a, r, name in zip(ga, gr, ['G', 'Cprev', 'wc', 'b', 'ln']):
-        grad_close(a, r, msg=name)
+
+    d64 = lambda t: None if t is None else t.detach().double().requires_grad_(True)
+    cases = [(N, 'full') for N in (1, 37, 1000, 70001)] + [(N, v) for v in ('no_cprev', 'no_ln') for N in (37, 70001)]
+    for N, variant in cases:
+        torch.manual_seed(h + N)
+        mk = lambda *s: torch.randn(*s, device=dev(), requires_grad=True)
+        G, Cp, wc, b, ln = mk(N, 4 * h), mk(N, h), mk(3, h), mk(4, h), mk(4, h)
+        if variant == 'no_cprev':
+            Cp = None
+        if variant == 'no_ln':
+            ln = None
+        ins = [t for t in (G, Cp, wc, b, ln) if t is not None]
+        names = [n for n, t in zip(['G', 'Cprev', 'wc', 'b', 'ln'], (G, Cp, wc, b, ln)) if t is not None]
+        rins = [d64(t) for t in (G, Cp, wc, b, ln)]
+        outs = ops.lstm_cell(G, Cp, wc, b, ln, Mesh())
+        refs = ref(*rins)
+        tag = f'N={N} {variant}'
+        for a, r, name in zip(outs, refs, ('O', 'H', 'C')):
+            close(a, r, atol=2e-5, msg=f'{tag} {name}')
+        gs = [torch.randn_like(o) for o in refs]
+        ga = torch.autograd.grad(outs, ins, [g.float() for g in gs])
+        gr = torch.autograd.grad(refs, [t for t in rins if t is not None], gs)
+        for a, r, name in zip(ga, gr, names):
+            grad_close(a, r, msg=f'{tag} {name}')
 
 
 def test_head_kernel_vs_torch():

@@ -185,7 +185,7 @@ def launched(monkeypatch):
     return names
 
 
-@pytest.mark.parametrize('h', [8, 16, 32])
+@pytest.mark.parametrize('h', [8, 16, 32, 64, 128])
 @pytest.mark.parametrize('pair', [False, True])
 def test_forward_only_lstm_cell_bit_identical(h, pair, launched):
     """qt_lstm_infer == qt_lstm_fwd bit for bit, on (N, 4h) gate sums and on the paired (N, 2, 4h) input the attention stacks

@@ -355,6 +355,78 @@ def test_every_supported_hidden_size_trains(conv, h, nl, nc):
         nfp.train_step(torch.cat([xt, xt], dim=-1), yt, None, mask=mask)
 
 
+@pytest.mark.parametrize('conv,h,nl,nc,cin', [('ChebConv', 8, 1, 2, 1), ('ChebConv', 32, 2, 3, 1), ('ChebConv', 64, 1, 3, 1),
+                                              ('ChebConv', 64, 1, 3, 5), ('ChebConv', 128, 1, 1, 1), ('ChebConv', 16, 2, 4, 1),
+                                              ('GCNConv', 16, 1, 2, 1), ('GCNConv', 64, 2, 2, 1), ('GCNConv', 128, 1, 2, 1)])
+def test_every_supported_hidden_size_step_vs_float64_oracle(conv, h, nl, nc, cin):
+    """The ChebConv / GCNConv configurations of test_every_supported_hidden_size_trains (and hidden 64 with 3 conv layers on 5
+    channels: a composed gate matrix of exactly 512 rows) through one forward and backward of Seq2Seq (dropout 0, 3 in, 2 out) on
+    a preset heterogeneous mesh, against the oracle's Seq2Seq run in float64 on the CPU on the same mesh: every output step, the
+    loss and every parameter gradient.  Hidden 64 / 128 take qt_dense2 + qt_lstm_fwd with the LayerNorm fused over 16 / 32 lanes.
+
+    Stacks of three or four ChebConvs have their own bound (outputs atol 2e-4, gradients 1e-3 x the tensor's largest entry):
+    their degree-6 / 8 polynomials are composed in weight space and rounded in fp32, and the error grows on the one-pixel nodes
+    of the high-interest region over five recurrent steps.  Measured on one MI355X against this float64 reference: worst
+    |got - ref| 8.3e-5 on an output (hidden 16, 4 conv layers; 7.5e-5 at hidden 32, 3 layers) and 3.6e-4 x max on a gradient
+    (encoder.rnns.0.b_c at hidden 16, 4 layers; 3.5e-4 x max on a decoder weight at hidden 64, 3 layers); the fp32 oracle itself
+    is 1.3e-5 away from float64 on the same nodes.  A single cell with 4 ChebConvs holds the default bounds
+    (tests/test_gpu_cell_oracle.py), and so does this test with one or two ChebConvs or any GCNConv stack."""
+    from model.graph_functions import create_static_heterogeneous_graph
+    from model.mpnnlstm import masked_mse
+    from model.seq2seq import Seq2Seq
+    from oracle import qt_oracle as O
+    from qtmpnn import synthetic
+    mask = np.zeros((64, 64), dtype=bool)
+    mask[44:, :20] = True
+    hir = np.zeros((64, 64), dtype=bool)
+    hir[8:14, 40:50] = True
+    gs = create_static_heterogeneous_graph((64, 64), 16, mask, high_interest_region=hir, use_edge_attrs=False, device=dev())
+    mesh = gs['mapping']
+    kw = dict(input_timesteps=3, input_features=cin + 3, output_timesteps=2, n_layers=nl, n_conv_layers=nc, convolution_type=conv)
+    torch.manual_seed(3)
+    ref = O.Seq2Seq(h, 0.0, -np.inf, **kw)
+    with torch.no_grad():
+        for p in ref.parameters():
+            p.add_(0.1 * torch.randn_like(p))
+    model = Seq2Seq(h, 0.0, -np.inf, **kw)
+    model.load_state_dict(ref.state_dict())
+    model.to(dev())
+    if cin == 5:                                     # 7 hops x (8 + 64) channels + 8 bias rows: the GEMM kernels' MAXQ
+        assert model.encoder.rnns[0].pack(8, None, (True,))[0].W.shape[0] == 512
+    ref.double()
+    clip = synthetic.make_clip(17, n_frames=5, pixel_noise=0.02)                         # (5, 64, 64, 1)
+    rng = np.random.default_rng(4)
+    x = np.concatenate([clip[:3]] + [rng.random((3, 64, 64, 1))] * (cin - 1), axis=-1).astype(np.float32)
+    y = clip[3:].astype(np.float32)
+    concat = rng.random((2, 64, 64, 1)).astype(np.float32)
+    xt, yt, ct = (torch.from_numpy(a).to(dev()) for a in (x, y, concat))
+    outs, meshes = model(xt, yt, ct, teacher_forcing_ratio=0, mask=mask, graph_structure=gs)
+    loss = masked_mse(outs, meshes, yt, mask)
+    loss.backward()
+    old = torch.get_default_dtype()
+    torch.set_default_dtype(torch.float64)           # (the oracle's zero states and constants follow the default dtype)
+    try:
+        gsr = dict(labels=mesh.labels[0].cpu().numpy(), n_pixels_per_node=mesh.npix.cpu().double(),
+                   edge_index=mesh.edge_index(True).cpu(), edge_attrs=mesh.edge_attrs(False).cpu().double())
+        o, maps, _ = ref(torch.from_numpy(x).double(), torch.from_numpy(concat).double(), mask=mask, graph_structure=gsr)
+        loss_r = O.clip_loss(o, maps, torch.from_numpy(y).double(), (64, 64), mask)
+        loss_r.backward()
+    finally:
+        torch.set_default_dtype(old)
+    assert len(outs) == len(o) == 2
+    deep = conv == 'ChebConv' and nc >= 3
+    for i, (a, r) in enumerate(zip(outs, o)):
+        close(a, r, atol=2e-4 if deep else 1e-5, msg=f'step {i}')
+    assert abs(float(loss.detach()) - float(loss_r)) <= 1e-4 * abs(float(loss_r)), (float(loss.detach()), float(loss_r))
+    refp = dict(ref.named_parameters())
+    for k, p in model.named_parameters():
+        r = refp[k].grad
+        if p.grad is None:
+            assert r is None or not r.any(), f'{k}: no gradient on the HIP path but the reference gradient is non-zero'
+            continue
+        grad_close(p.grad, r, rel_atol=1e-3 if deep else 5e-5, msg=k)
+
+
 def test_modules_refuse_node_tensors_of_another_mesh():
     """The modules take the Mesh where the reference takes edge_index; their kernels walk the mesh's rows and read the node tensors
     unchecked, so a tensor with another row count (the reference would die in an index error inside PyG) is refused before a launch."""

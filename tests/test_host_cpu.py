@@ -207,6 +207,18 @@ def test_unsupported_variants_raise_clearly():
     Seq2Seq(32, 0.1, 0.1, convolution_type='ChebConv', n_layers=4, n_conv_layers=3)        # (7 x 64 + 8 = 456)
 
 
+@pytest.mark.parametrize('conv,h,nc,cin', [('ChebConv', 64, 3, 8), ('GCNConv', 64, 5, 20)])
+def test_gate_rows_at_maxq_accepted_and_next_channel_step_refused(conv, h, nc, cin):
+    """The two configurations whose composed gate matrix has exactly 512 rows (the GEMM kernels' MAXQ quads; the GPU cell and
+    Seq2Seq tests run them) are accepted; one more input channel pads to the next 4 and needs 516 + rows: refused by name."""
+    from model.seq2seq import Seq2Seq
+    kc = (2 * nc if conv == 'ChebConv' else nc) + 1
+    assert kc * (cin + h) + (kc + (-kc) % 4) == 512
+    Seq2Seq(h, 0.0, 0.1, input_features=cin, n_layers=1, n_conv_layers=nc, convolution_type=conv)
+    with pytest.raises(ValueError, match='gate'):
+        Seq2Seq(h, 0.0, 0.1, input_features=cin + 1, n_layers=1, n_conv_layers=nc, convolution_type=conv)
+
+
 @pytest.mark.parametrize('n_conv', [1, 2])
 def test_pack_plan_equals_per_tensor_packing(n_conv):
     """ops.PackPlan (one gather of all parameters through recorded index maps) == the per-tensor stack / cat packing,
