@@ -30,29 +30,28 @@ class ChebConv(nn.Module):
         for lin in self.lins:
             nn.init.xavier_uniform_(lin.weight)
 
-    def cheb_coeffs(self):
-        """Coefficient matrices (K, in, out) of the Chebyshev series this layer applies, and its bias."""
-        return torch.stack([lin.weight for lin in self.lins]).transpose(1, 2), self.bias
-
-    def packed(self, in_pad=None, out_pad=None):
-        """[W_0^T; ...; W_{K-1}^T; bias; 0 0 0] as one ((K*in_pad)+4, out_pad) matrix, zero padded."""
-        cin, cout = in_pad or self.in_channels, out_pad or self.out_channels
-        w, _ = self.cheb_coeffs()                                                           # (K, in, out)
-        w = nn.functional.pad(w, (0, cout - self.out_channels, 0, cin - self.in_channels))
-        b = self.bias if self.bias is not None else w.new_zeros(self.out_channels)
-        tail = nn.functional.pad(b.unsqueeze(0), (0, cout - self.out_channels, 0, 3))        # bias row + 3 zero rows
-        return torch.cat([w.reshape(self.K * cin, cout), tail], dim=0)
-
-    # -- the same matrix as a data-movement layout over stand-in tensors (ops.PackPlan) -------------------------------
     def plan_params(self):
         return [lin.weight for lin in self.lins] + [self.bias]
 
+    def cheb_coeffs(self, T):
+        """Coefficient matrices (K, in, out) of the Chebyshev series this layer applies, from its plan_params() or index stand-ins of
+        them: the hook every layout takes a layer's weights through (GCNConv overrides it)."""
+        return torch.stack(T[:self.K]).transpose(1, 2)
+
     def plan_layout(self, T, fill, in_pad=None, out_pad=None):
+        """[W_0^T; ...; W_{K-1}^T; bias; 0 0 0] as one ((K*in_pad)+4, out_pad) matrix padded with `fill`, from plan_params() or
+        stand-ins of them (data movement only, see ops.PackPlan)."""
         cin, cout = in_pad or self.in_channels, out_pad or self.out_channels
-        w = torch.stack(T[:self.K]).transpose(1, 2)                                          # (K, in, out)
-        w = nn.functional.pad(w, (0, cout - self.out_channels, 0, cin - self.in_channels), value=fill)
-        tail = nn.functional.pad(T[self.K].unsqueeze(0), (0, cout - self.out_channels, 0, 3), value=fill)
+        w = nn.functional.pad(self.cheb_coeffs(T), (0, cout - self.out_channels, 0, cin - self.in_channels), value=fill)
+        tail = nn.functional.pad(T[-1].unsqueeze(0), (0, cout - self.out_channels, 0, 3), value=fill)    # bias row + 3 padding rows
         return torch.cat([w.reshape(self.K * cin, cout), tail], dim=0)
+
+    def packed(self, in_pad=None, out_pad=None):
+        """plan_layout of the parameters themselves, zero padded; a zero row stands in for the bias of a bias=False layer."""
+        T = self.plan_params()
+        if self.bias is None:
+            T[-1] = T[0].new_zeros(self.out_channels)
+        return self.plan_layout(T, 0.0, in_pad, out_pad)
 
     def plan_layout_projected(self, T, fill):
         """A K = 3 layer with ONE output channel as the (in + 4, 4) matrix [w_0 w_1 w_2 0 ; b 0 0 0 ; 0 ...]: the operand of
@@ -85,9 +84,12 @@ class GCNConv(ChebConv):
         self.bias = nn.Parameter(torch.zeros(out_channels))
         nn.init.xavier_uniform_(self.lin.weight)
 
-    def cheb_coeffs(self):
-        wt = self.lin.weight.t()
-        return torch.stack([torch.zeros_like(wt), -wt]), self.bias
+    def plan_params(self):
+        return [self.lin.weight, self.bias]
+
+    def cheb_coeffs(self, T):       # (the negation is arithmetic, not data movement: GCNConv layouts are evaluated directly, never planned)
+        wt = T[0].t()
+        return torch.stack([torch.zeros_like(wt), -wt])
 
 
 class TransformerConv(nn.Module):
@@ -111,17 +113,10 @@ class TransformerConv(nn.Module):
                 nn.init.zeros_(lin.bias)
 
     def pack(self):
-        """(W, We, accumulator) for one forward pass: the fused projection [q | k | v | skip] with its bias row, the padded
-        edge weight, and the gradient accumulator all uses of this convolution in the pass share (a recurrent cell calls it
-        once per time step: packing per call cost ~40 tiny kernels each time, forward + backward)."""
-        cin, cout = self.in_channels, self.out_channels
-        cin_p, cp = cin + (-cin) % 4, cout + (-cout) % 4
-        blocks = [self.lin_query, self.lin_key, self.lin_value, self.lin_skip]
-        w = torch.cat([nn.functional.pad(l.weight.t(), (0, cp - cout, 0, cin_p - cin)) for l in blocks], dim=1)   # (cin_p, 4 cp)
-        b = torch.cat([nn.functional.pad(l.bias, (0, cp - cout)) for l in blocks]).unsqueeze(0)
-        W = torch.cat([w, nn.functional.pad(b, (0, 0, 0, 3))], dim=0)                   # bias row + 3 zero rows
-        We = nn.functional.pad(self.lin_edge.weight, (0, 0, 0, cp - cout))
-        return PackedConv(W, We, ops.GradAcc(), ops.GradAcc())
+        """(W, We, accumulators) for one forward pass: the fused projection [q | k | v | skip] with its bias row, the padded edge
+        weight, and the gradient accumulators all uses of this convolution in the pass share (a recurrent cell calls it once per
+        time step: packing per call cost ~40 tiny kernels each time, forward + backward)."""
+        return TransformerConv.pack_many([self])[0]
 
     def plan_params(self):
         """The parameters in module order (= the stand-ins proj_layout receives)."""
@@ -144,31 +139,9 @@ class TransformerConv(nn.Module):
         return W, We
 
     @staticmethod
-    def stack_proj(convs):
-        """(W (n, cin_p + 4, 4 cp), We (n, cp, 2)) of n convolutions of one (in, out) shape: W[i] = [q | k | v | skip] of
-        convolution i with its bias row (the matrices pack() builds, in three stack / pad / cat launches)."""
-        return TransformerConv.proj_layout([c.plan_params() for c in convs], convs[0].in_channels, convs[0].out_channels, 0.0)
-
-    @staticmethod
     def pack_many(convs):
-        """[PackedConv] for a list of convolutions, one batched packing per (in, out) shape: the same matrices as pack()."""
-        out = [None] * len(convs)
-        groups = {}
-        for i, c in enumerate(convs):
-            groups.setdefault((c.in_channels, c.out_channels), []).append(i)
-        for (cin, cout), idxs in groups.items():
-            cin_p, cp = cin + (-cin) % 4, cout + (-cout) % 4
-            cs = [convs[i] for i in idxs]
-            blocks = [[c.lin_query, c.lin_key, c.lin_value, c.lin_skip] for c in cs]
-            w = torch.stack([l.weight for b4 in blocks for l in b4]).view(len(cs), 4, cout, cin)          # (G, 4, cout, cin)
-            w = nn.functional.pad(w.permute(0, 3, 1, 2), (0, cp - cout, 0, 0, 0, cin_p - cin))             # (G, cin_p, 4, cp)
-            b = torch.stack([l.bias for b4 in blocks for l in b4]).view(len(cs), 1, 4, cout)
-            b = nn.functional.pad(b, (0, cp - cout, 0, 0, 0, 3))                                            # bias row + 3 zero rows
-            W = torch.cat([w, b], dim=1).reshape(len(cs), cin_p + 4, 4 * cp)
-            We = nn.functional.pad(torch.stack([c.lin_edge.weight for c in cs]), (0, 0, 0, cp - cout))     # (G, cp, 2)
-            for i, Wk, Wek in zip(idxs, W.unbind(0), We.unbind(0)):          # (unbind: one stack in the backward)
-                out[i] = PackedConv(Wk, Wek, ops.GradAcc(), ops.GradAcc())
-        return out
+        """[PackedConv] for a list of convolutions: proj_layout of the parameters themselves, one batched evaluation per shape."""
+        return _pack_by_shape(convs, lambda c: (c.in_channels, c.out_channels), TransformerConv.proj_layout, PackedConv)
 
     def forward(self, x, edge_index, edge_weight=None, packed=None, return_attention_weights=None):
         """return_attention_weights=True (or PyG's positional flag in the `packed` slot): (out, (edge_index, alpha)) as PyG returns
@@ -189,11 +162,25 @@ class TransformerConv(nn.Module):
 
 
 class PackedConv:
-    """Packed weights of one attention convolution for one forward pass."""
+    """Packed weights of one attention convolution for one forward pass (+ the gradient accumulators of that pass)."""
     __slots__ = ('W', 'We', 'acc', 'acc_e')
 
-    def __init__(self, W, We, acc, acc_e):
-        self.W, self.We, self.acc, self.acc_e = W, We, acc, acc_e
+    def __init__(self, W, We):
+        self.W, self.We, self.acc, self.acc_e = W, We, ops.GradAcc(), ops.GradAcc()
+
+
+def _pack_by_shape(convs, shape, layout, packed):
+    """[packed(*matrices)] for a list of attention convolutions: `layout` (proj_layout and its like) evaluated on the parameters
+    themselves with zero padding, once per shape(conv) for all convolutions of that shape; each convolution gets its views of the
+    batched matrices (unbind: one stack in the backward, not a dozen launches per convolution -- 24+ convolutions per cell)."""
+    out, groups = [None] * len(convs), {}
+    for i, c in enumerate(convs):
+        groups.setdefault(shape(c), []).append(i)
+    for key, idxs in groups.items():
+        mats = layout([convs[i].plan_params() for i in idxs], *key, 0.0)
+        for i, *views in zip(idxs, *[m.unbind(0) for m in mats]):
+            out[i] = packed(*views)
+    return out
 
 
 class MHTransformerConv(nn.Module):
@@ -224,24 +211,28 @@ class MHTransformerConv(nn.Module):
             if lin.bias is not None:
                 nn.init.zeros_(lin.bias)
 
+    def plan_params(self):
+        """The parameters in module order (= the stand-ins _layout receives)."""
+        return [self.lin_key.weight, self.lin_key.bias, self.lin_query.weight, self.lin_query.bias, self.lin_value.weight,
+                self.lin_value.bias, self.lin_edge.weight, self.lin_skip.weight, self.lin_skip.bias, self.lin.weight, self.lin.bias]
+
     @staticmethod
-    def _layout(convs):
-        """(W (n, cin_p + 4, H 4 cp), We (n, H, cp, 2), Wt (n, H cp, cp), blin (n, cp)) of n convolutions of one shape: W[i] =
-        [q | k | v | skip] of every head, head-major, with the bias row + 3 zero rows; Wt = lin.weight^T split by head.  Channels
-        above out_channels (cp = out rounded up to 4) are zero everywhere, so the padding columns of cat and y stay zero."""
-        c0 = convs[0]
-        n, H, cin, cout = len(convs), c0.heads, c0.in_channels, c0.out_channels
+    def _layout(Ts, cin, cout, H, fill):
+        """(W (n, cin_p + 4, H 4 cp), We (n, H, cp, 2), Wt (n, H cp, cp), blin (n, cp)) of n convolutions of one shape from their
+        plan_params() lists (data movement only, padding = `fill`, like TransformerConv.proj_layout): W[i] = [q | k | v | skip] of
+        every head, head-major, with the bias row + 3 padding rows; Wt = lin.weight^T split by head.  Channels above out_channels
+        (cp = out rounded up to 4) are padding everywhere, so the padding columns of cat and y stay zero."""
+        n = len(Ts)
         cin_p, cp = cin + (-cin) % 4, cout + (-cout) % 4
-        blocks = [[c.lin_query, c.lin_key, c.lin_value, c.lin_skip] for c in convs]
-        w = torch.stack([l.weight for b4 in blocks for l in b4]).view(n, 4, H, cout, cin)
-        w = nn.functional.pad(w.permute(0, 4, 2, 1, 3), (0, cp - cout, 0, 0, 0, 0, 0, cin_p - cin))        # (n, cin_p, H, 4, cp)
-        b = torch.stack([l.bias for b4 in blocks for l in b4]).view(n, 4, H, cout).transpose(1, 2)
-        b = nn.functional.pad(b, (0, cp - cout)).reshape(n, 1, H * 4 * cp)
-        W = torch.cat([w.reshape(n, cin_p, H * 4 * cp), nn.functional.pad(b, (0, 0, 0, 3))], dim=1)
-        We = nn.functional.pad(torch.stack([c.lin_edge.weight for c in convs]).view(n, H, cout, 2), (0, 0, 0, cp - cout))
-        Wt = torch.stack([c.lin.weight for c in convs]).view(n, cout, H, cout).permute(0, 2, 3, 1)             # (n, H, c, o)
-        Wt = nn.functional.pad(Wt, (0, cp - cout, 0, cp - cout)).reshape(n, H * cp, cp)
-        bl = nn.functional.pad(torch.stack([c.lin.bias for c in convs]), (0, cp - cout))
+        w = torch.stack([t for T in Ts for t in (T[2], T[0], T[4], T[7])]).view(n, 4, H, cout, cin)
+        w = nn.functional.pad(w.permute(0, 4, 2, 1, 3), (0, cp - cout, 0, 0, 0, 0, 0, cin_p - cin), value=fill)  # (n, cin_p, H, 4, cp)
+        b = torch.stack([t for T in Ts for t in (T[3], T[1], T[5], T[8])]).view(n, 4, H, cout).transpose(1, 2)
+        b = nn.functional.pad(b, (0, cp - cout), value=fill).reshape(n, 1, H * 4 * cp)
+        W = torch.cat([w.reshape(n, cin_p, H * 4 * cp), nn.functional.pad(b, (0, 0, 0, 3), value=fill)], dim=1)
+        We = nn.functional.pad(torch.stack([T[6] for T in Ts]).view(n, H, cout, 2), (0, 0, 0, cp - cout), value=fill)
+        Wt = torch.stack([T[9] for T in Ts]).view(n, cout, H, cout).permute(0, 2, 3, 1)                         # (n, H, c, o)
+        Wt = nn.functional.pad(Wt, (0, cp - cout, 0, cp - cout), value=fill).reshape(n, H * cp, cp)
+        bl = nn.functional.pad(torch.stack([T[10] for T in Ts]), (0, cp - cout), value=fill)
         return W, We, Wt, bl
 
     def pack(self):
@@ -250,16 +241,8 @@ class MHTransformerConv(nn.Module):
 
     @staticmethod
     def pack_many(convs):
-        """[PackedMHConv] for a list of convolutions, one batched packing per (in, out, heads) shape: the same matrices as pack()."""
-        out = [None] * len(convs)
-        groups = {}
-        for i, c in enumerate(convs):
-            groups.setdefault((c.in_channels, c.out_channels, c.heads), []).append(i)
-        for idxs in groups.values():
-            W, We, Wt, bl = MHTransformerConv._layout([convs[i] for i in idxs])
-            for i, *t in zip(idxs, W.unbind(0), We.unbind(0), Wt.unbind(0), bl.unbind(0)):
-                out[i] = PackedMHConv(*t, ops.GradAcc(), ops.GradAcc(), ops.GradAcc())
-        return out
+        """[PackedMHConv] for a list of convolutions: _layout of the parameters themselves, one batched evaluation per shape."""
+        return _pack_by_shape(convs, lambda c: (c.in_channels, c.out_channels, c.heads), MHTransformerConv._layout, PackedMHConv)
 
     def forward(self, x, edge_index, edge_weight=None, packed=None, return_attention_weights=None):
         """return_attention_weights=True (or PyG's positional flag in the `packed` slot): (y, (edge_index, alpha)), alpha (E', heads)
@@ -282,11 +265,12 @@ class MHTransformerConv(nn.Module):
 
 
 class PackedMHConv:
-    """Packed weights of one MHTransformerConv for one forward pass."""
+    """Packed weights of one MHTransformerConv for one forward pass (+ the gradient accumulators of that pass)."""
     __slots__ = ('W', 'We', 'Wt', 'bl', 'acc', 'acc_e', 'acc_l')
 
-    def __init__(self, W, We, Wt, bl, acc, acc_e, acc_l):
-        self.W, self.We, self.Wt, self.bl, self.acc, self.acc_e, self.acc_l = W, We, Wt, bl, acc, acc_e, acc_l
+    def __init__(self, W, We, Wt, bl):
+        self.W, self.We, self.Wt, self.bl = W, We, Wt, bl
+        self.acc, self.acc_e, self.acc_l = ops.GradAcc(), ops.GradAcc(), ops.GradAcc()
 
 
 def _attention_flag(packed, flag):
@@ -432,139 +416,75 @@ class GConvLSTM(nn.Module):
                 setattr(self, f'w_c_{g}', nn.Parameter(torch.zeros(1, out_channels)))
             setattr(self, f'b_{g}', nn.Parameter(torch.zeros(1, out_channels)))
 
-    # -- weight packing (tiny, differentiable torch ops; once per forward pass) ----------
-    def _branch(self, prefix):
-        weights, biases = [], []
-        for l in range(self.n_conv_layers):
-            convs = [getattr(self, f'{prefix}_{g}').convolutions[l] for g in self.GATES]
-            if isinstance(convs[0], GCNConv):
-                weights.append(torch.stack([c.cheb_coeffs()[0] for c in convs]))
-            else:
-                w = torch.stack([lin.weight for c in convs for lin in c.lins])             # one copy: (4*K, h, in)
-                weights.append(w.view(4, len(convs[0].lins), *w.shape[1:]).transpose(-1, -2))
-            biases.append(torch.stack([c.bias for c in convs]))
-        return ops.compose_chebconvs(weights, biases)          # (4, K, in, h), (4, Ks, h)
-
+    # -- weight packing (once per forward pass): ONE set of layout functions, written with data-movement ops only, serves both the
+    # gather of a whole model's parameters (ops.PackPlan over stand-ins) and direct evaluation on the parameters (ops.pack_direct)
     @property
     def is_series(self):
         """True when every convolution is a Chebyshev series (ChebConv, GCNConv): the stacks compose in weight space."""
         return hasattr(self.conv_x_i.convolutions[0], 'cheb_coeffs')
 
-    def pack(self, in_pad=None, ln=None, variants=(True,)):
-        """One PackedCell per requested variant (with_h True / False); the variants share the peephole / bias
-        tensors and their gradient accumulator.  W: ((K*C + Ks_padded), 4h) for Z = [X (padded to in_pad) | H]."""
-        h = self.out_channels
-        if not self.is_series:          # attention convolutions are nonlinear: no weight-space composition; TransformerConv stacks run
-                                        # layer by layer (_pack_multi), MHTransformerConv ones one convolution after another
-            wc = torch.cat([self.w_c_i, self.w_c_f, self.w_c_o], dim=0)
-            b = torch.cat([self.b_i, self.b_f, self.b_c, self.b_o], dim=0)
-            acc_p = ops.GradAcc()
-            names = [f'{br}_{g}' for br in ('conv_x', 'conv_h') for g in self.GATES]
-            if isinstance(self.conv_x_i.convolutions[0], TransformerConv) and _MULTI_CONV and h % 4 == 0:
-                cells = [PackedCell(None, 0, 0, wc, b, ln, None, acc_p) for _ in variants]
-                multi = self._pack_multi(names)
-                for c in cells:
-                    c.multi = multi
-                return cells
-            if isinstance(self.conv_x_i.convolutions[0], (TransformerConv, MHTransformerConv)):
-                # all convolutions of one shape are packed together: a handful of stack / pad / cat launches per shape
-                # instead of a dozen per convolution (24+ convolutions per cell)
-                flat = [(n, l, c) for n in names for l, c in enumerate(getattr(self, n).convolutions)]
-                packed = type(self.conv_x_i.convolutions[0]).pack_many([c for _, _, c in flat])
-                convs = {n: [None] * self.n_conv_layers for n in names}
-                for (n, l, _), pc in zip(flat, packed):
-                    convs[n][l] = pc
-            else:
-                convs = {n: [c.pack() for c in getattr(self, n).convolutions] for n in names}
-            cells = [PackedCell(None, 0, 0, wc, b, ln, None, acc_p) for _ in variants]
-            for c in cells:
-                c.convs = convs             # the variants share the packed convolutions (and their accumulators)
-            return cells
-        Px, bx = self._branch('conv_x')
-        Ph, bh = self._branch('conv_h')
-        wc = torch.cat([self.w_c_i, self.w_c_f, self.w_c_o], dim=0)
-        b = torch.cat([self.b_i, self.b_f, self.b_c, self.b_o], dim=0)
-        return self._assemble(Px, bx, Ph, bh, wc, b, in_pad, ln, variants, ops.GradAcc())
-
-    def _pack_multi(self, names):
-        """Per layer ([W segments], We (8, C, 2), accumulator) for ops.multi_conv: the eight stacks run layer by layer, stack g =
-        head g in the order conv_x_{i,f,c,o}, conv_h_{i,f,c,o}.  Layer 0 has two input segments (X and H: the four stacks of a
-        branch share their input, so their projections are ONE matrix with 4 x 4C columns), deeper layers one (head g reads column
-        block g of the previous layer's output)."""
-        layers = []
-        for l in range(self.n_conv_layers):
-            convs = [getattr(self, n).convolutions[l] for n in names]
-            if l == 0:
-                Ws, Wes = [], []
-                for part in (convs[:4], convs[4:]):
-                    W, We = TransformerConv.stack_proj(part)                    # (4, cin_p + 4, 4C)
-                    Ws.append(W.permute(1, 0, 2).reshape(1, W.shape[1], 4 * W.shape[2]))
-                    Wes.append(We)
-                layers.append((Ws, torch.cat(Wes, dim=0), ops.GradAcc()))
-            else:
-                W, We = TransformerConv.stack_proj(convs)                       # (8, C + 4, 4C)
-                layers.append(([W], We, ops.GradAcc()))
-        return layers
-
-    # -- packing through one gather (ops.PackPlan): plain ChebConv stacks, and TransformerConv stacks on the layer-by-layer path ----
     @property
-    def _attention_plan(self):
-        return (_ATTN_PLAN and _MULTI_CONV and self.out_channels % 4 == 0 and
-                all(type(c) is TransformerConv for g in self.GATES for br in ('conv_x', 'conv_h')
-                    for c in getattr(self, f'{br}_{g}').convolutions))
+    def _layer_by_layer(self):
+        """True when the eight TransformerConv stacks run layer by layer (ops.multi_conv); else attention stacks (MHTransformerConv
+        ones always) run one convolution after another."""
+        return _MULTI_CONV and self.out_channels % 4 == 0 and type(self.conv_x_i.convolutions[0]) is TransformerConv
 
     @property
     def plannable(self):
-        return self._attention_plan or all(type(c) is ChebConv and c.bias is not None for g in self.GATES for br in ('conv_x', 'conv_h')
-                                           for c in getattr(self, f'{br}_{g}').convolutions)
+        return (_ATTN_PLAN and self._layer_by_layer) or all(type(c) is ChebConv and c.bias is not None for c in self._convs())
+
+    def _convs(self):
+        """The convolutions in module order: branch (conv_x, conv_h), gate, layer."""
+        return [c for br in ('conv_x', 'conv_h') for g in self.GATES for c in getattr(self, f'{br}_{g}').convolutions]
 
     def plan_params(self):
-        ps = []
-        for br in ('conv_x', 'conv_h'):
-            for g in self.GATES:
-                for conv in getattr(self, f'{br}_{g}').convolutions:
-                    ps += conv.plan_params()
-        return ps + [self.w_c_i, self.w_c_f, self.w_c_o, self.b_i, self.b_f, self.b_c, self.b_o]
+        """The parameters plan_layout reads, in module order (none of the convolutions that pack_from packs one by one)."""
+        convs = self._convs() if self.is_series or self._layer_by_layer else []
+        return [p for c in convs for p in c.plan_params()] + [self.w_c_i, self.w_c_f, self.w_c_o, self.b_i, self.b_f, self.b_c, self.b_o]
 
-    def _plan_layout_attention(self, T, fill, prefix):
-        """The matrices of _pack_multi from stand-ins: M0x / M0h (1, cin_p + 4, 4 x 4C) and E0 (8, C, 2) for layer 0, M<l> (8, C + 4,
-        4C) and E<l> for the deeper layers; wc (3, h), b (4, h)."""
-        L, h, per = self.n_conv_layers, self.out_channels, 9
-        conv = lambda bi, gi, l: T[((bi * 4 + gi) * L + l) * per:((bi * 4 + gi) * L + l + 1) * per]
-        tail = T[2 * 4 * L * per:]
-        out = {prefix + 'wc': torch.cat(tail[0:3], dim=0), prefix + 'b': torch.cat(tail[3:7], dim=0)}
-        for l in range(L):
-            if l == 0:
-                Wes = []
-                for bi, br in enumerate('xh'):
-                    W, We = TransformerConv.proj_layout([conv(bi, gi, 0) for gi in range(4)], self.in_channels if bi == 0 else h, h, fill)
-                    out[f'{prefix}M0{br}'] = W.permute(1, 0, 2).reshape(1, W.shape[1], 4 * W.shape[2])
-                    Wes.append(We)
-                out[prefix + 'E0'] = torch.cat(Wes, dim=0)
-            else:
-                W, We = TransformerConv.proj_layout([conv(bi, gi, l) for bi in range(2) for gi in range(4)], h, h, fill)
-                out[f'{prefix}M{l}'], out[f'{prefix}E{l}'] = W, We
-        return out
+    def pack(self, in_pad=None, ln=None, variants=(True,)):
+        """One PackedCell per requested variant (with_h True / False); the variants share the peephole / bias tensors and their
+        gradient accumulator.  W: ((K*C + Ks_padded), 4h) for Z = [X (padded to in_pad) | H].  plan_layout evaluated on the
+        parameters themselves; stacked series compose with torch ops, on the GPU as well."""
+        outs = ops.pack_direct(self.plan_params(), lambda T, fill: self.plan_layout(T, fill, '', in_pad, variants))
+        return self.pack_from(outs, '', in_pad, ln, variants, device_compose=False)
 
     def plan_layout(self, T, fill, prefix, in_pad=None, variants=(True,)):
-        """Outputs (named with `prefix`): wc (3, h), b (4, h) and, for one conv layer per stack, the gate matrix W of
-        every requested variant as (x-bias member, h-bias member) sums; for deeper stacks the per-layer weight / bias
-        stacks of both branches, which compose_chebconvs then combines."""
-        if self._attention_plan:
-            return self._plan_layout_attention(T, fill, prefix)
+        """Outputs (named with `prefix`) from plan_params() or stand-ins of them: wc (3, h), b (4, h) and
+        - layer-by-layer attention stacks: M0x / M0h (1, cin_p + 4, 4 x 4C) and E0 (8, C, 2) for layer 0, M<l> (8, C + 4, 4C) and
+          E<l> for the deeper layers -- stack g = head g in the order conv_x_{i,f,c,o}, conv_h_{i,f,c,o}.  Layer 0 has two input
+          segments (X and H: the four stacks of a branch share their input, so their projections are ONE matrix with 4 x 4C
+          columns), deeper layers one (head g reads column block g of the previous layer's output);
+        - series, one conv layer per stack: the gate matrix W of every requested variant as (x-bias member, h-bias member) sums;
+        - deeper series: the per-layer weight / bias stacks of both branches, which pack_from composes;
+        - other attention stacks: nothing more (pack_from packs them per convolution)."""
         L, h = self.n_conv_layers, self.out_channels
-        K = len(self.conv_x_i.convolutions[0].lins)
-        per = K + 1
+        per = (len(T) - 7) // (8 * L)
+        conv = lambda bi, gi, l: T[((bi * 4 + gi) * L + l) * per:((bi * 4 + gi) * L + l + 1) * per]
+        out = {prefix + 'wc': torch.cat(T[-7:-4], dim=0), prefix + 'b': torch.cat(T[-4:], dim=0)}
+        if self._layer_by_layer:
+            for l in range(L):
+                if l == 0:
+                    Wes = []
+                    for bi, br in enumerate('xh'):
+                        W, We = TransformerConv.proj_layout([conv(bi, gi, 0) for gi in range(4)], self.in_channels if bi == 0 else h, h, fill)
+                        out[f'{prefix}M0{br}'] = W.permute(1, 0, 2).reshape(1, W.shape[1], 4 * W.shape[2])
+                        Wes.append(We)
+                    out[prefix + 'E0'] = torch.cat(Wes, dim=0)
+                else:
+                    W, We = TransformerConv.proj_layout([conv(bi, gi, l) for bi in range(2) for gi in range(4)], h, h, fill)
+                    out[f'{prefix}M{l}'], out[f'{prefix}E{l}'] = W, We
+            return out
+        if not self.is_series:
+            return out
+        cs = self._convs()
 
         def Wt(bi, l):       # (4, K, in, h)
-            w = torch.stack([T[((bi * 4 + gi) * L + l) * per + k] for gi in range(4) for k in range(K)])
-            return w.view(4, K, *w.shape[1:]).transpose(-1, -2)
+            return torch.stack([cs[(bi * 4 + gi) * L + l].cheb_coeffs(conv(bi, gi, l)) for gi in range(4)])
 
         def Bs(bi, l):       # (4, h)
-            return torch.stack([T[((bi * 4 + gi) * L + l) * per + K] for gi in range(4)])
+            return torch.stack([conv(bi, gi, l)[-1] for gi in range(4)])
 
-        tail = T[2 * 4 * L * per:]
-        out = {prefix + 'wc': torch.cat(tail[0:3], dim=0), prefix + 'b': torch.cat(tail[3:7], dim=0)}
         if L > 1:
             for bi, br in enumerate('xh'):
                 for l in range(L):
@@ -578,27 +498,34 @@ class GConvLSTM(nn.Module):
         rows = lambda bs: nn.functional.pad(bs.unsqueeze(1).permute(1, 0, 2).reshape(1, 4 * h), (0, 0, 0, 3), value=fill)
         for with_h in variants:
             M = torch.cat([Px, Ph], dim=2) if with_h else Px
-            Wm = M.permute(1, 2, 0, 3).reshape(K * M.shape[2], 4 * h)
+            Wm = M.permute(1, 2, 0, 3).reshape(Px.shape[1] * M.shape[2], 4 * h)
             out[f'{prefix}W{int(with_h)}'] = (torch.cat([Wm, rows(Bs(0, 0))], dim=0),
                                               torch.cat([torch.full_like(Wm, fill), rows(Bs(1, 0))], dim=0))
         return out
 
-    def pack_from(self, outs, prefix, in_pad=None, ln=None, variants=(True,)):
-        """PackedCells from the outputs of a plan built with plan_layout (same arguments)."""
+    def pack_from(self, outs, prefix, in_pad=None, ln=None, variants=(True,), device_compose=True):
+        """PackedCells from the outputs of plan_layout (same arguments), gathered by a plan or evaluated directly.  device_compose:
+        stacked series whose matrices are on the GPU compose there, one launch per product (ops.compose_pack); False: with torch
+        ops everywhere (ops.compose_chebconvs + _assemble, the reference implementation of that composition)."""
         L, h = self.n_conv_layers, self.out_channels
         wc, b = outs[prefix + 'wc'], outs[prefix + 'b']
         acc_p = ops.GradAcc()
-        if self._attention_plan:
-            multi = [([outs[prefix + 'M0x'], outs[prefix + 'M0h']] if l == 0 else [outs[f'{prefix}M{l}']], outs[f'{prefix}E{l}'], ops.GradAcc())
-                     for l in range(L)]
+        if not self.is_series:
+            multi = convs = None
+            if self._layer_by_layer:
+                multi = [([outs[prefix + 'M0x'], outs[prefix + 'M0h']] if l == 0 else [outs[f'{prefix}M{l}']], outs[f'{prefix}E{l}'],
+                          ops.GradAcc()) for l in range(L)]
+            else:       # all convolutions of the cell packed together (pack_many), handed out per stack and layer
+                packed = iter(type(self.conv_x_i.convolutions[0]).pack_many(self._convs()))
+                convs = {f'{br}_{g}': [next(packed) for _ in range(L)] for br in ('conv_x', 'conv_h') for g in self.GATES}
             cells = [PackedCell(None, 0, 0, wc, b, ln, None, acc_p) for _ in variants]
-            for c in cells:
-                c.multi = multi
+            for c in cells:             # the variants share the packed convolutions (and their accumulators)
+                c.multi, c.convs = multi, convs
             return cells
         if L == 1:
-            K = len(self.conv_x_i.convolutions[0].lins)
+            K = self.conv_x_i.convolutions[0].K
             return [PackedCell(outs[f'{prefix}W{int(v)}'], K, 1, wc, b, ln, ops.GradAcc(), acc_p) for v in variants]
-        if wc.is_cuda:           # composition and layout on the device: one launch per product (ops.compose_pack)
+        if device_compose and wc.is_cuda:
             stacks = [[outs[f'{prefix}{n}{br}{l}'] for l in range(L)] for n, br in (('P', 'x'), ('B', 'x'), ('P', 'h'), ('B', 'h'))]
             Ws, WTs, Kc, Ksc = ops.compose_pack(*stacks, in_pad or self.in_channels, variants)
             cells = []

@@ -11,7 +11,7 @@ import torch
 import torch.nn as nn
 
 from model.graph_functions import Graph, _criterion
-from model.model import CONVOLUTION_KWARGS, GConvLSTM, _conv_class, _need_mesh
+from model.model import CONVOLUTION_KWARGS, ChebConv, GConvLSTM, PackedConv, TransformerConv, _conv_class, _need_mesh
 from qtmpnn import ops
 from qtmpnn._lib import on_device
 from qtmpnn.flat import flat_params, param_list
@@ -21,15 +21,33 @@ from qtmpnn.mesh import build_mesh, build_pixel_mesh, host_mask
 _PROJECT_FC2 = __import__('os').environ.get('QT_NO_PROJECT_FC2') != '1'      # (A/B switch, diagnostics)
 
 
-def _ln_params(*norms):
-    return torch.stack([p for n in norms for p in (n.weight, n.bias)])
-
-
 def _raise_on_nan(t, what):
     """image_to_graph's ValueError (graph_functions.py:626-627, 654-655) on the hot path's own tensors (one device sync)."""
     bad = torch.isnan(t)
     if bool(bad.any()):
         raise ValueError(f'Found NaNs in {what} data {int(bad.sum())} / {t.numel()}')
+
+
+def _pack_planned(module, key, params, spec, flat=None):
+    """finish(outs) of (layout, finish) = spec() with outs from ONE gather of `params` (ops.PackPlan, cached on the module per
+    key; a re-assigned Parameter or another flat buffer invalidates the plan).  flat: see ops.PackPlan."""
+    plans = module.__dict__.setdefault('_plans', {})
+    plan = plans.get(key)
+    if plan is None or not plan.same_params(params) or plan.flat is not flat:
+        layout, finish = spec()
+        plan = plans[key] = ops.PackPlan(params, layout, flat=flat)
+        plan.finish = finish            # (the closure depends on the module and the input width only: kept with the plan)
+    return plan.finish(plan())
+
+
+def _pack(module, in_pad):
+    """The weight pack of an Encoder / Decoder for one forward pass: finish(outs) of its plan_spec, with outs from one parameter
+    gather (cached per input width) when every layer is plannable, else from the same layout evaluated on the parameters
+    themselves (stacked series then compose with torch ops)."""
+    params, layout, finish = module.plan_spec(in_pad, device_compose=module.plannable)
+    if module.plannable:
+        return _pack_planned(module, (in_pad, params[0].device), params, lambda: (layout, finish))
+    return finish(ops.pack_direct(params, layout))
 
 
 class _NoCachesInPickle:
@@ -67,18 +85,14 @@ class Encoder(_NoCachesInPickle, nn.Module):
 
     def pack(self, in_pad):
         """Per-forward weight packing: layer 0 with and without a hidden state, upper layers without."""
-        if self.plannable:
-            return self._pack_planned(in_pad)
-        ln = _ln_params(self.norm_h, self.norm_c)
-        first, cont = self.rnns[0].pack(in_pad, ln, (False, True))
-        return dict(first=first, cont=cont, upper=[r.pack(None, ln, (False,))[0] for r in self.rnns[1:]])
+        return _pack(self, in_pad)
 
-    def plan_spec(self, in_pad):
-        """(params, layout, finish) of the encoder's weight packing as ONE parameter gather (ops.PackPlan): `layout` maps
-        stand-ins of the parameters to the packed matrices, `finish(outs)` turns the gathered matrices into the pack."""
-        params = [p for r in self.rnns for p in r.plan_params()] + [self.norm_h.weight, self.norm_h.bias,
-                                                                    self.norm_c.weight, self.norm_c.bias]
-        counts = [len(r.plan_params()) for r in self.rnns]
+    def plan_spec(self, in_pad, device_compose=True):
+        """(params, layout, finish) of the encoder's weight packing: `layout` maps the parameters (or stand-ins of them,
+        ops.PackPlan) to the packed matrices, `finish(outs)` turns those matrices into the pack."""
+        cells = [r.plan_params() for r in self.rnns]
+        params = [p for ps in cells for p in ps] + [self.norm_h.weight, self.norm_h.bias, self.norm_c.weight, self.norm_c.bias]
+        counts = [len(ps) for ps in cells]
 
         def layout(T, fill):
             out, o = {}, 0
@@ -91,19 +105,10 @@ class Encoder(_NoCachesInPickle, nn.Module):
 
         def finish(outs):
             ln = outs['ln']
-            first, cont = self.rnns[0].pack_from(outs, 'r0.', in_pad, ln, (False, True))
-            return dict(first=first, cont=cont,
-                        upper=[r.pack_from(outs, f'r{i + 1}.', None, ln, (False,))[0] for i, r in enumerate(self.rnns[1:])])
+            first, cont = self.rnns[0].pack_from(outs, 'r0.', in_pad, ln, (False, True), device_compose)
+            return dict(first=first, cont=cont, upper=[r.pack_from(outs, f'r{i + 1}.', None, ln, (False,), device_compose)[0]
+                                                       for i, r in enumerate(self.rnns[1:])])
         return params, layout, finish
-
-    def _pack_planned(self, in_pad):
-        """The same through ONE parameter gather for the whole encoder (ops.PackPlan, cached per input width)."""
-        plans = self.__dict__.setdefault('_plans', {})
-        key = (in_pad, self.norm_h.weight.device)
-        params, layout, finish = self.plan_spec(in_pad)
-        if key not in plans or not plans[key].same_params(params):       # (a re-assigned Parameter invalidates the plan)
-            plans[key] = ops.PackPlan(params, layout)
-        return finish(plans[key]())
 
     def run(self, X, mesh, H, C, pk):
         """One encoder step on packed weights; returns per-layer lists (no stacking on the hot path)."""
@@ -153,52 +158,40 @@ class Decoder(_NoCachesInPickle, nn.Module):
         return self.hidden_size + 4          # [relu(norm_o(O)) | concat | 0 0 0] keeps rows 16-byte aligned
 
     def pack(self, in_pad):
-        if self.plannable:
-            return self._pack_planned(in_pad)
-        ln = _ln_params(self.norm_h, self.norm_c)
-        series = hasattr(self.fc_out1, 'packed')
-        heads = None
-        if hasattr(type(self.fc_out1), 'pack_many'):        # attention head: both convolutions packed once per pass, not per step
-            heads = type(self.fc_out1).pack_many([self.fc_out1, self.fc_out2])
-        return dict(ln_o=_ln_params(self.norm_o), acc_o=ops.GradAcc(), heads=heads,
-                    rnns=[r.pack(in_pad if i == 0 else None, ln, (True,))[0] for i, r in enumerate(self.rnns)],
-                    fc1=self.fc_out1.packed(self.head_width, self.hidden_size) if series else None, acc1=ops.GradAcc(),
-                    fc2=self.fc_out2.packed(self.hidden_size, 4) if series else None, acc2=ops.GradAcc())
+        return _pack(self, in_pad)
 
     @property
     def plannable(self):
-        from model.model import ChebConv, TransformerConv
         return all(r.plannable for r in self.rnns) and any(type(self.fc_out1) is cls and type(self.fc_out2) is cls
                                                            for cls in (ChebConv, TransformerConv))
 
-    def plan_spec(self, in_pad):
-        """(params, layout, finish) of the decoder's weight packing as one parameter gather (see Encoder.plan_spec)."""
-        params = ([p for r in self.rnns for p in r.plan_params()] + self.fc_out1.plan_params() + self.fc_out2.plan_params()
-                  + [self.norm_h.weight, self.norm_h.bias, self.norm_c.weight, self.norm_c.bias,
-                     self.norm_o.weight, self.norm_o.bias])
-        counts = [len(r.plan_params()) for r in self.rnns]
-        n1, n2 = len(self.fc_out1.plan_params()), len(self.fc_out2.plan_params())
+    def plan_spec(self, in_pad, device_compose=True):
+        """(params, layout, finish) of the decoder's weight packing (see Encoder.plan_spec)."""
+        cells, p1, p2 = [r.plan_params() for r in self.rnns], self.fc_out1.plan_params(), self.fc_out2.plan_params()
+        params = ([p for ps in cells for p in ps] + p1 + p2 + [self.norm_h.weight, self.norm_h.bias, self.norm_c.weight,
+                                                                self.norm_c.bias, self.norm_o.weight, self.norm_o.bias])
+        counts, n1, n2 = [len(ps) for ps in cells], len(p1), len(p2)
 
         def layout(T, fill):
             out, o = {}, 0
             for i, (r, n) in enumerate(zip(self.rnns, counts)):
                 out.update(r.plan_layout(T[o:o + n], fill, f'r{i}.', in_pad if i == 0 else None, (True,)))
                 o += n
-            if hasattr(type(self.fc_out1), 'proj_layout'):          # attention head: the two convolutions' [q | k | v | skip] matrices
+            if isinstance(self.fc_out1, TransformerConv):           # attention head: the two convolutions' [q | k | v | skip] matrices
                 for nm, conv, n in (('h1', self.fc_out1, n1), ('h2', self.fc_out2, n2)):
-                    W, We = type(conv).proj_layout([T[o:o + n]], conv.in_channels, conv.out_channels, fill)
+                    W, We = conv.proj_layout([T[o:o + n]], conv.in_channels, conv.out_channels, fill)
                     out[nm + 'W'], out[nm + 'E'] = W[0], We[0]
                     o += n
-                out['ln'] = torch.stack(T[o:o + 4])
-                out['ln_o'] = torch.stack(T[o + 4:o + 6])
-                return out
-            out['fc1'] = self.fc_out1.plan_layout(T[o:o + n1], fill, self.head_width, self.hidden_size)
-            o += n1
-            if _PROJECT_FC2 and self.fc_out2.K == 3:
-                out['fc2c'] = self.fc_out2.plan_layout_projected(T[o:o + n2], fill)
-            else:
-                out['fc2'] = self.fc_out2.plan_layout(T[o:o + n2], fill, self.hidden_size, 4)
-            o += n2
+            elif isinstance(self.fc_out1, ChebConv):
+                out['fc1'] = self.fc_out1.plan_layout(T[o:o + n1], fill, self.head_width, self.hidden_size)
+                o += n1
+                if _PROJECT_FC2 and self.fc_out2.K == 3:
+                    out['fc2c'] = self.fc_out2.plan_layout_projected(T[o:o + n2], fill)
+                else:
+                    out['fc2'] = self.fc_out2.plan_layout(T[o:o + n2], fill, self.hidden_size, 4)
+                o += n2
+            else:                                                   # (other attention heads: finish packs them per convolution)
+                o += n1 + n2
             out['ln'] = torch.stack(T[o:o + 4])
             out['ln_o'] = torch.stack(T[o + 4:o + 6])
             return out
@@ -207,22 +200,14 @@ class Decoder(_NoCachesInPickle, nn.Module):
             ln = outs['ln']
             heads = None
             if 'h1W' in outs:
-                from model.model import PackedConv
-                heads = [PackedConv(outs[nm + 'W'], outs[nm + 'E'], ops.GradAcc(), ops.GradAcc()) for nm in ('h1', 'h2')]
+                heads = [PackedConv(outs[nm + 'W'], outs[nm + 'E']) for nm in ('h1', 'h2')]
+            elif 'fc1' not in outs:                                 # both convolutions packed once per pass, not per step
+                heads = type(self.fc_out1).pack_many([self.fc_out1, self.fc_out2])
             return dict(ln_o=outs['ln_o'], acc_o=ops.GradAcc(), heads=heads,
-                        rnns=[r.pack_from(outs, f'r{i}.', in_pad if i == 0 else None, ln, (True,))[0]
+                        rnns=[r.pack_from(outs, f'r{i}.', in_pad if i == 0 else None, ln, (True,), device_compose)[0]
                               for i, r in enumerate(self.rnns)],
                         fc1=outs.get('fc1'), acc1=ops.GradAcc(), fc2=outs.get('fc2'), fc2c=outs.get('fc2c'), acc2=ops.GradAcc())
         return params, layout, finish
-
-    def _pack_planned(self, in_pad):
-        """The same through ONE parameter gather for the whole decoder (ops.PackPlan, cached per input width)."""
-        plans = self.__dict__.setdefault('_plans', {})
-        key = (in_pad, self.norm_h.weight.device)
-        params, layout, finish = self.plan_spec(in_pad)
-        if key not in plans or not plans[key].same_params(params):
-            plans[key] = ops.PackPlan(params, layout)
-        return finish(plans[key]())
 
     def dropout_masks(self, steps, rows, device):
         """Inverted-dropout multipliers for `steps` decoder steps at once (one RNG launch instead of one per step);
@@ -355,12 +340,9 @@ class Seq2Seq(_NoCachesInPickle, nn.Module):
         if not (self.encoder.plannable and self.decoder.plannable):
             return self.encoder.pack(enc_in_pad), None          # the decoder packs itself when the rollout starts
         params = param_list(self)
-        fp = flat_params(self) if params[0].is_cuda else None
-        plans = self.__dict__.setdefault('_plans', {})
-        key = (enc_in_pad, params[0].device)
-        if key not in plans or not plans[key].same_params(params) or plans[key].flat is not fp:
-            ep, el, ef = self.encoder.plan_spec(enc_in_pad)
-            dp, dl, df = self.decoder.plan_spec(4)
+
+        def spec():
+            (ep, el, ef), (dp, dl, df) = self.encoder.plan_spec(enc_in_pad), self.decoder.plan_spec(4)
             pos = {id(p): i for i, p in enumerate(params)}
             ei, di = [pos[id(p)] for p in ep], [pos[id(p)] for p in dp]
 
@@ -368,12 +350,12 @@ class Seq2Seq(_NoCachesInPickle, nn.Module):
                 out = {'e.' + k: v for k, v in el([T[i] for i in ei], fill).items()}
                 out.update({'d.' + k: v for k, v in dl([T[i] for i in di], fill).items()})
                 return out
-            plans[key] = ops.PackPlan(params, layout, flat=fp)
-            plans[key].finish = (ef, df)        # (the closures depend on the modules and the input width only: kept with the plan)
-        ef, df = plans[key].finish
-        outs = plans[key]()
-        return (ef({k[2:]: v for k, v in outs.items() if k.startswith('e.')}),
-                df({k[2:]: v for k, v in outs.items() if k.startswith('d.')}))
+
+            def finish(outs):
+                return (ef({k[2:]: v for k, v in outs.items() if k.startswith('e.')}),
+                        df({k[2:]: v for k, v in outs.items() if k.startswith('d.')}))
+            return layout, finish
+        return _pack_planned(self, (enc_in_pad, params[0].device), params, spec, flat_params(self) if params[0].is_cuda else None)
 
     # -- mesh helpers -----------------------------------------------------------------
     def _mesh_from_image(self, img0, mask, hir, tiles=None):

@@ -123,7 +123,9 @@ class PackPlan:
     with `fill`); a tuple means the sum of its two members.  The plan records, for every output element, which parameter
     elements it is made of; the forward is then `flat[src0] + flat[src1]` on the concatenated parameters and the backward
     the transposed gather, whose result is handed to autograd as per-parameter views (no stack / unbind / slice
-    backward / AccumulateGrad copies: ~200 tiny kernels per training step with per-tensor torch ops)."""
+    backward / AccumulateGrad copies: ~200 tiny kernels per training step with per-tensor torch ops).
+    The same layout functions, evaluated on the parameters themselves (pack_direct), are the direct path of the modules no
+    plan covers: every packed matrix has ONE definition."""
 
     def __init__(self, params, layout, flat=None):
         self.params = list(params)
@@ -174,6 +176,12 @@ class PackPlan:
     def __call__(self):
         outs = _PackGather.apply(self, *self.params)
         return dict(zip(self.names, outs))
+
+
+def pack_direct(params, layout):
+    """What PackPlan(params, layout)() returns, computed by evaluating `layout` on the parameters themselves with zero padding;
+    ordinary autograd carries the backward."""
+    return {name: v[0] + unalias(v[1]) if isinstance(v, tuple) else v for name, v in layout(list(params), 0.0).items()}
 
 
 class _PackGather(Function):

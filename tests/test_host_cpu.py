@@ -221,8 +221,9 @@ def test_gate_rows_at_maxq_accepted_and_next_channel_step_refused(conv, h, nc, c
 
 @pytest.mark.parametrize('n_conv', [1, 2])
 def test_pack_plan_equals_per_tensor_packing(n_conv):
-    """ops.PackPlan (one gather of all parameters through recorded index maps) == the per-tensor stack / cat packing,
-    values and every parameter gradient; also the ChebConv head matrix with padding."""
+    """ops.PackPlan (one gather of all parameters through recorded index maps) == the same layout evaluated on the parameters
+    themselves (ops.pack_direct behind cell.pack / conv.packed), values and every parameter gradient; also the ChebConv head matrix
+    with padding.  What the layouts must contain is stated by the test_*_layout_* tests below."""
     import torch
     from model.model import ChebConv, GConvLSTM
     from qtmpnn import ops
@@ -255,8 +256,8 @@ def test_pack_plan_equals_per_tensor_packing(n_conv):
 
 
 def test_pack_plan_of_attention_models_equals_per_tensor_packing():
-    """TransformerConv cells and the attention decoder head through ops.PackPlan: the layer-by-layer matrices of
-    GConvLSTM._pack_multi / TransformerConv.pack_many bit for bit, and every parameter gradient (hidden 8 -> padded planes,
+    """TransformerConv cells and the attention decoder head through ops.PackPlan: the layer-by-layer matrices of the direct
+    evaluation (GConvLSTM.pack / TransformerConv.pack_many) bit for bit, and every parameter gradient (hidden 8 -> padded planes,
     6 input channels -> padded rows)."""
     import torch
     from model.model import GConvLSTM, TransformerConv
@@ -267,8 +268,7 @@ def test_pack_plan_of_attention_models_equals_per_tensor_packing():
     for p in cell.parameters():
         p.data.normal_()
     assert cell.plannable
-    names = [f'{br}_{g}' for br in ('conv_x', 'conv_h') for g in cell.GATES]
-    ref = cell._pack_multi(names)
+    ref = cell.pack(None, None, (False,))[0].multi
     params = cell.plan_params()
     assert len(params) == len(list(cell.parameters()))
     plan = ops.PackPlan(params, lambda T, fill: cell.plan_layout(T, fill, 'r.'))
@@ -291,6 +291,102 @@ def test_pack_plan_of_attention_models_equals_per_tensor_packing():
     assert pk['fc1'] is None and pk['fc2'] is None
     for a, b in zip(TransformerConv.pack_many([dec.fc_out1, dec.fc_out2]), pk['heads']):
         assert torch.equal(a.W, b.W) and torch.equal(a.We, b.We)
+
+
+def _randomised(module):
+    torch.manual_seed(3)
+    for p in module.parameters():
+        p.data.normal_()
+    return module
+
+
+@pytest.mark.parametrize('bias', [True, False])
+def test_chebconv_layout_stated_by_indexing(bias):
+    """ChebConv.packed with input and output padding: rows [k][in_pad channels], then the bias row and three zero rows."""
+    from model.model import ChebConv
+    conv = _randomised(ChebConv(5, 6, K=3, bias=bias))
+    want = torch.zeros(3 * 8 + 4, 8)
+    for k in range(3):
+        want[k * 8:k * 8 + 5, :6] = conv.lins[k].weight.t()
+    if bias:
+        want[24, :6] = conv.bias
+    assert torch.equal(conv.packed(8, 8), want)
+    assert torch.equal(conv.packed(), torch.cat([want[r:r + 5, :6] for r in (0, 8, 16)] + [want[24:, :6]]))
+
+
+def test_gcnconv_layout_stated_by_indexing():
+    """GCNConv as the Chebyshev series [0, -W^T]: order 0 is zero, order 1 the negated transposed weight."""
+    from model.model import GCNConv
+    conv = _randomised(GCNConv(5, 6))
+    want = torch.zeros(2 * 8 + 4, 8)
+    want[8:13, :6] = -conv.lin.weight.t()
+    want[16, :6] = conv.bias
+    assert torch.equal(conv.packed(8, 8), want)
+
+
+def _proj_want(conv, cin_p, cp):
+    """[q | k | v | skip] of one TransformerConv: (cin_p + 4, 4 cp), weights transposed, the bias row at cin_p, zeros elsewhere."""
+    cin, cout = conv.in_channels, conv.out_channels
+    want = torch.zeros(cin_p + 4, 4 * cp)
+    for j, lin in enumerate((conv.lin_query, conv.lin_key, conv.lin_value, conv.lin_skip)):
+        want[:cin, j * cp:j * cp + cout] = lin.weight.t()
+        want[cin_p, j * cp:j * cp + cout] = lin.bias
+    return want
+
+
+def test_transformerconv_layout_stated_by_indexing():
+    """TransformerConv.pack / pack_many for 6 -> 10 channels (both pad: rows to 8, column blocks to 12)."""
+    from model.model import TransformerConv
+    conv, other = _randomised(TransformerConv(6, 10)), _randomised(TransformerConv(8, 8))
+    want_e = torch.zeros(12, 2)
+    want_e[:10] = conv.lin_edge.weight
+    for pc in (conv.pack(), TransformerConv.pack_many([other, conv])[1]):
+        assert torch.equal(pc.W, _proj_want(conv, 8, 12)) and torch.equal(pc.We, want_e)
+
+
+def test_attention_cell_layout_stated_by_indexing():
+    """The layer-by-layer matrices of a TransformerConv cell (hidden 8, three layers, six inputs): layer 0 = the four x stacks side by
+    side on X's rows and the four h stacks side by side on H's rows, deeper layers one matrix per stack; stack order conv_x_{i,f,c,o},
+    conv_h_{i,f,c,o}."""
+    from model.model import GConvLSTM
+    cell = _randomised(GConvLSTM(6, 8, n_conv_layers=3, convolution_type='TransformerConv'))
+    pk = cell.pack(None, None, (True,))[0]
+    stacks = [getattr(cell, f'{br}_{g}').convolutions for br in ('conv_x', 'conv_h') for g in 'ifco']
+    (M0x, M0h), E0, _ = pk.multi[0]
+    assert torch.equal(M0x, torch.cat([_proj_want(st[0], 8, 8) for st in stacks[:4]], dim=1).unsqueeze(0))      # (1, 8 + 4, 4 x 32)
+    assert torch.equal(M0h, torch.cat([_proj_want(st[0], 8, 8) for st in stacks[4:]], dim=1).unsqueeze(0))
+    assert torch.equal(E0, torch.stack([st[0].lin_edge.weight for st in stacks]))
+    for l in (1, 2):
+        (M,), E, _ = pk.multi[l]
+        assert torch.equal(M, torch.stack([_proj_want(st[l], 8, 8) for st in stacks]))                            # (8, 8 + 4, 32)
+        assert torch.equal(E, torch.stack([st[l].lin_edge.weight for st in stacks]))
+    assert torch.equal(pk.wc, torch.cat([cell.w_c_i, cell.w_c_f, cell.w_c_o])) and torch.equal(pk.b, torch.cat([cell.b_i, cell.b_f, cell.b_c, cell.b_o]))
+
+
+@pytest.mark.parametrize('conv_type', ['ChebConv', 'GCNConv'])
+def test_single_layer_gate_matrix_stated_by_indexing(conv_type):
+    """The gate matrix of a cell with one conv layer per stack, 5 inputs padded to 8, hidden 8: rows [k][x channels | h channels]
+    (x channels only without a hidden state), columns gate-major i, f, c, o; the bias row is b_x + b_h in BOTH variants
+    (conv_h(0) is its bias), the three rows below it are zero."""
+    from model.model import GConvLSTM
+    cell = _randomised(GConvLSTM(5, 8, n_conv_layers=1, convolution_type=conv_type))
+    no_h, with_h = cell.pack(8, None, (False, True))
+
+    def coeffs(conv):       # (K, in, out)
+        if conv_type == 'GCNConv':
+            return [torch.zeros(conv.in_channels, 8), -conv.lin.weight.t()]
+        return [lin.weight.t() for lin in conv.lins]
+    K = 2 if conv_type == 'GCNConv' else 3
+    want1, want0 = torch.zeros(K * 16 + 4, 32), torch.zeros(K * 8 + 4, 32)
+    for gi, g in enumerate('ifco'):
+        cx, ch = getattr(cell, f'conv_x_{g}').convolutions[0], getattr(cell, f'conv_h_{g}').convolutions[0]
+        for k in range(K):
+            want1[k * 16:k * 16 + 5, gi * 8:gi * 8 + 8] = coeffs(cx)[k]
+            want1[k * 16 + 8:k * 16 + 16, gi * 8:gi * 8 + 8] = coeffs(ch)[k]
+            want0[k * 8:k * 8 + 5, gi * 8:gi * 8 + 8] = coeffs(cx)[k]
+        want1[K * 16, gi * 8:gi * 8 + 8] = want0[K * 8, gi * 8:gi * 8 + 8] = cx.bias + ch.bias
+    assert (with_h.K, with_h.Ks, no_h.K, no_h.Ks) == (K, 1, K, 1)
+    assert torch.equal(with_h.W, want1) and torch.equal(no_h.W, want0)
 
 
 def test_model_with_cached_plans_pickles_and_copies():
