@@ -66,14 +66,9 @@ struct AttnArgs {
 };
 
 // per-head views of the operands (head = blockIdx.y; a single convolution is head 0 of 1)
-#ifndef QT_ATTN_DESC
-#define QT_ATTN_DESC 3      // bit 0 / 1 / 2: the forward / target / source pass walks the heads from the last to the first
-#endif
+static constexpr int QT_ATTN_DESC = 3;      // bit 0 / 1 / 2: the forward / target / source pass walks the heads from the last to the first
 template <int PASS>
 __device__ __forceinline__ int head_setup(AttnArgs& a) {
-#ifdef QT_ATTN_HEADS_ASCENDING
-    const int hd = blockIdx.y;
-#else
     if (!((QT_ATTN_DESC >> PASS) & 1)) {
         const int hd0 = blockIdx.y;
         if (hd0) {
@@ -90,7 +85,6 @@ __device__ __forceinline__ int head_setup(AttnArgs& a) {
     // gradient after it takes its groups 7..0 (qt_proj_group, reverse).  cfg4t: 47.1 ms per step with every launch ascending,
     // 46.6 with the three passes descending, 46.2 with this order.
     const int hd = (int)gridDim.y - 1 - (int)blockIdx.y;
-#endif
     if (hd) {
         a.proj += hd * a.hs;
         a.We += (int64_t)hd * 2 * a.C;
@@ -137,15 +131,9 @@ __device__ __forceinline__ int xcd_block(int rows, int nodes_per_block) {
 #endif
 constexpr int EPT = QT_ATTN_EPT;
 // register budgets: waves per SIMD the forward / target / source kernels are compiled for (0 = the compiler's choice)
-#ifndef QT_ATTN_OCC_F
 #define QT_ATTN_OCC_F 0
-#endif
-#ifndef QT_ATTN_OCC_T
 #define QT_ATTN_OCC_T 0
-#endif
-#ifndef QT_ATTN_OCC_S
 #define QT_ATTN_OCC_S 0
-#endif
 #define QT_WAVES_ATTR_(n) __attribute__((amdgpu_waves_per_eu(n, n)))
 #define QT_WAVES_ATTR(n) QT_WAVES_ATTR_(n)
 #if QT_ATTN_OCC_F
@@ -163,9 +151,7 @@ constexpr int EPT = QT_ATTN_EPT;
 #else
 #define QT_ATTN_WAVES_S
 #endif
-#ifndef QT_ATTN_BS
-#define QT_ATTN_BS 64      // one wave per workgroup (forward 32.4 -> 31.0 us at the cfg4 shapes; 128: 31.3)
-#endif
+static constexpr int QT_ATTN_BS = 64;      // one wave per workgroup (forward 32.4 -> 31.0 us at the cfg4 shapes; 128: 31.3)
 // Addresses: the block bases (head, q / k / v / skip block) are uniform, so a row is reached as base + a 32-bit element offset
 // (one VGPR per address instead of a 64-bit pair; the host checks that a head's rows span < 2^31 floats).
 template <int LPN>
@@ -477,9 +463,7 @@ static int fill_args(AttnArgs* a, const int32_t* rowptr, const int32_t* col, con
 extern "C" int qt_attn_blocks(int N, int C) {
     if (N <= 0 || !c_ok(C)) return 0;
     const int need = qt_cdiv((int64_t)N * (C / 4), 256);
-#ifndef QT_ATTN_BLOCKS
-#define QT_ATTN_BLOCKS 4096
-#endif
+static constexpr int QT_ATTN_BLOCKS = 4096;
     return need < QT_ATTN_BLOCKS ? need : QT_ATTN_BLOCKS;     // (512 left two waves per SIMD for a gather-latency-bound sweep)
 }
 
@@ -542,13 +526,9 @@ extern "C" int qt_attn_bwd(const int32_t* rowptr, const int32_t* col, const floa
     a.ld_g = ld_g; a.accumulate = accumulate; a.rev = rev; a.coef = coef; a.E = E; a.ld_o = ld_o; a.gmod = gmod;
     a.ps = ps; a.hs = hs; a.hs_o = hs_o; a.hs_g = hs_g;
     const int grid = (qt_cdiv((int64_t)N * (C / 4), QT_ATTN_BS) + 7) & ~7;
-#if !defined(QT_EXP_ATTN_ONLY) || QT_EXP_ATTN_ONLY == 1       // (diagnostics builds time one pass alone)
     QT_ATTN_DISPATCH_BS(C, k_attn_bwd_target, dim3(grid, G), QT_ATTN_BS, stream, a, g, stats, out, gproj);
-#endif
     const int gridB = qt_attn_blocks(N, C);
-#if !defined(QT_EXP_ATTN_ONLY) || QT_EXP_ATTN_ONLY == 2
     QT_ATTN_DISPATCH(C, k_attn_bwd_source, dim3(gridB, G), stream, a, g, gproj, part);
-#endif
     QT_LAUNCHED();
     return QT_OK;
 }

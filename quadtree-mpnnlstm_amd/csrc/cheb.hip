@@ -24,10 +24,8 @@ struct SpmmPart {
     float* out;
     int C, ldx, ldp, ldq, xcd_chunk;      // row strides of x / p / q in floats (out rows are dense)
 };
+static constexpr int QT_SPMM_BS = 64;      // one wave per workgroup: 11.08 ms per training step against 11.12 (128) and 11.18 (256)
 template <int VEC, int RPT, int EPT>
-#ifndef QT_SPMM_BS
-#define QT_SPMM_BS 64      // one wave per workgroup: 11.08 ms per training step against 11.12 (128) and 11.18 (256)
-#endif
 __global__ __launch_bounds__(QT_SPMM_BS) void k_spmm(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
                                               const float* __restrict__ nrm, const int4* __restrict__ ell, int Ncap,
                                               const int32_t* __restrict__ n_dev,
@@ -326,15 +324,7 @@ struct GemmArgs {
     // floats after those of group z - 1.  ldo: row stride of the output plane (0 = Cb; a column block of a wider matrix)
     int ldo, zrev;
     int64_t gsA, gsB, gsO;
-#ifdef QT_GEMM_TIMING
-    long long* dbg;
-#endif
 };
-#ifdef QT_GEMM_TIMING
-#define QT_STAMP(i) do { if (g.dbg && threadIdx.x == 0) g.dbg[(int64_t)blockIdx.x * 8 + (i)] = wall_clock64(); } while (0)
-#else
-#define QT_STAMP(i) do {} while (0)
-#endif
 
 // ---- fp32 MFMA tiles (v_mfma_f32_32x32x2_f32: exact fp32 fma chain, 64 FLOP/clk/SIMD).
 // Operand maps (cdna_hip_programming.md section 3): lane l holds A[i = l & 31][k = l >> 5] and
@@ -399,16 +389,10 @@ __device__ __forceinline__ void build_quad_table(const PlaneSrc& A, const float*
 // MODE 0: out planes = act(A @ W).  Block = 128 node rows x (32 NT) output columns, wave w owns rows [32w, 32w+32).
 // A fragments go global -> VGPR directly (float4 per lane and k-quad); only W is staged in LDS (KWT x 32 NT floats).
 // NT = 2 for NB <= 64 (gate GEMM), NT = 4 for wide outputs (the data gradient, NB = K*C) so A is read only once.
+static constexpr int QT_GEMM_OCC = 4;
+static constexpr int QT_GEMM_OCC3 = 3;
+static constexpr int QT_GEMM_OCC4C = 2;
 template <int NT, int KWT, int CELL = 0>     // CELL: 0 = plain epilogue, else the lanes per node (h / 4) of the fused LSTM cell
-#ifndef QT_GEMM_OCC
-#define QT_GEMM_OCC 4
-#endif
-#ifndef QT_GEMM_OCC3
-#define QT_GEMM_OCC3 3
-#endif
-#ifndef QT_GEMM_OCC4C
-#define QT_GEMM_OCC4C 2
-#endif
 __global__ __launch_bounds__(256, (NT == 4 && CELL != 0) ? QT_GEMM_OCC4C : (NT == 3 ? QT_GEMM_OCC3 : QT_GEMM_OCC)) void k_gemm_fwd(GemmArgs g) {   // 4 workgroups per CU: all N/128 blocks of the
                                                                       // bench shape are resident at once (<= 128 registers)
     constexpr int BNT = 32 * NT;
@@ -424,7 +408,6 @@ __global__ __launch_bounds__(256, (NT == 4 && CELL != 0) ? QT_GEMM_OCC4C : (NT =
     const int j0 = blockIdx.y * BNT;
     const int64_t rows = qt_rows(g.n_dev, g.M);      // g.M stays the plane stride (capacity)
     if (i0 >= rows) return;
-    QT_STAMP(0);
     if (gridDim.z > 1) {
         const int z = g.zrev ? (int)gridDim.z - 1 - (int)blockIdx.z : (int)blockIdx.z;     // (zrev: groups from the last to the first)
         g.A.a0 += z * g.gsA;
@@ -457,7 +440,6 @@ __global__ __launch_bounds__(256, (NT == 4 && CELL != 0) ? QT_GEMM_OCC4C : (NT =
     for (int k0 = 0; k0 < g.K; k0 += KWT) {
         const int kn = min(KWT, g.K - k0);           // multiple of 4
         __syncthreads();                              // table ready / previous pass done with Bs
-        QT_STAMP(1);
         // W chunk -> LDS first (small, L2 resident) ...
         if (g.BT) {
             // ... from W^T: a column's k run is contiguous in memory and in LDS (conflict-free 16-byte stores)
@@ -484,7 +466,6 @@ __global__ __launch_bounds__(256, (NT == 4 && CELL != 0) ? QT_GEMM_OCC4C : (NT =
             *reinterpret_cast<float4*>(&Bt[c * PITCH + kq]) = make_float4(0.f, 0.f, 0.f, 0.f);
         }
         __syncthreads();
-        QT_STAMP(2);
         // ... then the MFMA stream.  The A quads (quad 2 j + half of this lane's row) come straight from global memory
         // through a 4-deep register ring loaded four k-groups ahead; the loop is a plain runtime loop with NO branch
         // around the MFMAs (conditionals there made hipcc shuttle the accumulators between VGPRs and AGPRs: 1088
@@ -514,7 +495,6 @@ __global__ __launch_bounds__(256, (NT == 4 && CELL != 0) ? QT_GEMM_OCC4C : (NT =
             }
         }
     }
-    QT_STAMP(3);
     float* Cs = Bt;                              // 128 rows x 64 columns per pass
     if constexpr (CELL != 0) {
         // LSTM epilogue: h / 4 adjacent lanes own a node, as in k_lstm_fwd (h = 8, 16 with NT = 2; h = 32 with NT = 4: all
@@ -575,7 +555,6 @@ __global__ __launch_bounds__(256, (NT == 4 && CELL != 0) ? QT_GEMM_OCC4C : (NT =
                     Cs[(wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * half) * 64 + u * 32 + l32] = acc[nt][r];
         }
         __syncthreads();
-        QT_STAMP(4);
 #pragma unroll
         for (int u = 0; u < BM * 16 / 256; ++u) {
             const int e = t + 256 * u;
@@ -599,7 +578,6 @@ __global__ __launch_bounds__(256, (NT == 4 && CELL != 0) ? QT_GEMM_OCC4C : (NT =
                 *reinterpret_cast<float4*>(plane_piece(g.outb, pl, i, ch - g.Cb, g.Cbb, g.M, g.out_sm, g.Cbb)) = v;
         }
     }
-    QT_STAMP(5);
 }
 
 // ---- persistent gate GEMM + LSTM cell (hidden 8 / 16): one 512-thread workgroup per CU, W staged ONCE, no workgroup barrier
@@ -613,9 +591,7 @@ __global__ __launch_bounds__(256, (NT == 4 && CELL != 0) ? QT_GEMM_OCC4C : (NT =
 // Work split: workgroup b owns the contiguous units [U b / G, U (b + 1) / G) of the U = ceil(rows / 32) units (valid rows
 // read on the device), its wave w takes every 8th of them.
 constexpr int GATE_P_MAXK = 256, GATE_P_MAXPITCH = GATE_P_MAXK + 8;
-#ifndef QT_GATE_STAGGER
-#define QT_GATE_STAGGER 0
-#endif
+static constexpr int QT_GATE_STAGGER = 0;
 template <int NT, int LPN, int R>
 __global__ __launch_bounds__(512, 2) void k_gate_cell_p(GemmArgs g, int pitch) {
     using namespace qtcell;
@@ -633,7 +609,6 @@ __global__ __launch_bounds__(512, 2) void k_gate_cell_p(GemmArgs g, int pitch) {
     const int nunits = (rows + 31) >> 5;
     const int u0 = (int)((int64_t)nunits * blockIdx.x / gridDim.x), u1 = (int)((int64_t)nunits * (blockIdx.x + 1) / gridDim.x);
     if (u0 >= u1) return;
-    QT_STAMP(0);
     const int nquad = g.K >> 2;
     build_quad_table(g.A, qptr, qstr, nquad);
     if (g.BT) {
@@ -654,7 +629,6 @@ __global__ __launch_bounds__(512, 2) void k_gate_cell_p(GemmArgs g, int pitch) {
     if (g.K & 4)                                          // an odd quad count: the last k-group's upper half reads zeros
         for (int c = t; c < BNT; c += 512) *reinterpret_cast<float4*>(&Bt[c * pitch + g.K]) = make_float4(0.f, 0.f, 0.f, 0.f);
     __syncthreads();                                      // the only workgroup barrier
-    QT_STAMP(1);
     int unit = u0 + wave;
     if (unit >= u1) return;
     const int nj = (g.K + 7) >> 3;
@@ -714,14 +688,10 @@ __global__ __launch_bounds__(512, 2) void k_gate_cell_p(GemmArgs g, int pitch) {
                 bq[nt] = *reinterpret_cast<const float4*>(&Bt[(nt * 32 + l32) * pitch + 8 * j + 4 * half]);
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
-#ifdef QT_EXP_NOMFMA
-                acc[nt][0] += a.x * bq[nt].x + a.y * bq[nt].y + a.z * bq[nt].z + a.w * bq[nt].w;
-#else
                 acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, bq[nt].x, acc[nt], 0, 0, 0);
                 acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, bq[nt].y, acc[nt], 0, 0, 0);
                 acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, bq[nt].z, acc[nt], 0, 0, 0);
                 acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, bq[nt].w, acc[nt], 0, 0, 0);
-#endif
             }
         };
         if constexpr (R > 0) {
@@ -743,7 +713,6 @@ __global__ __launch_bounds__(512, 2) void k_gate_cell_p(GemmArgs g, int pitch) {
             for (int j = 0; j < 4; ++j) ring[j] = ldq(nrow, nok, j);
         }
         // epilogue: accumulator columns -> this wave's staging rows -> h / 4 lanes per node
-        if (unit == u0) QT_STAMP(2);
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
         for (int u = 0; u < NT; ++u)
@@ -758,12 +727,7 @@ __global__ __launch_bounds__(512, 2) void k_gate_cell_p(GemmArgs g, int pitch) {
             const float* cs = Cs + row * CP + j0;
             const F4 gi = ld4(cs), gf = ld4(cs + h), gc = ld4(cs + 2 * h), go = ld4(cs + 3 * h);
             const F4 cp = {{cpre[ps].x, cpre[ps].y, cpre[ps].z, cpre[ps].w}};
-#ifdef QT_EXP_NOCELL
-            CellOut r;
-            r.I = gi; r.F = gf; r.T = gc; r.Og = go; r.hn = cp; r.cn = cp;
-#else
             const CellOut r = cell_forward<LPN>(gi, gf, gc, go, cp, cpar, h);
-#endif
             if (node < rows) {
                 if (g.O) st4(g.O + node * h + j0, r.Og);
                 st4(g.Hn + node * h + j0, r.hn);
@@ -775,11 +739,9 @@ __global__ __launch_bounds__(512, 2) void k_gate_cell_p(GemmArgs g, int pitch) {
                 st4(gs + 3 * h, r.Og);
             }
         }
-        if (unit == u0) QT_STAMP(3);
         if (!has_next) break;
         unit = nxt; my_row = nrow; row_ok = nok;
     }
-    QT_STAMP(4);
 }
 
 // ---- skinny shapes: few output columns (the decoder head: 16 or 4) or a short reduction (its data gradients: K = 16 or 4).
@@ -822,9 +784,7 @@ __global__ __launch_bounds__(256) void k_gemm_skinny(GemmArgs g) {
         if (ok && Q < nquad) r = gload4(qptr[Q] + row * qstr[Q]);
         return r;
     };
-#ifndef QT_SKINNY_INFLIGHT
-#define QT_SKINNY_INFLIGHT 4      // (8: +0.02 ms per step, 16: +0.07)
-#endif
+static constexpr int QT_SKINNY_INFLIGHT = 4;      // (8: +0.02 ms per step, 16: +0.07)
     for (int Q = 0; Q < nquad; Q += QT_SKINNY_INFLIGHT) {            // A quads in flight per trip (a trip is one dependent memory phase)
         float4 aq[QT_SKINNY_INFLIGHT];
 #pragma unroll
@@ -888,9 +848,7 @@ __global__ __launch_bounds__(256) void k_gemm_skinny(GemmArgs g) {
 // every operand quad is loaded ONCE and all of them are in flight together.  W rows come through scalar loads (uniform
 // addresses).  The same chain of fused multiply-adds per output element (k ascending): bit-identical to k_gemm_skinny.
 // Epilogue as k_gemm_skinny<64>: ReLU / ReLU-backward mask, the second product post_out = [act(out) | 1 0 0 0] @ post_W.
-#ifndef QT_ROW16_INF
-#define QT_ROW16_INF 8
-#endif
+static constexpr int QT_ROW16_INF = 8;
 __global__ __launch_bounds__(64) void k_gemm_row16(GemmArgs g) {
     __shared__ const float* qptr[MAXQ];
     __shared__ int qstr[MAXQ];
@@ -1495,9 +1453,7 @@ inline int wgrad_fw(int M) { return M <= 32 ? 1 : (M <= 64 ? 2 : 4); }
         else hipLaunchKernelGGL((K<4, 2>), grid_, dim3(256), 0, (hipStream_t)(stream_), arg_);                      \
     } while (0)
 constexpr int WGRAD_ROWS = 512;
-#ifndef QT_WG_ROWS
-#define QT_WG_ROWS 512      // 11.02 ms per training step against 11.07 (1024) and 11.20 (256)
-#endif
+static constexpr int QT_WG_ROWS = 512;      // 11.02 ms per training step against 11.07 (1024) and 11.20 (256)
 constexpr int WGRAD_GROUP_ROWS = QT_WG_ROWS;
 
 
@@ -1528,12 +1484,9 @@ struct DgradCellArgs {
 // BG: the right operand (the weight rows, <= 32 KB, L1 / L2 resident) is read straight from global memory by the lanes that
 // need it instead of being staged in LDS: the workgroup's LDS drops from 64 KB to 38 KB, so THREE workgroups fit a CU instead
 // of two -- more workgroups whose load / arithmetic / MFMA / store phases overlap.
-#ifndef QT_DGRAD_BG
-#define QT_DGRAD_BG 1
-#endif
-#ifndef QT_DGRAD_OCC
-#define QT_DGRAD_OCC 4      // 128 VGPRs (8-10 spilled): FOUR workgroups per CU = all 940 tiles of the bench shape resident at once
-#endif                    // (3: 138-155 VGPRs, 768 resident + a second round; 8.41 -> 8.34 ms per frozen step)
+static constexpr int QT_DGRAD_BG = 1;
+static constexpr int QT_DGRAD_OCC = 4;      // 128 VGPRs (8-10 spilled): FOUR workgroups per CU = all 940 tiles of the bench shape resident at once
+                          // (3: 138-155 VGPRs, 768 resident + a second round; 8.41 -> 8.34 ms per frozen step)
 template <int NT, int LPN, bool BG = (QT_DGRAD_BG != 0)>
 __global__ __launch_bounds__(256, BG ? QT_DGRAD_OCC : 2) void k_dgrad_cell(DgradCellArgs g) {
     using namespace qtcell;
@@ -1590,21 +1543,13 @@ __global__ __launch_bounds__(256, BG ? QT_DGRAD_OCC : 2) void k_dgrad_cell(Dgrad
                     for (int k = 0; k < 4; ++k) gyh.v[k] += h2.v[k];
                 }
             }
-#ifdef QT_EXP_DG_NOCELL
-            CellBwdOut o;
-            o.ggi = I; o.ggf = F; o.ggc = T; o.ggo = Og; o.gcp = cp;
-            acc[0][0] += gyh.v[0] + gyc.v[0] + go_in.v[0] + wci.v[0] + wcf.v[0] + wco.v[0] + gam_h.v[0] + gam_c.v[0];
-#else
             const CellBwdOut o = cell_backward<LPN>(I, F, T, Og, cp, gyh, gyc, go_in, wci, wcf, wco, gam_h, gam_c,
                                                     g.ln != nullptr, h, acc);
-#endif
             float* as = As + r * PITCH + j0;
             st4(as, o.ggi); st4(as + h, o.ggf); st4(as + 2 * h, o.ggc); st4(as + 3 * h, o.ggo);
             if (ok) {
-#ifndef QT_EXP_DG_NOGG
                 float* gg = g.gG + node * 4 * h + j0;
                 st4(gg, o.ggi); st4(gg + h, o.ggf); st4(gg + 2 * h, o.ggc); st4(gg + 3 * h, o.ggo);
-#endif
                 if (g.gCprev) st4(g.gCprev + node * h + j0, o.gcp);
             }
         }
@@ -1644,13 +1589,9 @@ __global__ __launch_bounds__(256, BG ? QT_DGRAD_OCC : 2) void k_dgrad_cell(Dgrad
 #pragma unroll
                     for (int q = 0; q < 8; ++q) { bhi[q] = (__bf16)0.0f; blo[q] = (__bf16)0.0f; }
                 }
-#ifdef QT_EXP_DG_NOMFMA
-                acc2[nt][0] += (float)ahi[0] * (float)bhi[0] + (float)alo[1] * (float)blo[1];
-#else
                 acc2[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ahi, bhi, acc2[nt], 0, 0, 0);
                 acc2[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ahi, blo, acc2[nt], 0, 0, 0);
                 acc2[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(alo, bhi, acc2[nt], 0, 0, 0);
-#endif
             }
         }
     } else {
@@ -2010,19 +1951,14 @@ static int plane_src(PlaneSrc* A, const char* fn, const float* a0, int lda0, con
     return QT_OK;
 }
 
-#ifdef QT_GEMM_TIMING
-static long long* g_dbg = nullptr;       // diagnostics build only (tools/exp_gemm_timing.py)
-extern "C" void qt_gemm_timing_buffer(long long* p) { g_dbg = p; }
-#endif
 
 static int spmm_part(SpmmPart* P, int* nblk, int N, int C, const float* x, int ldx, const float* p, int ldp, const float* q,
                      int ldq, float* out) {
     P->x = x; P->p = p; P->q = q; P->out = out; P->C = C;
     P->ldx = ldx > 0 ? ldx : C; P->ldp = ldp > 0 ? ldp : C; P->ldq = ldq > 0 ? ldq : C;
     int grid = qt_cdiv((int64_t)N * (C / 4), QT_SPMM_BS);
-    static const bool xcd = getenv("QT_SPMM_FLAT") == nullptr;
     P->xcd_chunk = 0;
-    if (xcd && grid >= 64) {
+    if (grid >= 64) {
         P->xcd_chunk = qt_cdiv(grid, 8);
         grid = P->xcd_chunk * 8;    // surplus workgroups fall past the row count and exit
     }
@@ -2048,9 +1984,7 @@ extern "C" int qt_spmm2(const int32_t* rowptr, const int32_t* col, const float* 
     spmm_part(&A, &na, N, Ca, xa, ldxa, pa, ldpa, qa, ldqa, outa);
     if (Cb) spmm_part(&B, &nb, N, Cb, xb, ldxb, pb, ldpb, qb, ldqb, outb);
     // 8 edges per trip for narrow rows (see qt_spmm); the wider part decides
-#ifndef QT_EPT8_MAXC
-#define QT_EPT8_MAXC 20
-#endif
+static constexpr int QT_EPT8_MAXC = 20;
     if (max(Ca, Cb) <= QT_EPT8_MAXC)
         hipLaunchKernelGGL((k_spmm<4, 1, 8>), dim3(na + nb), dim3(QT_SPMM_BS), 0, (hipStream_t)stream, rowptr, col, nrm, reinterpret_cast<const int4*>(ell), N, n_dev, A, B, na, alpha, beta, gamma);
     else
@@ -2109,12 +2043,8 @@ static inline int gemm_nt(int NB) {
     }
     return NB <= 64 ? 2 : best;
 }
-#ifndef QT_GEMM_KWT3
-#define QT_GEMM_KWT3 128
-#endif
-#ifndef QT_GEMM_KWT4
-#define QT_GEMM_KWT4 64      // k rows of W staged per pass by the 128-column tiles (NT = 4)
-#endif
+static constexpr int QT_GEMM_KWT3 = 128;
+static constexpr int QT_GEMM_KWT4 = 64;      // k rows of W staged per pass by the 128-column tiles (NT = 4)
 static void launch_gemm_fwd(const GemmArgs& g, int N, int G, hipStream_t stream) {
     switch (gemm_nt(g.NB)) {
         case 2: hipLaunchKernelGGL((k_gemm_fwd<2, 128>), dim3(qt_cdiv(N, BM), qt_cdiv(g.NB, 64), G), dim3(256), 0, stream, g); break;
@@ -2145,16 +2075,12 @@ extern "C" int qt_dense2(const float* a0, int lda0, const float* a_rest, const f
     if (N <= 0) return QT_OK;
     g.B = W; g.BT = WT; g.M = N; g.K = Ka * (Ca + Cab) + Ks; g.NB = Kb * (Cb + Cbb);
     g.outb = outb; g.Cbb = Cbb;
-#ifdef QT_GEMM_TIMING
-    g.dbg = g_dbg;
-#endif
     g.Kb = Kb; g.Cb = Cb; g.act = act; g.res = res; g.res_stride = res_stride; g.drop = drop; g.out = out; g.row0_step = 0; g.n_dev = n_dev; g.accumulate = 0;
     g.post_W = post_W; g.post_out = post_out;
     // default: exact fp32 MFMA (bit-for-bit a k-ordered fmaf chain).  QT_GEMM_BF16X3=1 opts into the bf16x3 split
     // kernels (fp32-level error, ~8 % faster on these memory/latency-shaped GEMMs: measured 27.7 vs 30.1 us).
     static const bool exact_fp32 = getenv("QT_GEMM_BF16X3") == nullptr;
-    static const bool no_skinny = getenv("QT_GEMM_NO_SKINNY") != nullptr;
-    if ((!no_skinny || post_W || act == QT_ACT_RELU_BWD) && g.NB <= 16 && W) {       // (wide outputs of short reductions measured slower here: 24.5 vs 14.5 us)
+    if (g.NB <= 16 && W) {       // (wide outputs of short reductions measured slower here: 24.5 vs 14.5 us)
         static const bool no_row16 = getenv("QT_GEMM_NO_ROW16") != nullptr;       // (A/B switch)
         if (g.NB <= 4)
             hipLaunchKernelGGL((k_gemm_skinny<256>), dim3(qt_cdiv(N, 256), 1, 1), dim3(256), 0, (hipStream_t)stream, g);
@@ -2206,9 +2132,6 @@ extern "C" int qt_proj_group(const float* A, int lda, int64_t gsA, int Ka, int C
     g.Kb = Kb; g.Cb = Cb; g.act = QT_ACT_NONE; g.out = out; g.n_dev = n_dev;
     g.ldo = ldo; g.gsA = gsA; g.gsB = gsW; g.gsO = gsO;
     g.zrev = reverse != 0;
-#ifdef QT_GEMM_TIMING
-    g.dbg = nullptr;
-#endif
     launch_gemm_fwd(g, N, G, (hipStream_t)stream);
     QT_LAUNCHED();
     return QT_OK;
@@ -2312,8 +2235,7 @@ extern "C" int qt_lstm_bwd_fused(const float* gO, int ld_go, const float* gHn, i
     QT_ARG(f.Kt <= 128, "the weight must have at most 128 rows (one accumulator tile column per wave)");
     const int NTc = qt_cdiv(NB, 32);
     // 64-row tiles, two 256-thread workgroups per CU (their LDS fits twice up to three column tiles); else 128-row tiles
-    static const bool tr128 = getenv("QT_FUSED_TR128") != nullptr;
-    const bool small = !tr128 && NTc <= 3;
+    const bool small = NTc <= 3;
     const int grid = small ? min(2 * qt_num_cus(), qt_cdiv(N, 64)) : min(qt_num_cus(), qt_cdiv(N, 128));
     QT_ARG(nslab >= grid, "slab too small: one (Kt, 4h) slab per workgroup, qt_lstm_fused_blocks() of them");
     if (N <= 0) return QT_OK;
@@ -2323,11 +2245,7 @@ extern "C" int qt_lstm_bwd_fused(const float* gO, int ld_go, const float* gHn, i
     g.gG = nullptr; g.gCprev = gCprev; g.part = part; g.accumulate = accumulate;
     g.BT = Wrows; g.M = N; g.NB = NB; g.Kb = Kb; g.Cb = Cb; g.Cbb = Cbb; g.out = out; g.outb = outb; g.n_dev = n_dev;
     f.slab = slab;
-#define QT_FUSED(NT_, LPN_)                                                                                                  \
-    do {                                                                                                                     \
-        if (small) hipLaunchKernelGGL((k_cell_bwd_fused<NT_, LPN_, 64>), dim3(grid), dim3(256), 0, (hipStream_t)stream, f);  \
-        else hipLaunchKernelGGL((k_cell_bwd_fused<NT_, LPN_, 128>), dim3(grid), dim3(512), 0, (hipStream_t)stream, f);       \
-    } while (0)
+#define QT_FUSED(NT_, LPN_) hipLaunchKernelGGL((k_cell_bwd_fused<NT_, LPN_, 64>), dim3(grid), dim3(256), 0, (hipStream_t)stream, f)
     if (h == 16) {
         if (NTc <= 1) QT_FUSED(1, 4);
         else if (NTc == 2) QT_FUSED(2, 4);
@@ -2362,12 +2280,8 @@ extern "C" int qt_dense_lstm(const float* a0, int lda0, const float* a_rest, con
     g.row0_step = 0; g.n_dev = n_dev; g.accumulate = 0;
     g.Cprev = Cprev; g.wc = wc; g.bias = b; g.ln = ln; g.ld_c = ld_c; g.h = h;
     g.O = O; g.Hn = Hn; g.Cn = Cn; g.gates = gates;
-#ifdef QT_GEMM_TIMING
-    g.dbg = g_dbg;
-#endif
     // hidden 8 / 16 with the whole W^T in LDS: the persistent wave-centric kernel (one workgroup per CU)
-    static const bool persistent = getenv("QT_GATE_CELL_TILED") == nullptr;
-    if (persistent && (h == 8 || h == 16) && g.K <= GATE_P_MAXK) {
+    if ((h == 8 || h == 16) && g.K <= GATE_P_MAXK) {
         const int pitch = g.K + (((g.K >> 2) & 1) ? 8 : 4);                 // pitch / 4 odd
         const int n_cu = qt_num_cus();
         const dim3 pgrid(min(n_cu, qt_cdiv(N, 32)), 1, 1);

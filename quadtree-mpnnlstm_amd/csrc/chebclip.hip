@@ -26,11 +26,9 @@
 namespace {
 
 // Threads per workgroup and rows gathered together, measured at the bench shape (K = 5, C = 4 + 16, forward / backward, us per
-// launch; tools/exp_clip.py): 1024 x 1 row: 21.4 / 21.3;  1024 x 2: 22.4 / 23.8;  512 x 2: 24.9 / 26.6;  512 x 4: 25.5 / 27.3 --
+// launch): 1024 x 1 row: 21.4 / 21.3;  1024 x 2: 22.4 / 23.8;  512 x 2: 24.9 / 26.6;  512 x 4: 25.5 / 27.3 --
 // sixteen waves that each wait on one row's five LDS reads beat eight waves with four rows in flight (per-hop launches: 29.6 / 31.4).
-#ifndef QT_CLIP_T
-#define QT_CLIP_T 1024
-#endif
+static constexpr int QT_CLIP_T = 1024;
 constexpr int CL_ROWS = QT_TAIL_REC_CAP;   // rows of a clip that fit: 2 planes x 4096 x 16 B = 128 KB
 constexpr int CL_T = QT_CLIP_T;            // threads per workgroup
 constexpr int CL_RPT = CL_ROWS / CL_T;     // rows per thread (6 registers per row for all hops: packed ELL columns, weights; the
@@ -73,15 +71,7 @@ struct ClipArgs {
     unsigned* err;                 // the caller's persistent error word (never reset by the library): bit 0 a wait for a neighbour
                                    // tile gave up, bit 1 a tile capacity of the mesh build was exceeded
     int T, nbj, s0, ns;            // tiles per clip, tiles per tile row; first slice and slice count of THIS launch
-#ifdef QT_CLIP_TIMING
-    long long* dbg;                // diagnostics build (tools/exp_clip_timing.py): 16 stamps per workgroup
-#endif
 };
-#ifdef QT_CLIP_TIMING
-#define CL_STAMP(i) do { if (g.dbg && threadIdx.x == 0) g.dbg[(int64_t)blockIdx.x * 16 + (i)] = wall_clock64(); } while (0)
-#else
-#define CL_STAMP(i) do {} while (0)
-#endif
 
 // the W channels of a slice row: a plain struct (independent registers: as one ext_vector value the 4-register tuples' alignment
 // cost the W = 4 kernels ~25 more registers and spills); memory accesses go through the matching vector type
@@ -180,7 +170,7 @@ __device__ __forceinline__ void gather_tail_csr(fvec<W>& a, const char* __restri
 //   also as the two halves of a 16-byte sc1 access; "granules for latency"): no drain, no separate flag, no dependent load
 //   behind a poll; a reader that catches a row between its two stores sees a stale tag in one half and polls again.  A first version with write-through rows + a
 //   drained per-tile hop flag + sc1 halo loads behind the poll took 6 - 7 us per hop -- no faster than a k_spmm launch per hop
-//   (8 us at 128 x 128 x 8 clips); with granules a hop costs ~4.3 us (tools/exp_tile.py: K = 5 at 128 x 128 x 8 clips 30 -> 21 us
+//   (8 us at 128 x 128 x 8 clips); with granules a hop costs ~4.3 us (profiles/r05_exp_tile.txt: K = 5 at 128 x 128 x 8 clips 30 -> 21 us
 //   forward, 32 -> 27 us backward; 32 channels 38 -> 25 / 46 -> 32), which is the chain boundary rows (0.6 us) -> store visible
 //   (~1.5 us) -> poll round trip (~1.5 us): what a cross-CU hand-off costs on this chip, tile size notwithstanding.  So the path
 //   pays for K >= 4 when all workgroups fit the CUs in one round, and is NOT taken otherwise (ops._tile_resident): two hops are
@@ -189,9 +179,7 @@ __device__ __forceinline__ void gather_tail_csr(fvec<W>& a, const char* __restri
 //   between launches or hipGraph replays; the exchange buffer is zeroed once per mesh build.
 // No dependence on dispatch order beyond forward progress: spins are bounded (a timeout sets the error word and the launch
 // finishes with garbage instead of hanging) and the launches are cut so that all workgroups of one are co-resident.
-#ifndef QT_TILE_SPIN_LIMIT
-#define QT_TILE_SPIN_LIMIT 200000u                         // polls of ~1 us: ~0.2 s before a poll gives up (a test build shrinks it)
-#endif
+static constexpr unsigned QT_TILE_SPIN_LIMIT = 200000u;       // polls of ~1 us: ~0.2 s before a poll gives up
 constexpr unsigned TILE_SPIN_LIMIT = QT_TILE_SPIN_LIMIT;
 static_assert((QT_TILE_HALO_CAP & (QT_TILE_HALO_CAP - 1)) == 0 && QT_TILE_HALO_CAP <= 256,
               "halo slots: a power of two (slot masks) of at most 256 (the boundary pool keeps a slot in 8 bits; waves 0-3 own them)");
@@ -264,7 +252,6 @@ __global__ __launch_bounds__(CL_T) void k_cheb_clip(ClipArgs g) {
         }
     }
     bool dead = false;                       // TILE: a poll timed out: no further waiting, the error word is set
-    CL_STAMP(0);
     const int K = g.K;
     const unsigned pstride = (unsigned)g.Ncap * (unsigned)C;      // (K * Ncap * C < 2^31: checked by the host entry -- 32-bit offsets)
 
@@ -303,11 +290,7 @@ __global__ __launch_bounds__(CL_T) void k_cheb_clip(ClipArgs g) {
         c4[u] = src[0];
         wb[u] = src[1];
         if constexpr (!BWD) {
-#ifdef QT_EXP_CLIP_SMZ            // (timing experiment: the first operand read as if it were stored slice-major -- wrong values, same buffer)
-            first[u] = ldg<W>(pt.z + (((unsigned)(ch >> 2) * (unsigned)g.Ncap + rowc[u]) * 4u + (unsigned)(ch & 3)));
-#else
             first[u] = ldg<W>(pt.z + (rowc[u] * (unsigned)pt.ld + ch));
-#endif
         } else {
             first[u] = ldg<W>(pt.planes + grad_off(K - 1, rowc[u]));
         }
@@ -351,7 +334,6 @@ __global__ __launch_bounds__(CL_T) void k_cheb_clip(ClipArgs g) {
             vstore<W>(HB + t * (4 * W), hv);
         }
     }
-    CL_STAMP(1);
     unsigned lc[CL_RPT][2];
     float w[CL_RPT][4];
     unsigned tinfo[CL_RPT];                 // record slots: pool base | tail edge count << 16 (base 0xffff: walk the CSR); 0 otherwise
@@ -390,15 +372,11 @@ __global__ __launch_bounds__(CL_T) void k_cheb_clip(ClipArgs g) {
             tinfo[u] = 0;
         }
     }
-    CL_STAMP(2);
     if constexpr (BWD) {       // A_{K-2} of the rows: needed at the end of the first hop's groups (requested here, not in the prologue:
 #pragma unroll                 // its registers would sit beside the ELL vectors' and spill)
         for (int u = 0; u < CL_RPT; ++u) nxt[u] = ldg<W>(pt.planes + grad_off(K - 2, rowc[u]));
     }
     lds_barrier();
-    CL_STAMP(3);
-    int stamp = 4;
-    (void)stamp;
     // One hop with the gathered plane at byte offset CO of Pl (compile-time: the hop loops below are unrolled by two, so the plane
     // offsets are instruction immediates).  Per row: its four gathers AND its own old value (OWN: the plane being overwritten) are
     // requested together -- one LDS round trip (the first version took two per row: 3.6 us per hop with 0.7 us of gather work
@@ -536,7 +514,6 @@ __global__ __launch_bounds__(CL_T) void k_cheb_clip(ClipArgs g) {
             }
         }
         lds_barrier();
-        CL_STAMP(stamp++);
     };
     using Co0 = std::integral_constant<unsigned, 0u>;
     using Co1 = std::integral_constant<unsigned, PLANE>;
@@ -553,9 +530,7 @@ __global__ __launch_bounds__(CL_T) void k_cheb_clip(ClipArgs g) {
             float* outp = pt.planes + ((unsigned)(k - 1) * pstride + (unsigned)(ch >> 2) * (unsigned)g.Ncap * 4u + (unsigned)(ch & 3));
             return [=](unsigned grow, const V& r, char* own) {
                 vstore<W>(own, r);
-#ifndef QT_EXP_CLIP_NOSTORE         // (timing experiment)
                 vstore<W>(outp + grow * 4u, r);
-#endif
             };
         };
         auto xch = [&](int k) { return Xch{(unsigned)k, k + 1 < K}; };
@@ -602,10 +577,6 @@ __global__ __launch_bounds__(CL_T) void k_cheb_clip(ClipArgs g) {
 }  // namespace
 
 extern "C" int qt_cheb_clip_rows(void) { return CL_ROWS; }
-#ifdef QT_CLIP_TIMING
-static long long* g_clip_dbg = nullptr;
-extern "C" void qt_clip_timing_buffer(long long* p) { g_clip_dbg = p; }
-#endif
 
 struct ClipMesh {       // the mesh operands both entry points share
     const int32_t *rowptr, *col;
@@ -640,9 +611,6 @@ static int clip_launch(bool bwd, const ClipMesh& m, int Ncap, int K, int Ca, con
     g.K = K;
     g.nsa = Ca / W;
     g.Ncap = Ncap;
-#ifdef QT_CLIP_TIMING
-    g.dbg = g_clip_dbg;
-#endif
     g.a = ClipPart{za, Pa, Ca, lda ? lda : Ca};
     g.b = ClipPart{zb, Pb, Cb, ldb ? ldb : Cb};
     const int grid = m.B * ((Ca + Cb) / W);
@@ -720,9 +688,6 @@ static int tile_launch(bool bwd, const TileMesh& m, int Ncap, int K, int Ca, con
     g.K = K;
     g.nsa = Ca / 4;
     g.Ncap = Ncap;
-#ifdef QT_CLIP_TIMING
-    g.dbg = nullptr;
-#endif
     g.a = ClipPart{za, Pa, Ca, lda ? lda : Ca};
     g.b = ClipPart{zb, Pb, Cb, ldb ? ldb : Cb};
     g.tile_off = m.tile_off;

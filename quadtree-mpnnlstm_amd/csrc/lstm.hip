@@ -260,9 +260,7 @@ extern "C" int qt_lstm_infer(const float* G, const float* G2, int ld_g, const fl
 extern "C" int qt_lstm_bwd_blocks(int N, int h) {
     if (N <= 0 || !h_ok(h)) return 0;
     const int need = qt_cdiv((int64_t)N * lanes_per_node(h), 256);
-#ifndef QT_LSTM_BLOCKS
-#define QT_LSTM_BLOCKS 512
-#endif
+static constexpr int QT_LSTM_BLOCKS = 512;
     return need < QT_LSTM_BLOCKS ? need : QT_LSTM_BLOCKS;
 }
 

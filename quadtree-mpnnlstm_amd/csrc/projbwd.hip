@@ -15,7 +15,7 @@
 // A cell's FIRST layer has the same shape turned sideways: the four stacks of a segment share ONE input (gsA = 0, rows lda apart:
 // the state may be a column block of a wider matrix) and their weights sit side by side in one (36, 4 x 128) matrix (ldw = 512,
 // gsW = 128).  Head h is group h: its workgroups write a PARTIAL data gradient (the caller adds the four) and slabs laid out like
-// the weight matrix.  Measured at the cfg4t shape (tools/exp_proj_bwd.py): 108 - 115 us + 17 us for the sum against 101 - 116 (data
+// the weight matrix.  Measured at the cfg4t shape (profiles/r05_exp_proj_bwd.txt): 108 - 115 us + 17 us for the sum against 101 - 116 (data
 // gradient) + 99 - 112 us (share of the deferred weight gradient).
 // Persistent: `nb` workgroups per group (all G nb of them resident), workgroup b of a group takes the row tiles b, b + nb, ...; the
 // next tile's operands are requested before the current tile's MFMA chain.  Each workgroup
@@ -54,19 +54,7 @@ struct ProjBwdArgs {
     int N;
     const int32_t* n_dev;
     int G, nb, accumulate, reverse;
-#ifdef QT_PB_TIMING
-    long long* dbg;         // diagnostics build (tools/exp_proj_bwd.py): accumulated clock ticks per phase and workgroup
-#endif
 };
-#ifdef QT_PB_TIMING
-#define PB_T0() long long pb_t = wall_clock64(); long long pb_acc[6] = {0, 0, 0, 0, 0, 0}
-#define PB_STAMP(i) do { const long long n_ = wall_clock64(); pb_acc[i] += n_ - pb_t; pb_t = n_; } while (0)
-#define PB_DUMP() do { if (a.dbg && (threadIdx.x & 63) == 0) for (int i_ = 0; i_ < 6; ++i_) a.dbg[((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 6 + i_] = pb_acc[i_]; } while (0)
-#else
-#define PB_T0() do {} while (0)
-#define PB_STAMP(i) do {} while (0)
-#define PB_DUMP() do {} while (0)
-#endif
 
 // 64-row tiles and 60 KB of LDS: TWO workgroups per CU, so that one's MFMA chain runs while the other stages its next tile (a first
 // version with 128-row tiles, one workgroup per CU and every wave doing both products ran 171 us per layer-use at the cfg4t shape:
@@ -145,16 +133,11 @@ __global__ __launch_bounds__(256, 2) void k_proj_bwd(ProjBwdArgs a) {
     float bs0 = 0.0f, bs1 = 0.0f;   // bias row: column sums over the rows of parity `half`
     const int ct = 2 * (wave & 1);  // first column tile of a weight gradient wave
     fetch(b);
-    PB_T0();
     for (int tile = b; tile < ntiles; tile += a.nb) {
         __syncthreads();            // the previous tile's MFMA chains are through with the LDS tiles (and Ws is in place)
-        PB_STAMP(0);
         stash();
-        PB_STAMP(1);
         __syncthreads();
-        PB_STAMP(2);
         fetch(tile + a.nb);         // in flight during the MFMA chains below
-        PB_STAMP(3);
         if (dwave) {
             // reduction index k = 8 j + 4 half + i in MFMA i of step j (the operand maps of k_gemm_fwd: a lane's float4 is four
             // consecutive k of its own row): one accumulator chain in qt_proj_group's order
@@ -191,7 +174,6 @@ __global__ __launch_bounds__(256, 2) void k_proj_bwd(ProjBwdArgs a) {
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
-            PB_STAMP(4);
             // register r of a lane = row (r & 3) + 8 (r >> 2) + 4 half, column l32.  Stored straight from the accumulators the tile
             // costs 16 dword stores per lane (1.4 us per tile of vector-memory issue); through the wave's own 32 x 32 LDS tile the
             // rows leave as 4 float4 stores per lane (lane = row l >> 1 + 32 u / 8 .., half a 128-byte row each)
@@ -205,7 +187,6 @@ __global__ __launch_bounds__(256, 2) void k_proj_bwd(ProjBwdArgs a) {
                 const float4 v = *reinterpret_cast<const float4*>(&os[rr * PB_AP + cc]);      // (same wave: LDS ops complete in order)
                 if (r0 + rr < rows) *reinterpret_cast<float4*>(gA + (r0 + rr) * a.ldo + cc) = v;
             }
-            PB_STAMP(5);
         } else {
             // rows 2 ks + half of the tile: A-operand = A[row][feature l32], B-operand = gP[row][column]
             const float* acol = &As[half * PB_AP + l32];
@@ -240,10 +221,8 @@ __global__ __launch_bounds__(256, 2) void k_proj_bwd(ProjBwdArgs a) {
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
-            PB_STAMP(4);
         }
     }
-    PB_DUMP();
     if (dwave) return;
     // this workgroup's slab of the weight gradient: rows 0 .. 31 from the accumulators, row 32 = the column sums (even + odd rows),
     // rows 33 .. 35 (the padding of the bias block) zero
@@ -283,10 +262,6 @@ __global__ __launch_bounds__(256, 2) void k_proj_bwd(ProjBwdArgs a) {
 }  // namespace
 
 extern "C" int qt_num_cus(void);
-#ifdef QT_PB_TIMING
-static long long* g_pb_dbg = nullptr;
-extern "C" void qt_proj_bwd_timing_buffer(long long* p) { g_pb_dbg = p; }
-#endif
 
 // Workgroups per group: the launch fills the chip once, every workgroup resident (two per CU: 60 KB of LDS each).
 extern "C" int qt_proj_bwd_blocks(int G) {
@@ -305,9 +280,6 @@ extern "C" int qt_proj_bwd(const float* gP, int64_t gsG, int64_t psG, const floa
     QT_ARG((((uintptr_t)gP | (uintptr_t)A | (uintptr_t)W) & 15) == 0, "gP / A / W must be 16-byte aligned");
     if (N <= 0) return QT_OK;
     ProjBwdArgs a = {gP, gsG, psG, A, gsA, lda, W, gsW, ldw, gA, gsO, ldo, part, N, n_dev, G, qt_proj_bwd_blocks(G), accumulate, reverse};
-#ifdef QT_PB_TIMING
-    a.dbg = g_pb_dbg;
-#endif
     hipLaunchKernelGGL(k_proj_bwd, dim3(G * a.nb), dim3(256), 0, (hipStream_t)stream, a);
     QT_LAUNCHED();
     return QT_OK;

@@ -32,9 +32,7 @@ static inline int qt_cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b);
 // its outstanding global stores / loads (vmcnt).  __syncthreads() drains both: on gfx9 stores count in vmcnt, so a barrier
 // behind a burst of row stores waits for their round trip (~1-2 us under load) although nobody reads them in this launch.
 // QT_LDS_BARRIER=0 restores __syncthreads() (A/B builds).
-#ifndef QT_LDS_BARRIER
 #define QT_LDS_BARRIER 1
-#endif
 __device__ __forceinline__ void qt_lds_barrier() {
 #if QT_LDS_BARRIER
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");

@@ -82,12 +82,8 @@ __device__ __forceinline__ void vstore(float* p, const Vec<VEC>& r, float scale)
 }
 
 // (experiment switches: the node kernel takes nodes up to QT_NODE_MAX_Z pixels wide, the tile kernel those from level QT_TILE_MIN_LV)
-#ifndef QT_TILE_MIN_LV
-#define QT_TILE_MIN_LV 3
-#endif
-#ifndef QT_NODE_MAX_Z
-#define QT_NODE_MAX_Z 4
-#endif
+static constexpr int QT_TILE_MIN_LV = 3;
+static constexpr int QT_NODE_MAX_Z = 4;
 template <int VEC>
 __device__ __forceinline__ void tile_body(const PoolArgs& a, int bx, int by, int ny, float* pyr) {
     const int t = threadIdx.x;
@@ -228,9 +224,7 @@ __device__ __forceinline__ void tile_body(const PoolArgs& a, int bx, int by, int
     }
 }
 
-#ifndef QT_POOL_OCC
-#define QT_POOL_OCC 1
-#endif
+static constexpr int QT_POOL_OCC = 1;
 template <int VEC>
 __global__ __launch_bounds__(256, QT_POOL_OCC) void k_pool(PoolArgs a) {
     __shared__ float pyr[(256 + 64 + 16 + 4 + 1) * VEC];
@@ -267,18 +261,12 @@ __global__ __launch_bounds__(256) void k_pool_targets(PoolArgs a, LossSeg sg, in
 // source-row gathers and the output stores move whole rows and consecutive threads write consecutive memory.  (The tile
 // kernel above touches 16 bytes of every row per workgroup and has only B * tiles workgroups of pixel-serial work:
 // 39 us for 68 channels at 64x64x32, against a ~16 us stream.)  Masked pixels inside a cell carry another label.
-#ifndef QT_NODES_BS
-#define QT_NODES_BS 256
-#endif
-#ifndef QT_POOL_CPT
-#define QT_POOL_CPT 1      // row chunks per thread
-#endif
+static constexpr int QT_NODES_BS = 256;
+static constexpr int QT_POOL_CPT = 1;      // row chunks per thread
 // thread = (node, group of CPT consecutive VEC-float chunks of its row), group fastest.  One chunk per thread is the fastest:
 // at the bench shape (68 channels, forward / backward transfer) 23.2 / 36.8 us with 1, 28.1 / 44.2 with 2, 37.1 / 66.6 with 4 --
 // the waves that hold a 2x2 / 4x4 node set the launch time, and more chunks per thread lengthen exactly those.
-#ifndef QT_POOL_CPT_A
-#define QT_POOL_CPT_A 2    // row chunks per thread of the direct-copy role
-#endif
+static constexpr int QT_POOL_CPT_A = 2;    // row chunks per thread of the direct-copy role
 // Direct-copy role of k_pool_nodes: destination nodes whose single source row is known (a.direct[i] >= 0: a single-pixel node of a
 // mesh -> mesh transfer) are a gathered row copy -- index -> CPTA chunks of the row in flight -> stores, no cell record, no pixel
 // loop.  They are nine tenths of a noisy frame's nodes; in their own workgroups they stream, instead of sharing waves with the few
@@ -618,9 +606,8 @@ static int pool_launch(PoolArgs& a, bool v4, const int32_t* cell, const int32_t*
         }
         const int cpt = v4 ? QT_POOL_CPT : 1, nch = v4 ? a.C / 4 : a.C;
         const int grid_b = qt_cdiv((int64_t)a.N * (a.src_labels ? 1 : a.S) * ((nch + cpt - 1) / cpt), QT_NODES_BS);
-        static const bool no_split = getenv("QT_POOL_NO_SPLIT") != nullptr;        // (diagnostics)
         const int cpta = v4 ? QT_POOL_CPT_A : 1;
-        const int grid_a = (a.direct && a.src_labels && !no_split) ? qt_cdiv((int64_t)a.N * ((nch + cpta - 1) / cpta), QT_NODES_BS) : 0;
+        const int grid_a = (a.direct && a.src_labels) ? qt_cdiv((int64_t)a.N * ((nch + cpta - 1) / cpta), QT_NODES_BS) : 0;
         if (v4)
             hipLaunchKernelGGL(k_pool_nodes<4>, dim3(grid_b + grid_a), dim3(QT_NODES_BS), 0, stream, a, grid_b);
         else

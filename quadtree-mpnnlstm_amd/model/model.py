@@ -5,7 +5,6 @@ by fused HIP kernels (qtmpnn.ops) on a `Mesh` instead of per-module PyG calls.
 Where the reference passes (edge_index, edge_weight) these modules take the Mesh in the edge_index
 slot; the Mesh already holds the ChebConv normalisation, which PyG recomputes in every call.
 """
-import os
 
 import torch
 import torch.nn as nn
@@ -13,8 +12,7 @@ import torch.nn as nn
 from qtmpnn import ops
 from qtmpnn.mesh import Mesh
 
-_ATTN_PLAN = os.environ.get('QT_NO_ATTN_PLAN') != '1'        # (A/B switch: attention models pack per tensor, torch Adam)
-_MULTI_CONV = os.environ.get('QT_NO_MULTI_CONV') != '1'      # (diagnostics: one projection + attention launch pair per convolution)
+_MULTI_CONV = True     # comparator: tests/test_gpu_ops.py sets it False (one projection + attention launch pair per convolution)
 
 
 class ChebConv(nn.Module):
@@ -431,7 +429,7 @@ class GConvLSTM(nn.Module):
 
     @property
     def plannable(self):
-        return (_ATTN_PLAN and self._layer_by_layer) or all(type(c) is ChebConv and c.bias is not None for c in self._convs())
+        return self._layer_by_layer or all(type(c) is ChebConv and c.bias is not None for c in self._convs())
 
     def _convs(self):
         """The convolutions in module order: branch (conv_x, conv_h), gate, layer."""

@@ -18,9 +18,6 @@ from qtmpnn.flat import flat_params, param_list
 from qtmpnn.mesh import build_mesh, build_pixel_mesh, host_mask
 
 
-_PROJECT_FC2 = __import__('os').environ.get('QT_NO_PROJECT_FC2') != '1'      # (A/B switch, diagnostics)
-
-
 def _raise_on_nan(t, what):
     """image_to_graph's ValueError (graph_functions.py:626-627, 654-655) on the hot path's own tensors (one device sync)."""
     bad = torch.isnan(t)
@@ -185,7 +182,7 @@ class Decoder(_NoCachesInPickle, nn.Module):
             elif isinstance(self.fc_out1, ChebConv):
                 out['fc1'] = self.fc_out1.plan_layout(T[o:o + n1], fill, self.head_width, self.hidden_size)
                 o += n1
-                if _PROJECT_FC2 and self.fc_out2.K == 3:
+                if self.fc_out2.K == 3:
                     out['fc2c'] = self.fc_out2.plan_layout_projected(T[o:o + n2], fill)
                 else:
                     out['fc2'] = self.fc_out2.plan_layout(T[o:o + n2], fill, self.hidden_size, 4)
@@ -589,7 +586,7 @@ class Seq2Seq(_NoCachesInPickle, nn.Module):
                     and data.storage_offset() == b4.storage_offset() and data.stride(0) == 4)
             # the state goes across as its parts and comes back as column views of one matrix: nothing is concatenated
             # (on the tile-resident transfer the next decoder input [value | position, size] is assembled by the same launch)
-            fold = ops._DEC_FOLD and ops.clip_remesh_ok(old, new)
+            fold = ops.clip_remesh_ok(old, new)
             val4, *parts = ops.remesh_transfer([b4 if wide else data.expand(-1, 4).contiguous(), *hidden, *cell], old, new,
                                                [4] + [h] * (2 * L), dec_input=fold)
             val = None

@@ -9,7 +9,7 @@ import os
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# QT_LIB_PATH: an alternative build of the same library (A/B timing of kernel variants on one box; diagnostics only)
+# QT_LIB_PATH: another build of the same library (the small-caps build of csrc/Makefile, loaded by child processes of the tests)
 LIB_PATH = os.environ.get('QT_LIB_PATH') or os.path.join(_HERE, 'libqtmpnn_hip.so')
 
 _P, _I, _L, _F = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float

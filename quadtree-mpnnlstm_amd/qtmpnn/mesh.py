@@ -20,7 +20,8 @@ CONDITIONS = ('max_larger_than', 'max_smaller_than', 'min_larger_than', 'min_sma
 _MASKS = {}
 _TILE_ERR = {}           # device -> the persistent error word of the tile-resident launches (tile_error_word / check_tile_errors)
 _TILE_USED = set()       # devices that issued a tile-resident launch since their word was last checked
-_TILE_CHEB = os.environ.get('QT_NO_TILE_CHEB') != '1'      # (A/B switch: 1 = frames of several base cells stay on one k_spmm launch per hop)
+_TILE_CHEB = os.environ.get('QT_NO_TILE_CHEB') != '1'      # (1 = frames of several base cells stay on one k_spmm launch per hop: the way out check_tile_errors names)
+_STAGE1_QUADS = True   # comparator: tests/test_gpu_mesh.py sets it False (stage 1 of the quadtree build without the quad pass)
 _ONES1 = {}
 
 
@@ -233,8 +234,7 @@ def spmm2(mesh, xs, alpha, ps, beta, qs, gamma, outs):
             args += [xs[i].shape[1], x, ldx, p, ldp, q, ldq, ptr(outs[i])]
         else:
             args += [0, None, 0, None, 0, None, 0, None]
-    ell = ptr(mesh.ell) if os.environ.get('QT_SPMM_NO_ELL') != '1' else None
-    _lib.call('qt_spmm2', ptr(mesh.rowptr), ptr(mesh.col), ptr(mesh.nrm), mesh.N, ptr(mesh.n_dev), *args, alpha, beta, gamma, ell)
+    _lib.call('qt_spmm2', ptr(mesh.rowptr), ptr(mesh.col), ptr(mesh.nrm), mesh.N, ptr(mesh.n_dev), *args, alpha, beta, gamma, ptr(mesh.ell))
 
 
 def build_mesh(src=None, prev=None, B=1, n=None, m=None, thresh=0.05, condition='max_larger_than', mask=None,
@@ -277,26 +277,25 @@ def build_mesh(src=None, prev=None, B=1, n=None, m=None, thresh=0.05, condition=
     local_id = torch.empty(B, n, m, **i32)
     level = torch.empty(B, n, m, dtype=torch.uint8, device=device)
     # 64 x 64 base cells are decomposed by four workgroups each (one per quadrant): leaf counts per quadrant, in DFS order
-    quads = int(max_size == 64 and os.environ.get('QT_NO_STAGE1_QUADS') != '1')
+    quads = int(max_size == 64 and _STAGE1_QUADS)
     ncnt = B * nbase * (4 if quads else 1)
     cnt = torch.empty(ncnt, **i32)
     offs = torch.empty(ncnt + 1, **i32)
     tmp = torch.empty(ncnt // 1024 + 8, **i32)
-    direct = src is None and os.environ.get('QT_NO_DIRECT_SRC') != '1'
-    # bwd_src (per OLD node: the new node under its single pixel) is completed by stage 3, which writes only the entries of old
-    # nodes whose head pixel carries their label; stage 1 fills it with -1 first, so an entry nobody writes reads "no direct row"
-    bwd_src = torch.empty(max(old.N, 1), **i32) if direct else None
-    fill_len = bwd_src.numel() if direct else 0
+    bwd_src = None
     if src is not None:
         _lib.call('qt_quadtree_stage1', ptr(src), src.shape[1], src.shape[2], None, 0, None, B, n, m, max_size,
                   float(thresh), CONDITIONS.index(condition), ptr(mk), ptr(hr), ptr(local_id), ptr(level), ptr(cnt), quads,
                   None, 0)
     else:
+        # bwd_src (per OLD node: the new node under its single pixel) is completed by stage 3, which writes only the entries of old
+        # nodes whose head pixel carries their label; stage 1 fills it with -1 first, so an entry nobody writes reads "no direct row"
+        bwd_src = torch.empty(max(old.N, 1), **i32)
         _lib.call('qt_quadtree_stage1', None, 0, 0, ptr(nodeval), nodeval.stride(0) if nodeval.numel() > 1 else 1,
                   ptr(old.labels), B, n, m, max_size,
                   float(thresh), CONDITIONS.index(condition), ptr(mk), ptr(hr), ptr(local_id), ptr(level), ptr(cnt), quads,
-                  ptr(bwd_src), fill_len)
-    fused_scan = static and ncnt <= 1024 and os.environ.get('QT_NO_FUSED_SCAN') != '1'   # stage 3 scans the counts itself
+                  ptr(bwd_src), bwd_src.numel())
+    fused_scan = static and ncnt <= 1024   # stage 3 scans the counts itself
     if not fused_scan:
         _lib.call('qt_scan_i32', ptr(cnt), ptr(offs), ncnt, ptr(tmp))
     N = B * n * m if static else int(offs[-1].item())     # dynamic mode: the one host sync of a mesh build
@@ -315,7 +314,7 @@ def build_mesh(src=None, prev=None, B=1, n=None, m=None, thresh=0.05, condition=
     size_norm = size_norm if size_norm is not None else (max_size / 2) ** 2
     old_lab = old_lvl = None
     cell_off = torch.empty(B * nbase + 1, **i32)
-    if direct:
+    if src is None:
         import weakref
         ms.built_from = weakref.ref(old)
         ms.fwd_src = torch.empty(max(N, 1), **i32)         # (stage 3 writes every valid node's entry)

@@ -13,8 +13,8 @@ from ._lib import ptr
 from .mesh import spmm, spmm2
 
 ACT_NONE, ACT_RELU, ACT_TANH_RES, ACT_RELU_BWD = 0, 1, 2, 3
-_HEAD_DGRAD = os.environ.get('QT_NO_HEAD_DGRAD') != '1'    # (A/B switch: 1 = the head's two backward products as two launches)
-_HEAD_FUSE = os.environ.get('QT_NO_HEAD_FUSE') != '1'      # (A/B switch: 1 = the decoder head's two products as two launches each way)
+_HEAD_DGRAD = True     # comparator: tests/test_gpu_ops.py sets it False (the head's two backward products as two launches)
+_HEAD_FUSE = True      # comparator: tests/test_gpu_ops.py sets it False (the decoder head's two products as two launches each way)
 
 # Arithmetic of the backward pass's gate-GEMM data gradient (gG W^T).  False (default): exact fp32 products on the fp32 MFMA,
 # like every other product of the path and like the reference (model/model.py:394-463 is fp32 throughout).  True: the opt-in
@@ -270,12 +270,12 @@ def _plane_args(Zs, TZs):
     return a + [None, 0, None]
 
 
-_CLIP_CHEB = os.environ.get('QT_NO_CLIP_CHEB') != '1'      # (A/B switch: 1 = one k_spmm launch per hop everywhere)
+_CLIP_CHEB = True      # comparator: tests/test_gpu_ops.py sets it False (one k_spmm launch per hop everywhere)
 # Recurrences of at least this many planes take the clip-resident launch.  Its fixed cost (~4 us: one memory phase that fills the
 # registers and LDS) is paid once per launch and a hop costs ~4 us against ~7.4 us for a k_spmm launch at the bench shape
-# (tools/exp_clip.py): K = 5 (stacks of two ChebConvs) 21.4 vs 29.6 us forward, 21.3 vs 31.4 us backward; K = 3 13.4 vs 14.6 and
+# (measured): K = 5 (stacks of two ChebConvs) 21.4 vs 29.6 us forward, 21.3 vs 31.4 us backward; K = 3 13.4 vs 14.6 and
 # 14.3 vs 15.4; K = 2 (one hop) 8.4 vs 6.3: a single hop stays on k_spmm.
-_CLIP_MIN_K = int(os.environ.get('QT_CLIP_MIN_K', '3'))
+_CLIP_MIN_K = 3
 _CLIP_ROWS = []
 
 
@@ -296,14 +296,14 @@ def _clip_resident(mesh, widths, K):
             and len(widths) <= 2 and all(w % 4 == 0 for w in widths) and getattr(mesh, 'node_off', None) is not None)
 
 
-_TILE_MIN_K = int(os.environ.get('QT_TILE_MIN_K', '4'))
+_TILE_MIN_K = 4
 _NUM_CUS = []
 
 
 def _tile_resident(mesh, widths, K):
     """True when the K - 1 hops of a recurrence on a frame of SEVERAL 64 x 64 base cells run as ONE tile-resident launch
     (csrc/chebclip.hip, TILE = true): one workgroup per (clip, tile, 4-channel slice), the rows on tile borders exchanged between
-    the tiles of a clip after every hop.  Taken where it was measured faster than one k_spmm launch per hop (tools/exp_tile.py):
+    the tiles of a clip after every hop.  Taken where it was measured faster than one k_spmm launch per hop (profiles/r05_exp_tile.txt):
     at least three hops (a hop costs ~4.3 us here -- a cross-CU hand-off -- against 7 - 8 us per k_spmm launch, after a ~5 us
     prologue) and all workgroups resident in one round (8 clips x 4 tiles x 5 .. 8 slices; 640 workgroups -- hidden 32 on 16
     clips -- would take three rounds and lose)."""
@@ -1078,8 +1078,7 @@ def pyg_attention(mesh, alpha_e, alpha_s):
     return edge_index, alpha.t().contiguous()
 
 
-_PROJ_BWD_FUSED = os.environ.get('QT_NO_PROJ_BWD_FUSED') != '1'      # (A/B switch)
-_PROJ_BWD_SHARED = os.environ.get('QT_NO_PROJ_BWD_SHARED') != '1'    # (A/B switch: the first-layer segments too)
+_PROJ_BWD_FUSED = True     # comparator: tests/test_gpu_ops.py sets it False (qt_dense2 per group + the deferred grouped weight gradient)
 _STATS = {'skip_alias': 0}      # (how often a layer's gradient array was completed in place: tests look at it)
 
 
@@ -1186,7 +1185,7 @@ class _MultiConv(Function):
                 continue
             heads = co // (4 * C)
             if (_PROJ_BWD_FUSED and N > 0 and cin == 32 and C == 32 and ctx.needs_input_grad[8 + nseg + s] and W.is_contiguous()
-                    and ((gin > 1 and heads == 1 and A.is_contiguous()) or (_PROJ_BWD_SHARED and gin == 1 and heads > 1 and lda % 4 == 0 and A.data_ptr() % 16 == 0))):
+                    and ((gin > 1 and heads == 1 and A.is_contiguous()) or (gin == 1 and heads > 1 and lda % 4 == 0 and A.data_ptr() % 16 == 0))):
                 # data gradient AND this use's weight gradient in one pass over the gradient planes (csrc/projbwd.hip): the planes are
                 # read once and need not be kept for the deferred grouped weight gradient
                 G_s = gin * heads
@@ -1373,6 +1372,10 @@ def _lstm_backward(gO, gHn, gCn, gates, Cprev, wc, ln, mesh, acc, use_idx, dgrad
     return gG, gCp, psum[0:3], psum[3:7], (psum[7:11] if ln is not None else None)
 
 
+_DGRAD_FUSION = True      # comparator: tests/test_gpu_ops.py sets it False (the backward as qt_lstm_bwd + qt_dense2)
+_WGRAD_FUSION = False     # measured loser with a test of its own: tests/test_gpu_ops.py sets it True (qt_lstm_bwd_fused)
+
+
 class _GateCell(Function):
     """cheb_poly (no activation) + lstm_cell as one op for hidden sizes 8, 16, 32: the gate GEMM runs the cell in its epilogue
     (qt_dense_lstm), so the (N, 4h) pre-activations are never written.  Z = [Za | Zb] (Zb may be None).  The raw output
@@ -1429,17 +1432,17 @@ class _GateCell(Function):
         NB = K * sum(Cs[i] for i in live)
         dgrad = planes = None
         w_fused = False
-        if N > 0 and live and h in (8, 16) and 16 < NB <= 128 and os.environ.get('QT_NO_DGRAD_FUSION') != '1':
+        if N > 0 and live and h in (8, 16) and 16 < NB <= 128 and _DGRAD_FUSION:
             # the cell backward and the data gradient of the gate GEMM in one launch: gG feeds the MFMA loop from LDS
             Wb, _ = _dgrad_weight(W, K, Cs, live, ctx.acc_w)
             planes = [Zs[0].new_empty(K, N, Cs[i]) for i in live]
             osm = int(_clip_resident(ctx.mesh, [Cs[i] for i in live], K))      # planes 1.. slice-major for the fused Clenshaw
             dgrad = (Wb, K, [Cs[i] for i in live], planes, osm)
-            # ... and, on request, the weight gradient too (qt_lstm_bwd_fused: gG never leaves the launch).  OFF by default: at
+            # ... and, with _WGRAD_FUSION, the weight gradient too (qt_lstm_bwd_fused: gG never leaves the launch).  OFF: at
             # the bench shape the persistent launch takes 71 us against 47 + 21 us for this launch plus its share of the
             # deferred weight gradient -- fp32 MFMA issues on the vector pipe, so its 18 us of MFMA time, the cell arithmetic
             # and the memory phases add up instead of overlapping (HISTORY.md section C); 9.17 vs 8.98 ms per step.
-            if (os.environ.get('QT_WGRAD_FUSION') == '1' and not ctx.sm and ctx.needs_input_grad[2] and ctx.acc_w is not None
+            if (_WGRAD_FUSION and not ctx.sm and ctx.needs_input_grad[2] and ctx.acc_w is not None
                     and W.shape[0] <= 128 and NB <= (128 if h == 16 else 64)):
                 ksp = (ctx.Ks + 3) // 4 * 4
                 S = ctx.mesh.cheb_ones(ctx.Ks) if ctx.Ks else None
@@ -1463,15 +1466,12 @@ class _GateCell(Function):
         return gZa, gZb, gW, gCp, gwc, gb, gln, None, None, None, None, None, None, None
 
 
-_FORWARD_ONLY = os.environ.get('QT_NO_FORWARD_ONLY') != '1'      # (A/B switch: 1 = the training launches also without autograd)
-
-
 def _forward_only(*ts):
     """True when no backward can follow: autograd is off, or none of the tensors needs a gradient.  lstm_cell then takes the
     forward-only launch (qt_lstm_infer), which skips the store of the (N, 4h) gate activations.  (The gate GEMM with the cell
     as its epilogue, qt_dense_lstm, keeps its store: skipping it there measured no gain, 28.40 vs 28.66 us per launch at
     hidden 32 and none at hidden 16 -- the launch is bound by its GEMM, not by those bytes.)"""
-    return _FORWARD_ONLY and (not torch.is_grad_enabled() or not any(t is not None and t.requires_grad for t in ts))
+    return not torch.is_grad_enabled() or not any(t is not None and t.requires_grad for t in ts)
 
 
 def _lstm_cell_infer(G, Cprev, wc, b, ln, mesh):
@@ -1674,7 +1674,7 @@ def gather_frame_into(val, mesh, out, t):
     return out
 
 
-_CLIP_REMESH = os.environ.get('QT_NO_CLIP_REMESH') != '1'      # (A/B switch: 1 = the general node / tile kernels everywhere)
+_CLIP_REMESH = True     # comparator: tests/test_gpu_ops.py sets it False (the general node / tile kernels everywhere)
 
 
 def _remesh_raw(dst, src, parts, outs, src_inv, mean, posfeat=None, first_only=False):
@@ -1736,9 +1736,6 @@ class _Remesh(Function):
         if old.N > 0:
             _remesh_raw(old, new, parts, gvals, True, False, first_only=ctx.dec)
         return (None, None, None, None, *gvals)
-
-
-_DEC_FOLD = os.environ.get('QT_NO_DEC_FOLD') != '1'           # (A/B switch)
 
 
 def clip_remesh_ok(old, new):

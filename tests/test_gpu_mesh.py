@@ -140,6 +140,7 @@ def test_stage1_four_workgroups_per_base_cell_equals_one(shape, masked, monkeypa
     DFS order, k_quadtree_stage1q) against one workgroup per base cell: labels, levels, cells, node offsets, CSR bit for bit --
     image sizes that are no multiples of 64 or 32 (quadrants partly or wholly outside the image), land mask + high-interest
     region, base cells that do not split at all (one level-6 leaf), meshes decided by node values of an old mesh, static mode."""
+    from qtmpnn import mesh as mesh_mod
     from qtmpnn import synthetic
     from qtmpnn.mesh import build_mesh
     n, m = shape
@@ -157,7 +158,7 @@ def test_stage1_four_workgroups_per_base_cell_equals_one(shape, masked, monkeypa
     src = torch.from_numpy(img).to(dev())
 
     def build(quads, static, prev=None):
-        monkeypatch.setenv('QT_NO_STAGE1_QUADS', '0' if quads else '1')
+        monkeypatch.setattr(mesh_mod, '_STAGE1_QUADS', quads)
         if prev is None:
             return build_mesh(src=src, thresh=0.1, mask=mask, high_interest_region=hir, static=static)
         return build_mesh(prev=prev, thresh=0.1, mask=mask, high_interest_region=hir, static=static)

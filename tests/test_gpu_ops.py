@@ -712,7 +712,7 @@ def test_projection_backward_in_one_pass_shared_input(N, valid):
 def test_transformer_cell_hidden32_one_pass_projection_backward_equals_two_launch_path(cin_x):
     """A hidden-32 TransformerConv cell, three layers deep (what ice_exp.py:153-162 runs; cin_x = 32: an upper cell of the stack,
     whose X segment is fused as well): the backward with the one-pass projection backward (default) against the data-gradient
-    launch + deferred grouped weight gradient (QT_NO_PROJ_BWD_FUSED).  Deeper layers: same reduction order, but a first-layer
+    launch + deferred grouped weight gradient (ops._PROJ_BWD_FUSED = False).  Deeper layers: same reduction order, but a first-layer
     segment's data gradient is now the sum of four per-head partials -> input gradients at 1e-5 of their scale, like the weight
     gradients (another summation order over the rows)."""
     from model.model import GConvLSTM
@@ -806,7 +806,7 @@ def test_bf16x3_gemm_matches_fp32_gemm():
 
 
 @pytest.mark.parametrize('with_c,h,K', [(True, 16, 3), (False, 16, 3), (True, 8, 3), (True, 32, 3), (True, 32, 7), (False, 32, 5)])
-def test_fused_gate_cell_equals_gemm_then_cell(with_c, h, K):
+def test_fused_gate_cell_equals_gemm_then_cell(with_c, h, K, monkeypatch):
     """qt_dense_lstm (the cell as the gate GEMM's epilogue, h = 8 / 16 / 32) on Z given as two row-strided column views [X | H]
     == qt_dense on the whole Z followed by qt_lstm_fwd, bit for bit, forward and every gradient; a node count that is
     not a multiple of the 128-row tile."""
@@ -830,14 +830,11 @@ def test_fused_gate_cell_equals_gemm_then_cell(with_c, h, K):
         grads = torch.autograd.grad(outs, ins, gs)
         return [o.detach() for o in outs] + list(grads)
 
-    import os
     names = ['O', 'H', 'C'] + [n for n, t in zip(('gZ', 'gW', 'gCp', 'gwc', 'gb', 'gln'), (Z, W, Cp, wc, b, ln)) if t is not None]
-    os.environ['QT_NO_DGRAD_FUSION'] = '1'            # backward as qt_lstm_bwd + qt_dense2: everything bit for bit
-    try:
+    with monkeypatch.context() as mp:
+        mp.setattr(ops, '_DGRAD_FUSION', False)       # backward as qt_lstm_bwd + qt_dense2: everything bit for bit
         for a, r, n in zip(run(True), run(False), names):
             assert torch.equal(a, r), n
-    finally:
-        del os.environ['QT_NO_DGRAD_FUSION']
     # default backward: the cell backward and the data gradient in one launch (qt_lstm_bwd_dgrad, h = 8 / 16 / 32).  The forward and
     # the state / weight gradients stay bit-identical; the parameter partials are summed per 128-node workgroup instead of
     # per grid-stride sweep (fp32 rounding); the data gradient is the exact fp32 product (the split-bf16 form is opt-in:
@@ -1452,13 +1449,14 @@ def test_attention_dropout_epoch_counter():
 
 @pytest.mark.parametrize('name', ['mnist64_h16', 'mnist64_noise_h8'])
 def test_fused_cell_backward_with_weight_gradient_matches_reference(name, monkeypatch):
-    """qt_lstm_bwd_fused (opt-in: QT_WGRAD_FUSION=1 -- cell backward, data gradient and weight gradient of a gate-cell use in
+    """qt_lstm_bwd_fused (opt-in: ops._WGRAD_FUSION -- cell backward, data gradient and weight gradient of a gate-cell use in
     one persistent launch, gG never written): the rollout's loss and all parameter gradients against the reference trace,
     hidden 16 (64-row tiles, 2 + 3 column tiles) and hidden 8."""
     from helpers import golden, grad_close, load_state
     from model.mpnnlstm import masked_mse
     from model.seq2seq import Seq2Seq
-    monkeypatch.setenv('QT_WGRAD_FUSION', '1')
+    from qtmpnn import ops
+    monkeypatch.setattr(ops, '_WGRAD_FUSION', True)
     g = golden(f'rollout_{name}.npz')
     x, y, concat = (torch.from_numpy(g[k]).to(dev()) for k in ('x', 'y', 'concat'))
     model = Seq2Seq(hidden_size=int(g['hidden']), dropout=0.0, thresh=float(g['thresh']), input_timesteps=x.shape[0],

@@ -468,29 +468,47 @@ def test_library_issues_only_kernels_on_the_callers_stream():
 def test_library_keeps_no_mutable_global_state():
     """SURVEY 8(b) / INTEGRATION.md section 2: "no global state, thread-safe per stream" -- the only file-scope variable of
     the library is the thread-local error string; tuning knobs are arguments (round 3 had a process-wide slice-width switch,
-    `qt_cheb_clip_width`; it is the `width` argument of qt_cheb_clip_fwd / _bwd now).  Diagnostics builds (`#ifdef
-    QT_*_TIMING` blocks: in-kernel time stamps, never part of the shipped library) are exempt."""
+    `qt_cheb_clip_width`; it is the `width` argument of qt_cheb_clip_fwd / _bwd now).  Function-scope `static const bool x =
+    getenv(...)` latches are process-wide state too: only the two that select a comparator kernel for a test remain."""
     import glob
     decl = re.compile(r'^(?:static\s+)?(?:thread_local\s+)?(?:unsigned\s+|long\s+)*[A-Za-z_][\w:<>]*[\s\*&]+\**\s*(g_\w+|\w+)\s*(?:\[[^\]]*\])?\s*(?:=[^;(]*)?;\s*$')
-    found = []
+    found, env = [], []
     for f in sorted(glob.glob(os.path.join(ROOT, 'quadtree-mpnnlstm_amd', 'csrc', '*.h*'))):
         text = re.sub(r'/\*.*?\*/', '', open(f).read(), flags=re.S)
-        depth, timing, stack = 0, 0, []
+        depth = 0
         for line in text.split('\n'):
             code = re.sub(r'//.*', '', line).rstrip()
             st = code.strip()
-            if st.startswith('#if'):
-                stack.append(bool(re.search(r'QT_\w*TIMING', st)))
-                timing += stack[-1]
-            elif st.startswith('#endif') and stack:
-                timing -= stack.pop()
+            env += re.findall(r'getenv\s*\(\s*([^)]*?)\s*\)', code)
             if st.startswith('#'):
                 continue
-            if depth == 0 and not timing and st and not st.startswith(('constexpr', 'static constexpr', 'const ', 'static const ',
-                                                                       'using ', 'typedef', 'extern', 'template', 'namespace',
-                                                                       'struct', '}', 'return')):
+            if depth == 0 and st and not st.startswith(('constexpr', 'static constexpr', 'const ', 'static const ',
+                                                        'using ', 'typedef', 'extern', 'template', 'namespace',
+                                                        'struct', '}', 'return')):
                 m = decl.match(st)
                 if m and '(' not in st.split('=')[0]:
                     found.append((os.path.basename(f), st))
             depth += code.count('{') - code.count('}')
     assert [s for _, s in found] == ['static thread_local char g_qt_err[512] = "";'], found
+    assert sorted(env) == ['"QT_GEMM_BF16X3"', '"QT_GEMM_NO_ROW16"'], env
+
+
+# the QT_* variables the Python packages read: each is used by bench.py, by a test, or named in a message a user acts on
+ENV_KEEP = {'QT_LIB_PATH', 'QT_DGRAD_SPLIT_BF16', 'QT_SHARED_GPU', 'QT_DIST_BACKEND', 'QT_NO_TILE_CHEB'}
+
+
+def test_no_experiment_switches_grow_back():
+    """A/B switches live in tests (module flags set with monkeypatch), not in the environment: the packages read no QT_*
+    variable beyond ENV_KEEP, and csrc/ has no experiment (QT_EXP_*) or in-kernel time-stamp (*_TIMING) build branches."""
+    import glob
+    names = set()
+    for f in glob.glob(os.path.join(ROOT, 'quadtree-mpnnlstm_amd', '**', '*.py'), recursive=True):
+        for line in open(f):
+            if 'environ' in line:
+                names |= set(re.findall(r"""environ[^#\n]*?['"](QT_\w+)['"]""", line))
+    assert names <= ENV_KEEP, sorted(names - ENV_KEEP)
+    assert {'QT_LIB_PATH', 'QT_DGRAD_SPLIT_BF16', 'QT_SHARED_GPU', 'QT_NO_TILE_CHEB'} <= names, sorted(names)
+    for f in glob.glob(os.path.join(ROOT, 'quadtree-mpnnlstm_amd', 'csrc', '*')):
+        if os.path.isfile(f) and not f.endswith(('.o', '.so')):
+            text = open(f).read()
+            assert 'QT_EXP_' not in text and '_TIMING' not in text, os.path.basename(f)

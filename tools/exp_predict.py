@@ -1,10 +1,9 @@
 """Eager against graphed NextFramePredictorS2S.predict(), ms per clip, as ice_inf.py / the end of ice_exp.py call it (a loader of
-single clips), and the forward-only cell launches against the training launches under no_grad (QT_NO_FORWARD_ONLY's switch).
+single clips).
     python tools/exp_predict.py mnist     (a) the notebook's predictor: 64 x 64, in = 10 / out = 10, hidden 16, 2 layers, ChebConv
     python tools/exp_predict.py ice       (b) 128 x 128 pixelwise, TransformerConv, hidden 32, 3 conv layers, land mask, climatology,
                                               in = 10 / out = 90 (I10O90)
-    --hidden 32: (a) at hidden 32;  --quick: one timed call per variant; --cells infer|train: only the forward-only or only the training cell launches; --eager:
-    eager predict only (the last three for a profiler run per variant)."""
+    --hidden 32: (a) at hidden 32;  --quick: one timed call per variant; --eager: eager predict only (for a profiler run)."""
 import os
 import sys
 import time
@@ -17,12 +16,11 @@ from torch.utils.data import DataLoader
 
 from helpers import TinyIceDataset, TinyMovingMNISTDataset
 from model.mpnnlstm import NextFramePredictorS2S
-from qtmpnn import ops, synthetic
+from qtmpnn import synthetic
 
 dev = torch.device('cuda', 0)
 kind = sys.argv[1] if len(sys.argv) > 1 else 'mnist'
 quick = '--quick' in sys.argv
-cells = sys.argv[sys.argv.index('--cells') + 1] if '--cells' in sys.argv else 'both'
 eager_only = '--eager' in sys.argv
 hidden = int(sys.argv[sys.argv.index('--hidden') + 1]) if '--hidden' in sys.argv else 16       # (a) only: 32 takes k_gemm_fwd's cell
 
@@ -53,27 +51,24 @@ loader = DataLoader(ds, batch_size=1, shuffle=False)
 n = len(ds)
 ref = None
 print(f'{kind}: {n} clips of {nfp.input_timesteps} in / {nfp.output_timesteps} out, {tuple(ds.image_shape)}')
-for fwd_only in {'both': (True, False), 'infer': (True,), 'train': (False,)}[cells]:
-    ops._FORWARD_ONLY = fwd_only
-    for use_graph in ((False,) if eager_only else (False, True)):
-        nfp.predict(loader, clim, mask=mask, use_graph=use_graph)          # first call: packing, caches, allocator
-        reps = 1 if quick else 3
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(reps):
-            pred = nfp.predict(loader, clim, mask=mask, use_graph=use_graph)
-        torch.cuda.synchronize()
-        ms = (time.perf_counter() - t0) * 1e3 / (reps * n)
-        if ref is None:
-            ref = pred
-        diff = float(np.nanmax(np.abs(pred - ref)))
-        print(f'{kind}: {"graphed" if use_graph else "eager  "} predict, {"forward-only" if fwd_only else "training    "} cell launches: '
-              f'{ms:8.2f} ms per clip (capture included, once per call of {n} clips; max |diff| vs first row {diff:.2e})')
+for use_graph in ((False,) if eager_only else (False, True)):
+    nfp.predict(loader, clim, mask=mask, use_graph=use_graph)          # first call: packing, caches, allocator
+    reps = 1 if quick else 3
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        pred = nfp.predict(loader, clim, mask=mask, use_graph=use_graph)
+    torch.cuda.synchronize()
+    ms = (time.perf_counter() - t0) * 1e3 / (reps * n)
+    if ref is None:
+        ref = pred
+    diff = float(np.nanmax(np.abs(pred - ref)))
+    print(f'{kind}: {"graphed" if use_graph else "eager  "} predict: '
+          f'{ms:8.2f} ms per clip (capture included, once per call of {n} clips; max |diff| vs first row {diff:.2e})')
 
-if eager_only or cells != 'both':
+if eager_only:
     sys.exit(0)
 # steady state of a captured rollout: replay + the one host copy per clip (what every clip after the first of a key costs)
-ops._FORWARD_ONLY = True
 x, _, launch = next(iter(loader))
 x = nfp._clip(x)
 concat = nfp.get_climatology_array(clim, launch) if clim is not None else None
