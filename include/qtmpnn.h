@@ -254,6 +254,25 @@ int qt_sse_rollout_bwd(int nseg, const float* const* outs, const int* out_stride
                        const float* const* sys, const int* Ns, const int32_t* const* n_devs, const float* g, int W,
                        float* const* gouts, void* stream);
 
+/* qt_score_rollout: forecast verification of a rollout (no gradient), shaped like qt_sse_rollout: up to 16 output steps per
+ * call, one mesh per step, grid (ceil(P/1024), B, nseg).  Per (step z, clip b, 1024-pixel tile) and per source s it writes
+ * 8 floats, partial[(((z*B + b)*ntile + tile)*S + s)*8 + slot], over the tile's counted pixels:
+ *   slot 0  n (counted pixels)              slot 4  hits: f > thr and y > thr
+ *   slot 1  sum d, d = f_s[p] - y[p]        slot 5  over (false alarm): f > thr and not y > thr
+ *   slot 2  sum |d|                         slot 6  under (miss): not f > thr and y > thr
+ *   slot 3  sum d^2                         slot 7  correct negatives
+ * Sources: s = 0 the model, f = outs[z][labels[z][b*P + p] * out_strides[z]]; then the dense baselines that are given
+ * (base1, base2; NULL = absent, S counts the sources present): f = base[b*clip_stride + z*step_stride + p] -- a step stride
+ * of 0 makes one frame serve every lead time (persistence), y's strides make it a per-step field (climatology).
+ * A pixel is counted iff 0 <= label < node count (n_devs[z] when given, else Ns[z]: capturable, as qt_gather_frame) and,
+ * when pix_mask (n*m, u8) is given, pix_mask[p] == 0.  Comparisons are strict > in fp32.  No atomics, fixed summation order
+ * (per thread in pixel order, 64-lane butterflies, (w0 + w1) + (w2 + w3)): the same inputs give the same bits. */
+int qt_score_rollout(int nseg, const float* const* outs, const int* out_strides, const int32_t* const* labels,
+                     const int* Ns, const int32_t* const* n_devs, const float* y, int64_t y_clip_stride,
+                     int64_t y_step_stride, const float* base1, int64_t base1_clip_stride, int64_t base1_step_stride,
+                     const float* base2, int64_t base2_clip_stride, int64_t base2_step_stride,
+                     const uint8_t* pix_mask, float thr, int B, int n, int m, float* partial, void* stream);
+
 /* gradient of the qt_sse partial sums with respect to the node values, written as full rows of width W (column 0 carries
  * the value, the rest zeros): gout[i, 0] = 2 * g[0] * (npix[i] * out[i * out_stride] - sy[i]), sy = per-node sum of y. */
 int qt_sse_bwd(const float* out, int out_stride, const float* npix, const float* sy, const float* g, int N,

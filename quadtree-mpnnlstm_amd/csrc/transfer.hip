@@ -522,6 +522,87 @@ __global__ __launch_bounds__(256) void k_sse_multi(LossSeg sg, const float* __re
         partial[((int64_t)z * B + b) * gridDim.x + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+// Forecast verification of a rollout: k_sse_multi's reads with more accumulators, kept per (step, clip, tile) and per
+// source (the model's node values through the labels, then up to two dense baseline fields), no gradient.
+struct ScoreSeg {
+    const float* out[16];         // node values of the step (column 0 of rows of out_stride floats)
+    const int32_t* labels[16];
+    const int32_t* n_dev[16];
+    int out_stride[16], N[16];
+};
+struct ScoreBase {
+    const float* f;               // dense field: step z of clip b starts at f + b*clip_stride + z*step_stride
+    int64_t clip_stride, step_stride;
+};
+
+// Per tile: n, then per source [sum d, sum |d|, sum d^2, hits, over, under]; the correct negatives are n - hits - over - under
+// (every counted pixel falls in exactly one of the four classes, and the counts are integers <= 1024: exact in fp32).
+template <int S>
+__global__ __launch_bounds__(256) void k_score_multi(ScoreSeg sg, const float* __restrict__ y, int64_t y_clip_stride,
+                                                     int64_t y_step_stride, ScoreBase b1, ScoreBase b2,
+                                                     const uint8_t* __restrict__ pix_mask, float thr, int64_t P, int B,
+                                                     float* __restrict__ partial) {
+    constexpr int NV = 1 + 6 * S;
+    __shared__ float red[4][NV];
+    const int b = blockIdx.y, z = blockIdx.z;
+    const float* out = sg.out[z];
+    const int32_t* labels = sg.labels[z] + (int64_t)b * P;
+    const int os = sg.out_stride[z];
+    const int rows = qt_rows(sg.n_dev[z], sg.N[z]);
+    const float* yz = y + z * y_step_stride + b * y_clip_stride;
+    const float* f1 = S > 1 ? b1.f + z * b1.step_stride + b * b1.clip_stride : nullptr;
+    const float* f2 = S > 2 ? b2.f + z * b2.step_stride + b * b2.clip_stride : nullptr;
+    float acc[NV];
+#pragma unroll
+    for (int v = 0; v < NV; ++v) acc[v] = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int64_t p = (int64_t)blockIdx.x * 1024 + k * 256 + threadIdx.x;
+        if (p >= P) continue;
+        const int lab = labels[p];
+        if (lab < 0 || lab >= rows || (pix_mask && pix_mask[p])) continue;
+        const float t = yz[p];
+        const bool ty = t > thr;
+        float f[S];
+        f[0] = out[(int64_t)lab * os];
+        if (S > 1) f[1] = f1[p];
+        if (S > 2) f[2] = f2[p];
+        acc[0] += 1.0f;
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+            float* a = acc + 1 + 6 * s;
+            const float d = f[s] - t;
+            const bool tf = f[s] > thr;
+            a[0] += d;
+            a[1] += fabsf(d);
+            a[2] += d * d;
+            a[3] += (tf && ty) ? 1.0f : 0.0f;
+            a[4] += (tf && !ty) ? 1.0f : 0.0f;
+            a[5] += (!tf && ty) ? 1.0f : 0.0f;
+        }
+    }
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) acc[v] += __shfl_xor(acc[v], d, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int v = 0; v < NV; ++v) red[threadIdx.x >> 6][v] = acc[v];
+    }
+    __syncthreads();
+    if (threadIdx.x < 8 * S) {
+        const int s = threadIdx.x >> 3, slot = threadIdx.x & 7;
+        auto total = [&](int v) { return (red[0][v] + red[1][v]) + (red[2][v] + red[3][v]); };
+        const int v0 = 1 + 6 * s;
+        float r;
+        if (slot == 0) r = total(0);
+        else if (slot < 7) r = total(v0 + slot - 1);
+        else r = total(0) - total(v0 + 3) - total(v0 + 4) - total(v0 + 5);
+        partial[((((int64_t)z * B + b) * gridDim.x + blockIdx.x) * S + s) * 8 + slot] = r;
+    }
+}
+
 __global__ void k_sse_bwd_multi(LossSeg sg, const float* __restrict__ g, int W) {
     const int z = blockIdx.y;
     const unsigned idx = blockIdx.x * blockDim.x + threadIdx.x;
@@ -573,6 +654,35 @@ extern "C" int qt_sse_rollout(int nseg, const float* const* outs, const int* out
     a.out_stride = 1; a.out_coff = 0; a.tiles_r = qt_cdiv(n, 64); a.tiles_c = qt_cdiv(m, 64);
     hipLaunchKernelGGL(k_pool_targets, dim3(B * a.tiles_r * a.tiles_c, 1, nseg), dim3(256), 0, (hipStream_t)stream, a, sg,
                        y_step_stride);
+    QT_LAUNCHED();
+    return QT_OK;
+}
+
+extern "C" int qt_score_rollout(int nseg, const float* const* outs, const int* out_strides, const int32_t* const* labels,
+                                const int* Ns, const int32_t* const* n_devs, const float* y, int64_t y_clip_stride,
+                                int64_t y_step_stride, const float* base1, int64_t base1_clip_stride, int64_t base1_step_stride,
+                                const float* base2, int64_t base2_clip_stride, int64_t base2_step_stride,
+                                const uint8_t* pix_mask, float thr, int B, int n, int m, float* partial, void* stream) {
+    QT_ARG(nseg >= 1 && nseg <= 16, "nseg must be 1..16");
+    QT_ARG(outs && out_strides && labels && Ns && n_devs && y && partial, "null pointer");
+    QT_ARG(B > 0 && B <= 65535 && n > 0 && m > 0, "bad sizes");
+    QT_ARG(y_clip_stride >= 0 && y_step_stride >= 0 && base1_clip_stride >= 0 && base1_step_stride >= 0 &&
+           base2_clip_stride >= 0 && base2_step_stride >= 0, "negative stride");
+    ScoreSeg sg = {};
+    for (int z = 0; z < nseg; ++z) {
+        QT_ARG(labels[z] && Ns[z] >= 0 && (outs[z] || Ns[z] == 0) && out_strides[z] >= 1, "bad segment");
+        sg.out[z] = outs[z]; sg.out_stride[z] = out_strides[z]; sg.labels[z] = labels[z]; sg.N[z] = Ns[z]; sg.n_dev[z] = n_devs[z];
+    }
+    // the sources present, in order: the kernel's partial rows are sized for them
+    ScoreBase bs[2] = {};
+    int nb = 0;
+    if (base1) bs[nb++] = {base1, base1_clip_stride, base1_step_stride};
+    if (base2) bs[nb++] = {base2, base2_clip_stride, base2_step_stride};
+    const int64_t P = (int64_t)n * m;
+    const dim3 grid(qt_cdiv(P, 1024), B, nseg);
+    auto k = nb == 0 ? k_score_multi<1> : nb == 1 ? k_score_multi<2> : k_score_multi<3>;
+    hipLaunchKernelGGL(k, grid, dim3(256), 0, (hipStream_t)stream, sg, y, y_clip_stride, y_step_stride, bs[0], bs[1], pix_mask, thr,
+                       P, B, partial);
     QT_LAUNCHED();
     return QT_OK;
 }

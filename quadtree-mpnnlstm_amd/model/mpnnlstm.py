@@ -365,28 +365,38 @@ class NextFramePredictorS2S(NextFramePredictor):
         state an eager rollout advances is advanced by a replay too: Python's `random` (unroll_output draws once per output step)
         and the attention-dropout seed counter.  In train() mode every replay draws new dropout masks (torch's graph-safe RNG
         for the decoder, the device counter ops.dropout_epoch for attention)."""
-        import random
-        model = self.model
-        model.static_shapes = True
-        T_out = self.output_timesteps
+        self.model.static_shapes = True
         B = 1 if x.dim() == 4 else x.shape[0]
         sx = x.clone()
         sc = concat_layers.clone() if concat_layers is not None else None
-        out = torch.empty(B, T_out, x.shape[-3], x.shape[-2], 1, device=x.device)
+        out = torch.empty(B, self.output_timesteps, x.shape[-3], x.shape[-2], 1, device=x.device)
 
         def rollout():
             with torch.no_grad():
-                y_hat, meshes = model(sx, concat_layers=sc, teacher_forcing_ratio=0, mask=mask,
-                                      high_interest_region=high_interest_region, graph_structure=graph_structure)
+                y_hat, meshes = self.model(sx, concat_layers=sc, teacher_forcing_ratio=0, mask=mask,
+                                           high_interest_region=high_interest_region, graph_structure=graph_structure)
                 for t, (o, ms) in enumerate(zip(y_hat, meshes)):
                     ops.gather_frame_into(o, ms, out, t)
             return out
 
+        def load(x, concat_layers=None):
+            sx.copy_(x)
+            if sc is not None:
+                sc.copy_(concat_layers)
+        return self._graphed_inference(rollout, load)
+
+    def _graphed_inference(self, body, load):
+        """Warm-up, capture and replay of a no-grad inference body (make_graphed_rollout, make_graphed_scores).  body() reads the
+        caller's static inputs and returns a device tensor; load(...) copies a batch into them.  The returned replay(...) loads,
+        replays, advances the host state like an eager rollout and returns the capture's result tensor; replay.warmup is a copy
+        of the eager warm-up's result."""
+        import random
+        T_out = self.output_timesteps
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         calls0 = ops._ATTN_CALLS[0]
         with torch.cuda.stream(side):
-            warm = rollout().clone()
+            warm = body().clone()
         torch.cuda.current_stream().wait_stream(side)
         calls1 = ops._ATTN_CALLS[0]
         # the capture records launches without running them: whatever host state it advances is put back, and every replay
@@ -394,7 +404,7 @@ class NextFramePredictorS2S(NextFramePredictor):
         rstate = random.getstate()
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph, stream=side, capture_error_mode='thread_local'):
-            rollout()
+            result = body()
         random.setstate(rstate)
         ops._ATTN_CALLS[0] = calls1
         from qtmpnn import mesh as _mesh
@@ -402,17 +412,39 @@ class NextFramePredictorS2S(NextFramePredictor):
         check_tile_errors(always=uses_tiles)
 
         @on_device(lambda *a, **k: self.device)
-        def replay(x, concat_layers=None):
-            sx.copy_(x)
-            if sc is not None:
-                sc.copy_(concat_layers)
+        def replay(*a, **k):
+            load(*a, **k)
             graph.replay()
             for _ in range(T_out):
                 random.random()
             ops._ATTN_CALLS[0] += calls1 - calls0
-            return out
+            return result
         replay.warmup = warm
         return replay
+
+    @on_device(lambda self, *a, **k: self.device)
+    def make_graphed_scores(self, x, y, concat_layers=None, mask=None, high_interest_region=None, graph_structure=None,
+                            threshold=0.15):
+        """make_graphed_rollout with the verification sums in place of the frames: the capture holds the rollout and
+        ops.rollout_scores (model, persistence = channel 0 of the last input frame, climatology = concat_layers when given), no
+        frame gather.  Returns `scores(x, y, concat) -> (T_out, B, S, 8)` float64 device tensor; `scores.warmup` is the given
+        batch's."""
+        self.model.static_shapes = True
+        sx, sy = x.clone(), y.clone()
+        sc = concat_layers.clone() if concat_layers is not None else None
+
+        def scores():
+            with torch.no_grad():
+                y_hat, meshes = self.model(sx, concat_layers=sc, teacher_forcing_ratio=0, mask=mask,
+                                           high_interest_region=high_interest_region, graph_structure=graph_structure)
+                return ops.rollout_scores(y_hat, meshes, sy, threshold, persistence=sx[..., -1, :, :, 0], climatology=sc)
+
+        def load(x, y, concat_layers=None):
+            sx.copy_(x)
+            sy.copy_(y)
+            if sc is not None:
+                sc.copy_(concat_layers)
+        return self._graphed_inference(scores, load)
 
     @on_device(lambda self, *a, **k: self.device)
     def train(self, loader_train, loader_test, climatology=None, n_epochs=200, lr=0.01, lr_decay=0.95, mask=None,
@@ -553,5 +585,44 @@ class NextFramePredictorS2S(NextFramePredictor):
                        graph_structure=graph_structure)
         return records
 
-    def score(self, x, y, rollout=None):
-        pass
+    @on_device(lambda self, *a, **k: self.device)
+    def score(self, loader, climatology=None, mask=None, high_interest_region=None, graph_structure=None, use_graph=False,
+              threshold=0.15):
+        """Forecast verification over a loader -> qtmpnn.score.Scores (beyond the reference, whose score() is empty; the numbers
+        are those its ice_results.py computes from predict()'s array: masked RMSE and ice / no-ice accuracy per launch date and
+        lead time, for the model and the baselines).
+
+        predict()'s loop and arguments, with the loader's y: every batch leaves eight sums per (lead time, clip, source) on the
+        device (ops.rollout_scores: the head's outputs read through the labels, no frame is built) and makes one host copy of
+        them.  Sources: 'model', 'persistence' (channel 0 of the last input frame at every lead time) and, with `climatology`,
+        'climatology' (the daily normals the decoder gets).  `threshold` separates ice from no ice (strict >); with binary=True
+        the outputs are probabilities and a caller passes 0.5.  use_graph=True replays rollout + sums as one hipGraph per
+        distinct batch shape, as predict(use_graph=True) does (make_graphed_scores)."""
+        from qtmpnn.score import Scores
+        self.model.to(self.device)
+        sums = []
+        graphed, static0 = {}, self.model.static_shapes
+        try:
+            for x, y, launch_date in loader:
+                x, y = self._clip(x), self._clip(y)
+                concat = self.get_climatology_array(climatology, launch_date) if climatology is not None else None
+                if use_graph:
+                    key = (tuple(x.shape), tuple(y.shape), None if concat is None else tuple(concat.shape), self.model.training)
+                    if key not in graphed:
+                        graphed[key] = self.make_graphed_scores(x, y, concat, mask=mask, high_interest_region=high_interest_region,
+                                                                graph_structure=graph_structure, threshold=threshold)
+                        part = graphed[key].warmup
+                    else:
+                        part = graphed[key](x, y, concat)
+                else:
+                    with torch.no_grad():
+                        y_hat, meshes = self.model(x, concat_layers=concat, teacher_forcing_ratio=0, mask=mask,
+                                                   high_interest_region=high_interest_region, graph_structure=graph_structure)
+                        part = ops.rollout_scores(y_hat, meshes, y, threshold, persistence=x[..., -1, :, :, 0], climatology=concat)
+                sums.append(np.moveaxis(part.cpu().numpy(), 0, 1))      # (T, B, S, 8) -> (B, T, S, 8)
+        finally:
+            graphed.clear()
+            self.model.static_shapes = static0
+        check_tile_errors(always=True)
+        sources = ('model', 'persistence') + (('climatology',) if climatology is not None else ())
+        return Scores(np.concatenate(sums, 0), sources)

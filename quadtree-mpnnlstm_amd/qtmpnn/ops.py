@@ -1956,6 +1956,52 @@ def rollout_sse_partials(outputs, y, meshes):
     return _RolloutSSE.apply(y.view(B, T, meshes[0].P), tuple(meshes), *outs)
 
 
+def rollout_scores(outputs, meshes, y, threshold=0.15, persistence=None, climatology=None, per_tile=False):
+    """Verification sums of a rollout, float64 (T, B, S, 8) on the device (qt_score_rollout; the slot table is in
+    include/qtmpnn.h): per output step, clip and source [n, sum d, sum |d|, sum d^2, hits, over, under, correct negatives] over
+    the counted pixels, d = forecast - y, the classes at `threshold` (strict >).  Sources: the model (outputs[t] (N_t, 1) or
+    (N_t, W): column 0 is read in place through the step's labels), then the dense baselines that are given: `persistence`
+    (B*P values, one frame for every lead time, or B*T*P) and `climatology` (likewise).  y: B*T*P values laid out (B, T, P).
+    Pixels without a node, and those under meshes[0].loss_mask, are not counted.  No autograd, no host read: capturable.
+    per_tile=True returns the launch's own fp32 partials (T, B, ceil(P/1024), S, 8) instead of their float64 sum over the tiles."""
+    import ctypes
+    if not outputs or len(outputs) != len(meshes):
+        raise ValueError(f'rollout_scores: {len(outputs)} output steps for {len(meshes)} meshes')
+    outs = [o.detach() for o in outputs]        # (a column view of the head's 4-wide rows is read through its row stride)
+    for o in outs:
+        if not (o.is_cuda and o.dtype == torch.float32 and o.dim() == 2 and o.shape[1] >= 1):
+            raise ValueError(f'rollout_scores: outputs must be fp32 (N, W) matrices on the GPU, got {o.dtype} {tuple(o.shape)} on {o.device}')
+    m0 = meshes[0]
+    B, T, P = m0.B, len(outs), m0.P
+
+    def dense(t, what, counts):
+        if t.numel() not in counts:
+            raise ValueError(f'rollout_scores: {what} has {t.numel()} elements for {B} clip(s) x {T} steps of {P} pixels '
+                             f'(expected {" or ".join(str(c) for c in counts)})')
+        t = t.detach().to(outs[0].device, torch.float32).contiguous()
+        return (t, T * P, P) if t.numel() == B * T * P else (t, P, 0)      # (field, clip stride, step stride)
+    y = dense(y, 'y', (B * T * P,))[0]
+    bases = [dense(t, name, (B * P, B * T * P)) for t, name in ((persistence, 'persistence'), (climatology, 'climatology'))
+             if t is not None]
+    S = 1 + len(bases)
+    bases += [(None, 0, 0)] * (2 - len(bases))
+    nt = -(P // -1024)
+    part = outs[0].new_empty(T, B, nt, S, 8)
+    vp, ip = ctypes.c_void_p, ctypes.c_int
+    for z0 in range(0, T, 16):
+        sl = slice(z0, min(z0 + 16, T))
+        n = sl.stop - sl.start
+        base_args = []
+        for t, cs, ss in bases:
+            base_args += [None if t is None else t.data_ptr() + 4 * z0 * ss, cs, ss]
+        _lib.call('qt_score_rollout', n, (vp * n)(*[o.data_ptr() for o in outs[sl]]),
+                  (ip * n)(*[max(o.stride(0), 1) for o in outs[sl]]), (vp * n)(*[ms.labels.data_ptr() for ms in meshes[sl]]),
+                  (ip * n)(*[o.shape[0] for o in outs[sl]]), (vp * n)(*[ptr(ms.n_dev) for ms in meshes[sl]]),
+                  y.data_ptr() + 4 * z0 * P, T * P, P, *base_args, ptr(m0.loss_mask), float(threshold), B, m0.n, m0.m,
+                  ptr(part[z0:]))
+    return part if per_tile else part.double().sum(2)
+
+
 def step_sse_partials(out, y, mesh):
     """`out` (N, 1); when it is column 0 of a wider contiguous matrix (the head's 4-wide output) the op runs on that
     matrix, so the gradient is written once as full rows instead of slice_backward's zero-fill + copy."""
