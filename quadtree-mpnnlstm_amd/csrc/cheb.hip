@@ -591,7 +591,6 @@ __global__ __launch_bounds__(256, (NT == 4 && CELL != 0) ? QT_GEMM_OCC4C : (NT =
 // Work split: workgroup b owns the contiguous units [U b / G, U (b + 1) / G) of the U = ceil(rows / 32) units (valid rows
 // read on the device), its wave w takes every 8th of them.
 constexpr int GATE_P_MAXK = 256, GATE_P_MAXPITCH = GATE_P_MAXK + 8;
-static constexpr int QT_GATE_STAGGER = 0;
 template <int NT, int LPN, int R>
 __global__ __launch_bounds__(512, 2) void k_gate_cell_p(GemmArgs g, int pitch) {
     using namespace qtcell;
@@ -632,19 +631,39 @@ __global__ __launch_bounds__(512, 2) void k_gate_cell_p(GemmArgs g, int pitch) {
     int unit = u0 + wave;
     if (unit >= u1) return;
     const int nj = (g.K + 7) >> 3;
-    // Every A load is UNCONDITIONAL (row and quad clamped to valid ones, the value zeroed by a select): a load inside a
-    // branch makes hipcc's s_waitcnt bookkeeping fall back to draining the whole queue at the next use, which serialised
-    // the stream (41 us per launch at the bench shape, whatever the ring depth).
-    const int64_t last_row = rows - 1;
-    auto ldq = [&](int64_t row, bool ok, int j) {
+    // Every A load is UNCONDITIONAL (row and quad clamped to valid ones): a load inside a branch makes hipcc's s_waitcnt
+    // bookkeeping fall back to draining the whole queue at the next use, which serialised the stream (41 us per launch at
+    // the bench shape, whatever the ring depth).  A row past the valid ones re-reads the last valid row: an accumulator
+    // row depends on its own A row only and the epilogue stores no such row, so its values need no zeroing.  Only a quad
+    // past the last one is zeroed (an odd quad count: the upper half of the last k-group; with R > 0 that can only be
+    // ring slot R - 1, as nj == R means nquad >= 2 R - 1).  The row is a 32-bit int (rows is one), so row x stride is one
+    // 32 x 32 -> 64-bit multiply-add; with R > 0 the table entries of slot j are the same for every unit and stay in registers.
+    const int last_row = rows - 1;
+    const float* qp[R > 0 ? R : 1];
+    int qs[R > 0 ? R : 1];
+    if constexpr (R > 0) {
+#pragma unroll
+        for (int j = 0; j < R; ++j) {
+            const int q = 2 * j + half, qc = q < nquad ? q : 0;
+            qp[j] = qptr[qc];
+            qs[j] = qstr[qc];
+        }
+    }
+    auto ldq = [&](int row, int j) {          // row: already clamped to the valid ones
         const int q = 2 * j + half;
-        const bool use = ok && q < nquad;
-        const int qc = q < nquad ? q : 0;
-        const float4 r = gload4(qptr[qc] + (row <= last_row ? row : last_row) * qstr[qc]);
-        return make_float4(use ? r.x : 0.f, use ? r.y : 0.f, use ? r.z : 0.f, use ? r.w : 0.f);
+        if constexpr (R > 0) {
+            const float4 r = gload4(qp[j] + (int64_t)row * qs[j]);
+            if (j < R - 1) return r;
+            const bool use = q < nquad;
+            return make_float4(use ? r.x : 0.f, use ? r.y : 0.f, use ? r.z : 0.f, use ? r.w : 0.f);
+        } else {
+            const bool use = q < nquad;
+            const int qc = use ? q : 0;
+            const float4 r = gload4(qptr[qc] + (int64_t)row * qstr[qc]);
+            return make_float4(use ? r.x : 0.f, use ? r.y : 0.f, use ? r.z : 0.f, use ? r.w : 0.f);
+        }
     };
-    int64_t my_row = (int64_t)unit * 32 + l32;
-    bool row_ok = my_row < rows;
+    int my_row = min(unit * 32 + l32, last_row);
     // The A operand is streamed once and shared with no other wave: it goes global -> VGPR, and what bounds the stream is the
     // bytes a CU keeps in flight (8 waves x 4 quads of 1 KiB = 32 KiB ran at 2.5 TB/s).  R > 0: the ring holds a WHOLE unit
     // (nj <= R steps, the j loop fully unrolled so that ring[j] is a fixed register): step j consumes ring[j] and at once
@@ -652,17 +671,9 @@ __global__ __launch_bounds__(512, 2) void k_gate_cell_p(GemmArgs g, int pitch) {
     // R == 0 (any nj): the 4-deep rotating ring of k_gemm_fwd.
     float4 ring[R > 0 ? R : 4];
 #pragma unroll
-    for (int j = 0; j < (R > 0 ? R : 4); ++j) ring[j] = ldq(my_row, row_ok, j);
+    for (int j = 0; j < (R > 0 ? R : 4); ++j) ring[j] = ldq(my_row, j);
     const int nl = lane / LPN, j0 = (lane - nl * LPN) * 4;
     const CellParams cpar = cell_params(g.wc, g.bias, g.ln, h, j0);      // in registers for the whole launch
-    // Stagger: the two waves of a SIMD (w and w + 4) run the same program; started together they sit in their MFMA chains
-    // together (matrix pipe shared: 2 x 6.7k cycles) and then in their epilogues together (VALU issue shared: the cell's
-    // sigmoids / tanhs are ~6k cycles per unit) -- in-kernel stamps showed 7.7 + 7.5 us per unit that way.  Waves 4..7 start
-    // half a unit late, so one wave's epilogue runs beside the other's MFMA chain.
-    if (wave >= 4) {
-#pragma unroll 1
-        for (int i = 0; i < QT_GATE_STAGGER; ++i) __builtin_amdgcn_s_sleep(64);       // 64 x 64 clocks per trip
-    }
     while (true) {
         // this unit's previous cell states (one node per epilogue pass and lane group): requested before the MFMA chain
         float4 cpre[NPASS];
@@ -674,8 +685,7 @@ __global__ __launch_bounds__(512, 2) void k_gate_cell_p(GemmArgs g, int pitch) {
         }
         const int nxt = unit + 8;
         const bool has_next = nxt < u1;
-        const int64_t nrow = (int64_t)nxt * 32 + l32;
-        const bool nok = has_next && nrow < rows;
+        const int nrow = has_next ? min(nxt * 32 + l32, last_row) : last_row;       // (no next unit: a valid address, unused values)
         f32x16 acc[NT];
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt)
@@ -698,19 +708,19 @@ __global__ __launch_bounds__(512, 2) void k_gate_cell_p(GemmArgs g, int pitch) {
 #pragma unroll
             for (int j = 0; j < R; ++j) {     // nj == R (the host picks the instance): straight-line code, no branch
                 const float4 a = ring[j];
-                ring[j] = ldq(nrow, nok, j);
+                ring[j] = ldq(nrow, j);
                 step(a, j);
             }
         } else {
             for (int j = 0; j < nj; ++j) {
                 const float4 a = ring[0];
                 ring[0] = ring[1]; ring[1] = ring[2]; ring[2] = ring[3];
-                ring[3] = ldq(my_row, row_ok, j + 4);
+                ring[3] = ldq(my_row, j + 4);
                 step(a, j);
             }
             // the next unit's first quads fly during this unit's epilogue
 #pragma unroll
-            for (int j = 0; j < 4; ++j) ring[j] = ldq(nrow, nok, j);
+            for (int j = 0; j < 4; ++j) ring[j] = ldq(nrow, j);
         }
         // epilogue: accumulator columns -> this wave's staging rows -> h / 4 lanes per node
         __builtin_amdgcn_wave_barrier();
@@ -727,7 +737,7 @@ __global__ __launch_bounds__(512, 2) void k_gate_cell_p(GemmArgs g, int pitch) {
             const float* cs = Cs + row * CP + j0;
             const F4 gi = ld4(cs), gf = ld4(cs + h), gc = ld4(cs + 2 * h), go = ld4(cs + 3 * h);
             const F4 cp = {{cpre[ps].x, cpre[ps].y, cpre[ps].z, cpre[ps].w}};
-            const CellOut r = cell_forward<LPN>(gi, gf, gc, go, cp, cpar, h);
+            const CellOut r = cell_forward<LPN>(gi, gf, gc, go, cp, cpar);
             if (node < rows) {
                 if (g.O) st4(g.O + node * h + j0, r.Og);
                 st4(g.Hn + node * h + j0, r.hn);
@@ -740,7 +750,7 @@ __global__ __launch_bounds__(512, 2) void k_gate_cell_p(GemmArgs g, int pitch) {
             }
         }
         if (!has_next) break;
-        unit = nxt; my_row = nrow; row_ok = nok;
+        unit = nxt; my_row = nrow;
     }
 }
 
@@ -1498,7 +1508,7 @@ __global__ __launch_bounds__(256, BG ? QT_DGRAD_OCC : 2) void k_dgrad_cell(Dgrad
     const int l32 = lane & 31, half = lane >> 5;
     const int64_t i0 = (int64_t)blockIdx.x * BM;
     const int64_t rows = qt_rows(g.n_dev, g.M);
-    const int h = g.h;
+    constexpr int h = 4 * LPN;     // (== g.h: the host picks the instance by it)
     if (i0 >= rows) return;        // past the valid rows: nothing to add to the partials (the slab rows start at zero)
     // W chunk (all of it: K = 4h fits one pass) -> LDS; independent of the cell phase below
     if constexpr (!BG) {
@@ -1544,7 +1554,7 @@ __global__ __launch_bounds__(256, BG ? QT_DGRAD_OCC : 2) void k_dgrad_cell(Dgrad
                 }
             }
             const CellBwdOut o = cell_backward<LPN>(I, F, T, Og, cp, gyh, gyc, go_in, wci, wcf, wco, gam_h, gam_c,
-                                                    g.ln != nullptr, h, acc);
+                                                    g.ln != nullptr, acc);
             float* as = As + r * PITCH + j0;
             st4(as, o.ggi); st4(as + h, o.ggf); st4(as + 2 * h, o.ggc); st4(as + 3 * h, o.ggo);
             if (ok) {
@@ -1602,9 +1612,10 @@ __global__ __launch_bounds__(256, BG ? QT_DGRAD_OCC : 2) void k_dgrad_cell(Dgrad
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
             if constexpr (BG) {
-                const int c = nt * 32 + l32;                  // (columns past NB: clamped load, zeroed value)
-                const float4 w = gload4(g.BT + (int64_t)(c < g.NB ? c : 0) * K + 8 * j + 4 * half);
-                bq[nt] = c < g.NB ? w : make_float4(0.f, 0.f, 0.f, 0.f);
+                // (columns past NB: a clamped load.  An accumulator column depends on its own column of the operand only and
+                // the epilogue stores no column past NB, so the value needs no zeroing: 4 NT selects per k-group saved)
+                const int c = nt * 32 + l32;
+                bq[nt] = gload4(g.BT + (int64_t)(c < g.NB ? c : 0) * K + 8 * j + 4 * half);
             } else {
                 bq[nt] = *reinterpret_cast<const float4*>(&Bt[(nt * 32 + l32) * PITCH + 8 * j + 4 * half]);
             }
@@ -1836,7 +1847,7 @@ __global__ __launch_bounds__(4 * TR, 2) void k_cell_bwd_fused(CellBwdFusedArgs f
                     gam_c = ld4(g.ln + 2 * h + j0);
                 }
                 const CellBwdOut o = cell_backward<LPN>(I, F, T, Og, cp, gyh, gyc, go_in, wci, wcf, wco, gam_h, gam_c,
-                                                        g.ln != nullptr, h, pacc);
+                                                        g.ln != nullptr, pacc);
                 float* as = Gt + crow * GP + j0;
                 st4(as, o.ggi); st4(as + h, o.ggf); st4(as + 2 * h, o.ggc); st4(as + 3 * h, o.ggo);
                 if (ok && g.gCprev) st4(g.gCprev + node * h + j0, o.gcp);

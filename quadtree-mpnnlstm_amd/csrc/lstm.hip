@@ -85,7 +85,7 @@ __global__ __launch_bounds__(256) void k_lstm_bwd(const float* __restrict__ gO, 
         if (gCn) gyc = ld4(gCn + node * ld_gc + j0);
         F4 go_in = {{0, 0, 0, 0}};
         if (gO) go_in = ld4(gO + node * ld_go + j0);
-        const CellBwdOut r = cell_backward<LPN>(I, F, T, Og, cp, gyh, gyc, go_in, wci, wcf, wco, gam_h, gam_c, ln != nullptr, h, acc);
+        const CellBwdOut r = cell_backward<LPN>(I, F, T, Og, cp, gyh, gyc, go_in, wci, wcf, wco, gam_h, gam_c, ln != nullptr, acc);
         const F4 &ggi = r.ggi, &ggf = r.ggf, &ggc = r.ggc, &ggo = r.ggo, &gcp = r.gcp;
         float* gg = gG + node * 4 * h + j0;
         st4(gg, ggi);
@@ -109,7 +109,7 @@ __global__ __launch_bounds__(256) void k_head_fwd(const float* __restrict__ O, c
     const F4 x = ld4(O + node * ld_o + j0);
     F4 xh;
     float r;
-    layer_norm<LPN>(x, h, &xh, &r);
+    layer_norm<LPN>(x, &xh, &r);
     const F4 gm = ld4(ln_o + j0), bt = ld4(ln_o + h + j0);
     F4 y;
 #pragma unroll
@@ -143,7 +143,7 @@ __global__ __launch_bounds__(256) void k_head_bwd(const float* __restrict__ gZ, 
         const F4 x = ld4(O + node * ld_o + j0);
         F4 xh;
         float r;
-        layer_norm<LPN>(x, h, &xh, &r);
+        layer_norm<LPN>(x, &xh, &r);
         F4 gy = ld4(gZ + node * (gZb ? h : hp) + j0);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -151,7 +151,7 @@ __global__ __launch_bounds__(256) void k_head_bwd(const float* __restrict__ gZ, 
             acc[0][k] += gy.v[k] * xh.v[k];
             acc[1][k] += gy.v[k];
         }
-        st4(gO + node * h + j0, layer_norm_bwd<LPN>(gy, gm, xh, r, h));
+        st4(gO + node * h + j0, layer_norm_bwd<LPN>(gy, gm, xh, r));
         if (li == 0 && gconcat) gconcat[node] = gZb ? gZb[node * (hp - h)] : gZ[node * hp + h];
     }
     block_param_reduce<LPN, 2>(acc, h, sm, part + (int64_t)blockIdx.x * 2 * h, accumulate);

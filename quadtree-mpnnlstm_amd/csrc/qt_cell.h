@@ -23,10 +23,31 @@ __device__ __forceinline__ float tanhf_(float x) {
     return copysignf(ax < 0.125f ? small : big, x);
 }
 
+// v of lane l ^ D for the lane distances a DPP operand modifier can express (quad permutes for 1 and 2, a rotation of the
+// 16-lane row by 8): the exchange rides on the add itself (v_add_f32_dpp), where __shfl_xor is a ds_bpermute_b32 -- an LDS
+// instruction, its lane-index arithmetic and an lgkmcnt wait per step.  Same operands, same order: the same bits.  The
+// source lane must be active (every lane of a node's group calls these together).
+template <int D>
+__device__ __forceinline__ float lane_xor(float v) {
+    static_assert(D == 1 || D == 2 || D == 8, "no DPP control for this distance");
+    constexpr int ctrl = D == 1 ? 0xB1 /* quad_perm:[1,0,3,2] */ : D == 2 ? 0x4E /* quad_perm:[2,3,0,1] */ : 0x128 /* row_ror:8 */;
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), ctrl, 0xf, 0xf, true));
+}
+// v of lane l + D of the same 16-lane row (row_shl:D; zero past the row's end)
+template <int D>
+__device__ __forceinline__ float lane_up(float v) {
+    static_assert(D >= 1 && D <= 15, "row_shl:1 .. 15");
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x100 + D, 0xf, 0xf, true));
+}
+
 template <int LPN>
 __device__ __forceinline__ float group_sum(float v) {
+    if constexpr (LPN > 1) v += lane_xor<1>(v);
+    if constexpr (LPN > 2) v += lane_xor<2>(v);
+    if constexpr (LPN > 4) v += __shfl_xor(v, 4, 64);
+    if constexpr (LPN > 8) v += lane_xor<8>(v);
 #pragma unroll
-    for (int d = 1; d < LPN; d <<= 1) v += __shfl_xor(v, d, 64);
+    for (int d = 16; d < LPN; d <<= 1) v += __shfl_xor(v, d, 64);
     return v;
 }
 
@@ -41,17 +62,20 @@ __device__ __forceinline__ void st4(float* p, const F4& a) {
     *reinterpret_cast<float4*>(p) = make_float4(a.v[0], a.v[1], a.v[2], a.v[3]);
 }
 
-// y = gamma * xhat + beta over the group's h values; returns xhat and rstd
+// y = gamma * xhat + beta over the group's h = 4 LPN values; returns xhat and rstd.  The means are products with the exact
+// 1 / h (h is a power of two: the same bits as the IEEE division by a run-time h, which costs ~10 instructions each).
 template <int LPN>
-__device__ __forceinline__ void layer_norm(const F4& x, int h, F4* xhat, float* rstd) {
-    const float mean = group_sum<LPN>((x.v[0] + x.v[1]) + (x.v[2] + x.v[3])) / (float)h;
+__device__ __forceinline__ void layer_norm(const F4& x, F4* xhat, float* rstd) {
+    static_assert((LPN & (LPN - 1)) == 0, "1 / h must be exact");
+    constexpr float inv_h = 1.0f / (4 * LPN);
+    const float mean = group_sum<LPN>((x.v[0] + x.v[1]) + (x.v[2] + x.v[3])) * inv_h;
     float sq = 0.0f;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const float d = x.v[k] - mean;
         sq += d * d;
     }
-    const float var = group_sum<LPN>(sq) / (float)h;
+    const float var = group_sum<LPN>(sq) * inv_h;
     *rstd = 1.0f / sqrtf(var + LN_EPS);
 #pragma unroll
     for (int k = 0; k < 4; ++k) xhat->v[k] = (x.v[k] - mean) * (*rstd);
@@ -59,7 +83,8 @@ __device__ __forceinline__ void layer_norm(const F4& x, int h, F4* xhat, float* 
 
 // gx = rstd * (gxh - mean(gxh) - xhat * mean(gxh * xhat)),  gxh = gy * gamma
 template <int LPN>
-__device__ __forceinline__ F4 layer_norm_bwd(const F4& gy, const F4& gamma, const F4& xhat, float rstd, int h) {
+__device__ __forceinline__ F4 layer_norm_bwd(const F4& gy, const F4& gamma, const F4& xhat, float rstd) {
+    constexpr float inv_h = 1.0f / (4 * LPN);
     F4 gxh;
     float s1 = 0.0f, s2 = 0.0f;
 #pragma unroll
@@ -68,8 +93,8 @@ __device__ __forceinline__ F4 layer_norm_bwd(const F4& gy, const F4& gamma, cons
         s1 += gxh.v[k];
         s2 += gxh.v[k] * xhat.v[k];
     }
-    s1 = group_sum<LPN>(s1) / (float)h;
-    s2 = group_sum<LPN>(s2) / (float)h;
+    s1 = group_sum<LPN>(s1) * inv_h;
+    s2 = group_sum<LPN>(s2) * inv_h;
     F4 gx;
 #pragma unroll
     for (int k = 0; k < 4; ++k) gx.v[k] = rstd * (gxh.v[k] - s1 - xhat.v[k] * s2);
@@ -108,7 +133,7 @@ __device__ __forceinline__ CellParams cell_params(const float* __restrict__ wc, 
 
 template <int LPN>
 __device__ __forceinline__ CellOut cell_forward(const F4& gi, const F4& gf, const F4& gc, const F4& go, const F4& cp,
-                                                const CellParams& P, int h) {
+                                                const CellParams& P) {
     CellOut r;
     F4 Hr;
 #pragma unroll
@@ -125,8 +150,8 @@ __device__ __forceinline__ CellOut cell_forward(const F4& gi, const F4& gf, cons
     if (P.has_ln) {
         F4 xh, xc;
         float rh, rc;
-        layer_norm<LPN>(Hr, h, &xh, &rh);
-        layer_norm<LPN>(r.Cr, h, &xc, &rc);
+        layer_norm<LPN>(Hr, &xh, &rh);
+        layer_norm<LPN>(r.Cr, &xc, &rc);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             r.hn.v[k] = P.gh.v[k] * xh.v[k] + P.bh.v[k];
@@ -140,7 +165,7 @@ template <int LPN>
 __device__ __forceinline__ CellOut cell_forward(const F4& gi, const F4& gf, const F4& gc, const F4& go, const F4& cp,
                                                 const float* __restrict__ wc, const float* __restrict__ b,
                                                 const float* __restrict__ ln, int h, int j0) {
-    return cell_forward<LPN>(gi, gf, gc, go, cp, cell_params(wc, b, ln, h, j0), h);
+    return cell_forward<LPN>(gi, gf, gc, go, cp, cell_params(wc, b, ln, h, j0));
 }
 
 // Backward of one cell update for 4 hidden units of a node (lane group as in cell_forward).  acc[11][4] collects this
@@ -152,7 +177,7 @@ template <int LPN>
 __device__ __forceinline__ CellBwdOut cell_backward(const F4& I, const F4& F, const F4& T, const F4& Og, const F4& cp,
                                                     const F4& gyh, const F4& gyc, const F4& go_in, const F4& wci,
                                                     const F4& wcf, const F4& wco, const F4& gam_h, const F4& gam_c,
-                                                    bool has_ln, int h, float (&acc)[11][4]) {
+                                                    bool has_ln, float (&acc)[11][4]) {
     F4 Cr, Hr, tc;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -164,10 +189,10 @@ __device__ __forceinline__ CellBwdOut cell_backward(const F4& I, const F4& F, co
     F4 gHr = gyh, gCr = gyc;
     if (has_ln) {
         float rh, rc;
-        layer_norm<LPN>(Hr, h, &xh, &rh);
-        layer_norm<LPN>(Cr, h, &xc, &rc);
-        gHr = layer_norm_bwd<LPN>(gyh, gam_h, xh, rh, h);
-        gCr = layer_norm_bwd<LPN>(gyc, gam_c, xc, rc, h);
+        layer_norm<LPN>(Hr, &xh, &rh);
+        layer_norm<LPN>(Cr, &xc, &rc);
+        gHr = layer_norm_bwd<LPN>(gyh, gam_h, xh, rh);
+        gCr = layer_norm_bwd<LPN>(gyc, gam_c, xc, rc);
     }
     CellBwdOut o;
 #pragma unroll
@@ -195,6 +220,21 @@ __device__ __forceinline__ CellBwdOut cell_backward(const F4& I, const F4& F, co
     return o;
 }
 
+// Sum over a wave of the values that lanes LPN apart hold (the same hidden units of the wave's 64 / LPN nodes); the result is
+// valid in lanes 0 .. LPN-1 only.  The additions are those of the xor butterfly (v[l] + v[l ^ d], d = LPN, 2 LPN, .. 32) as
+// lanes < LPN see it; inside a 16-lane row the partner comes through DPP (lane l + d: what l ^ d is for the lanes that
+// count), across rows through ds_bpermute.
+template <int LPN>
+__device__ __forceinline__ float wave_strided_sum(float v) {
+    if constexpr (LPN <= 1) v += lane_up<1>(v);
+    if constexpr (LPN <= 2) v += lane_up<2>(v);
+    if constexpr (LPN <= 4) v += lane_up<4>(v);
+    if constexpr (LPN <= 8) v += lane_up<8>(v);
+#pragma unroll
+    for (int d = (LPN > 16 ? LPN : 16); d < 64; d <<= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+
 // reduce NACC*4 per-thread accumulators over a 256-thread workgroup into part_row[NACC * h]; sm: 4 * LPN * NACC * 4 floats
 template <int LPN, int NACC>
 __device__ __forceinline__ void block_param_reduce(float (&acc)[NACC][4], int h, float* sm, float* part_row, int accumulate) {
@@ -202,12 +242,7 @@ __device__ __forceinline__ void block_param_reduce(float (&acc)[NACC][4], int h,
 #pragma unroll
     for (int a = 0; a < NACC; ++a)
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            float v = acc[a][k];
-#pragma unroll
-            for (int d = LPN; d < 64; d <<= 1) v += __shfl_xor(v, d, 64);
-            acc[a][k] = v;
-        }
+        for (int k = 0; k < 4; ++k) acc[a][k] = wave_strided_sum<LPN>(acc[a][k]);
     if (lane < LPN) {
 #pragma unroll
         for (int a = 0; a < NACC; ++a)
