@@ -273,6 +273,21 @@ int qt_score_rollout(int nseg, const float* const* outs, const int* out_strides,
                      const float* base2, int64_t base2_clip_stride, int64_t base2_step_stride,
                      const uint8_t* pix_mask, float thr, int B, int n, int m, float* partial, void* stream);
 
+/* qt_score_maps: the same eight sums kept per pixel and summed over the clips (error maps per lead time).  The arguments up
+ * to m are qt_score_rollout's, with its sources, counting rule, fp32 d = f - y and strict > classes; grid (ceil(P/256), nseg),
+ * one thread per pixel of a step.  Step z ACCUMULATES into maps + z*maps_step_stride, a float64 block (S, 8, P) in the slot
+ * order above: maps[z*maps_step_stride + (s*8 + slot)*P + p] += the slot's term of pixel p, over the B clips in clip order
+ * (maps_step_stride >= S*8*P; the caller zeroes the buffer once).  The owning thread loads its running sums, adds each
+ * clip's term in double (d widened from fp32, so d^2 is exact) and stores them: no atomics, and the result is the
+ * left-to-right float64 sum over all clips added so far, however they were split into calls.  Calls that share `maps` must
+ * be ordered (one stream).  A pixel that no clip counts is left as it is. */
+int qt_score_maps(int nseg, const float* const* outs, const int* out_strides, const int32_t* const* labels,
+                  const int* Ns, const int32_t* const* n_devs, const float* y, int64_t y_clip_stride,
+                  int64_t y_step_stride, const float* base1, int64_t base1_clip_stride, int64_t base1_step_stride,
+                  const float* base2, int64_t base2_clip_stride, int64_t base2_step_stride,
+                  const uint8_t* pix_mask, float thr, int B, int n, int m, double* maps, int64_t maps_step_stride,
+                  void* stream);
+
 /* gradient of the qt_sse partial sums with respect to the node values, written as full rows of width W (column 0 carries
  * the value, the rest zeros): gout[i, 0] = 2 * g[0] * (npix[i] * out[i * out_stride] - sy[i]), sy = per-node sum of y. */
 int qt_sse_bwd(const float* out, int out_stride, const float* npix, const float* sy, const float* g, int N,

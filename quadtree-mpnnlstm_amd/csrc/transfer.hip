@@ -603,6 +603,77 @@ __global__ __launch_bounds__(256) void k_score_multi(ScoreSeg sg, const float* _
     }
 }
 
+// Per-pixel verification sums: k_score_multi's reads and counting rule, kept per pixel and summed over the clips instead of
+// per clip and summed over the pixels.  One thread owns pixel p of step z and is the only writer of its 8 * S running doubles
+// (maps + z * maps_step_stride, laid out (S, 8, P)): it loads the three sums of every source, adds the clips' terms to them
+// one by one in clip order in double, and stores them; the class counts are integers (exact in any order) and are added to
+// their running values at the end.  d = f - y is formed in fp32 as in k_score_multi and then widened; d * d of a widened fp32
+// is exact in double, so contracting it into the add changes no bit.  The result is the left-to-right float64 sum over every
+// clip that was ever added, however the clips were batched.  No atomics, no LDS, no cross-thread step; launches that share
+// `maps` are ordered by their stream.
+template <int S>
+__global__ __launch_bounds__(256) void k_score_maps(ScoreSeg sg, const float* __restrict__ y, int64_t y_clip_stride,
+                                                    int64_t y_step_stride, ScoreBase b1, ScoreBase b2,
+                                                    const uint8_t* __restrict__ pix_mask, float thr, int64_t P, int B,
+                                                    double* __restrict__ maps, int64_t maps_step_stride) {
+    const int z = blockIdx.y;
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= P || (pix_mask && pix_mask[p])) return;         // a masked pixel counts in no clip: its doubles stay as they are
+    const float* out = sg.out[z];
+    const int32_t* labels = sg.labels[z] + p;
+    const int os = sg.out_stride[z];
+    const int rows = qt_rows(sg.n_dev[z], sg.N[z]);
+    const float* yz = y + z * y_step_stride + p;
+    const float* f1 = S > 1 ? b1.f + z * b1.step_stride + p : nullptr;
+    const float* f2 = S > 2 ? b2.f + z * b2.step_stride + p : nullptr;
+    double* mz = maps + z * maps_step_stride + p;             // slot k of source s: mz[(s * 8 + k) * P]
+    double sum[S][3];
+    int cls[S][3], n = 0;
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            sum[s][k] = mz[(s * 8 + 1 + k) * P];
+            cls[s][k] = 0;
+        }
+    }
+    for (int b = 0; b < B; ++b) {
+        const int lab = labels[b * P];
+        if (lab < 0 || lab >= rows) continue;
+        const float t = yz[b * y_clip_stride];
+        const bool ty = t > thr;
+        float f[S];
+        f[0] = out[(int64_t)lab * os];
+        if (S > 1) f[1] = f1[b * b1.clip_stride];
+        if (S > 2) f[2] = f2[b * b2.clip_stride];
+        ++n;
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+            const float d32 = f[s] - t;
+            const double d = (double)d32;
+            const bool tf = f[s] > thr;
+            sum[s][0] += d;
+            sum[s][1] += fabs(d);
+            sum[s][2] += d * d;
+            cls[s][0] += (tf && ty) ? 1 : 0;
+            cls[s][1] += (tf && !ty) ? 1 : 0;
+            cls[s][2] += (!tf && ty) ? 1 : 0;
+        }
+    }
+    if (n == 0) return;                                       // no clip of this launch has a node here: nothing to add
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+        double* m = mz + (int64_t)s * 8 * P;
+        m[0] += (double)n;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            m[(1 + k) * P] = sum[s][k];
+            m[(4 + k) * P] += (double)cls[s][k];
+        }
+        m[7 * P] += (double)(n - cls[s][0] - cls[s][1] - cls[s][2]);
+    }
+}
+
 __global__ void k_sse_bwd_multi(LossSeg sg, const float* __restrict__ g, int W) {
     const int z = blockIdx.y;
     const unsigned idx = blockIdx.x * blockDim.x + threadIdx.x;
@@ -683,6 +754,36 @@ extern "C" int qt_score_rollout(int nseg, const float* const* outs, const int* o
     auto k = nb == 0 ? k_score_multi<1> : nb == 1 ? k_score_multi<2> : k_score_multi<3>;
     hipLaunchKernelGGL(k, grid, dim3(256), 0, (hipStream_t)stream, sg, y, y_clip_stride, y_step_stride, bs[0], bs[1], pix_mask, thr,
                        P, B, partial);
+    QT_LAUNCHED();
+    return QT_OK;
+}
+
+extern "C" int qt_score_maps(int nseg, const float* const* outs, const int* out_strides, const int32_t* const* labels,
+                             const int* Ns, const int32_t* const* n_devs, const float* y, int64_t y_clip_stride,
+                             int64_t y_step_stride, const float* base1, int64_t base1_clip_stride, int64_t base1_step_stride,
+                             const float* base2, int64_t base2_clip_stride, int64_t base2_step_stride,
+                             const uint8_t* pix_mask, float thr, int B, int n, int m, double* maps, int64_t maps_step_stride,
+                             void* stream) {
+    QT_ARG(nseg >= 1 && nseg <= 16, "nseg must be 1..16");
+    QT_ARG(outs && out_strides && labels && Ns && n_devs && y && maps, "null pointer");
+    QT_ARG(B > 0 && n > 0 && m > 0, "bad sizes");
+    QT_ARG(y_clip_stride >= 0 && y_step_stride >= 0 && base1_clip_stride >= 0 && base1_step_stride >= 0 &&
+           base2_clip_stride >= 0 && base2_step_stride >= 0, "negative stride");
+    ScoreSeg sg = {};
+    for (int z = 0; z < nseg; ++z) {
+        QT_ARG(labels[z] && Ns[z] >= 0 && (outs[z] || Ns[z] == 0) && out_strides[z] >= 1, "bad segment");
+        sg.out[z] = outs[z]; sg.out_stride[z] = out_strides[z]; sg.labels[z] = labels[z]; sg.N[z] = Ns[z]; sg.n_dev[z] = n_devs[z];
+    }
+    ScoreBase bs[2] = {};
+    int nb = 0;
+    if (base1) bs[nb++] = {base1, base1_clip_stride, base1_step_stride};
+    if (base2) bs[nb++] = {base2, base2_clip_stride, base2_step_stride};
+    const int64_t P = (int64_t)n * m;
+    // a step's (S, 8, P) block must fit its stride, or step z would write into step z + 1
+    QT_ARG(maps_step_stride >= (int64_t)(1 + nb) * 8 * P, "maps_step_stride is smaller than S*8*n*m");
+    auto k = nb == 0 ? k_score_maps<1> : nb == 1 ? k_score_maps<2> : k_score_maps<3>;
+    hipLaunchKernelGGL(k, dim3(qt_cdiv(P, 256), nseg), dim3(256), 0, (hipStream_t)stream, sg, y, y_clip_stride, y_step_stride,
+                       bs[0], bs[1], pix_mask, thr, P, B, maps, maps_step_stride);
     QT_LAUNCHED();
     return QT_OK;
 }

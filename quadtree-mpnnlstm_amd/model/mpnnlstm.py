@@ -424,11 +424,13 @@ class NextFramePredictorS2S(NextFramePredictor):
 
     @on_device(lambda self, *a, **k: self.device)
     def make_graphed_scores(self, x, y, concat_layers=None, mask=None, high_interest_region=None, graph_structure=None,
-                            threshold=0.15):
+                            threshold=0.15, maps=None):
         """make_graphed_rollout with the verification sums in place of the frames: the capture holds the rollout and
         ops.rollout_scores (model, persistence = channel 0 of the last input frame, climatology = concat_layers when given), no
         frame gather.  Returns `scores(x, y, concat) -> (T_out, B, S, 8)` float64 device tensor; `scores.warmup` is the given
-        batch's."""
+        batch's.  maps: a float64 (T_out, S, 8, P) device buffer that the body also adds the batch's per-pixel sums into
+        (ops.rollout_score_maps).  The warm-up runs the body once and the capture records it without running, so the given
+        batch is added exactly once, and every replay adds its batch once."""
         self.model.static_shapes = True
         sx, sy = x.clone(), y.clone()
         sc = concat_layers.clone() if concat_layers is not None else None
@@ -437,7 +439,10 @@ class NextFramePredictorS2S(NextFramePredictor):
             with torch.no_grad():
                 y_hat, meshes = self.model(sx, concat_layers=sc, teacher_forcing_ratio=0, mask=mask,
                                            high_interest_region=high_interest_region, graph_structure=graph_structure)
-                return ops.rollout_scores(y_hat, meshes, sy, threshold, persistence=sx[..., -1, :, :, 0], climatology=sc)
+                part = ops.rollout_scores(y_hat, meshes, sy, threshold, persistence=sx[..., -1, :, :, 0], climatology=sc)
+                if maps is not None:
+                    ops.rollout_score_maps(y_hat, meshes, sy, maps, threshold, persistence=sx[..., -1, :, :, 0], climatology=sc)
+                return part
 
         def load(x, y, concat_layers=None):
             sx.copy_(x)
@@ -597,20 +602,44 @@ class NextFramePredictorS2S(NextFramePredictor):
         them.  Sources: 'model', 'persistence' (channel 0 of the last input frame at every lead time) and, with `climatology`,
         'climatology' (the daily normals the decoder gets).  `threshold` separates ice from no ice (strict >); with binary=True
         the outputs are probabilities and a caller passes 0.5.  use_graph=True replays rollout + sums as one hipGraph per
-        distinct batch shape, as predict(use_graph=True) does (make_graphed_scores)."""
-        from qtmpnn.score import Scores
+        distinct batch shape, as predict(use_graph=True) does (make_graphed_scores).  `.maps` of the result is None: score_maps()
+        is this call with the per-pixel maps as well."""
+        return self._score(loader, climatology, mask, high_interest_region, graph_structure, use_graph, threshold, False)
+
+    @on_device(lambda self, *a, **k: self.device)
+    def score_maps(self, loader, climatology=None, mask=None, high_interest_region=None, graph_structure=None, use_graph=False,
+                   threshold=0.15):
+        """score() with per-pixel maps from the same pass: the returned Scores has the same `.sums`, bit for bit, and `.maps`, a
+        qtmpnn.score.ScoreMaps of (T_out, S, 8, W, H) float64: the eight sums per lead time, source and pixel, over every clip
+        of the loader (where the ice edge is over- or under-forecast, where the model beats climatology; `.pooled(weights=...)`
+        for cell areas or a region).  The first batch allocates the zeroed device buffer, every batch adds into it right after
+        its sums (ops.rollout_score_maps; inside the capture with use_graph=True) and one host copy follows the last batch.
+        Every batch must have the first one's frame shape."""
+        return self._score(loader, climatology, mask, high_interest_region, graph_structure, use_graph, threshold, True)
+
+    def _score(self, loader, climatology, mask, high_interest_region, graph_structure, use_graph, threshold, with_maps):
+        from qtmpnn.score import ScoreMaps, Scores
         self.model.to(self.device)
-        sums = []
+        sources = ('model', 'persistence') + (('climatology',) if climatology is not None else ())
+        sums, maps, frame = [], None, None
         graphed, static0 = {}, self.model.static_shapes
         try:
             for x, y, launch_date in loader:
                 x, y = self._clip(x), self._clip(y)
                 concat = self.get_climatology_array(climatology, launch_date) if climatology is not None else None
+                if with_maps:
+                    if maps is None:
+                        frame = tuple(x.shape[-3:-1])
+                        maps = torch.zeros(self.output_timesteps, len(sources), 8, frame[0] * frame[1], dtype=torch.float64,
+                                           device=x.device)
+                    elif tuple(x.shape[-3:-1]) != frame:
+                        raise ValueError(f'score_maps: a batch of {tuple(x.shape[-3:-1])} frames after {frame} ones: maps need '
+                                         'one grid (use one loader per grid)')
                 if use_graph:
                     key = (tuple(x.shape), tuple(y.shape), None if concat is None else tuple(concat.shape), self.model.training)
                     if key not in graphed:
                         graphed[key] = self.make_graphed_scores(x, y, concat, mask=mask, high_interest_region=high_interest_region,
-                                                                graph_structure=graph_structure, threshold=threshold)
+                                                                graph_structure=graph_structure, threshold=threshold, maps=maps)
                         part = graphed[key].warmup
                     else:
                         part = graphed[key](x, y, concat)
@@ -619,10 +648,14 @@ class NextFramePredictorS2S(NextFramePredictor):
                         y_hat, meshes = self.model(x, concat_layers=concat, teacher_forcing_ratio=0, mask=mask,
                                                    high_interest_region=high_interest_region, graph_structure=graph_structure)
                         part = ops.rollout_scores(y_hat, meshes, y, threshold, persistence=x[..., -1, :, :, 0], climatology=concat)
+                        if with_maps:
+                            ops.rollout_score_maps(y_hat, meshes, y, maps, threshold, persistence=x[..., -1, :, :, 0],
+                                                   climatology=concat)
                 sums.append(np.moveaxis(part.cpu().numpy(), 0, 1))      # (T, B, S, 8) -> (B, T, S, 8)
+            if with_maps and maps is not None:
+                maps = ScoreMaps(maps.cpu().numpy().reshape(*maps.shape[:3], *frame), sources)
         finally:
             graphed.clear()
             self.model.static_shapes = static0
         check_tile_errors(always=True)
-        sources = ('model', 'persistence') + (('climatology',) if climatology is not None else ())
-        return Scores(np.concatenate(sums, 0), sources)
+        return Scores(np.concatenate(sums, 0), sources, maps=maps)

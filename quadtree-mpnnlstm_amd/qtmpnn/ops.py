@@ -1956,27 +1956,21 @@ def rollout_sse_partials(outputs, y, meshes):
     return _RolloutSSE.apply(y.view(B, T, meshes[0].P), tuple(meshes), *outs)
 
 
-def rollout_scores(outputs, meshes, y, threshold=0.15, persistence=None, climatology=None, per_tile=False):
-    """Verification sums of a rollout, float64 (T, B, S, 8) on the device (qt_score_rollout; the slot table is in
-    include/qtmpnn.h): per output step, clip and source [n, sum d, sum |d|, sum d^2, hits, over, under, correct negatives] over
-    the counted pixels, d = forecast - y, the classes at `threshold` (strict >).  Sources: the model (outputs[t] (N_t, 1) or
-    (N_t, W): column 0 is read in place through the step's labels), then the dense baselines that are given: `persistence`
-    (B*P values, one frame for every lead time, or B*T*P) and `climatology` (likewise).  y: B*T*P values laid out (B, T, P).
-    Pixels without a node, and those under meshes[0].loss_mask, are not counted.  No autograd, no host read: capturable.
-    per_tile=True returns the launch's own fp32 partials (T, B, ceil(P/1024), S, 8) instead of their float64 sum over the tiles."""
-    import ctypes
+def _score_args(who, outputs, meshes, y, persistence, climatology):
+    """The checked operands rollout_scores and rollout_score_maps share: (outs, y, bases, S, B, T, P), bases = two
+    (field or None, clip stride, step stride).  Refusals carry `who`."""
     if not outputs or len(outputs) != len(meshes):
-        raise ValueError(f'rollout_scores: {len(outputs)} output steps for {len(meshes)} meshes')
+        raise ValueError(f'{who}: {len(outputs)} output steps for {len(meshes)} meshes')
     outs = [o.detach() for o in outputs]        # (a column view of the head's 4-wide rows is read through its row stride)
     for o in outs:
         if not (o.is_cuda and o.dtype == torch.float32 and o.dim() == 2 and o.shape[1] >= 1):
-            raise ValueError(f'rollout_scores: outputs must be fp32 (N, W) matrices on the GPU, got {o.dtype} {tuple(o.shape)} on {o.device}')
+            raise ValueError(f'{who}: outputs must be fp32 (N, W) matrices on the GPU, got {o.dtype} {tuple(o.shape)} on {o.device}')
     m0 = meshes[0]
     B, T, P = m0.B, len(outs), m0.P
 
     def dense(t, what, counts):
         if t.numel() not in counts:
-            raise ValueError(f'rollout_scores: {what} has {t.numel()} elements for {B} clip(s) x {T} steps of {P} pixels '
+            raise ValueError(f'{who}: {what} has {t.numel()} elements for {B} clip(s) x {T} steps of {P} pixels '
                              f'(expected {" or ".join(str(c) for c in counts)})')
         t = t.detach().to(outs[0].device, torch.float32).contiguous()
         return (t, T * P, P) if t.numel() == B * T * P else (t, P, 0)      # (field, clip stride, step stride)
@@ -1985,8 +1979,13 @@ def rollout_scores(outputs, meshes, y, threshold=0.15, persistence=None, climato
              if t is not None]
     S = 1 + len(bases)
     bases += [(None, 0, 0)] * (2 - len(bases))
-    nt = -(P // -1024)
-    part = outs[0].new_empty(T, B, nt, S, 8)
+    return outs, y, bases, S, B, T, P
+
+
+def _score_chunks(entry, outs, meshes, y, bases, threshold, B, T, P, tail):
+    """One launch of `entry` per 16 output steps; tail(z0) -> the entry's arguments after m (its result buffer at step z0)."""
+    import ctypes
+    m0 = meshes[0]
     vp, ip = ctypes.c_void_p, ctypes.c_int
     for z0 in range(0, T, 16):
         sl = slice(z0, min(z0 + 16, T))
@@ -1994,12 +1993,42 @@ def rollout_scores(outputs, meshes, y, threshold=0.15, persistence=None, climato
         base_args = []
         for t, cs, ss in bases:
             base_args += [None if t is None else t.data_ptr() + 4 * z0 * ss, cs, ss]
-        _lib.call('qt_score_rollout', n, (vp * n)(*[o.data_ptr() for o in outs[sl]]),
+        _lib.call(entry, n, (vp * n)(*[o.data_ptr() for o in outs[sl]]),
                   (ip * n)(*[max(o.stride(0), 1) for o in outs[sl]]), (vp * n)(*[ms.labels.data_ptr() for ms in meshes[sl]]),
                   (ip * n)(*[o.shape[0] for o in outs[sl]]), (vp * n)(*[ptr(ms.n_dev) for ms in meshes[sl]]),
                   y.data_ptr() + 4 * z0 * P, T * P, P, *base_args, ptr(m0.loss_mask), float(threshold), B, m0.n, m0.m,
-                  ptr(part[z0:]))
+                  *tail(z0))
+
+
+def rollout_scores(outputs, meshes, y, threshold=0.15, persistence=None, climatology=None, per_tile=False):
+    """Verification sums of a rollout, float64 (T, B, S, 8) on the device (qt_score_rollout; the slot table is in
+    include/qtmpnn.h): per output step, clip and source [n, sum d, sum |d|, sum d^2, hits, over, under, correct negatives] over
+    the counted pixels, d = forecast - y, the classes at `threshold` (strict >).  Sources: the model (outputs[t] (N_t, 1) or
+    (N_t, W): column 0 is read in place through the step's labels), then the dense baselines that are given: `persistence`
+    (B*P values, one frame for every lead time, or B*T*P) and `climatology` (likewise).  y: B*T*P values laid out (B, T, P).
+    Pixels without a node, and those under meshes[0].loss_mask, are not counted.  No autograd, no host read: capturable.
+    per_tile=True returns the launch's own fp32 partials (T, B, ceil(P/1024), S, 8) instead of their float64 sum over the tiles."""
+    outs, y, bases, S, B, T, P = _score_args('rollout_scores', outputs, meshes, y, persistence, climatology)
+    nt = -(P // -1024)
+    part = outs[0].new_empty(T, B, nt, S, 8)
+    _score_chunks('qt_score_rollout', outs, meshes, y, bases, threshold, B, T, P, lambda z0: (ptr(part[z0:]),))
     return part if per_tile else part.double().sum(2)
+
+
+def rollout_score_maps(outputs, meshes, y, maps, threshold=0.15, persistence=None, climatology=None):
+    """rollout_scores' eight sums kept per pixel and summed over the clips: `maps`, a float64 (T, S, 8, P) tensor on the
+    outputs' device, is accumulated in place (qt_score_maps) and returned.  Operands, sources, counting rule and classes are
+    rollout_scores'.  Every pixel's running sums take this batch's clips one by one in clip order in float64, so a buffer
+    zeroed once holds the left-to-right sum over all clips of all calls, however they were batched; calls that share `maps`
+    must run on one stream.  No autograd, no host read: capturable."""
+    outs, y, bases, S, B, T, P = _score_args('rollout_score_maps', outputs, meshes, y, persistence, climatology)
+    if not (isinstance(maps, torch.Tensor) and maps.dtype == torch.float64 and maps.device == outs[0].device
+            and tuple(maps.shape) == (T, S, 8, P) and maps.is_contiguous()):
+        got = f'{maps.dtype} {tuple(maps.shape)} on {maps.device}' if isinstance(maps, torch.Tensor) else type(maps).__name__
+        raise ValueError(f'rollout_score_maps: maps must be a contiguous float64 {(T, S, 8, P)} tensor on {outs[0].device} '
+                         f'({T} steps, {S} source(s), {P} pixels), got {got}')
+    _score_chunks('qt_score_maps', outs, meshes, y, bases, threshold, B, T, P, lambda z0: (ptr(maps[z0:]), S * 8 * P))
+    return maps
 
 
 def step_sse_partials(out, y, mesh):

@@ -1,7 +1,9 @@
 """Forecast verification numbers as NextFramePredictorS2S.score() returns them (numpy only).
 
 The device leaves eight sums per (clip, lead time, source) over the counted pixels (ops.rollout_scores, qt_score_rollout);
-everything a user reads is derived from them here, so pooling over clips is pooling of sums, never a mean of ratios."""
+everything a user reads is derived from them here, so pooling over clips is pooling of sums, never a mean of ratios.
+ScoreMaps holds the same eight sums per pixel, pooled over the clips (ops.rollout_score_maps, qt_score_maps): error maps per
+lead time, and sums over a region or weighted by cell area."""
 import numpy as np
 
 SLOTS = ('n', 'sum_d', 'sum_abs_d', 'sum_sq_d', 'hits', 'over', 'under', 'correct_negatives')
@@ -20,11 +22,13 @@ def derive(sums):
 
 class Scores:
     """sums (n_clips, T_out, S, 8) float64 in SLOTS order, sources: S names ('model', 'persistence', 'climatology').
-    Every metric of METRICS is a method metric(source='model') -> (n_clips, T_out); by_lead pools the clips."""
+    Every metric of METRICS is a method metric(source='model') -> (n_clips, T_out); by_lead pools the clips.  maps: the
+    ScoreMaps of the same pass, or None."""
 
-    def __init__(self, sums, sources):
+    def __init__(self, sums, sources, maps=None):
         self.sums = np.asarray(sums, dtype=np.float64)
         self.sources = tuple(sources)
+        self.maps = maps
         if self.sums.ndim != 4 or self.sums.shape[2:] != (len(self.sources), 8):
             raise ValueError(f'sums of shape {self.sums.shape} for sources {self.sources}: expected (n_clips, T_out, {len(self.sources)}, 8)')
 
@@ -42,5 +46,39 @@ class Scores:
         return derive(self._of(source).sum(axis=0))
 
 
+class ScoreMaps:
+    """sums (T_out, S, 8, W, H) float64 in SLOTS order: per lead time, source and pixel, summed over every clip of the loader.
+    Every metric of METRICS is a method metric(source='model') -> (T_out, W, H); a pixel that no clip counts (masked, no
+    node) has n == 0 and NaN ratios.  pooled() sums the pixels, optionally weighted, before the ratios are formed."""
+
+    def __init__(self, sums, sources):
+        self.sums = np.asarray(sums, dtype=np.float64)
+        self.sources = tuple(sources)
+        if self.sums.ndim != 5 or self.sums.shape[1:3] != (len(self.sources), 8):
+            raise ValueError(f'ScoreMaps: sums of shape {self.sums.shape} for sources {self.sources}: expected '
+                             f'(T_out, {len(self.sources)}, 8, W, H)')
+
+    def _of(self, source):
+        if source not in self.sources:
+            raise KeyError(f'no source {source!r} in these maps (have {self.sources})')
+        return self.sums[:, self.sources.index(source)]                    # (T_out, 8, W, H)
+
+    def metrics(self, source='model'):
+        """{metric: (T_out, W, H)} per lead time and pixel."""
+        return derive(np.moveaxis(self._of(source), 1, -1))
+
+    def pooled(self, source='model', weights=None):
+        """{metric: (T_out,)} from the sums over the pixels.  weights (W, H) multiplies every slot of a pixel first: cell areas
+        (over / under / iiee become areas, n the counted area, rmse area-weighted), a 0/1 region, or their product."""
+        s = self._of(source)
+        if weights is not None:
+            w = np.asarray(weights, dtype=np.float64)
+            if w.shape != s.shape[2:]:
+                raise ValueError(f'ScoreMaps.pooled: weights of shape {w.shape} for maps of {s.shape[2:]} pixels')
+            s = s * w
+        return derive(s.sum(axis=(-2, -1)))
+
+
 for _name in METRICS:
     setattr(Scores, _name, (lambda name: lambda self, source='model': self.metrics(source)[name])(_name))
+    setattr(ScoreMaps, _name, (lambda name: lambda self, source='model': self.metrics(source)[name])(_name))
