@@ -558,8 +558,9 @@ def test_multi_head_attention_equals_separate_calls():
 
 def test_multi_head_attention_dropout_draws_one_mask_per_head():
     """Heads of one launch must not share their attention-dropout mask (the reference's convolutions draw independently): with
-    identical operands in every head the outputs agree without dropout and differ with it, and forward and backward use the
-    same mask (the gradient of sum(out) w.r.t. v is the dropped attention weight: zero exactly where the forward dropped)."""
+    identical operands in every head the outputs agree without dropout and differ with it, and the attention mass that survives,
+    scaled by 1 / keep, stays near 1 on average.  That forward and backward use the same mask, and which one, is checked pair by
+    pair in tests/test_gpu_attn_f64.py::test_dropout_mask_edge_by_edge."""
     from qtmpnn import ops, synthetic
     from qtmpnn.mesh import build_mesh
     c = synthetic.make_clip(11, canvas=(64, 64), n_digits=2, n_frames=1, pixel_noise=0.0)
