@@ -288,6 +288,39 @@ int qt_score_maps(int nseg, const float* const* outs, const int* out_strides, co
                   const uint8_t* pix_mask, float thr, int B, int n, int m, double* maps, int64_t maps_step_stride,
                   void* stream);
 
+/* qt_event_scan: event dates of a rollout along its time axis -- the day a pixel opens and stays open (break-up, target 0)
+ * or closes and stays closed (freeze-up, target 1).  The arguments up to m are qt_score_rollout's with ONE optional dense
+ * field (`base`, NULL = absent): up to 16 output steps per call, one mesh per step.  Sources, S1 = 2 + (base given):
+ *   s = 0  observed   y[b*y_clip_stride + z*y_step_stride + p]
+ *   s = 1  model      outs[z][labels[z][b*P + p] * out_strides[z]]
+ *   s = 2  base       base[b*base_clip_stride + z*base_step_stride + p]   (climatology)
+ * Ice state a_s[z][p] = f_s[z][p] > thr, launch state a0[p] = launch[b*launch_clip_stride + p] > thr (strict, fp32), g =
+ * (target != 0).  dates (B, S1, P) int32, per clip, source and pixel:
+ *   >= 0  the smallest step z (0-based over the whole rollout) with a_s[z] = ... = a_s[z + k - 1] = g, all inside the rollout
+ *   -1    no event: a0 == g (already in the target state at launch), or no run of k steps completes within the rollout
+ *   -2    not counted: pix_mask[p] != 0, or at ANY step the label is not in 0 <= label < node count (n_devs[z] when given,
+ *         else Ns[z]), for every source and even when an event had been found before that step
+ * z0 is the rollout index of the call's first step.  A call with z0 == 0 initialises dates and runs (no memset needed, a
+ * graph replay is idempotent); a call with z0 > 0 continues from what the previous call stored, so the chunks of a rollout
+ * must be ordered (one stream).  runs (B, S1, P) int32 is the state carried between the calls: the length of the current
+ * run of g, or -1 for a pixel with a0 == g (never advanced).  Grid (ceil(P/256), B), one thread per pixel of a clip: it reads
+ * its label once per step, keeps run and date of every source in registers and stores them once.  No atomics, no LDS. */
+int qt_event_scan(int nseg, const float* const* outs, const int* out_strides, const int32_t* const* labels,
+                  const int* Ns, const int32_t* const* n_devs, const float* y, int64_t y_clip_stride,
+                  int64_t y_step_stride, const float* base, int64_t base_clip_stride, int64_t base_step_stride,
+                  const uint8_t* pix_mask, float thr, int B, int n, int m, const float* launch,
+                  int64_t launch_clip_stride, int target, int k, int z0, int32_t* dates, int32_t* runs, void* stream);
+
+/* qt_event_sums: the date errors of qt_event_scan's result summed over the counted pixels (date_observed != -2), per clip and
+ * forecast source s = 1 .. S1-1: sums[(b*(S1-1) + s-1)*8 + slot], int64, e = date_s - date_observed where both are >= 0:
+ *   slot 0  counted pixels                  slot 4  hits: both have an event
+ *   slot 1  sum e                           slot 5  false alarms: the forecast only
+ *   slot 2  sum |e|                         slot 6  misses: the observed only
+ *   slot 3  sum e^2                         slot 7  neither
+ * Grid (B, S1-1), one workgroup per (clip, forecast source); integer accumulation in a fixed order: exact, and every slot is
+ * written (zeros included). */
+int qt_event_sums(const int32_t* dates, int S1, int B, int n, int m, int64_t* sums, void* stream);
+
 /* gradient of the qt_sse partial sums with respect to the node values, written as full rows of width W (column 0 carries
  * the value, the rest zeros): gout[i, 0] = 2 * g[0] * (npix[i] * out[i * out_stride] - sy[i]), sy = per-node sum of y. */
 int qt_sse_bwd(const float* out, int out_stride, const float* npix, const float* sy, const float* g, int N,

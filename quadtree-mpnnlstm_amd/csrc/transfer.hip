@@ -674,6 +674,113 @@ __global__ __launch_bounds__(256) void k_score_maps(ScoreSeg sg, const float* __
     }
 }
 
+// Event dates of a rollout (break-up / freeze-up): the first output step from which a pixel stays in the target state g for k
+// consecutive steps, per source (observed, model, optionally one dense field).  k_score_maps' reads and counting rule, but along
+// the time axis: one thread owns pixel p of clip b, reads its label once per step and serves every source from it, and carries
+// per source the current run length and the date in registers over the chunk's steps.  A launch with z0 == 0 initialises the
+// state (date -2 under the mask, else -1; run 0, or -1 where the launch frame is already in the target state: such a pixel has
+// no event, and a negative run is never advanced), a launch with z0 > 0 loads what the previous chunk stored.  A pixel without
+// a valid node at any step ends as -2 for every source.  No atomics, no LDS, no cross-thread step; chunks are ordered by their
+// stream.
+template <int S1>
+__global__ __launch_bounds__(256) void k_event_scan(ScoreSeg sg, int nseg, const float* __restrict__ y, int64_t y_clip_stride,
+                                                    int64_t y_step_stride, ScoreBase b1, const uint8_t* __restrict__ pix_mask,
+                                                    const float* __restrict__ launch, int64_t launch_clip_stride, float thr,
+                                                    int target, int k, int z0, int64_t P, int32_t* __restrict__ dates,
+                                                    int32_t* __restrict__ runs) {
+    const int b = blockIdx.y;
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= P) return;
+    const bool g = target != 0;
+    const int64_t st = ((int64_t)b * S1) * P + p;             // source s of this pixel: st + s * P
+    int date[S1], run[S1];
+    if (z0 == 0) {
+        const int d0 = (pix_mask && pix_mask[p]) ? -2 : -1;
+        const int r0 = ((launch[b * launch_clip_stride + p] > thr) == g) ? -1 : 0;
+#pragma unroll
+        for (int s = 0; s < S1; ++s) {
+            date[s] = d0;
+            run[s] = r0;
+        }
+    } else {
+#pragma unroll
+        for (int s = 0; s < S1; ++s) {
+            date[s] = dates[st + s * P];
+            run[s] = runs[st + s * P];
+        }
+    }
+    bool dead = date[0] == -2;                                // masked, or without a node at an earlier step
+    const float* yp = y + b * y_clip_stride + p;
+    const float* fp = S1 > 2 ? b1.f + b * b1.clip_stride + p : nullptr;
+    for (int z = 0; z < nseg && !dead; ++z) {
+        const int lab = sg.labels[z][(int64_t)b * P + p];
+        if (lab < 0 || lab >= qt_rows(sg.n_dev[z], sg.N[z])) {
+            dead = true;
+            break;
+        }
+        float f[S1];
+        f[0] = yp[z * y_step_stride];
+        f[1] = sg.out[z][(int64_t)lab * sg.out_stride[z]];
+        if (S1 > 2) f[2] = fp[z * b1.step_stride];
+#pragma unroll
+        for (int s = 0; s < S1; ++s) {
+            if (run[s] < 0) continue;
+            run[s] = ((f[s] > thr) == g) ? run[s] + 1 : 0;
+            if (run[s] >= k && date[s] == -1) date[s] = z0 + z - k + 1;
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < S1; ++s) {
+        dates[st + s * P] = dead ? -2 : date[s];
+        runs[st + s * P] = run[s];
+    }
+}
+
+// The eight sums of the date errors per (clip, forecast source): one workgroup each, every thread over its pixels in pixel
+// order in int64, then 64-lane butterflies and (w0 + w1) + (w2 + w3).  Integers: exact in any order.
+__global__ __launch_bounds__(256) void k_event_sums(const int32_t* __restrict__ dates, int S1, int64_t P,
+                                                    int64_t* __restrict__ sums) {
+    __shared__ long long red[4][8];
+    const int b = blockIdx.x, s = 1 + blockIdx.y;             // source 0 is the observed one
+    const int32_t* dob = dates + ((int64_t)b * S1) * P;
+    const int32_t* dfc = dob + (int64_t)s * P;
+    long long acc[8];
+#pragma unroll
+    for (int v = 0; v < 8; ++v) acc[v] = 0;
+    for (int64_t p = threadIdx.x; p < P; p += 256) {
+        const int o = dob[p], f = dfc[p];
+        if (o == -2) continue;
+        acc[0] += 1;
+        if (o >= 0 && f >= 0) {
+            const long long e = (long long)f - o;
+            acc[1] += e;
+            acc[2] += e < 0 ? -e : e;
+            acc[3] += e * e;
+            acc[4] += 1;
+        } else if (f >= 0) {
+            acc[5] += 1;
+        } else if (o >= 0) {
+            acc[6] += 1;
+        } else {
+            acc[7] += 1;
+        }
+    }
+#pragma unroll
+    for (int v = 0; v < 8; ++v) {
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) acc[v] += __shfl_xor(acc[v], d, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int v = 0; v < 8; ++v) red[threadIdx.x >> 6][v] = acc[v];
+    }
+    __syncthreads();
+    if (threadIdx.x < 8) {
+        const int v = threadIdx.x;
+        sums[((int64_t)b * (S1 - 1) + (s - 1)) * 8 + v] = (int64_t)((red[0][v] + red[1][v]) + (red[2][v] + red[3][v]));
+    }
+}
+
 __global__ void k_sse_bwd_multi(LossSeg sg, const float* __restrict__ g, int W) {
     const int z = blockIdx.y;
     const unsigned idx = blockIdx.x * blockDim.x + threadIdx.x;
@@ -784,6 +891,44 @@ extern "C" int qt_score_maps(int nseg, const float* const* outs, const int* out_
     auto k = nb == 0 ? k_score_maps<1> : nb == 1 ? k_score_maps<2> : k_score_maps<3>;
     hipLaunchKernelGGL(k, dim3(qt_cdiv(P, 256), nseg), dim3(256), 0, (hipStream_t)stream, sg, y, y_clip_stride, y_step_stride,
                        bs[0], bs[1], pix_mask, thr, P, B, maps, maps_step_stride);
+    QT_LAUNCHED();
+    return QT_OK;
+}
+
+extern "C" int qt_event_scan(int nseg, const float* const* outs, const int* out_strides, const int32_t* const* labels,
+                             const int* Ns, const int32_t* const* n_devs, const float* y, int64_t y_clip_stride,
+                             int64_t y_step_stride, const float* base, int64_t base_clip_stride, int64_t base_step_stride,
+                             const uint8_t* pix_mask, float thr, int B, int n, int m, const float* launch,
+                             int64_t launch_clip_stride, int target, int k, int z0, int32_t* dates, int32_t* runs,
+                             void* stream) {
+    QT_ARG(nseg >= 1 && nseg <= 16, "nseg must be 1..16");
+    QT_ARG(outs && out_strides && labels && Ns && n_devs && y && launch, "null pointer");
+    QT_ARG(dates && runs, "null dates / runs");
+    QT_ARG(B > 0 && B <= 65535 && n > 0 && m > 0, "bad sizes");
+    QT_ARG(y_clip_stride >= 0 && y_step_stride >= 0 && base_clip_stride >= 0 && base_step_stride >= 0 &&
+           launch_clip_stride >= 0, "negative stride");
+    QT_ARG(target == 0 || target == 1, "target must be 0 (no ice: break-up) or 1 (ice: freeze-up)");
+    QT_ARG(k >= 1, "k (persist) must be >= 1");
+    QT_ARG(z0 >= 0, "z0 must be >= 0");
+    ScoreSeg sg = {};
+    for (int z = 0; z < nseg; ++z) {
+        QT_ARG(labels[z] && Ns[z] >= 0 && (outs[z] || Ns[z] == 0) && out_strides[z] >= 1, "bad segment");
+        sg.out[z] = outs[z]; sg.out_stride[z] = out_strides[z]; sg.labels[z] = labels[z]; sg.N[z] = Ns[z]; sg.n_dev[z] = n_devs[z];
+    }
+    const ScoreBase b1 = {base, base_clip_stride, base_step_stride};
+    const int64_t P = (int64_t)n * m;
+    auto kern = base ? k_event_scan<3> : k_event_scan<2>;
+    hipLaunchKernelGGL(kern, dim3(qt_cdiv(P, 256), B), dim3(256), 0, (hipStream_t)stream, sg, nseg, y, y_clip_stride,
+                       y_step_stride, b1, pix_mask, launch, launch_clip_stride, thr, target, k, z0, P, dates, runs);
+    QT_LAUNCHED();
+    return QT_OK;
+}
+
+extern "C" int qt_event_sums(const int32_t* dates, int S1, int B, int n, int m, int64_t* sums, void* stream) {
+    QT_ARG(dates && sums, "null dates / sums");
+    QT_ARG(S1 == 2 || S1 == 3, "S1 must be 2 or 3");
+    QT_ARG(B > 0 && B <= 65535 && n > 0 && m > 0, "bad sizes");
+    hipLaunchKernelGGL(k_event_sums, dim3(B, S1 - 1), dim3(256), 0, (hipStream_t)stream, dates, S1, (int64_t)n * m, sums);
     QT_LAUNCHED();
     return QT_OK;
 }

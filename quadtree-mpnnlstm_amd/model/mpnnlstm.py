@@ -452,6 +452,31 @@ class NextFramePredictorS2S(NextFramePredictor):
         return self._graphed_inference(scores, load)
 
     @on_device(lambda self, *a, **k: self.device)
+    def make_graphed_events(self, x, y, concat_layers=None, mask=None, high_interest_region=None, graph_structure=None,
+                            threshold=0.15, kind='breakup', persist=5):
+        """make_graphed_scores with the event dates in place of the verification sums: the capture holds the rollout, the
+        date scan of every 16 steps and the sums of the date errors (ops.rollout_event_dates: launch state = channel 0 of the
+        last input frame, climatology = concat_layers when given), no frame gather.  Returns `events(x, y, concat)` -> one
+        int32 device buffer, the int64 sums (B, S1 - 1, 8) followed by the dates (B, S1, P) (split_event_buffer);
+        `events.warmup` is the given batch's.  The scan's first launch initialises its state, so a replay needs no memset."""
+        self.model.static_shapes = True
+        sx, sy = x.clone(), y.clone()
+        sc = concat_layers.clone() if concat_layers is not None else None
+
+        def events():
+            with torch.no_grad():
+                y_hat, meshes = self.model(sx, concat_layers=sc, teacher_forcing_ratio=0, mask=mask,
+                                           high_interest_region=high_interest_region, graph_structure=graph_structure)
+                return ops._event_buffer(y_hat, meshes, sy, sx[..., -1, :, :, 0], threshold, kind, persist, sc)[0]
+
+        def load(x, y, concat_layers=None):
+            sx.copy_(x)
+            sy.copy_(y)
+            if sc is not None:
+                sc.copy_(concat_layers)
+        return self._graphed_inference(events, load)
+
+    @on_device(lambda self, *a, **k: self.device)
     def train(self, loader_train, loader_test, climatology=None, n_epochs=200, lr=0.01, lr_decay=0.95, mask=None,
               high_interest_region=None, truncated_backprop=45, graph_structure=None, use_graph=False):
         """The reference's training loop (mpnnlstm.py:186-387).  use_graph=True (beyond the reference) replays the whole training
@@ -659,3 +684,62 @@ class NextFramePredictorS2S(NextFramePredictor):
             self.model.static_shapes = static0
         check_tile_errors(always=True)
         return Scores(np.concatenate(sums, 0), sources, maps=maps)
+
+    @on_device(lambda self, *a, **k: self.device)
+    def event_dates(self, loader, climatology=None, mask=None, high_interest_region=None, graph_structure=None, use_graph=False,
+                    threshold=0.15, kind='breakup', persist=5):
+        """Break-up / freeze-up dates over a loader -> qtmpnn.events.EventDates (beyond the reference): per clip, source and
+        pixel the first output step from which the pixel is no ice (kind='breakup') or ice ('freezeup') for `persist`
+        consecutive steps, ice = value > threshold (strict); -1 where there is no such step or the pixel is in that state at
+        launch already (channel 0 of the last input frame), -2 where the pixel is masked or has no node at some step.
+        Sources: 'observed' (the loader's y), 'model' and, with `climatology`, 'climatology'; `.sums` compares the forecast
+        sources' dates with the observed ones (hits, false alarms, misses, date errors in days).
+
+        score()'s loop and arguments: the dates are scanned on the device along the rollout's time axis (the head's outputs
+        read through every step's labels, no frame is built; ops.rollout_event_dates) and every batch makes one host copy of
+        dates and sums.  use_graph=True replays rollout + scan + sums as one hipGraph per distinct batch shape
+        (make_graphed_events)."""
+        from qtmpnn.events import EventDates
+        if kind not in ops.EVENT_KINDS:
+            raise ValueError(f'event_dates: kind must be one of {ops.EVENT_KINDS}, got {kind!r}')
+        if not (isinstance(persist, int) and 1 <= persist <= self.output_timesteps):
+            raise ValueError(f'event_dates: persist must be an integer in 1..{self.output_timesteps} (the output steps), '
+                             f'got {persist!r}')
+        self.model.to(self.device)
+        sources = ('observed', 'model') + (('climatology',) if climatology is not None else ())
+        S1 = len(sources)
+        dates, sums = [], []
+        graphed, static0 = {}, self.model.static_shapes
+        try:
+            for x, y, launch_date in loader:
+                x, y = self._clip(x), self._clip(y)
+                concat = self.get_climatology_array(climatology, launch_date) if climatology is not None else None
+                if use_graph:
+                    key = (tuple(x.shape), tuple(y.shape), None if concat is None else tuple(concat.shape), self.model.training)
+                    if key not in graphed:
+                        graphed[key] = self.make_graphed_events(x, y, concat, mask=mask, high_interest_region=high_interest_region,
+                                                                graph_structure=graph_structure, threshold=threshold, kind=kind,
+                                                                persist=persist)
+                        buf = graphed[key].warmup
+                    else:
+                        buf = graphed[key](x, y, concat)
+                else:
+                    with torch.no_grad():
+                        y_hat, meshes = self.model(x, concat_layers=concat, teacher_forcing_ratio=0, mask=mask,
+                                                   high_interest_region=high_interest_region, graph_structure=graph_structure)
+                        buf = ops._event_buffer(y_hat, meshes, y, x[..., -1, :, :, 0], threshold, kind, persist, concat)[0]
+                B = 1 if x.dim() == 4 else x.shape[0]
+                d, s = split_event_buffer(buf.cpu().numpy(), B, S1, tuple(x.shape[-3:-1]))
+                dates.append(d)
+                sums.append(s)
+        finally:
+            graphed.clear()
+            self.model.static_shapes = static0
+        check_tile_errors(always=True)
+        return EventDates(np.concatenate(dates, 0), np.concatenate(sums, 0), sources, kind, persist, threshold)
+
+
+def split_event_buffer(buf, B, S1, frame):
+    """Host copy of ops.rollout_event_dates' buffer -> (dates (B, S1, W, H) int32, sums (B, S1 - 1, 8) int64)."""
+    nsum = 2 * B * (S1 - 1) * 8
+    return buf[nsum:].reshape(B, S1, *frame), buf[:nsum].view(np.int64).reshape(B, S1 - 1, 8)

@@ -2031,6 +2031,46 @@ def rollout_score_maps(outputs, meshes, y, maps, threshold=0.15, persistence=Non
     return maps
 
 
+EVENT_KINDS = ('breakup', 'freezeup')      # the target state of an event: no ice (False) / ice (True)
+
+
+def _event_buffer(outputs, meshes, y, launch, threshold, kind, persist, climatology):
+    """rollout_event_dates' launches -> (buf, dates, sums): one int32 device buffer that holds the int64 sums (first) and
+    the dates, so that a caller copies both to the host at once, and the two views of it."""
+    who = 'rollout_event_dates'
+    outs, y, bases, _, B, T, P = _score_args(who, outputs, meshes, y, None, climatology)
+    if not isinstance(launch, torch.Tensor) or launch.numel() != B * P:
+        got = launch.numel() if isinstance(launch, torch.Tensor) else type(launch).__name__
+        raise ValueError(f'{who}: launch has {got} elements for {B} clip(s) of {P} pixels (expected {B * P})')
+    if kind not in EVENT_KINDS:
+        raise ValueError(f'{who}: kind must be one of {EVENT_KINDS}, got {kind!r}')
+    if not (isinstance(persist, int) and 1 <= persist <= T):
+        raise ValueError(f'{who}: persist must be an integer in 1..{T} (the rollout has {T} steps), got {persist!r}')
+    launch = launch.detach().to(outs[0].device, torch.float32).contiguous()
+    S1 = 2 + (bases[0][0] is not None)
+    m0 = meshes[0]
+    nsum = 2 * B * (S1 - 1) * 8                 # the int64 sums come first: 8-byte aligned whatever B * S1 * P is
+    buf = torch.empty(nsum + B * S1 * P, dtype=torch.int32, device=outs[0].device)
+    sums, dates = buf[:nsum].view(torch.int64).view(B, S1 - 1, 8), buf[nsum:].view(B, S1, P)
+    runs = torch.empty_like(dates)              # the state between chunks; the z0 == 0 launch initialises both
+    _score_chunks('qt_event_scan', outs, meshes, y, bases[:1], threshold, B, T, P,
+                  lambda z0: (ptr(launch), P, int(kind == 'freezeup'), persist, z0, ptr(dates), ptr(runs)))
+    _lib.call('qt_event_sums', ptr(dates), S1, B, m0.n, m0.m, ptr(sums))
+    return buf, dates, sums
+
+
+def rollout_event_dates(outputs, meshes, y, launch, threshold=0.15, kind='breakup', persist=5, climatology=None):
+    """Event dates of a rollout -> (dates int32 (B, S1, P), sums int64 (B, S1 - 1, 8)) on the device (qt_event_scan per 16
+    steps, then qt_event_sums; date codes and slot table in include/qtmpnn.h).  The event of `kind` is the first output step
+    from which a pixel is no ice ('breakup') or ice ('freezeup') for `persist` consecutive steps, ice = value > threshold
+    (strict, fp32); pixels already in that state in `launch` (B*P values: channel 0 of the last input frame) have none.
+    Sources: observed (y, B*T*P values laid out (B, T, P)), model (outputs[t] read in place through the step's labels, as
+    rollout_scores) and `climatology` when given (a dense field as rollout_scores'); sums compare each forecast source with
+    the observed dates.  Pixels without a node at any step, and those under meshes[0].loss_mask, are -2 and not counted.
+    No autograd, no host read: capturable, and a replay gives the same bits."""
+    return _event_buffer(outputs, meshes, y, launch, threshold, kind, persist, climatology)[1:]
+
+
 def step_sse_partials(out, y, mesh):
     """`out` (N, 1); when it is column 0 of a wider contiguous matrix (the head's 4-wide output) the op runs on that
     matrix, so the gradient is written once as full rows instead of slice_backward's zero-fill + copy."""
