@@ -1,7 +1,8 @@
 // Mesh <-> image transfers by label map: flatten / unflatten
 // (model/graph_functions.py:391-419, 451-458) without the dense (N, P) mapping, the fused
 // remesh transfer of seq2seq.py:440-442 + 474-477, and the masked squared error of
-// mpnnlstm.py:243-246.
+// mpnnlstm.py:243-246 (the training loss: k_sse*, k_pool_targets).  The verification
+// kernels that read a rollout the same way (scores, maps, event dates) are in verify.hip.
 //
 // k_pool: one workgroup per 64x64 image tile.  Each thread owns a 4x4 pixel block and
 // builds the 2x2 / 4x4 sums in registers; 8x8 .. 64x64 sums go through a small LDS
@@ -522,265 +523,6 @@ __global__ __launch_bounds__(256) void k_sse_multi(LossSeg sg, const float* __re
         partial[((int64_t)z * B + b) * gridDim.x + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-// Forecast verification of a rollout: k_sse_multi's reads with more accumulators, kept per (step, clip, tile) and per
-// source (the model's node values through the labels, then up to two dense baseline fields), no gradient.
-struct ScoreSeg {
-    const float* out[16];         // node values of the step (column 0 of rows of out_stride floats)
-    const int32_t* labels[16];
-    const int32_t* n_dev[16];
-    int out_stride[16], N[16];
-};
-struct ScoreBase {
-    const float* f;               // dense field: step z of clip b starts at f + b*clip_stride + z*step_stride
-    int64_t clip_stride, step_stride;
-};
-
-// Per tile: n, then per source [sum d, sum |d|, sum d^2, hits, over, under]; the correct negatives are n - hits - over - under
-// (every counted pixel falls in exactly one of the four classes, and the counts are integers <= 1024: exact in fp32).
-template <int S>
-__global__ __launch_bounds__(256) void k_score_multi(ScoreSeg sg, const float* __restrict__ y, int64_t y_clip_stride,
-                                                     int64_t y_step_stride, ScoreBase b1, ScoreBase b2,
-                                                     const uint8_t* __restrict__ pix_mask, float thr, int64_t P, int B,
-                                                     float* __restrict__ partial) {
-    constexpr int NV = 1 + 6 * S;
-    __shared__ float red[4][NV];
-    const int b = blockIdx.y, z = blockIdx.z;
-    const float* out = sg.out[z];
-    const int32_t* labels = sg.labels[z] + (int64_t)b * P;
-    const int os = sg.out_stride[z];
-    const int rows = qt_rows(sg.n_dev[z], sg.N[z]);
-    const float* yz = y + z * y_step_stride + b * y_clip_stride;
-    const float* f1 = S > 1 ? b1.f + z * b1.step_stride + b * b1.clip_stride : nullptr;
-    const float* f2 = S > 2 ? b2.f + z * b2.step_stride + b * b2.clip_stride : nullptr;
-    float acc[NV];
-#pragma unroll
-    for (int v = 0; v < NV; ++v) acc[v] = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int64_t p = (int64_t)blockIdx.x * 1024 + k * 256 + threadIdx.x;
-        if (p >= P) continue;
-        const int lab = labels[p];
-        if (lab < 0 || lab >= rows || (pix_mask && pix_mask[p])) continue;
-        const float t = yz[p];
-        const bool ty = t > thr;
-        float f[S];
-        f[0] = out[(int64_t)lab * os];
-        if (S > 1) f[1] = f1[p];
-        if (S > 2) f[2] = f2[p];
-        acc[0] += 1.0f;
-#pragma unroll
-        for (int s = 0; s < S; ++s) {
-            float* a = acc + 1 + 6 * s;
-            const float d = f[s] - t;
-            const bool tf = f[s] > thr;
-            a[0] += d;
-            a[1] += fabsf(d);
-            a[2] += d * d;
-            a[3] += (tf && ty) ? 1.0f : 0.0f;
-            a[4] += (tf && !ty) ? 1.0f : 0.0f;
-            a[5] += (!tf && ty) ? 1.0f : 0.0f;
-        }
-    }
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) acc[v] += __shfl_xor(acc[v], d, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int v = 0; v < NV; ++v) red[threadIdx.x >> 6][v] = acc[v];
-    }
-    __syncthreads();
-    if (threadIdx.x < 8 * S) {
-        const int s = threadIdx.x >> 3, slot = threadIdx.x & 7;
-        auto total = [&](int v) { return (red[0][v] + red[1][v]) + (red[2][v] + red[3][v]); };
-        const int v0 = 1 + 6 * s;
-        float r;
-        if (slot == 0) r = total(0);
-        else if (slot < 7) r = total(v0 + slot - 1);
-        else r = total(0) - total(v0 + 3) - total(v0 + 4) - total(v0 + 5);
-        partial[((((int64_t)z * B + b) * gridDim.x + blockIdx.x) * S + s) * 8 + slot] = r;
-    }
-}
-
-// Per-pixel verification sums: k_score_multi's reads and counting rule, kept per pixel and summed over the clips instead of
-// per clip and summed over the pixels.  One thread owns pixel p of step z and is the only writer of its 8 * S running doubles
-// (maps + z * maps_step_stride, laid out (S, 8, P)): it loads the three sums of every source, adds the clips' terms to them
-// one by one in clip order in double, and stores them; the class counts are integers (exact in any order) and are added to
-// their running values at the end.  d = f - y is formed in fp32 as in k_score_multi and then widened; d * d of a widened fp32
-// is exact in double, so contracting it into the add changes no bit.  The result is the left-to-right float64 sum over every
-// clip that was ever added, however the clips were batched.  No atomics, no LDS, no cross-thread step; launches that share
-// `maps` are ordered by their stream.
-template <int S>
-__global__ __launch_bounds__(256) void k_score_maps(ScoreSeg sg, const float* __restrict__ y, int64_t y_clip_stride,
-                                                    int64_t y_step_stride, ScoreBase b1, ScoreBase b2,
-                                                    const uint8_t* __restrict__ pix_mask, float thr, int64_t P, int B,
-                                                    double* __restrict__ maps, int64_t maps_step_stride) {
-    const int z = blockIdx.y;
-    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (p >= P || (pix_mask && pix_mask[p])) return;         // a masked pixel counts in no clip: its doubles stay as they are
-    const float* out = sg.out[z];
-    const int32_t* labels = sg.labels[z] + p;
-    const int os = sg.out_stride[z];
-    const int rows = qt_rows(sg.n_dev[z], sg.N[z]);
-    const float* yz = y + z * y_step_stride + p;
-    const float* f1 = S > 1 ? b1.f + z * b1.step_stride + p : nullptr;
-    const float* f2 = S > 2 ? b2.f + z * b2.step_stride + p : nullptr;
-    double* mz = maps + z * maps_step_stride + p;             // slot k of source s: mz[(s * 8 + k) * P]
-    double sum[S][3];
-    int cls[S][3], n = 0;
-#pragma unroll
-    for (int s = 0; s < S; ++s) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            sum[s][k] = mz[(s * 8 + 1 + k) * P];
-            cls[s][k] = 0;
-        }
-    }
-    for (int b = 0; b < B; ++b) {
-        const int lab = labels[b * P];
-        if (lab < 0 || lab >= rows) continue;
-        const float t = yz[b * y_clip_stride];
-        const bool ty = t > thr;
-        float f[S];
-        f[0] = out[(int64_t)lab * os];
-        if (S > 1) f[1] = f1[b * b1.clip_stride];
-        if (S > 2) f[2] = f2[b * b2.clip_stride];
-        ++n;
-#pragma unroll
-        for (int s = 0; s < S; ++s) {
-            const float d32 = f[s] - t;
-            const double d = (double)d32;
-            const bool tf = f[s] > thr;
-            sum[s][0] += d;
-            sum[s][1] += fabs(d);
-            sum[s][2] += d * d;
-            cls[s][0] += (tf && ty) ? 1 : 0;
-            cls[s][1] += (tf && !ty) ? 1 : 0;
-            cls[s][2] += (!tf && ty) ? 1 : 0;
-        }
-    }
-    if (n == 0) return;                                       // no clip of this launch has a node here: nothing to add
-#pragma unroll
-    for (int s = 0; s < S; ++s) {
-        double* m = mz + (int64_t)s * 8 * P;
-        m[0] += (double)n;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            m[(1 + k) * P] = sum[s][k];
-            m[(4 + k) * P] += (double)cls[s][k];
-        }
-        m[7 * P] += (double)(n - cls[s][0] - cls[s][1] - cls[s][2]);
-    }
-}
-
-// Event dates of a rollout (break-up / freeze-up): the first output step from which a pixel stays in the target state g for k
-// consecutive steps, per source (observed, model, optionally one dense field).  k_score_maps' reads and counting rule, but along
-// the time axis: one thread owns pixel p of clip b, reads its label once per step and serves every source from it, and carries
-// per source the current run length and the date in registers over the chunk's steps.  A launch with z0 == 0 initialises the
-// state (date -2 under the mask, else -1; run 0, or -1 where the launch frame is already in the target state: such a pixel has
-// no event, and a negative run is never advanced), a launch with z0 > 0 loads what the previous chunk stored.  A pixel without
-// a valid node at any step ends as -2 for every source.  No atomics, no LDS, no cross-thread step; chunks are ordered by their
-// stream.
-template <int S1>
-__global__ __launch_bounds__(256) void k_event_scan(ScoreSeg sg, int nseg, const float* __restrict__ y, int64_t y_clip_stride,
-                                                    int64_t y_step_stride, ScoreBase b1, const uint8_t* __restrict__ pix_mask,
-                                                    const float* __restrict__ launch, int64_t launch_clip_stride, float thr,
-                                                    int target, int k, int z0, int64_t P, int32_t* __restrict__ dates,
-                                                    int32_t* __restrict__ runs) {
-    const int b = blockIdx.y;
-    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (p >= P) return;
-    const bool g = target != 0;
-    const int64_t st = ((int64_t)b * S1) * P + p;             // source s of this pixel: st + s * P
-    int date[S1], run[S1];
-    if (z0 == 0) {
-        const int d0 = (pix_mask && pix_mask[p]) ? -2 : -1;
-        const int r0 = ((launch[b * launch_clip_stride + p] > thr) == g) ? -1 : 0;
-#pragma unroll
-        for (int s = 0; s < S1; ++s) {
-            date[s] = d0;
-            run[s] = r0;
-        }
-    } else {
-#pragma unroll
-        for (int s = 0; s < S1; ++s) {
-            date[s] = dates[st + s * P];
-            run[s] = runs[st + s * P];
-        }
-    }
-    bool dead = date[0] == -2;                                // masked, or without a node at an earlier step
-    const float* yp = y + b * y_clip_stride + p;
-    const float* fp = S1 > 2 ? b1.f + b * b1.clip_stride + p : nullptr;
-    for (int z = 0; z < nseg && !dead; ++z) {
-        const int lab = sg.labels[z][(int64_t)b * P + p];
-        if (lab < 0 || lab >= qt_rows(sg.n_dev[z], sg.N[z])) {
-            dead = true;
-            break;
-        }
-        float f[S1];
-        f[0] = yp[z * y_step_stride];
-        f[1] = sg.out[z][(int64_t)lab * sg.out_stride[z]];
-        if (S1 > 2) f[2] = fp[z * b1.step_stride];
-#pragma unroll
-        for (int s = 0; s < S1; ++s) {
-            if (run[s] < 0) continue;
-            run[s] = ((f[s] > thr) == g) ? run[s] + 1 : 0;
-            if (run[s] >= k && date[s] == -1) date[s] = z0 + z - k + 1;
-        }
-    }
-#pragma unroll
-    for (int s = 0; s < S1; ++s) {
-        dates[st + s * P] = dead ? -2 : date[s];
-        runs[st + s * P] = run[s];
-    }
-}
-
-// The eight sums of the date errors per (clip, forecast source): one workgroup each, every thread over its pixels in pixel
-// order in int64, then 64-lane butterflies and (w0 + w1) + (w2 + w3).  Integers: exact in any order.
-__global__ __launch_bounds__(256) void k_event_sums(const int32_t* __restrict__ dates, int S1, int64_t P,
-                                                    int64_t* __restrict__ sums) {
-    __shared__ long long red[4][8];
-    const int b = blockIdx.x, s = 1 + blockIdx.y;             // source 0 is the observed one
-    const int32_t* dob = dates + ((int64_t)b * S1) * P;
-    const int32_t* dfc = dob + (int64_t)s * P;
-    long long acc[8];
-#pragma unroll
-    for (int v = 0; v < 8; ++v) acc[v] = 0;
-    for (int64_t p = threadIdx.x; p < P; p += 256) {
-        const int o = dob[p], f = dfc[p];
-        if (o == -2) continue;
-        acc[0] += 1;
-        if (o >= 0 && f >= 0) {
-            const long long e = (long long)f - o;
-            acc[1] += e;
-            acc[2] += e < 0 ? -e : e;
-            acc[3] += e * e;
-            acc[4] += 1;
-        } else if (f >= 0) {
-            acc[5] += 1;
-        } else if (o >= 0) {
-            acc[6] += 1;
-        } else {
-            acc[7] += 1;
-        }
-    }
-#pragma unroll
-    for (int v = 0; v < 8; ++v) {
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) acc[v] += __shfl_xor(acc[v], d, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int v = 0; v < 8; ++v) red[threadIdx.x >> 6][v] = acc[v];
-    }
-    __syncthreads();
-    if (threadIdx.x < 8) {
-        const int v = threadIdx.x;
-        sums[((int64_t)b * (S1 - 1) + (s - 1)) * 8 + v] = (int64_t)((red[0][v] + red[1][v]) + (red[2][v] + red[3][v]));
-    }
-}
-
 __global__ void k_sse_bwd_multi(LossSeg sg, const float* __restrict__ g, int W) {
     const int z = blockIdx.y;
     const unsigned idx = blockIdx.x * blockDim.x + threadIdx.x;
@@ -832,103 +574,6 @@ extern "C" int qt_sse_rollout(int nseg, const float* const* outs, const int* out
     a.out_stride = 1; a.out_coff = 0; a.tiles_r = qt_cdiv(n, 64); a.tiles_c = qt_cdiv(m, 64);
     hipLaunchKernelGGL(k_pool_targets, dim3(B * a.tiles_r * a.tiles_c, 1, nseg), dim3(256), 0, (hipStream_t)stream, a, sg,
                        y_step_stride);
-    QT_LAUNCHED();
-    return QT_OK;
-}
-
-extern "C" int qt_score_rollout(int nseg, const float* const* outs, const int* out_strides, const int32_t* const* labels,
-                                const int* Ns, const int32_t* const* n_devs, const float* y, int64_t y_clip_stride,
-                                int64_t y_step_stride, const float* base1, int64_t base1_clip_stride, int64_t base1_step_stride,
-                                const float* base2, int64_t base2_clip_stride, int64_t base2_step_stride,
-                                const uint8_t* pix_mask, float thr, int B, int n, int m, float* partial, void* stream) {
-    QT_ARG(nseg >= 1 && nseg <= 16, "nseg must be 1..16");
-    QT_ARG(outs && out_strides && labels && Ns && n_devs && y && partial, "null pointer");
-    QT_ARG(B > 0 && B <= 65535 && n > 0 && m > 0, "bad sizes");
-    QT_ARG(y_clip_stride >= 0 && y_step_stride >= 0 && base1_clip_stride >= 0 && base1_step_stride >= 0 &&
-           base2_clip_stride >= 0 && base2_step_stride >= 0, "negative stride");
-    ScoreSeg sg = {};
-    for (int z = 0; z < nseg; ++z) {
-        QT_ARG(labels[z] && Ns[z] >= 0 && (outs[z] || Ns[z] == 0) && out_strides[z] >= 1, "bad segment");
-        sg.out[z] = outs[z]; sg.out_stride[z] = out_strides[z]; sg.labels[z] = labels[z]; sg.N[z] = Ns[z]; sg.n_dev[z] = n_devs[z];
-    }
-    // the sources present, in order: the kernel's partial rows are sized for them
-    ScoreBase bs[2] = {};
-    int nb = 0;
-    if (base1) bs[nb++] = {base1, base1_clip_stride, base1_step_stride};
-    if (base2) bs[nb++] = {base2, base2_clip_stride, base2_step_stride};
-    const int64_t P = (int64_t)n * m;
-    const dim3 grid(qt_cdiv(P, 1024), B, nseg);
-    auto k = nb == 0 ? k_score_multi<1> : nb == 1 ? k_score_multi<2> : k_score_multi<3>;
-    hipLaunchKernelGGL(k, grid, dim3(256), 0, (hipStream_t)stream, sg, y, y_clip_stride, y_step_stride, bs[0], bs[1], pix_mask, thr,
-                       P, B, partial);
-    QT_LAUNCHED();
-    return QT_OK;
-}
-
-extern "C" int qt_score_maps(int nseg, const float* const* outs, const int* out_strides, const int32_t* const* labels,
-                             const int* Ns, const int32_t* const* n_devs, const float* y, int64_t y_clip_stride,
-                             int64_t y_step_stride, const float* base1, int64_t base1_clip_stride, int64_t base1_step_stride,
-                             const float* base2, int64_t base2_clip_stride, int64_t base2_step_stride,
-                             const uint8_t* pix_mask, float thr, int B, int n, int m, double* maps, int64_t maps_step_stride,
-                             void* stream) {
-    QT_ARG(nseg >= 1 && nseg <= 16, "nseg must be 1..16");
-    QT_ARG(outs && out_strides && labels && Ns && n_devs && y && maps, "null pointer");
-    QT_ARG(B > 0 && n > 0 && m > 0, "bad sizes");
-    QT_ARG(y_clip_stride >= 0 && y_step_stride >= 0 && base1_clip_stride >= 0 && base1_step_stride >= 0 &&
-           base2_clip_stride >= 0 && base2_step_stride >= 0, "negative stride");
-    ScoreSeg sg = {};
-    for (int z = 0; z < nseg; ++z) {
-        QT_ARG(labels[z] && Ns[z] >= 0 && (outs[z] || Ns[z] == 0) && out_strides[z] >= 1, "bad segment");
-        sg.out[z] = outs[z]; sg.out_stride[z] = out_strides[z]; sg.labels[z] = labels[z]; sg.N[z] = Ns[z]; sg.n_dev[z] = n_devs[z];
-    }
-    ScoreBase bs[2] = {};
-    int nb = 0;
-    if (base1) bs[nb++] = {base1, base1_clip_stride, base1_step_stride};
-    if (base2) bs[nb++] = {base2, base2_clip_stride, base2_step_stride};
-    const int64_t P = (int64_t)n * m;
-    // a step's (S, 8, P) block must fit its stride, or step z would write into step z + 1
-    QT_ARG(maps_step_stride >= (int64_t)(1 + nb) * 8 * P, "maps_step_stride is smaller than S*8*n*m");
-    auto k = nb == 0 ? k_score_maps<1> : nb == 1 ? k_score_maps<2> : k_score_maps<3>;
-    hipLaunchKernelGGL(k, dim3(qt_cdiv(P, 256), nseg), dim3(256), 0, (hipStream_t)stream, sg, y, y_clip_stride, y_step_stride,
-                       bs[0], bs[1], pix_mask, thr, P, B, maps, maps_step_stride);
-    QT_LAUNCHED();
-    return QT_OK;
-}
-
-extern "C" int qt_event_scan(int nseg, const float* const* outs, const int* out_strides, const int32_t* const* labels,
-                             const int* Ns, const int32_t* const* n_devs, const float* y, int64_t y_clip_stride,
-                             int64_t y_step_stride, const float* base, int64_t base_clip_stride, int64_t base_step_stride,
-                             const uint8_t* pix_mask, float thr, int B, int n, int m, const float* launch,
-                             int64_t launch_clip_stride, int target, int k, int z0, int32_t* dates, int32_t* runs,
-                             void* stream) {
-    QT_ARG(nseg >= 1 && nseg <= 16, "nseg must be 1..16");
-    QT_ARG(outs && out_strides && labels && Ns && n_devs && y && launch, "null pointer");
-    QT_ARG(dates && runs, "null dates / runs");
-    QT_ARG(B > 0 && B <= 65535 && n > 0 && m > 0, "bad sizes");
-    QT_ARG(y_clip_stride >= 0 && y_step_stride >= 0 && base_clip_stride >= 0 && base_step_stride >= 0 &&
-           launch_clip_stride >= 0, "negative stride");
-    QT_ARG(target == 0 || target == 1, "target must be 0 (no ice: break-up) or 1 (ice: freeze-up)");
-    QT_ARG(k >= 1, "k (persist) must be >= 1");
-    QT_ARG(z0 >= 0, "z0 must be >= 0");
-    ScoreSeg sg = {};
-    for (int z = 0; z < nseg; ++z) {
-        QT_ARG(labels[z] && Ns[z] >= 0 && (outs[z] || Ns[z] == 0) && out_strides[z] >= 1, "bad segment");
-        sg.out[z] = outs[z]; sg.out_stride[z] = out_strides[z]; sg.labels[z] = labels[z]; sg.N[z] = Ns[z]; sg.n_dev[z] = n_devs[z];
-    }
-    const ScoreBase b1 = {base, base_clip_stride, base_step_stride};
-    const int64_t P = (int64_t)n * m;
-    auto kern = base ? k_event_scan<3> : k_event_scan<2>;
-    hipLaunchKernelGGL(kern, dim3(qt_cdiv(P, 256), B), dim3(256), 0, (hipStream_t)stream, sg, nseg, y, y_clip_stride,
-                       y_step_stride, b1, pix_mask, launch, launch_clip_stride, thr, target, k, z0, P, dates, runs);
-    QT_LAUNCHED();
-    return QT_OK;
-}
-
-extern "C" int qt_event_sums(const int32_t* dates, int S1, int B, int n, int m, int64_t* sums, void* stream) {
-    QT_ARG(dates && sums, "null dates / sums");
-    QT_ARG(S1 == 2 || S1 == 3, "S1 must be 2 or 3");
-    QT_ARG(B > 0 && B <= 65535 && n > 0 && m > 0, "bad sizes");
-    hipLaunchKernelGGL(k_event_sums, dim3(B, S1 - 1), dim3(256), 0, (hipStream_t)stream, dates, S1, (int64_t)n * m, sums);
     QT_LAUNCHED();
     return QT_OK;
 }

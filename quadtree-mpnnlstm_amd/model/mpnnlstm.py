@@ -61,6 +61,43 @@ def masked_mse(outputs, meshes, y, mask=None, binary=False):
     return part.sum() / float(mesh0.B * len(outputs) * n_valid)        # one reduction for all steps
 
 
+def launch_frame(x):
+    """Channel 0 of the last input frame, (W, H) or (B, W, H): the persistence forecast of every lead time, and the state at launch
+    that the event dates count from."""
+    return x[..., -1, :, :, 0]
+
+
+# The products of one inference rollout.  Each is reduce(y_hat, meshes, x, y, concat) -> one device tensor, written once: the
+# eager branch of the inference loop and the captured body (NextFramePredictorS2S._graphed_product) call the same function.
+def frames_product(x, T_out):
+    """Frames: every step gathered by one launch into its slot of a (B, T_out, W, H, 1) stack for batches shaped like x."""
+    out = torch.empty(1 if x.dim() == 4 else x.shape[0], T_out, x.shape[-3], x.shape[-2], 1, device=x.device)
+
+    def reduce(y_hat, meshes, x, y, concat):
+        for t, (o, ms) in enumerate(zip(y_hat, meshes)):
+            ops.gather_frame_into(o, ms, out, t)
+        return out
+    return reduce
+
+
+def sums_product(threshold, maps=None):
+    """Sums: the (T_out, B, S, 8) float64 verification sums of model, persistence and (with concat) climatology; with `maps`, a
+    float64 (T_out, S, 8, P) device buffer, the batch's per-pixel sums are added into it as well."""
+    def reduce(y_hat, meshes, x, y, concat):
+        part = ops.rollout_scores(y_hat, meshes, y, threshold, persistence=launch_frame(x), climatology=concat)
+        if maps is not None:
+            ops.rollout_score_maps(y_hat, meshes, y, maps, threshold, persistence=launch_frame(x), climatology=concat)
+        return part
+    return reduce
+
+
+def events_product(threshold, kind, persist):
+    """Event buffer: int32, the int64 sums (B, S1 - 1, 8) followed by the dates (B, S1, P) (split_event_buffer)."""
+    def reduce(y_hat, meshes, x, y, concat):
+        return ops._event_buffer(y_hat, meshes, y, launch_frame(x), threshold, kind, persist, concat)[0]
+    return reduce
+
+
 class NextFramePredictor(ABC):
     """The abstract trainer facade of the reference (model/mpnnlstm.py:34-79; moving_mnist_example.ipynb cell 2 imports it):
     it holds the decomposition settings and names the three methods a predictor offers.  `thresh` is kept as given here;
@@ -365,28 +402,32 @@ class NextFramePredictorS2S(NextFramePredictor):
         state an eager rollout advances is advanced by a replay too: Python's `random` (unroll_output draws once per output step)
         and the attention-dropout seed counter.  In train() mode every replay draws new dropout masks (torch's graph-safe RNG
         for the decoder, the device counter ops.dropout_epoch for attention)."""
+        return self._graphed_product(frames_product(x, self.output_timesteps), x, None, concat_layers, mask=mask,
+                                     high_interest_region=high_interest_region, graph_structure=graph_structure)
+
+    def _graphed_product(self, reduce, x, y, concat_layers, **fwd):
+        """The capture of one rollout (forward arguments `fwd`) and its product `reduce` on static copies of the batch; y is None
+        for a product that does not read it, and replay's arguments are then (x, concat), else (x, y, concat)."""
         self.model.static_shapes = True
-        B = 1 if x.dim() == 4 else x.shape[0]
-        sx = x.clone()
-        sc = concat_layers.clone() if concat_layers is not None else None
-        out = torch.empty(B, self.output_timesteps, x.shape[-3], x.shape[-2], 1, device=x.device)
+        sx, sy, sc = (t if t is None else t.clone() for t in (x, y, concat_layers))
 
-        def rollout():
+        def body():
             with torch.no_grad():
-                y_hat, meshes = self.model(sx, concat_layers=sc, teacher_forcing_ratio=0, mask=mask,
-                                           high_interest_region=high_interest_region, graph_structure=graph_structure)
-                for t, (o, ms) in enumerate(zip(y_hat, meshes)):
-                    ops.gather_frame_into(o, ms, out, t)
-            return out
+                y_hat, meshes = self.model(sx, concat_layers=sc, teacher_forcing_ratio=0, **fwd)
+                return reduce(y_hat, meshes, sx, sy, sc)
 
-        def load(x, concat_layers=None):
+        def load(x, y, concat_layers):
             sx.copy_(x)
+            if sy is not None:
+                sy.copy_(y)
             if sc is not None:
                 sc.copy_(concat_layers)
-        return self._graphed_inference(rollout, load)
+        if y is None:
+            return self._graphed_inference(body, lambda x, concat_layers=None: load(x, None, concat_layers))
+        return self._graphed_inference(body, lambda x, y, concat_layers=None: load(x, y, concat_layers))
 
     def _graphed_inference(self, body, load):
-        """Warm-up, capture and replay of a no-grad inference body (make_graphed_rollout, make_graphed_scores).  body() reads the
+        """Warm-up, capture and replay of a no-grad inference body (_graphed_product).  body() reads the
         caller's static inputs and returns a device tensor; load(...) copies a batch into them.  The returned replay(...) loads,
         replays, advances the host state like an eager rollout and returns the capture's result tensor; replay.warmup is a copy
         of the eager warm-up's result."""
@@ -431,25 +472,8 @@ class NextFramePredictorS2S(NextFramePredictor):
         batch's.  maps: a float64 (T_out, S, 8, P) device buffer that the body also adds the batch's per-pixel sums into
         (ops.rollout_score_maps).  The warm-up runs the body once and the capture records it without running, so the given
         batch is added exactly once, and every replay adds its batch once."""
-        self.model.static_shapes = True
-        sx, sy = x.clone(), y.clone()
-        sc = concat_layers.clone() if concat_layers is not None else None
-
-        def scores():
-            with torch.no_grad():
-                y_hat, meshes = self.model(sx, concat_layers=sc, teacher_forcing_ratio=0, mask=mask,
-                                           high_interest_region=high_interest_region, graph_structure=graph_structure)
-                part = ops.rollout_scores(y_hat, meshes, sy, threshold, persistence=sx[..., -1, :, :, 0], climatology=sc)
-                if maps is not None:
-                    ops.rollout_score_maps(y_hat, meshes, sy, maps, threshold, persistence=sx[..., -1, :, :, 0], climatology=sc)
-                return part
-
-        def load(x, y, concat_layers=None):
-            sx.copy_(x)
-            sy.copy_(y)
-            if sc is not None:
-                sc.copy_(concat_layers)
-        return self._graphed_inference(scores, load)
+        return self._graphed_product(sums_product(threshold, maps), x, y, concat_layers, mask=mask,
+                                     high_interest_region=high_interest_region, graph_structure=graph_structure)
 
     @on_device(lambda self, *a, **k: self.device)
     def make_graphed_events(self, x, y, concat_layers=None, mask=None, high_interest_region=None, graph_structure=None,
@@ -459,22 +483,8 @@ class NextFramePredictorS2S(NextFramePredictor):
         last input frame, climatology = concat_layers when given), no frame gather.  Returns `events(x, y, concat)` -> one
         int32 device buffer, the int64 sums (B, S1 - 1, 8) followed by the dates (B, S1, P) (split_event_buffer);
         `events.warmup` is the given batch's.  The scan's first launch initialises its state, so a replay needs no memset."""
-        self.model.static_shapes = True
-        sx, sy = x.clone(), y.clone()
-        sc = concat_layers.clone() if concat_layers is not None else None
-
-        def events():
-            with torch.no_grad():
-                y_hat, meshes = self.model(sx, concat_layers=sc, teacher_forcing_ratio=0, mask=mask,
-                                           high_interest_region=high_interest_region, graph_structure=graph_structure)
-                return ops._event_buffer(y_hat, meshes, sy, sx[..., -1, :, :, 0], threshold, kind, persist, sc)[0]
-
-        def load(x, y, concat_layers=None):
-            sx.copy_(x)
-            sy.copy_(y)
-            if sc is not None:
-                sc.copy_(concat_layers)
-        return self._graphed_inference(events, load)
+        return self._graphed_product(events_product(threshold, kind, persist), x, y, concat_layers, mask=mask,
+                                     high_interest_region=high_interest_region, graph_structure=graph_structure)
 
     @on_device(lambda self, *a, **k: self.device)
     def train(self, loader_train, loader_test, climatology=None, n_epochs=200, lr=0.01, lr_decay=0.95, mask=None,
@@ -574,34 +584,56 @@ class NextFramePredictorS2S(NextFramePredictor):
         static mode as the warm-up, and its result is the one returned), later batches copy into the captured inputs, replay and
         make one host copy.  The graphs are dropped and `static_shapes` is restored when the call returns."""
         image_shape = loader.dataset.image_shape
-        self.model.to(self.device)
         preds = []
+
+        def reference_frames(y_hat, meshes, x, y, concat):      # the reference's path, in the caller's (non-static) mode
+            frames = [unflatten(o, ms, image_shape, mask).cpu().numpy() for o, ms in zip(y_hat, meshes)]
+            return np.stack(frames, axis=0)[None] if x.dim() == 4 else np.stack(frames, axis=1)
+
+        if use_graph:           # the stack comes back with one host copy per batch
+            product = lambda x: frames_product(x, self.output_timesteps)
+            consume = lambda stack, x: preds.extend(stack.cpu().numpy())
+        else:
+            product, consume = lambda x: reference_frames, lambda frames, x: preds.extend(frames)
+        self._inference(loader, climatology, product, consume, use_graph, reads_y=False, mask=mask,
+                        high_interest_region=high_interest_region, graph_structure=graph_structure)
+        return np.stack(preds, 0)
+
+    def _inference(self, loader, climatology, product, consume, use_graph, reads_y=True, begin=None, **fwd):
+        """The inference loop of predict, score, score_maps and event_dates: per batch begin(x), if given, then one no-grad
+        rollout (teacher forcing 0, forward arguments `fwd`) reduced by a reduce(y_hat, meshes, x, y, concat), see frames_product,
+        whose result goes to consume(result, x); x is the clipped batch.  product(x) makes the reduce: for every batch of an eager
+        call, for every capture of a graphed one, so it must not do what every batch needs (that is begin's).  use_graph: each
+        distinct (x shape, y shape where the product reads y, climatology shape, train / eval mode) is captured once per call on
+        first sight (_graphed_product); that batch's result is the eager static-mode warm-up's, later batches of the key are
+        replays.  The graphs are dropped and `static_shapes` is restored when the call ends, also by an exception of begin or
+        consume; the tile error word is read once after the last batch."""
+        self.model.to(self.device)
         graphed, static0 = {}, self.model.static_shapes
         try:
             for x, y, launch_date in loader:
-                x = self._clip(x)
+                x, y = self._clip(x), self._clip(y) if reads_y else None
                 concat = self.get_climatology_array(climatology, launch_date) if climatology is not None else None
+                if begin is not None:
+                    begin(x)
+                batch = (x, concat) if y is None else (x, y, concat)
                 if use_graph:
-                    key = (tuple(x.shape), None if concat is None else tuple(concat.shape), self.model.training)
+                    key = tuple(None if t is None else tuple(t.shape) for t in batch) + (self.model.training,)
                     if key not in graphed:
-                        graphed[key] = self.make_graphed_rollout(x, concat, mask=mask, high_interest_region=high_interest_region,
-                                                                 graph_structure=graph_structure)
-                        stack = graphed[key].warmup
+                        graphed[key] = self._graphed_product(product(x), x, y, concat, **fwd)
+                        result = graphed[key].warmup
                     else:
-                        stack = graphed[key](x, concat)
-                    preds.extend(list(stack.cpu().numpy()))
-                    continue
-                with torch.no_grad():
-                    y_hat, meshes = self.model(x, concat_layers=concat, teacher_forcing_ratio=0, mask=mask,
-                                               high_interest_region=high_interest_region, graph_structure=graph_structure)
-                    frames = [unflatten(o, ms, image_shape, mask).cpu().numpy() for o, ms in zip(y_hat, meshes)]
-                frames = np.stack(frames, axis=0 if x.dim() == 4 else 1)
-                preds.extend([frames] if x.dim() == 4 else list(frames))
+                        result = graphed[key](*batch)
+                else:
+                    reduce = product(x)
+                    with torch.no_grad():
+                        y_hat, meshes = self.model(x, concat_layers=concat, teacher_forcing_ratio=0, **fwd)
+                        result = reduce(y_hat, meshes, x, y, concat)
+                consume(result, x)
         finally:
             graphed.clear()
             self.model.static_shapes = static0
         check_tile_errors(always=True)
-        return np.stack(preds, 0)
 
     @on_device(lambda self, *a, **k: self.device)
     def attention_weights(self, x, concat_layers=None, mask=None, high_interest_region=None, graph_structure=None, select=None):
@@ -644,45 +676,25 @@ class NextFramePredictorS2S(NextFramePredictor):
 
     def _score(self, loader, climatology, mask, high_interest_region, graph_structure, use_graph, threshold, with_maps):
         from qtmpnn.score import ScoreMaps, Scores
-        self.model.to(self.device)
         sources = ('model', 'persistence') + (('climatology',) if climatology is not None else ())
         sums, maps, frame = [], None, None
-        graphed, static0 = {}, self.model.static_shapes
-        try:
-            for x, y, launch_date in loader:
-                x, y = self._clip(x), self._clip(y)
-                concat = self.get_climatology_array(climatology, launch_date) if climatology is not None else None
-                if with_maps:
-                    if maps is None:
-                        frame = tuple(x.shape[-3:-1])
-                        maps = torch.zeros(self.output_timesteps, len(sources), 8, frame[0] * frame[1], dtype=torch.float64,
-                                           device=x.device)
-                    elif tuple(x.shape[-3:-1]) != frame:
-                        raise ValueError(f'score_maps: a batch of {tuple(x.shape[-3:-1])} frames after {frame} ones: maps need '
-                                         'one grid (use one loader per grid)')
-                if use_graph:
-                    key = (tuple(x.shape), tuple(y.shape), None if concat is None else tuple(concat.shape), self.model.training)
-                    if key not in graphed:
-                        graphed[key] = self.make_graphed_scores(x, y, concat, mask=mask, high_interest_region=high_interest_region,
-                                                                graph_structure=graph_structure, threshold=threshold, maps=maps)
-                        part = graphed[key].warmup
-                    else:
-                        part = graphed[key](x, y, concat)
-                else:
-                    with torch.no_grad():
-                        y_hat, meshes = self.model(x, concat_layers=concat, teacher_forcing_ratio=0, mask=mask,
-                                                   high_interest_region=high_interest_region, graph_structure=graph_structure)
-                        part = ops.rollout_scores(y_hat, meshes, y, threshold, persistence=x[..., -1, :, :, 0], climatology=concat)
-                        if with_maps:
-                            ops.rollout_score_maps(y_hat, meshes, y, maps, threshold, persistence=x[..., -1, :, :, 0],
-                                                   climatology=concat)
-                sums.append(np.moveaxis(part.cpu().numpy(), 0, 1))      # (T, B, S, 8) -> (B, T, S, 8)
-            if with_maps and maps is not None:
-                maps = ScoreMaps(maps.cpu().numpy().reshape(*maps.shape[:3], *frame), sources)
-        finally:
-            graphed.clear()
-            self.model.static_shapes = static0
-        check_tile_errors(always=True)
+
+        def begin(x):           # the maps buffer exists, zeroed, before the first batch's forward; every batch has its grid
+            nonlocal maps, frame
+            if maps is None:
+                frame = tuple(x.shape[-3:-1])
+                maps = torch.zeros(self.output_timesteps, len(sources), 8, frame[0] * frame[1], dtype=torch.float64,
+                                   device=x.device)
+            elif tuple(x.shape[-3:-1]) != frame:
+                raise ValueError(f'score_maps: a batch of {tuple(x.shape[-3:-1])} frames after {frame} ones: maps need '
+                                 'one grid (use one loader per grid)')
+
+        self._inference(loader, climatology, lambda x: sums_product(threshold, maps),
+                        lambda part, x: sums.append(np.moveaxis(part.cpu().numpy(), 0, 1)),      # (T, B, S, 8) -> (B, T, S, 8)
+                        use_graph, begin=begin if with_maps else None, mask=mask, high_interest_region=high_interest_region,
+                        graph_structure=graph_structure)
+        if maps is not None:
+            maps = ScoreMaps(maps.cpu().numpy().reshape(*maps.shape[:3], *frame), sources)
         return Scores(np.concatenate(sums, 0), sources, maps=maps)
 
     @on_device(lambda self, *a, **k: self.device)
@@ -705,37 +717,17 @@ class NextFramePredictorS2S(NextFramePredictor):
         if not (isinstance(persist, int) and 1 <= persist <= self.output_timesteps):
             raise ValueError(f'event_dates: persist must be an integer in 1..{self.output_timesteps} (the output steps), '
                              f'got {persist!r}')
-        self.model.to(self.device)
         sources = ('observed', 'model') + (('climatology',) if climatology is not None else ())
-        S1 = len(sources)
         dates, sums = [], []
-        graphed, static0 = {}, self.model.static_shapes
-        try:
-            for x, y, launch_date in loader:
-                x, y = self._clip(x), self._clip(y)
-                concat = self.get_climatology_array(climatology, launch_date) if climatology is not None else None
-                if use_graph:
-                    key = (tuple(x.shape), tuple(y.shape), None if concat is None else tuple(concat.shape), self.model.training)
-                    if key not in graphed:
-                        graphed[key] = self.make_graphed_events(x, y, concat, mask=mask, high_interest_region=high_interest_region,
-                                                                graph_structure=graph_structure, threshold=threshold, kind=kind,
-                                                                persist=persist)
-                        buf = graphed[key].warmup
-                    else:
-                        buf = graphed[key](x, y, concat)
-                else:
-                    with torch.no_grad():
-                        y_hat, meshes = self.model(x, concat_layers=concat, teacher_forcing_ratio=0, mask=mask,
-                                                   high_interest_region=high_interest_region, graph_structure=graph_structure)
-                        buf = ops._event_buffer(y_hat, meshes, y, x[..., -1, :, :, 0], threshold, kind, persist, concat)[0]
-                B = 1 if x.dim() == 4 else x.shape[0]
-                d, s = split_event_buffer(buf.cpu().numpy(), B, S1, tuple(x.shape[-3:-1]))
-                dates.append(d)
-                sums.append(s)
-        finally:
-            graphed.clear()
-            self.model.static_shapes = static0
-        check_tile_errors(always=True)
+
+        def consume(buf, x):
+            d, s = split_event_buffer(buf.cpu().numpy(), 1 if x.dim() == 4 else x.shape[0], len(sources), tuple(x.shape[-3:-1]))
+            dates.append(d)
+            sums.append(s)
+
+        reduce = events_product(threshold, kind, persist)
+        self._inference(loader, climatology, lambda x: reduce, consume, use_graph, mask=mask,
+                        high_interest_region=high_interest_region, graph_structure=graph_structure)
         return EventDates(np.concatenate(dates, 0), np.concatenate(sums, 0), sources, kind, persist, threshold)
 
 

@@ -131,9 +131,12 @@ def test_graphed_predict_equals_eager(name):
     assert _same(nfp.predict(loader, clim, use_graph=True, **extra), graphed)
 
 
-def test_graphed_predict_leaves_host_state_as_eager():
-    """After an eval()-mode predict: static_shapes restored, Python's `random` advanced as by the eager call, and the next
-    eager training step (attention + decoder dropout in train() mode) gives the eager run's loss."""
+@pytest.mark.parametrize('call', ['predict', 'score', 'event_dates'])
+def test_graphed_predict_leaves_host_state_as_eager(call):
+    """After an eval()-mode predict / score / event_dates (one loop serves them all): static_shapes restored, Python's `random`
+    advanced as by the eager call, and the next eager training step (attention + decoder dropout in train() mode) gives the
+    eager run's loss.  The graphed products themselves are pinned against the static-mode eager ones in their own files; the
+    predict case keeps its comparison with the default eager array."""
     from qtmpnn import ops
 
     def run(use_graph):
@@ -142,20 +145,22 @@ def test_graphed_predict_leaves_host_state_as_eager():
         ops._ATTN_CALLS[0] = 0
         ops.dropout_epoch(dev()).zero_()
         nfp.model.eval()
-        pred = nfp.predict(loader, clim, use_graph=use_graph, **extra)
+        kw = dict(kind='breakup', persist=2) if call == 'event_dates' else {}
+        res = getattr(nfp, call)(loader, clim, use_graph=use_graph, **extra, **kw)
         state, static = random.getstate(), nfp.model.static_shapes
         nfp.model.train()
         nfp.initiate_training(lr=1e-3, lr_decay=0.95)
         x, y, launch = loader[0]
         concat = nfp.get_climatology_array(clim, launch)
         loss = float(nfp.train_step(nfp._clip(x), nfp._clip(y), concat, extra['mask']))
-        return pred, state, static, loss
-    p_e, s_e, st_e, l_e = run(False)
-    p_g, s_g, st_g, l_g = run(True)
+        return res, state, static, loss
+    r_e, s_e, st_e, l_e = run(False)
+    r_g, s_g, st_g, l_g = run(True)
     assert st_e is False and st_g is False
     assert s_g == s_e
     assert l_g == l_e, (l_g, l_e)
-    np.testing.assert_allclose(np.nan_to_num(p_g), np.nan_to_num(p_e), rtol=0, atol=1e-6)
+    if call == 'predict':
+        np.testing.assert_allclose(np.nan_to_num(r_g), np.nan_to_num(r_e), rtol=0, atol=1e-6)
 
 
 def test_graphed_predict_dropout_per_replay():
