@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Instruction counts by class, per basic block, of one kernel in a gfx950 assembly listing.
 
-    hipcc --offload-arch=gfx950 -O3 -std=c++17 -S --cuda-device-only quadtree-mpnnlstm_amd/csrc/cheb.hip -o cheb.s
-    python profiles/isa_count.py cheb.s 'k_gate_cell_pILi2ELi4ELi8E'
+    hipcc --offload-arch=gfx950 -O3 -std=c++17 -S --cuda-device-only quadtree-mpnnlstm_amd/csrc/gatecell.hip -o gatecell.s
+    python profiles/isa_count.py gatecell.s 'k_gate_cell_pILi2ELi4ELi8E'
 
 Prints one line per basic block (label, instruction count, counts by class) and the kernel's total.  The unit loop of a
 persistent kernel is the block(s) a backward branch returns to; straight-line kernels have their phases in label order.

@@ -1,5 +1,5 @@
-// Device helpers of the peephole graph-LSTM cell shared by lstm.hip (stand-alone cell kernels) and cheb.hip (the gate GEMM
-// with the cell fused into its epilogue): model/model.py:394-428 + the LayerNorms of model/seq2seq.py:64-75, 140-151.
+// Device helpers of the peephole graph-LSTM cell shared by lstm.hip (stand-alone cell kernels), gemm.hip (the gate GEMM
+// with the cell fused into its epilogue) and gatecell.hip (the persistent gate-cell launches): model/model.py:394-428 + the LayerNorms of model/seq2seq.py:64-75, 140-151.
 #pragma once
 #include "qt_common.h"
 

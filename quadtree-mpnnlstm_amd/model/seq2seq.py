@@ -287,7 +287,7 @@ class Seq2Seq(_NoCachesInPickle, nn.Module):
                              f'hidden sizes {sizes} (the reference scripts use 16 and 32)')
         if convolution_type in ('ChebConv', 'GCNConv'):
             # the stacked convolutions of a cell are composed into ONE Chebyshev series over [X | H]: its gate GEMM reduces over
-            # (hops + 1) x (input + hidden channels) + bias rows, and the GEMM kernels take at most 512 (csrc/cheb.hip: MAXQ)
+            # (hops + 1) x (input + hidden channels) + bias rows, and the GEMM kernels take at most 512 (csrc/qt_gemm.h: MAXQ)
             kc = n_conv_layers * (2 if convolution_type == 'ChebConv' else 1) + 1
             pad4 = lambda v: v + (-v) % 4
             widths = [pad4(input_features) + hidden_size, 4 + hidden_size] + ([2 * hidden_size] if n_layers > 1 else [])

@@ -262,6 +262,11 @@ def _ld(t):
     return t.stride(0) if t.shape[0] > 1 else t.shape[1]
 
 
+def _b(parts, absent=0):
+    """Part b of a one- or two-part operand: its width from a list of widths (0: none), its tensor (absent=None) from a list of tensors."""
+    return parts[1] if len(parts) > 1 else absent
+
+
 def _plane_args(Zs, TZs):
     """(a0, lda0, a_rest, a0b, lda0b, a_restb) of the C ABI."""
     a = [ptr(Zs[0]), _ld(Zs[0]), ptr(TZs[0])]
@@ -456,14 +461,14 @@ def _cheb_backward(Zs, TZs, W, G, mesh, K, Ks, acc, use_idx, need_gZ, need_gW, g
             if split is not None and Co >= 64 and Co % 16 == 0 and K * sum(Cl) >= 64:
                 # wide gate matrices (hidden 32: 128 columns in, K C >= 64 out): the fp32-MFMA rate bounds the exact product (narrow
                 # products are memory-bound and stay exact); split-bf16, gradients only
-                _lib.call('qt_dense_sb', ptr(G), 0, Co, ptr(split[0]), ptr(split[1]), K, Cl[0], Cl[1] if len(Cl) > 1 else 0, N,
-                          ptr(mesh.n_dev), ptr(gTs[0]), ptr(gTs[1]) if len(Cl) > 1 else None)
+                _lib.call('qt_dense_sb', ptr(G), 0, Co, ptr(split[0]), ptr(split[1]), K, Cl[0], _b(Cl), N,
+                          ptr(mesh.n_dev), ptr(gTs[0]), ptr(_b(gTs, None)))
             else:
                 gsm = int(clip)
                 _lib.call('qt_dense2', ptr(G), 0, None, None, 0, None, 1, Co, 0, ptr(Wb) if skinny else None,
                           None if skinny else ptr(Wb), None, 0, None, K, Cl[0],
-                          Cl[1] if len(Cl) > 1 else 0, N, ptr(mesh.n_dev), ACT_NONE, None, 0, None, ptr(gTs[0]),
-                          ptr(gTs[1]) if len(Cl) > 1 else None, 2 * gsm, None, None)
+                          _b(Cl), N, ptr(mesh.n_dev), ACT_NONE, None, 0, None, ptr(gTs[0]),
+                          ptr(_b(gTs, None)), 2 * gsm, None, None)
         # Clenshaw: b_k = A_k + 2 L^ b_{k+1} - b_{k+2}, in place;  gZ = A_0 + L^ b_1 - b_2
         if clip:                                # all hops in one launch; only plane 0 (= gZ) is rewritten
             clip_clenshaw(mesh, gTs, K, gsm)
@@ -490,7 +495,7 @@ def _cheb_backward(Zs, TZs, W, G, mesh, K, Ks, acc, use_idx, need_gZ, need_gW, g
             if N > 0:
                 nblk = _lib.value('qt_wgrad_blocks', N)
                 part = Zs[0].new_empty(nblk, W.shape[0], Co)
-                _lib.call('qt_wgrad', *_plane_args(Zs, TZs), K, Cs[0], Cs[1] if len(Cs) > 1 else 0, ptr(S), ksp, ptr(G), Co, N,
+                _lib.call('qt_wgrad', *_plane_args(Zs, TZs), K, Cs[0], _b(Cs), ptr(S), ksp, ptr(G), Co, N,
                           ptr(mesh.n_dev), 0, ptr(part), sm)
                 _lib.call('qt_colsum', ptr(part), nblk, W.numel(), ptr(gW))
         else:
@@ -539,7 +544,7 @@ class _ChebPoly(Function):
             W2 = _c(W2.float())
             assert Co == 16 and W2.shape == (Co + 4, 4) and act in (ACT_NONE, ACT_RELU), (Co, W2.shape, act)
             U = Y.new_empty(N, 4)
-        _lib.call('qt_dense2', *_plane_args(Zs, TZs), K, Cs[0], Cs[1] if len(Cs) > 1 else 0, ptr(W),
+        _lib.call('qt_dense2', *_plane_args(Zs, TZs), K, Cs[0], _b(Cs), ptr(W),
                   None if W2 is not None else ptr(_w_t(W, acc)), ptr(S), ksp,
                   ptr(W[K * sum(Cs):]) if Ks else None, 1, Co, 0, N, ptr(mesh.n_dev), act, ptr(res), _row_stride(res), ptr(drop),
                   ptr(Y), None, sm, ptr(W2), ptr(U))
@@ -1283,23 +1288,30 @@ def multi_conv(segments, We, mesh, c_real, dropout_p=0.0, training=False, acc=No
 
 
 # ------------------------------------------------------------------------------ LSTM cell
+def _cell_launch(entry, G, Cprev, wc, b, ln, mesh, keep_gates):
+    """One launch of the stand-alone cell: qt_lstm_fwd (keep_gates: the (N, 4h) gate activations are stored for the backward pass)
+    or qt_lstm_infer (no such argument).  Returns ((O, Hn, Cn), (gates, Cprev, wc, ln) as the launch read them, pair)."""
+    G = _c(G)
+    pair = G.dim() == 3                     # (N, 2, 4h): the conv_x and conv_h sums side by side, added inside the kernel
+    assert not pair or G.shape[1] == 2
+    N, h4 = G.shape[0], G.shape[-1]
+    h = h4 // 4
+    wc, b, ln = _c(wc), _c(b), _c(ln)
+    Cprev, ld_c = _rows(Cprev)
+    O, Hn, Cn = (G.new_empty(N, h) for _ in range(3))
+    gates = G.new_empty(N, h4) if keep_gates else None
+    _lib.call(entry, ptr(G), G.data_ptr() + 4 * h4 if pair else None, 2 * h4 if pair else h4, ptr(Cprev), ld_c, ptr(wc),
+              ptr(b), ptr(ln), N, ptr(mesh.n_dev), h, ptr(O), ptr(Hn), ptr(Cn), *([ptr(gates)] if keep_gates else []))
+    return (O, Hn, Cn), (gates, Cprev, wc, ln), pair
+
+
 class _LstmCell(Function):
     """(O, LayerNorm_h(H'), LayerNorm_c(C')) from gate pre-activations (model/model.py:394-428,
     model/seq2seq.py:64-75)."""
 
     @staticmethod
     def forward(ctx, G, Cprev, wc, b, ln, mesh, acc):
-        G = _c(G)
-        ctx.pair = G.dim() == 3             # (N, 2, 4h): the conv_x and conv_h sums side by side, added inside the kernel
-        assert not ctx.pair or G.shape[1] == 2
-        N, h4 = G.shape[0], G.shape[-1]
-        h = h4 // 4
-        wc, b, ln = _c(wc), _c(b), _c(ln)
-        Cprev, ld_c = _rows(Cprev)
-        O, Hn, Cn = (G.new_empty(N, h) for _ in range(3))
-        gates = G.new_empty(N, h4)
-        _lib.call('qt_lstm_fwd', ptr(G), G.data_ptr() + 4 * h4 if ctx.pair else None, 2 * h4 if ctx.pair else h4, ptr(Cprev), ld_c, ptr(wc),
-                  ptr(b), ptr(ln), N, ptr(mesh.n_dev), h, ptr(O), ptr(Hn), ptr(Cn), ptr(gates))
+        (O, Hn, Cn), (gates, Cprev, wc, ln), ctx.pair = _cell_launch('qt_lstm_fwd', G, Cprev, wc, b, ln, mesh, True)
         ctx.save_for_backward(gates, Cprev, wc, ln)
         ctx.mesh, ctx.acc = mesh, acc
         ctx.use_idx = acc.enter() if acc is not None else 0
@@ -1346,15 +1358,15 @@ def _lstm_backward(gO, gHn, gCn, gates, Cprev, wc, ln, mesh, acc, use_idx, dgrad
         gG = None                                   # the gate gradients stay inside the launch
         _lib.call('qt_lstm_bwd_fused', ptr(gO), ld_go, ptr(gHn), ld_gh, ptr(gCn), ld_gc, ptr(gates), ptr(Cprev), ld_c,
                   ptr(wc), ptr(ln), N, ptr(mesh.n_dev), h, ptr(gCp), ptr(part), 0 if acc is None else 1,
-                  ptr(Wrows), K, Cl[0], Cl[1] if len(Cl) > 1 else 0, ptr(planes[0]), ptr(planes[1]) if len(Cl) > 1 else None,
-                  *_plane_args(Zs, TZs), K, Cs[0], Cs[1] if len(Cs) > 1 else 0, ptr(S), ksp, ptr(wslab), wslab.shape[0])
+                  ptr(Wrows), K, Cl[0], _b(Cl), ptr(planes[0]), ptr(_b(planes, None)),
+                  *_plane_args(Zs, TZs), K, Cs[0], _b(Cs), ptr(S), ksp, ptr(wslab), wslab.shape[0])
     elif N > 0 and dgrad is not None:
         Wrows, K, Cl, planes, out_sm = dgrad
         split = Wrows.__dict__.get('_qt_split') if hasattr(Wrows, '__dict__') else None
         _lib.call('qt_lstm_bwd_dgrad', ptr(gO), ld_go, ptr(gHn), ld_gh, ptr(gCn), ld_gc, ptr(gates), ptr(Cprev), ld_c,
                   ptr(wc), ptr(ln), N, ptr(mesh.n_dev), h, ptr(gG), ptr(gCp), ptr(part), 0 if acc is None else 1,
                   ptr(Wrows), ptr(split[0]) if split else None, ptr(split[1]) if split else None, K, Cl[0],
-                  Cl[1] if len(Cl) > 1 else 0, ptr(planes[0]), ptr(planes[1]) if len(Cl) > 1 else None, int(out_sm),
+                  _b(Cl), ptr(planes[0]), ptr(_b(planes, None)), int(out_sm),
                   ptr(gHn2), ld_gh2, ptr(add0))
     elif N > 0:
         if acc is None and nblk > _lib.value('qt_lstm_bwd_blocks', N, h):
@@ -1396,7 +1408,7 @@ class _GateCell(Function):
         Cprev, ld_c = _rows(Cprev)
         Hn, Cn = (Zs[0].new_empty(N, h) for _ in range(2))
         gates = Zs[0].new_empty(N, 4 * h)
-        _lib.call('qt_dense_lstm', *_plane_args(Zs, TZs), K, Cs[0], Cs[1] if len(Cs) > 1 else 0, ptr(W), ptr(_w_t(W, acc_w)), ptr(S), ksp,
+        _lib.call('qt_dense_lstm', *_plane_args(Zs, TZs), K, Cs[0], _b(Cs), ptr(W), ptr(_w_t(W, acc_w)), ptr(S), ksp,
                   ptr(W[K * sum(Cs):]) if Ks else None, h, N, ptr(mesh.n_dev), ptr(Cprev), ld_c, ptr(wc), ptr(b), ptr(ln),
                   None, ptr(Hn), ptr(Cn), ptr(gates), sm)
         ctx.save_for_backward(*Zs, *TZs, W, gates, Cprev, wc, ln)
@@ -1476,17 +1488,7 @@ def _forward_only(*ts):
 
 def _lstm_cell_infer(G, Cprev, wc, b, ln, mesh):
     """_LstmCell.forward without the saved gates."""
-    G = _c(G)
-    pair = G.dim() == 3
-    assert not pair or G.shape[1] == 2
-    N, h4 = G.shape[0], G.shape[-1]
-    h = h4 // 4
-    wc, b, ln = _c(wc), _c(b), _c(ln)
-    Cprev, ld_c = _rows(Cprev)
-    O, Hn, Cn = (G.new_empty(N, h) for _ in range(3))
-    _lib.call('qt_lstm_infer', ptr(G), G.data_ptr() + 4 * h4 if pair else None, 2 * h4 if pair else h4, ptr(Cprev), ld_c, ptr(wc),
-              ptr(b), ptr(ln), N, ptr(mesh.n_dev), h, ptr(O), ptr(Hn), ptr(Cn))
-    return O, Hn, Cn
+    return _cell_launch('qt_lstm_infer', G, Cprev, wc, b, ln, mesh, False)[0]
 
 
 def gate_cell(X, H, W, Cprev, wc, b, ln, mesh, K, Ks, acc_w=None, acc_p=None, alias_h=False, pass_x=False):

@@ -84,6 +84,44 @@ def test_bad_arguments_fail_loudly_without_gpu():
         assert name.encode() in lib.qt_last_error(), (name, lib.qt_last_error())
 
 
+_CELL_BWD_COMMON = 'gO ld_go gHn ld_gh gCn ld_gc gates Cprev ld_c wc ln N n_dev h'
+_CELL_BWD_PARAMS = {
+    'qt_lstm_bwd_dgrad': _CELL_BWD_COMMON + ' gG gCprev part accumulate Wrows Whi Wlo Kb Cb Cbb out outb out_sm gHn2 ld_gh2 add0 stream',
+    'qt_lstm_bwd_fused': _CELL_BWD_COMMON + ' gCprev part accumulate Wrows Kb Cb Cbb out outb a0 lda0 a_rest a0b lda0b a_restb Ka Ca Cab S Ks'
+                                            ' slab nslab stream',
+}
+
+
+@pytest.mark.parametrize('entry', sorted(_CELL_BWD_PARAMS))
+def test_cell_backward_entries_share_their_refusals(entry):
+    """The checks that qt_lstm_bwd_dgrad and qt_lstm_bwd_fused make through one shared setup, from both entries: a consistent
+    argument list is accepted, and each single fault is refused with -1 under the entry's own name.  N = 0 and made-up, 16-byte
+    aligned addresses: every check runs before the `N <= 0` return, so nothing is launched or dereferenced."""
+    from qtmpnn import _lib
+    lib = _lib.load()
+    names = _CELL_BWD_PARAMS[entry].split()
+    pointers = {'gO', 'gHn', 'gCn', 'gates', 'Cprev', 'wc', 'ln', 'gG', 'gCprev', 'part', 'Wrows', 'out', 'outb', 'a0', 'a_rest', 'a0b',
+                'a_restb', 'S', 'slab'}
+    good = {n: 0x10000 + 0x1000 * i for i, n in enumerate(names) if n in pointers}
+    good.update(n_dev=None, stream=None, Whi=None, Wlo=None, gHn2=None, add0=None, ld_gh2=0, N=0, h=16, accumulate=0, out_sm=0,
+                ld_go=16, ld_gh=16, ld_gc=16, ld_c=16, Kb=3, Cb=16, Cbb=4,            # NB = 60 output columns
+                lda0=16, lda0b=4, Ka=3, Ca=16, Cab=4, Ks=4, nslab=1)                   # a weight of 64 rows
+    call = lambda **change: getattr(lib, entry)(*[{**good, **change}[n] for n in names])
+    assert call() == 0, lib.qt_last_error()
+    faults = {
+        'hidden size 12': dict(h=12),
+        'plane width 6': dict(Cb=6),
+        '180 output columns (limit 128)': dict(Kb=9),
+        'row stride below h': dict(ld_gh=8),
+        'row stride not a multiple of 4': dict(ld_gc=18),
+        'misaligned Wrows': dict(Wrows=good['Wrows'] + 4),
+        'part b without outb': dict(outb=None),
+    }
+    for what, change in faults.items():
+        assert call(**change) == -1, what
+        assert entry.encode() in lib.qt_last_error(), (what, lib.qt_last_error())
+
+
 def test_product_path_refuses_cpu_tensors():
     from qtmpnn.mesh import build_mesh
     with pytest.raises(RuntimeError, match='GPU'):
