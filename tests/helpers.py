@@ -55,6 +55,38 @@ def mesh_from_golden_graph(g):
                       condition=str(g['condition']), mask=mask, high_interest_region=hir)
 
 
+def _tile_mesh(kind, B, static=False):
+    """Meshes of several 64 x 64 base cells: (mesh, criterion image)."""
+    from qtmpnn import synthetic
+    from qtmpnn.mesh import build_mesh
+    mask = tf = None
+    thresh = 0.1
+    if kind == 'mnist128_sparse':                      # big cells across tile borders
+        img = np.stack([synthetic.make_clip(30 + i, canvas=(128, 128), n_digits=2, n_frames=1, pixel_noise=0.0)[0, ..., 0] for i in range(B)])
+    elif kind == 'mnist128_noisy':                     # nearly one node per pixel: tiles of ~4096 rows, 250 halo rows each
+        img = np.stack([synthetic.make_clip(40 + i, canvas=(128, 128), n_digits=2, n_frames=1, pixel_noise=0.05)[0, ..., 0] for i in range(B)])
+    elif kind == 'wide64x128':
+        img = np.stack([synthetic.make_clip(50 + i, canvas=(128, 64), n_digits=1, n_frames=1, pixel_noise=0.02)[0, ..., 0] for i in range(B)])
+    elif kind in ('one_busy_tile', 'masked_tile'):
+        # one tile at full resolution beside tiles that are ONE 64 x 64 cell each (a row with ~64 neighbours in another tile per side),
+        # and the same with one whole tile under the mask (an empty tile: its workgroups only count themselves out)
+        rng = np.random.default_rng(70)
+        img = np.zeros((B, 128, 128), np.float32)
+        img[:, :64, :64] = rng.random((B, 64, 64)).astype(np.float32)
+        img[:, 64:, 64:80] = 0.5 * rng.random((B, 64, 16)).astype(np.float32)
+        if kind == 'masked_tile':
+            mask = np.zeros((128, 128), dtype=bool)
+            mask[:64, 64:] = True
+        thresh = 0.3
+    else:
+        shape = (96, 128) if kind == 'ice96x128' else (256, 256)
+        clips = [synthetic.make_ice_like(60 + i, shape=shape, channels=1, n_frames=1) for i in range(B)]
+        img = np.stack([abs(abs(c[0][0, ..., 0] - 0.5) - 0.5) for c in clips])
+        mask, thresh = clips[0][1], 0.15
+    mesh = build_mesh(src=torch.from_numpy(np.ascontiguousarray(img)).to(dev()), thresh=thresh, mask=mask, static=static)
+    return mesh, img
+
+
 def climatology_from_base(base):
     """(1, 365, w, h) daily normals from the (w, h) base field a fixture stores (the formula of tests/golden/make_golden.py)."""
     d = np.arange(365, dtype=np.float32)[:, None, None]

@@ -3,7 +3,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import close, dev, golden, grad_close, load_state
+from helpers import _tile_mesh, close, dev, golden, grad_close, load_state
 
 pytestmark = pytest.mark.gpu
 
@@ -934,39 +934,6 @@ def test_clip_resident_pool_overflow_walks_the_csr():
     env = dict(os.environ, QT_LIB_PATH=lib)
     r = subprocess.run([sys.executable, os.path.join(here, '_clip_overflow_child.py')], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and 'overflow ok' in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
-
-
-def _tile_mesh(kind, B, static=False):
-    """Meshes of several 64 x 64 base cells: (mesh, criterion image)."""
-    from qtmpnn import synthetic
-    from qtmpnn.mesh import build_mesh
-    from helpers import dist_from_05
-    mask = tf = None
-    thresh = 0.1
-    if kind == 'mnist128_sparse':                      # big cells across tile borders
-        img = np.stack([synthetic.make_clip(30 + i, canvas=(128, 128), n_digits=2, n_frames=1, pixel_noise=0.0)[0, ..., 0] for i in range(B)])
-    elif kind == 'mnist128_noisy':                     # nearly one node per pixel: tiles of ~4096 rows, 250 halo rows each
-        img = np.stack([synthetic.make_clip(40 + i, canvas=(128, 128), n_digits=2, n_frames=1, pixel_noise=0.05)[0, ..., 0] for i in range(B)])
-    elif kind == 'wide64x128':
-        img = np.stack([synthetic.make_clip(50 + i, canvas=(128, 64), n_digits=1, n_frames=1, pixel_noise=0.02)[0, ..., 0] for i in range(B)])
-    elif kind in ('one_busy_tile', 'masked_tile'):
-        # one tile at full resolution beside tiles that are ONE 64 x 64 cell each (a row with ~64 neighbours in another tile per side),
-        # and the same with one whole tile under the mask (an empty tile: its workgroups only count themselves out)
-        rng = np.random.default_rng(70)
-        img = np.zeros((B, 128, 128), np.float32)
-        img[:, :64, :64] = rng.random((B, 64, 64)).astype(np.float32)
-        img[:, 64:, 64:80] = 0.5 * rng.random((B, 64, 16)).astype(np.float32)
-        if kind == 'masked_tile':
-            mask = np.zeros((128, 128), dtype=bool)
-            mask[:64, 64:] = True
-        thresh = 0.3
-    else:
-        shape = (96, 128) if kind == 'ice96x128' else (256, 256)
-        clips = [synthetic.make_ice_like(60 + i, shape=shape, channels=1, n_frames=1) for i in range(B)]
-        img = np.stack([abs(abs(c[0][0, ..., 0] - 0.5) - 0.5) for c in clips])
-        mask, thresh = clips[0][1], 0.15
-    mesh = build_mesh(src=torch.from_numpy(np.ascontiguousarray(img)).to(dev()), thresh=thresh, mask=mask, static=static)
-    return mesh, img
 
 
 @pytest.mark.parametrize('kind,B', [('mnist128_sparse', 2), ('mnist128_noisy', 1), ('wide64x128', 3), ('ice96x128', 2), ('ice256', 1),
