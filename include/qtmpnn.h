@@ -254,6 +254,18 @@ int qt_sse_rollout_bwd(int nseg, const float* const* outs, const int* out_stride
                        const float* const* sys, const int* Ns, const int32_t* const* n_devs, const float* g, int W,
                        float* const* gouts, void* stream);
 
+/* The weighted form of the two calls above: partial = sum of lam[z] * w[p] * (out[labels[p]] - y[p])^2 with w (n*m) the
+ * pixel weights of a frame and lam (nseg) the weights of this call's steps, both fp32 device arrays (non-negative; the
+ * caller forms the divisor).  swys[z] (N_z, 2) receives per node [sum of w | sum of w*y] over the node's pixels, and
+ * qt_wsse_rollout_bwd writes gouts[z][i, 0] = 2 g lam[z] (sw_i out_i - swy_i), zeros in columns 1..W-1, rows up to n_devs[z]
+ * where given.  No atomics: the same bits on every run. */
+int qt_wsse_rollout(int nseg, const float* const* outs, const int* out_strides, const int32_t* const* labels,
+                    const uint8_t* const* levels, const int* Ns, float* const* swys, const float* y, int64_t y_clip_stride,
+                    int64_t y_step_stride, const float* w, const float* lam, int B, int n, int m, float* partial, void* stream);
+int qt_wsse_rollout_bwd(int nseg, const float* const* outs, const int* out_strides, const float* const* swys,
+                        const int* Ns, const int32_t* const* n_devs, const float* g, const float* lam, int W,
+                        float* const* gouts, void* stream);
+
 /* qt_score_rollout: forecast verification of a rollout (no gradient), shaped like qt_sse_rollout: up to 16 output steps per
  * call, one mesh per step, grid (ceil(P/1024), B, nseg).  Per (step z, clip b, 1024-pixel tile) and per source s it writes
  * 8 floats, partial[(((z*B + b)*ntile + tile)*S + s)*8 + slot], over the tile's counted pixels:

@@ -49,7 +49,7 @@ struct Vec {
 // address of channel chunk `ch` (VEC floats) of source node `sl`
 template <int VEC>
 __device__ __forceinline__ const float* src_chunk(const PoolArgs& a, int64_t sl, int ch) {
-    if (VEC == 1 || a.nparts == 0) return a.src_val + sl * a.C + ch * VEC;
+    if (VEC != 4 || a.nparts == 0) return a.src_val + sl * a.C + ch * VEC;
     int s = 0;
     while (ch >= a.part_end[s]) ++s;
     return a.part[s] + sl * a.part_ld[s] + (ch - (s ? a.part_end[s - 1] : 0)) * 4;
@@ -58,7 +58,7 @@ __device__ __forceinline__ const float* src_chunk(const PoolArgs& a, int64_t sl,
 // address of channel chunk `ch` of output node `node` (step s)
 template <int VEC>
 __device__ __forceinline__ float* dst_chunk(const PoolArgs& a, int s, int64_t node, int ch) {
-    if (VEC == 1 || a.noparts == 0) return a.out + ((int64_t)s * a.N + node) * a.out_stride + a.out_coff + ch * VEC;
+    if (VEC != 4 || a.noparts == 0) return a.out + ((int64_t)s * a.N + node) * a.out_stride + a.out_coff + ch * VEC;
     int o = 0;
     while (ch >= a.opart_end[o]) ++o;
     return a.opart[o] + node * a.opart_w[o] + (ch - (o ? a.opart_end[o - 1] : 0)) * 4;
@@ -85,8 +85,11 @@ __device__ __forceinline__ void vstore(float* p, const Vec<VEC>& r, float scale)
 // (experiment switches: the node kernel takes nodes up to QT_NODE_MAX_Z pixels wide, the tile kernel those from level QT_TILE_MIN_LV)
 static constexpr int QT_TILE_MIN_LV = 3;
 static constexpr int QT_NODE_MAX_Z = 4;
-template <int VEC>
-__device__ __forceinline__ void tile_body(const PoolArgs& a, int bx, int by, int ny, float* pyr) {
+// WY (compile time; the weighted loss, k_pool_wtargets): the image is one channel y and the two "channels" summed are the pixel
+// weight and its product with y, (w_p, w_p y_p), formed in registers at the load: VEC = 2, rows [sum w | sum w y] of `out`.
+template <int VEC, bool WY = false>
+__device__ __forceinline__ void tile_body(const PoolArgs& a, int bx, int by, int ny, float* pyr, const float* wmap = nullptr) {
+    static_assert(!WY || VEC == 2, "the weighted target sums are pairs");
     const int t = threadIdx.x;
     const int tiles = a.tiles_r * a.tiles_c;
     const int b = bx / tiles, tile = bx % tiles;
@@ -159,7 +162,13 @@ __device__ __forceinline__ void tile_body(const PoolArgs& a, int bx, int by, int
                         for (int k = 0; k < VEC; ++k) x.v[k] *= sscale[q];
                     }
                 } else if (lab[q] >= 0) {
-                    x = vload<VEC>(a.img + (int64_t)b * a.img_clip_stride + ((int64_t)s * P + (int64_t)r * a.m + c) * a.C + ch * VEC);
+                    if constexpr (WY) {
+                        const int64_t p = (int64_t)r * a.m + c;
+                        x.v[0] = wmap[p];
+                        x.v[1] = x.v[0] * a.img[(int64_t)b * a.img_clip_stride + (int64_t)s * P + p];
+                    } else {
+                        x = vload<VEC>(a.img + (int64_t)b * a.img_clip_stride + ((int64_t)s * P + (int64_t)r * a.m + c) * a.C + ch * VEC);
+                    }
                 }
                 val[q] = x;
             }
@@ -256,6 +265,19 @@ __global__ __launch_bounds__(256) void k_pool_targets(PoolArgs a, LossSeg sg, in
     a.N = sg.N[z];
     a.out = sg.sy[z];
     tile_body<1>(a, blockIdx.x, 0, 1, pyr);
+}
+
+// The weighted loss: per node [sum of w_p | sum of w_p y_p] over its pixels, rows of 2 floats in sg.sy[z], by the same tree.
+__global__ __launch_bounds__(256) void k_pool_wtargets(PoolArgs a, LossSeg sg, int64_t y_step_stride, const float* __restrict__ w) {
+    __shared__ float pyr[(256 + 64 + 16 + 4 + 1) * 2];
+    const int z = blockIdx.z;
+    a.img = a.img + z * y_step_stride;
+    a.labels = sg.labels[z];
+    a.level = sg.level[z];
+    a.npix = sg.npix[z];
+    a.N = sg.N[z];
+    a.out = sg.sy[z];
+    tile_body<2, true>(a, blockIdx.x, 0, 1, pyr, w);
 }
 
 // Node-centric transfer for nodes of 1x1 .. 4x4 pixels: thread = (node, float4 chunk of its row), chunk fastest, so the
@@ -523,6 +545,49 @@ __global__ __launch_bounds__(256) void k_sse_multi(LossSeg sg, const float* __re
         partial[((int64_t)z * B + b) * gridDim.x + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+// k_sse_multi with a weight per pixel and per step: partial = sum of lam[z] w[p] (out[label] - y)^2, same reduction order
+__global__ __launch_bounds__(256) void k_wsse_multi(LossSeg sg, const float* __restrict__ y, int64_t y_clip_stride,
+                                                    int64_t y_step_stride, const float* __restrict__ w,
+                                                    const float* __restrict__ lam, int64_t P, int B, float* __restrict__ partial) {
+    __shared__ float red[4];
+    const int b = blockIdx.y, z = blockIdx.z;
+    const float* out = sg.out[z];
+    const int32_t* labels = sg.labels[z];
+    const int os = sg.out_stride[z];
+    const float* yz = y + z * y_step_stride + b * y_clip_stride;
+    const float lz = lam[z];
+    float acc = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int64_t p = (int64_t)blockIdx.x * 1024 + k * 256 + threadIdx.x;
+        if (p < P) {
+            const int lab = labels[b * P + p];
+            if (lab >= 0) {
+                const float d = out[(int64_t)lab * os] - yz[p];
+                acc += lz * (w[p] * (d * d));
+            }
+        }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0)
+        partial[((int64_t)z * B + b) * gridDim.x + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// gradient rows of the weighted loss: sg.sy[z] holds the (N, 2) rows [sum w | sum w y] of k_pool_wtargets
+__global__ void k_wsse_bwd_multi(LossSeg sg, const float* __restrict__ g, const float* __restrict__ lam, int W) {
+    const int z = blockIdx.y;
+    const unsigned idx = blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = idx / (unsigned)W;
+    if (i >= qt_rows(sg.n_dev[z], sg.N[z])) return;
+    const float* out = sg.out[z];
+    const float* sw = sg.sy[z];
+    sg.gout[z][idx] = (idx - (unsigned)i * (unsigned)W) == 0
+                          ? 2.0f * g[0] * lam[z] * (sw[2 * i] * out[i * sg.out_stride[z]] - sw[2 * i + 1]) : 0.0f;
+}
+
 __global__ void k_sse_bwd_multi(LossSeg sg, const float* __restrict__ g, int W) {
     const int z = blockIdx.y;
     const unsigned idx = blockIdx.x * blockDim.x + threadIdx.x;
@@ -593,6 +658,51 @@ extern "C" int qt_sse_rollout_bwd(int nseg, const float* const* outs, const int*
     QT_ARG((int64_t)nmax * W + 256 < ((int64_t)1 << 31), "N * W too large for 32-bit thread indices");
     if (nmax <= 0) return QT_OK;
     hipLaunchKernelGGL(k_sse_bwd_multi, dim3(qt_cdiv((int64_t)nmax * W, 256), nseg), dim3(256), 0, (hipStream_t)stream, sg, g, W);
+    QT_LAUNCHED();
+    return QT_OK;
+}
+
+extern "C" int qt_wsse_rollout(int nseg, const float* const* outs, const int* out_strides, const int32_t* const* labels,
+                               const uint8_t* const* levels, const int* Ns, float* const* swys, const float* y,
+                               int64_t y_clip_stride, int64_t y_step_stride, const float* w, const float* lam, int B, int n, int m,
+                               float* partial, void* stream) {
+    QT_ARG(nseg >= 1 && nseg <= 16 && outs && out_strides && labels && levels && Ns && swys && y && partial && B > 0, "bad arguments");
+    QT_ARG(w && lam, "null weights: w (n*m) and lam (nseg) are device arrays");
+    QT_ARG(n > 0 && m > 0 && y_clip_stride >= 0 && y_step_stride >= 0, "bad sizes");
+    LossSeg sg = {};
+    for (int z = 0; z < nseg; ++z) {
+        QT_ARG(outs[z] && labels[z] && levels[z] && swys[z] && out_strides[z] >= 1 && Ns[z] >= 0, "null segment pointer");
+        sg.out[z] = outs[z]; sg.out_stride[z] = out_strides[z]; sg.labels[z] = labels[z]; sg.level[z] = levels[z];
+        sg.N[z] = Ns[z]; sg.sy[z] = swys[z];
+    }
+    const int64_t P = (int64_t)n * m;
+    hipLaunchKernelGGL(k_wsse_multi, dim3(qt_cdiv(P, 1024), B, nseg), dim3(256), 0, (hipStream_t)stream, sg, y, y_clip_stride,
+                       y_step_stride, w, lam, P, B, partial);
+    QT_LAUNCHED();
+    PoolArgs a = {};
+    a.img = y; a.S = 1; a.img_clip_stride = y_clip_stride; a.C = 2; a.mean = 0; a.B = B; a.n = n; a.m = m;
+    a.out_stride = 2; a.out_coff = 0; a.tiles_r = qt_cdiv(n, 64); a.tiles_c = qt_cdiv(m, 64);
+    hipLaunchKernelGGL(k_pool_wtargets, dim3(B * a.tiles_r * a.tiles_c, 1, nseg), dim3(256), 0, (hipStream_t)stream, a, sg,
+                       y_step_stride, w);
+    QT_LAUNCHED();
+    return QT_OK;
+}
+
+extern "C" int qt_wsse_rollout_bwd(int nseg, const float* const* outs, const int* out_strides, const float* const* swys,
+                                   const int* Ns, const int32_t* const* n_devs, const float* g, const float* lam, int W,
+                                   float* const* gouts, void* stream) {
+    QT_ARG(nseg >= 1 && nseg <= 16 && outs && out_strides && swys && Ns && n_devs && g && lam && gouts && W >= 1, "bad arguments");
+    LossSeg sg = {};
+    int nmax = 0;
+    for (int z = 0; z < nseg; ++z) {
+        QT_ARG(outs[z] && swys[z] && gouts[z] && out_strides[z] >= 1, "null segment pointer");
+        sg.out[z] = outs[z]; sg.out_stride[z] = out_strides[z]; sg.sy[z] = (float*)swys[z];
+        sg.N[z] = Ns[z]; sg.n_dev[z] = n_devs[z]; sg.gout[z] = gouts[z];
+        nmax = Ns[z] > nmax ? Ns[z] : nmax;
+    }
+    QT_ARG((int64_t)nmax * W + 256 < ((int64_t)1 << 31), "N * W too large for 32-bit thread indices");
+    if (nmax <= 0) return QT_OK;
+    hipLaunchKernelGGL(k_wsse_bwd_multi, dim3(qt_cdiv((int64_t)nmax * W, 256), nseg), dim3(256), 0, (hipStream_t)stream, sg, g, lam, W);
     QT_LAUNCHED();
     return QT_OK;
 }

@@ -37,10 +37,86 @@ except Exception:                           # tensorboard is not installed in th
             pass
 
 
-def masked_mse(outputs, meshes, y, mask=None, binary=False):
+class LossWeights:
+    """The checked weights of the weighted training loss: `weights` (W, H), non-negative pixel weights (None: ones), and
+    `lead_weights` (T_out,), non-negative weights of the output steps (None: ones).  Everything is checked here, on the host and
+    before any launch -- shape, finite, non-negative, a positive sum (of the pixel weights over the pixels `mask` leaves) -- and
+    each refusal is a ValueError that names the argument.  The sums of the divisor are float64 sums of the float32 values the
+    kernels read.  to(device) uploads the two arrays once; chunk(steps) is the view of a truncated-BPTT chunk."""
+
+    def __init__(self, weights, lead_weights, shape, T_out, mask=None):
+        shape, self.T = tuple(int(v) for v in shape), int(T_out)
+        mask = host_mask(mask)
+        if mask is not None and tuple(mask.shape) != shape:
+            raise ValueError(f'mask: shape {tuple(mask.shape)} for frames of {shape}')
+
+        def host(a, name, want):
+            if a is None:
+                return np.ones(want, np.float32)
+            a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+            if a.dtype == object or a.dtype.kind not in 'fiub':
+                raise ValueError(f'{name}: a numeric array is needed, got dtype {a.dtype}')
+            if tuple(a.shape) != want:
+                raise ValueError(f'{name}: shape {tuple(a.shape)}, expected {want}')
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if not np.isfinite(a).all():
+                raise ValueError(f'{name}: NaN or infinite entries')
+            if (a < 0).any():
+                raise ValueError(f'{name}: negative entries')
+            return a
+        self.w_host = host(weights, 'loss_weights', shape)
+        self.lam_host = host(lead_weights, 'lead_weights', (self.T,))
+        self.sum_w = float(self.w_host.astype(np.float64)[slice(None) if mask is None else ~mask].sum())
+        self.sum_lam = float(self.lam_host.astype(np.float64).sum())
+        if not self.sum_w > 0:
+            raise ValueError('loss_weights: the weights of the unmasked pixels sum to 0')
+        if not self.sum_lam > 0:
+            raise ValueError('lead_weights: the weights sum to 0')
+        self.shape, self.w, self.lam = shape, None, None
+
+    def to(self, device):
+        device = torch.device(device)
+        if self.w is None or self.w.device.type != device.type or device.index not in (None, self.w.device.index):
+            self.w = torch.from_numpy(self.w_host).reshape(-1).to(device)
+            self.lam = torch.from_numpy(self.lam_host).to(device)
+        return self
+
+    def chunk(self, steps):
+        """The weights of the output steps range `steps`: the same pixel weights, lead_weights[steps] and their own sum."""
+        c = object.__new__(LossWeights)
+        c.__dict__.update(self.__dict__)
+        c.T = len(steps)
+        c.lam_host = self.lam_host[steps.start:steps.stop]
+        c.sum_lam = float(c.lam_host.astype(np.float64).sum())
+        if not c.sum_lam > 0:
+            raise ValueError(f'lead_weights: the weights of the truncated chunk of steps [{steps.start}, {steps.stop}) sum to 0')
+        c.lam = None if self.lam is None else self.lam[steps.start:steps.stop]
+        return c
+
+
+def loss_weights_of(weights, lead_weights, shape, T_out, mask=None, binary=False):
+    """None when neither weight is given (the unweighted loss, untouched), a LossWeights as it is, else the checked pair."""
+    if weights is None and lead_weights is None:
+        return None
+    if binary:
+        raise ValueError('loss_weights / lead_weights: the weighted loss is the squared error; binary=True (BCE) takes no weights')
+    if isinstance(weights, LossWeights):
+        if lead_weights is not None:
+            raise ValueError('lead_weights: already part of the LossWeights passed as the pixel weights')
+        if weights.shape != tuple(shape) or weights.T != T_out:
+            raise ValueError(f'loss_weights: prepared for {weights.T} steps of {weights.shape} frames, not {T_out} of {tuple(shape)}')
+        return weights
+    return LossWeights(weights, lead_weights, shape, T_out, mask)
+
+
+def masked_mse(outputs, meshes, y, mask=None, binary=False, weights=None, lead_weights=None):
     """MSELoss(y_hat[:, ~mask], y[:, ~mask]) of mpnnlstm.py:243-246 without building y_hat:
     sum over steps of the per-mesh squared error, divided by (clips x steps x unmasked pixels).
-    y: (T_out, W, H, 1) or (B, T_out, W, H, 1)."""
+    y: (T_out, W, H, 1) or (B, T_out, W, H, 1).
+
+    Beyond the reference: weights (W, H) >= 0 and / or lead_weights (T_out,) >= 0 (a missing one is ones; or one LossWeights as
+    `weights`) give  sum lam_t w_p d^2 / (B sum_t lam_t sum_{p unmasked} w_p)  over the same counted pixels, the divisor formed
+    on the host in float64.  Unit weights are the unweighted loss; with neither given nothing here changes."""
     if y.dim() == 4:
         y = y.unsqueeze(0)
     mesh0 = meshes[0]
@@ -48,6 +124,15 @@ def masked_mse(outputs, meshes, y, mask=None, binary=False):
     if tuple(y.shape) != want:      # (the loss kernels read B x P targets per step straight from this buffer)
         raise ValueError(f'targets of shape {tuple(y.shape)} for {mesh0.B} clip(s) x {len(outputs)} output steps of {mesh0.n} x {mesh0.m} '
                          f'frames: expected (T_out, W, H, 1) or (B, T_out, W, H, 1) = {want}')
+    lw = loss_weights_of(weights, lead_weights, (mesh0.n, mesh0.m), len(outputs), mask, binary)
+    if lw is not None:
+        y = y.to(outputs[0].device)
+        lw.to(y.device)
+        part = ops.rollout_wsse_partials(outputs, y, meshes, lw.w, lw.lam) if y.shape[1] == len(outputs) else None
+        if part is None:        # loss_mask meshes, odd layouts: step by step, composed (ops.step_wsse_partials)
+            part = torch.cat([ops.step_wsse_partials(out, y[:, t], mesh, lw.w, lw.lam[t])
+                              for t, (out, mesh) in enumerate(zip(outputs, meshes))])
+        return part.sum() / float(mesh0.B * lw.sum_lam * lw.sum_w)
     mask = host_mask(mask)
     n_valid = mesh0.P if mask is None else int((~mask).sum())
     if binary:
@@ -192,10 +277,20 @@ class NextFramePredictorS2S(NextFramePredictor):
         self.training_initiated = True
 
     # -- the measured unit -----------------------------------------------------------
-    def forward_loss(self, x, y, concat_layers=None, mask=None, high_interest_region=None, graph_structure=None):
+    def forward_loss(self, x, y, concat_layers=None, mask=None, high_interest_region=None, graph_structure=None,
+                     loss_weights=None, lead_weights=None):
+        """loss_weights (W, H) / lead_weights (T_out,): the weighted loss of masked_mse (checked before the rollout starts)."""
+        lw = self._loss_weights(x, mask, loss_weights, lead_weights)
         y_hat, meshes = self.model(x, y, concat_layers, teacher_forcing_ratio=0, mask=mask,
                                    high_interest_region=high_interest_region, graph_structure=graph_structure)
-        return masked_mse(y_hat, meshes, y, mask, self.binary)
+        if lw is None:
+            return masked_mse(y_hat, meshes, y, mask, self.binary)
+        return masked_mse(y_hat, meshes, y, mask, self.binary, weights=lw)
+
+    def _loss_weights(self, x, mask, loss_weights, lead_weights):
+        """The checked, uploaded weights of this predictor's loss for batches shaped like x (None: unweighted)."""
+        lw = loss_weights_of(loss_weights, lead_weights, tuple(x.shape[-3:-1]), self.output_timesteps, mask, self.binary)
+        return lw if lw is None else lw.to(self.device if self.device is not None else x.device)
 
     def zero_grad(self):
         """Drop all gradients (set to None, like optimizer.zero_grad(set_to_none=True) on the reference's per-tensor optimizer)."""
@@ -240,11 +335,13 @@ class NextFramePredictorS2S(NextFramePredictor):
 
     @on_device(lambda self, *a, **k: self.device)
     def train_step(self, x, y, concat_layers=None, mask=None, high_interest_region=None, graph_structure=None,
-                   max_norm=10.0):
+                   max_norm=10.0, loss_weights=None, lead_weights=None):
         """zero_grad -> forward -> masked MSE -> backward -> [all-reduce] -> clip_grad_norm_(10) -> Adam
-        (mpnnlstm.py:229-257).  x: (T_in, W, H, C) or (B, T_in, W, H, C).  Returns the loss tensor."""
+        (mpnnlstm.py:229-257).  x: (T_in, W, H, C) or (B, T_in, W, H, C).  Returns the loss tensor.
+        loss_weights / lead_weights: the weighted loss (masked_mse)."""
+        lw = self._loss_weights(x, mask, loss_weights, lead_weights)
         self.zero_grad()
-        loss = self.forward_loss(x, y, concat_layers, mask, high_interest_region, graph_structure)
+        loss = self.forward_loss(x, y, concat_layers, mask, high_interest_region, graph_structure, loss_weights=lw)
         loss.backward()
         self._clip_and_step(self._grads_ready(self._world(), self.process_group), max_norm)
         check_tile_errors()          # (reads the device only when this step issued tile-resident launches; raises on a failed one)
@@ -252,7 +349,7 @@ class NextFramePredictorS2S(NextFramePredictor):
 
     @on_device(lambda self, *a, **k: self.device)
     def truncated_backward(self, x, y, concat_layers, mask, high_interest_region=None, graph_structure=None,
-                           truncated_backprop=45):
+                           truncated_backprop=45, loss_weights=None, lead_weights=None):
         """The reference's truncated-BPTT loop (mpnnlstm.py:281-315), quirks included: every chunk re-runs the encoder
         and unrolls ITS steps from the encoder state, `zero_grad` runs per chunk (so only the last chunk's gradient
         survives to optimizer.step()), and the chunk bound is min(start + tb, T_out + 1).  Returns the chunk losses.
@@ -260,25 +357,35 @@ class NextFramePredictorS2S(NextFramePredictor):
         Beyond the reference: a chunk is clamped to the steps that exist, range(max(step - tb, 0), min(step, T_out)).  HEAD
         unrolls range(step - tb, step) as it stands, which leaves [0, T_out) whenever tb does not divide T_out -- the default
         tb = 45 with the notebook's T_out = 10 gives range(-34, 11) and ends in an IndexError at y[unroll_steps] (:308).
-        Where HEAD runs (tb divides T_out: ice_exp.py exp 5 / 6) the clamp changes nothing."""
+        Where HEAD runs (tb divides T_out: ice_exp.py exp 5 / 6) the clamp changes nothing.
+
+        loss_weights / lead_weights: the weighted loss; a chunk takes lead_weights[steps] and divides by that slice's sum (every
+        chunk's slice is checked before the first one runs)."""
         losses, step = [], 0
         if y.dim() == 4:
             y = y.unsqueeze(0)
+        lw = self._loss_weights(x, mask, loss_weights, lead_weights)
+        chunks = []
         while step < self.output_timesteps:
             step = min(step + truncated_backprop, self.output_timesteps + 1)
             steps = range(max(step - truncated_backprop, 0), min(step, self.output_timesteps))
+            chunks.append((steps, None if lw is None else lw.chunk(steps)))
+        for steps, lwc in chunks:
             self.zero_grad()
             self.model.process_inputs(x, mask=mask, high_interest_region=high_interest_region, graph_structure=graph_structure)
             y_hat, meshes = self.model.unroll_output(steps, y, concat_layers=concat_layers, teacher_forcing_ratio=0, mask=mask,
                                                      high_interest_region=high_interest_region, remesh_every=1)
-            loss = masked_mse(y_hat, meshes, y[:, steps.start:steps.stop], mask, self.binary)
+            if lwc is None:
+                loss = masked_mse(y_hat, meshes, y[:, steps.start:steps.stop], mask, self.binary)
+            else:
+                loss = masked_mse(y_hat, meshes, y[:, steps.start:steps.stop], mask, self.binary, weights=lwc)
             loss.backward()
             losses.append(loss.detach())
         return losses
 
     @on_device(lambda self, *a, **k: self.device)
     def make_graphed_step(self, x, y, concat_layers=None, mask=None, high_interest_region=None, max_norm=10.0,
-                          warmup=2, graph_structure=None, force_multi=False):
+                          warmup=2, graph_structure=None, force_multi=False, loss_weights=None, lead_weights=None):
         """Capture one whole training step in hipGraphs and return `step(x, y, concat) -> loss`.
 
         The rollout is data dependent (every decoder step re-meshes on its own output), so the capture runs in
@@ -291,6 +398,8 @@ class NextFramePredictorS2S(NextFramePredictor):
         force_multi: take the multi-rank structure (graph1, all-reduce, graph2) also in a process group of ONE rank -- the
         collective then averages over one rank, i.e. changes nothing, but RCCL, its stream ordering against the two graph
         replays and the capture beside its watchdog thread all run for real (tests/test_gpu_dist.py; bench.py --force-multi).
+        loss_weights / lead_weights: the weighted loss (masked_mse); checked and uploaded once, here, and the captured step reads
+        the two device arrays -- step(x, y, concat) keeps its signature.
         """
         import torch.distributed as dist
         if force_multi and not (dist.is_available() and dist.is_initialized()):
@@ -304,10 +413,11 @@ class NextFramePredictorS2S(NextFramePredictor):
             self.initiate_training(float(lr), self.scheduler.gamma, capturable=True)
         sx, sy = x.clone(), y.clone()
         sc = concat_layers.clone() if concat_layers is not None else None
+        lw = self._loss_weights(x, mask, loss_weights, lead_weights)
 
         def fwd_bwd():
             self.zero_grad()
-            loss = self.forward_loss(sx, sy, sc, mask, high_interest_region, graph_structure)
+            loss = self.forward_loss(sx, sy, sc, mask, high_interest_region, graph_structure, loss_weights=lw)
             loss.backward()
             return loss.detach()
 
@@ -389,6 +499,7 @@ class NextFramePredictorS2S(NextFramePredictor):
                 check_tile_errors(always=True)
             return static_loss
         step.check = lambda: check_tile_errors(always=uses_tiles)
+        step.loss_weights = lw          # the graph reads the two device arrays at every replay: they live as long as the step
         return step
 
     @on_device(lambda self, *a, **k: self.device)
@@ -488,13 +599,16 @@ class NextFramePredictorS2S(NextFramePredictor):
 
     @on_device(lambda self, *a, **k: self.device)
     def train(self, loader_train, loader_test, climatology=None, n_epochs=200, lr=0.01, lr_decay=0.95, mask=None,
-              high_interest_region=None, truncated_backprop=45, graph_structure=None, use_graph=False):
+              high_interest_region=None, truncated_backprop=45, graph_structure=None, use_graph=False, loss_weights=None,
+              lead_weights=None):
         """The reference's training loop (mpnnlstm.py:186-387).  use_graph=True (beyond the reference) replays the whole training
         step as a hipGraph: one graph is captured per distinct batch shape on first sight (that batch's own update runs eagerly just
         before the capture) and the learning-rate schedule keeps working because the capturable optimizer holds lr in a device
         tensor that StepLR updates in place.  It needs the step to be ONE rollout: truncated_backprop in (0, None), or a truncation
         length that covers all output steps (the default 45 with the notebook's 10: the truncated loop is then a single chunk over
-        the whole rollout, without gradient clipping -- mpnnlstm.py:311 is commented out -- and that is what is captured)."""
+        the whole rollout, without gradient clipping -- mpnnlstm.py:311 is commented out -- and that is what is captured).
+        loss_weights (W, H) / lead_weights (T_out,) (beyond the reference): the weighted loss of masked_mse, for the training
+        steps and for the test pass alike; checked and uploaded once."""
         image_shape = loader_train.dataset.image_shape
         truncate_ = truncated_backprop not in (0, None)
         single_chunk = truncate_ and truncated_backprop >= self.output_timesteps
@@ -508,6 +622,9 @@ class NextFramePredictorS2S(NextFramePredictor):
             mshape = tuple(host_mask(mask).shape) if not hasattr(mask, 'shape') else tuple(mask.shape)
             assert mshape == tuple(image_shape), f'Mask and image shapes do not match. Got {mshape} and {image_shape}'
         truncate = truncate_ and not (use_graph and single_chunk)
+        lw = loss_weights_of(loss_weights, lead_weights, tuple(image_shape), self.output_timesteps, mask, self.binary)
+        if lw is not None:
+            lw.to(self.device if self.device is not None else 'cpu')
         st = time.time()
         batch_step = 0
         for epoch in range(n_epochs):
@@ -518,7 +635,7 @@ class NextFramePredictorS2S(NextFramePredictor):
                 concat = self.get_climatology_array(climatology, launch_date) if climatology is not None else None
                 if truncate:
                     loss = self.truncated_backward(x, y, concat, mask, high_interest_region, graph_structure,
-                                                   truncated_backprop)[-1]
+                                                   truncated_backprop, loss_weights=lw)[-1]
                     # no gradient clipping in this branch (:311 is commented out)
                     self._clip_and_step(self._grads_ready(self._world(), self.process_group), None)
                 elif use_graph:
@@ -526,12 +643,12 @@ class NextFramePredictorS2S(NextFramePredictor):
                     if key not in graphed:      # first sight of this batch shape: its update runs eagerly, then the capture
                         graphed[key] = self.make_graphed_step(x, y, concat, mask=mask, high_interest_region=high_interest_region,
                                                               warmup=1, graph_structure=graph_structure,
-                                                              max_norm=None if single_chunk else 10.0)
+                                                              max_norm=None if single_chunk else 10.0, loss_weights=lw)
                         loss = self.last_warmup_loss
                     else:
                         loss = graphed[key](x, y, concat)
                 else:
-                    loss = self.train_step(x, y, concat, mask, high_interest_region, graph_structure)
+                    loss = self.train_step(x, y, concat, mask, high_interest_region, graph_structure, loss_weights=lw)
                     if self.debug:      # gradient norms of the two halves of the model (:259-276; clipped like the reference's)
                         for part in ('encoder', 'decoder'):
                             gs = [p.grad.detach().norm() for p in getattr(self.model, part).parameters() if p.grad is not None]
@@ -545,7 +662,8 @@ class NextFramePredictorS2S(NextFramePredictor):
                 x, y = self._clip(x), self._clip(y)
                 concat = self.get_climatology_array(climatology, launch_date) if climatology is not None else None
                 with torch.no_grad():
-                    running_test += self.forward_loss(x, y, concat, mask, high_interest_region, graph_structure).item()
+                    running_test += self.forward_loss(x, y, concat, mask, high_interest_region, graph_structure,
+                                                      loss_weights=lw).item()
                 steps_test += 1
             check_tile_errors(always=True)      # once per epoch: the graph-replayed steps and the test loop report only here
             running, running_test = running / (steps + 1), running_test / (steps_test + 1)   # (+1 as the reference, :360-361)

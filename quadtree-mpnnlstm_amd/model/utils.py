@@ -30,6 +30,21 @@ def add_positional_encoding(x):
     return np.concatenate((x, np.broadcast_to(pe, (n, w, h, 2))), axis=-1)
 
 
+def cell_area_weights(latitudes, n_lon):
+    """Relative cell areas of a regular latitude-longitude grid (beyond the reference): cos(latitude in degrees), one row per
+    latitude, repeated over n_lon columns and scaled to mean 1; float32 (len(latitudes), n_lon).  The map to pass as
+    `loss_weights` to the trainer and as `weights` to ScoreMaps.pooled."""
+    lat = np.asarray(latitudes, dtype=np.float64).reshape(-1)
+    if lat.size == 0 or int(n_lon) < 1:
+        raise ValueError(f'latitudes / n_lon: an empty grid ({lat.size} x {n_lon})')
+    if not np.isfinite(lat).all() or (np.abs(lat) > 90).any():
+        raise ValueError('latitudes: degrees in [-90, 90] are needed')
+    c = np.where(np.abs(lat) < 90, np.cos(np.deg2rad(lat)), 0.0)        # (cos(pi / 2) is 6e-17 in float64: a pole has no area)
+    if not c.sum() > 0:
+        raise ValueError('latitudes: every row lies at a pole (all areas are 0)')
+    return np.repeat((c / c.mean())[:, None], int(n_lon), axis=1).astype(np.float32)
+
+
 def get_n_params(model):
     """Number of parameters of a torch module (model/utils.py:19-27)."""
     return sum(p.numel() for p in model.parameters())

@@ -1958,6 +1958,88 @@ def rollout_sse_partials(outputs, y, meshes):
     return _RolloutSSE.apply(y.view(B, T, meshes[0].P), tuple(meshes), *outs)
 
 
+class _RolloutWSSE(Function):
+    """_RolloutSSE with a weight per pixel and per output step (qt_wsse_rollout / _bwd): partial sums of
+    lam[t] w[p] (out_t[label] - y)^2, three launches per 16 steps.  w: (P,) and lam: (T,) fp32 device tensors, no gradient.
+    The backward reads per node [sum w | sum w y] (N_t, 2), summed by the pooling tree of the unweighted target sums."""
+
+    @staticmethod
+    def forward(ctx, y, meshes, w, lam, *outs):
+        import ctypes
+        B, T, P = y.shape
+        m0 = meshes[0]
+        nt = -(P // -1024)
+        part = outs[0].new_empty(T, B * nt)
+        swys = [o.new_empty(ms.N, 2) for o, ms in zip(outs, meshes)]
+        vp, ip = ctypes.c_void_p, ctypes.c_int
+        for z0 in range(0, T, 16):
+            sl = slice(z0, min(z0 + 16, T))
+            n = sl.stop - sl.start
+            _lib.call('qt_wsse_rollout', n, (vp * n)(*[o.data_ptr() for o in outs[sl]]), (ip * n)(*[o.stride(0) for o in outs[sl]]),
+                      (vp * n)(*[ms.labels.data_ptr() for ms in meshes[sl]]), (vp * n)(*[ms.level.data_ptr() for ms in meshes[sl]]),
+                      (ip * n)(*[ms.N for ms in meshes[sl]]), (vp * n)(*[t.data_ptr() for t in swys[sl]]),
+                      y.data_ptr() + 4 * z0 * P, T * P, P, ptr(w), lam.data_ptr() + 4 * z0, B, m0.n, m0.m, ptr(part[z0:]))
+        ctx.save_for_backward(lam, *outs, *swys)
+        ctx.meshes = meshes
+        return part
+
+    @staticmethod
+    def backward(ctx, g):
+        import ctypes
+        meshes = ctx.meshes
+        T = len(meshes)
+        lam, outs, swys = ctx.saved_tensors[0], ctx.saved_tensors[1:1 + T], ctx.saved_tensors[1 + T:]
+        gouts = [torch.empty_like(o) for o in outs]
+        g1 = g.reshape(-1)[:1].contiguous()      # every partial has the same upstream gradient (they are only ever summed)
+        vp, ip = ctypes.c_void_p, ctypes.c_int
+        W = outs[0].shape[1]
+        for z0 in range(0, T, 16):
+            sl = slice(z0, min(z0 + 16, T))
+            n = sl.stop - sl.start
+            _lib.call('qt_wsse_rollout_bwd', n, (vp * n)(*[o.data_ptr() for o in outs[sl]]), (ip * n)(*[o.stride(0) for o in outs[sl]]),
+                      (vp * n)(*[t.data_ptr() for t in swys[sl]]), (ip * n)(*[ms.N for ms in meshes[sl]]),
+                      (vp * n)(*[ms.n_dev.data_ptr() if ms.n_dev is not None else None for ms in meshes[sl]]),
+                      ptr(g1), lam.data_ptr() + 4 * z0, W, (vp * n)(*[t.data_ptr() for t in gouts[sl]]))
+        return (None, None, None, None, *gouts)
+
+
+def _check_loss_weights(w, lam, mesh, T):
+    for t, what, count in ((w, 'w', mesh.P), (lam, 'lam', T)):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == count):
+            raise ValueError(f'{what}: a contiguous fp32 device tensor of {count} entries is needed')
+
+
+def rollout_wsse_partials(outputs, y, meshes, w, lam):
+    """Partial sums of lam[t] * w[p] * (squared error) of every output step (their total is the numerator of the weighted
+    loss), or None exactly where rollout_sse_partials returns None (per-pixel loss_mask of preset meshes, odd layouts): the
+    caller then goes step by step through step_wsse_partials.  w: (W, H) or (P,) pixel weights, lam: (T,) step weights, both
+    fp32 on the outputs' device and already checked (non-negative, finite); they carry no gradient."""
+    if not outputs or any(ms.loss_mask is not None or ms.N == 0 for ms in meshes):
+        return None
+    outs = [_full_rows(o) for o in outputs]
+    W = outs[0].shape[1]
+    if any(o.dtype != torch.float32 or not o.is_contiguous() or o.shape[1] != W or not o.is_cuda for o in outs):
+        return None
+    B, T = meshes[0].B, len(outs)
+    if y.dtype != torch.float32 or not y.is_contiguous() or y.numel() != B * T * meshes[0].P:
+        return None
+    _check_loss_weights(w, lam, meshes[0], T)
+    return _RolloutWSSE.apply(y.view(B, T, meshes[0].P), tuple(meshes), w.view(-1), lam, *outs)
+
+
+def step_wsse_partials(out, y, mesh, w, lam_t):
+    """One step of the weighted squared error where the rollout launches do not apply: lam_t * sum of keep * w * d^2 with
+    keep = the pixel has a node and is not under mesh.loss_mask.  A composition of differentiable ops (the counted weights,
+    gather_pixels, then the step's weight), like the loss_mask branch of step_sse_partials: NOT the tuned path.  w: (P,)
+    fp32 device tensor, lam_t: 0-dim device tensor."""
+    keep = (mesh.labels.view(mesh.B, mesh.P) >= 0).float() * w.view(1, mesh.P)
+    if mesh.loss_mask is not None:
+        keep = keep * (mesh.loss_mask == 0).float().view(1, mesh.P)
+    img = gather_pixels(out[:, :1], mesh).view(mesh.B, mesh.P)
+    d = img - y.reshape(mesh.B, mesh.P).float()
+    return (lam_t * (keep * (d * d)).sum()).view(1)
+
+
 def _score_args(who, outputs, meshes, y, persistence, climatology):
     """The checked operands rollout_scores and rollout_score_maps share: (outs, y, bases, S, B, T, P), bases = two
     (field or None, clip stride, step stride).  Refusals carry `who`."""
