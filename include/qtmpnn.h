@@ -266,6 +266,19 @@ int qt_wsse_rollout_bwd(int nseg, const float* const* outs, const int* out_strid
                         const int* Ns, const int32_t* const* n_devs, const float* g, const float* lam, int W,
                         float* const* gouts, void* stream);
 
+/* The binary cross-entropy of an ice / no-ice head in the shape of qt_sse_rollout (same arguments, same grid, same partial
+ * layout): with o = outs[z][labels[p]*stride], L1 = max(log o, -100) and L0 = max(log(1 - o), -100) (torch's clamp),
+ * partial[z][b*ntile + tile] = - sum over the tile's pixels with a node of (y L1 + (1 - y) L0); sys[z] as qt_sse_rollout.
+ * qt_bce_rollout_bwd (arguments of qt_sse_rollout_bwd) writes gouts[z][i, 0] = g (npix_i o_i - sy_i) / max(o_i (1 - o_i), 1e-12),
+ * torch's BCE gradient summed over the node's pixels (finite at o = 0 and o = 1), zeros in columns 1..W-1, rows up to n_devs[z]
+ * where given.  No atomics: the same bits on every run. */
+int qt_bce_rollout(int nseg, const float* const* outs, const int* out_strides, const int32_t* const* labels,
+                   const uint8_t* const* levels, const int* Ns, float* const* sys, const float* y, int64_t y_clip_stride,
+                   int64_t y_step_stride, int B, int n, int m, float* partial, void* stream);
+int qt_bce_rollout_bwd(int nseg, const float* const* outs, const int* out_strides, const float* const* npixs,
+                       const float* const* sys, const int* Ns, const int32_t* const* n_devs, const float* g, int W,
+                       float* const* gouts, void* stream);
+
 /* qt_score_rollout: forecast verification of a rollout (no gradient), shaped like qt_sse_rollout: up to 16 output steps per
  * call, one mesh per step, grid (ceil(P/1024), B, nseg).  Per (step z, clip b, 1024-pixel tile) and per source s it writes
  * 8 floats, partial[(((z*B + b)*ntile + tile)*S + s)*8 + slot], over the tile's counted pixels:

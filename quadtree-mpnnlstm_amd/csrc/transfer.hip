@@ -588,6 +588,54 @@ __global__ void k_wsse_bwd_multi(LossSeg sg, const float* __restrict__ g, const 
                           ? 2.0f * g[0] * lam[z] * (sw[2 * i] * out[i * sg.out_stride[z]] - sw[2 * i + 1]) : 0.0f;
 }
 
+// k_sse_multi for the binary head: partial = - sum of y max(log o, -100) + (1 - y) max(log(1 - o), -100) (torch's BCELoss with
+// its clamp), same grid and reduction order.  logf / log1pf are the accurate library functions: log(1 - o) is taken as
+// log1pf(-o), because the rounding of 1 - o alone is an error of 2^-25 / (1 - o) in the logarithm, 25 units in the last place of
+// log(1 - o) at o = 0.02.  The clamp comes before the product, so y = 0 beside o = 0 gives 0 and not 0 * -inf.
+__global__ __launch_bounds__(256) void k_bce_multi(LossSeg sg, const float* __restrict__ y, int64_t y_clip_stride,
+                                                   int64_t y_step_stride, int64_t P, int B, float* __restrict__ partial) {
+    __shared__ float red[4];
+    const int b = blockIdx.y, z = blockIdx.z;
+    const float* out = sg.out[z];
+    const int32_t* labels = sg.labels[z];
+    const int os = sg.out_stride[z];
+    const float* yz = y + z * y_step_stride + b * y_clip_stride;
+    float acc = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int64_t p = (int64_t)blockIdx.x * 1024 + k * 256 + threadIdx.x;
+        if (p < P) {
+            const int lab = labels[b * P + p];
+            if (lab >= 0) {
+                const float o = out[(int64_t)lab * os], t = yz[p];
+                const float l1 = fmaxf(logf(o), -100.0f), l0 = fmaxf(log1pf(-o), -100.0f);
+                acc -= t * l1 + (1.0f - t) * l0;
+            }
+        }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0)
+        partial[((int64_t)z * B + b) * gridDim.x + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// gradient rows of the binary cross-entropy: torch's (o - y) / max(o (1 - o), 1e-12) summed over the node's pixels (linear in y,
+// so the node sums npix and sy suffice); the clamped product keeps the row finite at o = 0 and o = 1
+__global__ void k_bce_bwd_multi(LossSeg sg, const float* __restrict__ g, int W) {
+    const int z = blockIdx.y;
+    const unsigned idx = blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = idx / (unsigned)W;
+    if (i >= qt_rows(sg.n_dev[z], sg.N[z])) return;
+    float v = 0.0f;
+    if ((idx - (unsigned)i * (unsigned)W) == 0) {
+        const float o = sg.out[z][i * sg.out_stride[z]];
+        v = g[0] * (sg.npix[z][i] * o - sg.sy[z][i]) / fmaxf(o * (1.0f - o), 1e-12f);
+    }
+    sg.gout[z][idx] = v;
+}
+
 __global__ void k_sse_bwd_multi(LossSeg sg, const float* __restrict__ g, int W) {
     const int z = blockIdx.y;
     const unsigned idx = blockIdx.x * blockDim.x + threadIdx.x;
@@ -658,6 +706,49 @@ extern "C" int qt_sse_rollout_bwd(int nseg, const float* const* outs, const int*
     QT_ARG((int64_t)nmax * W + 256 < ((int64_t)1 << 31), "N * W too large for 32-bit thread indices");
     if (nmax <= 0) return QT_OK;
     hipLaunchKernelGGL(k_sse_bwd_multi, dim3(qt_cdiv((int64_t)nmax * W, 256), nseg), dim3(256), 0, (hipStream_t)stream, sg, g, W);
+    QT_LAUNCHED();
+    return QT_OK;
+}
+
+extern "C" int qt_bce_rollout(int nseg, const float* const* outs, const int* out_strides, const int32_t* const* labels,
+                              const uint8_t* const* levels, const int* Ns, float* const* sys, const float* y,
+                              int64_t y_clip_stride, int64_t y_step_stride, int B, int n, int m, float* partial, void* stream) {
+    QT_ARG(nseg >= 1 && nseg <= 16 && outs && out_strides && labels && levels && Ns && sys && y && partial && B > 0, "bad arguments");
+    QT_ARG(n > 0 && m > 0 && y_clip_stride >= 0 && y_step_stride >= 0, "bad sizes");
+    LossSeg sg = {};
+    for (int z = 0; z < nseg; ++z) {
+        QT_ARG(outs[z] && labels[z] && levels[z] && sys[z] && out_strides[z] >= 1 && Ns[z] >= 0, "null segment pointer");
+        sg.out[z] = outs[z]; sg.out_stride[z] = out_strides[z]; sg.labels[z] = labels[z]; sg.level[z] = levels[z];
+        sg.N[z] = Ns[z]; sg.sy[z] = sys[z];
+    }
+    const int64_t P = (int64_t)n * m;
+    hipLaunchKernelGGL(k_bce_multi, dim3(qt_cdiv(P, 1024), B, nseg), dim3(256), 0, (hipStream_t)stream, sg, y, y_clip_stride,
+                       y_step_stride, P, B, partial);
+    QT_LAUNCHED();
+    PoolArgs a = {};
+    a.img = y; a.S = 1; a.img_clip_stride = y_clip_stride; a.C = 1; a.mean = 0; a.B = B; a.n = n; a.m = m;
+    a.out_stride = 1; a.out_coff = 0; a.tiles_r = qt_cdiv(n, 64); a.tiles_c = qt_cdiv(m, 64);
+    hipLaunchKernelGGL(k_pool_targets, dim3(B * a.tiles_r * a.tiles_c, 1, nseg), dim3(256), 0, (hipStream_t)stream, a, sg,
+                       y_step_stride);
+    QT_LAUNCHED();
+    return QT_OK;
+}
+
+extern "C" int qt_bce_rollout_bwd(int nseg, const float* const* outs, const int* out_strides, const float* const* npixs,
+                                  const float* const* sys, const int* Ns, const int32_t* const* n_devs, const float* g, int W,
+                                  float* const* gouts, void* stream) {
+    QT_ARG(nseg >= 1 && nseg <= 16 && outs && out_strides && npixs && sys && Ns && n_devs && g && gouts && W >= 1, "bad arguments");
+    LossSeg sg = {};
+    int nmax = 0;
+    for (int z = 0; z < nseg; ++z) {
+        QT_ARG(outs[z] && npixs[z] && sys[z] && gouts[z] && out_strides[z] >= 1, "null segment pointer");
+        sg.out[z] = outs[z]; sg.out_stride[z] = out_strides[z]; sg.npix[z] = npixs[z]; sg.sy[z] = (float*)sys[z];
+        sg.N[z] = Ns[z]; sg.n_dev[z] = n_devs[z]; sg.gout[z] = gouts[z];
+        nmax = Ns[z] > nmax ? Ns[z] : nmax;
+    }
+    QT_ARG((int64_t)nmax * W + 256 < ((int64_t)1 << 31), "N * W too large for 32-bit thread indices");
+    if (nmax <= 0) return QT_OK;
+    hipLaunchKernelGGL(k_bce_bwd_multi, dim3(qt_cdiv((int64_t)nmax * W, 256), nseg), dim3(256), 0, (hipStream_t)stream, sg, g, W);
     QT_LAUNCHED();
     return QT_OK;
 }

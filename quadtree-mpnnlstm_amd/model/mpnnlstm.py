@@ -109,14 +109,22 @@ def loss_weights_of(weights, lead_weights, shape, T_out, mask=None, binary=False
     return LossWeights(weights, lead_weights, shape, T_out, mask)
 
 
-def masked_mse(outputs, meshes, y, mask=None, binary=False, weights=None, lead_weights=None):
+def masked_mse(outputs, meshes, y, mask=None, binary=False, weights=None, lead_weights=None, fused=False):
     """MSELoss(y_hat[:, ~mask], y[:, ~mask]) of mpnnlstm.py:243-246 without building y_hat:
     sum over steps of the per-mesh squared error, divided by (clips x steps x unmasked pixels).
     y: (T_out, W, H, 1) or (B, T_out, W, H, 1).
 
     Beyond the reference: weights (W, H) >= 0 and / or lead_weights (T_out,) >= 0 (a missing one is ones; or one LossWeights as
     `weights`) give  sum lam_t w_p d^2 / (B sum_t lam_t sum_{p unmasked} w_p)  over the same counted pixels, the divisor formed
-    on the host in float64.  Unit weights are the unweighted loss; with neither given nothing here changes."""
+    on the host in float64.  Unit weights are the unweighted loss; with neither given nothing here changes.
+
+    binary=True is the reference's BCELoss on the sigmoid output.  As it stands it builds the (B, T, W, H, 1) frames and calls
+    torch (a host-side boolean index: not capturable).  fused=True (binary only) takes the rollout launches instead
+    (ops.rollout_bce_partials: no frames, no host read, the same bits on every run) and divides by B * T_out * unmasked pixels,
+    the divisor of torch's mean; it is what a captured step runs."""
+    if fused and not binary:
+        raise ValueError('fused: fused=True selects the fused binary cross-entropy and needs binary=True (the squared error always '
+                         'runs through the rollout launches)')
     if y.dim() == 4:
         y = y.unsqueeze(0)
     mesh0 = meshes[0]
@@ -135,6 +143,12 @@ def masked_mse(outputs, meshes, y, mask=None, binary=False, weights=None, lead_w
         return part.sum() / float(mesh0.B * lw.sum_lam * lw.sum_w)
     mask = host_mask(mask)
     n_valid = mesh0.P if mask is None else int((~mask).sum())
+    if binary and fused:
+        y = y.to(outputs[0].device)
+        part = ops.rollout_bce_partials(outputs, y, meshes) if y.shape[1] == len(outputs) else None
+        if part is None:        # loss_mask meshes, odd layouts: step by step, composed (ops.step_bce_partials)
+            part = torch.cat([ops.step_bce_partials(out, y[:, t], mesh) for t, (out, mesh) in enumerate(zip(outputs, meshes))])
+        return part.sum() / float(mesh0.B * len(outputs) * n_valid)
     if binary:
         y_hat = torch.stack([unflatten(o, ms, (ms.n, ms.m)).reshape(ms.B, ms.n, ms.m, 1) for o, ms in zip(outputs, meshes)], 1)
         keep = torch.ones(mesh0.n, mesh0.m, dtype=torch.bool) if mask is None else ~torch.as_tensor(mask)
@@ -278,13 +292,16 @@ class NextFramePredictorS2S(NextFramePredictor):
 
     # -- the measured unit -----------------------------------------------------------
     def forward_loss(self, x, y, concat_layers=None, mask=None, high_interest_region=None, graph_structure=None,
-                     loss_weights=None, lead_weights=None):
-        """loss_weights (W, H) / lead_weights (T_out,): the weighted loss of masked_mse (checked before the rollout starts)."""
+                     fused=False, loss_weights=None, lead_weights=None):
+        """loss_weights (W, H) / lead_weights (T_out,): the weighted loss of masked_mse (checked before the rollout starts).
+        fused=True (binary predictors only): the fused binary cross-entropy of masked_mse."""
+        if fused and not self.binary:
+            raise ValueError('fused: fused=True selects the fused binary cross-entropy and needs a binary=True predictor')
         lw = self._loss_weights(x, mask, loss_weights, lead_weights)
         y_hat, meshes = self.model(x, y, concat_layers, teacher_forcing_ratio=0, mask=mask,
                                    high_interest_region=high_interest_region, graph_structure=graph_structure)
         if lw is None:
-            return masked_mse(y_hat, meshes, y, mask, self.binary)
+            return masked_mse(y_hat, meshes, y, mask, self.binary, fused=fused)
         return masked_mse(y_hat, meshes, y, mask, self.binary, weights=lw)
 
     def _loss_weights(self, x, mask, loss_weights, lead_weights):
@@ -335,13 +352,14 @@ class NextFramePredictorS2S(NextFramePredictor):
 
     @on_device(lambda self, *a, **k: self.device)
     def train_step(self, x, y, concat_layers=None, mask=None, high_interest_region=None, graph_structure=None,
-                   max_norm=10.0, loss_weights=None, lead_weights=None):
+                   max_norm=10.0, fused=False, loss_weights=None, lead_weights=None):
         """zero_grad -> forward -> masked MSE -> backward -> [all-reduce] -> clip_grad_norm_(10) -> Adam
         (mpnnlstm.py:229-257).  x: (T_in, W, H, C) or (B, T_in, W, H, C).  Returns the loss tensor.
-        loss_weights / lead_weights: the weighted loss (masked_mse)."""
+        loss_weights / lead_weights: the weighted loss (masked_mse).  fused=True (binary predictors only): the fused binary
+        cross-entropy of masked_mse, the loss a captured step runs."""
         lw = self._loss_weights(x, mask, loss_weights, lead_weights)
         self.zero_grad()
-        loss = self.forward_loss(x, y, concat_layers, mask, high_interest_region, graph_structure, loss_weights=lw)
+        loss = self.forward_loss(x, y, concat_layers, mask, high_interest_region, graph_structure, fused=fused, loss_weights=lw)
         loss.backward()
         self._clip_and_step(self._grads_ready(self._world(), self.process_group), max_norm)
         check_tile_errors()          # (reads the device only when this step issued tile-resident launches; raises on a failed one)
@@ -400,6 +418,8 @@ class NextFramePredictorS2S(NextFramePredictor):
         replays and the capture beside its watchdog thread all run for real (tests/test_gpu_dist.py; bench.py --force-multi).
         loss_weights / lead_weights: the weighted loss (masked_mse); checked and uploaded once, here, and the captured step reads
         the two device arrays -- step(x, y, concat) keeps its signature.
+        A binary=True predictor runs the fused binary cross-entropy (masked_mse(fused=True)) in the warm-up steps and in the
+        capture alike: torch's BCELoss path indexes with a host mask and cannot be captured.
         """
         import torch.distributed as dist
         if force_multi and not (dist.is_available() and dist.is_initialized()):
@@ -417,7 +437,7 @@ class NextFramePredictorS2S(NextFramePredictor):
 
         def fwd_bwd():
             self.zero_grad()
-            loss = self.forward_loss(sx, sy, sc, mask, high_interest_region, graph_structure, loss_weights=lw)
+            loss = self.forward_loss(sx, sy, sc, mask, high_interest_region, graph_structure, fused=self.binary, loss_weights=lw)
             loss.backward()
             return loss.detach()
 

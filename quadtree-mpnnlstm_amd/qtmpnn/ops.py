@@ -1958,6 +1958,81 @@ def rollout_sse_partials(outputs, y, meshes):
     return _RolloutSSE.apply(y.view(B, T, meshes[0].P), tuple(meshes), *outs)
 
 
+class _RolloutBCE(Function):
+    """_RolloutSSE for the binary head (qt_bce_rollout / _bwd): partial sums of torch's BCELoss numerator,
+    -(y max(log o, -100) + (1 - y) max(log(1 - o), -100)), o = column 0 of outs[t], three launches per 16 steps.  The backward
+    reads the same per-node target sums as _RolloutSSE's."""
+
+    @staticmethod
+    def forward(ctx, y, meshes, *outs):
+        import ctypes
+        B, T, P = y.shape
+        m0 = meshes[0]
+        nt = -(P // -1024)
+        part = outs[0].new_empty(T, B * nt)
+        sys_ = [o.new_empty(ms.N) for o, ms in zip(outs, meshes)]
+        vp, ip = ctypes.c_void_p, ctypes.c_int
+        for z0 in range(0, T, 16):
+            sl = slice(z0, min(z0 + 16, T))
+            n = sl.stop - sl.start
+            _lib.call('qt_bce_rollout', n, (vp * n)(*[o.data_ptr() for o in outs[sl]]), (ip * n)(*[o.stride(0) for o in outs[sl]]),
+                      (vp * n)(*[ms.labels.data_ptr() for ms in meshes[sl]]), (vp * n)(*[ms.level.data_ptr() for ms in meshes[sl]]),
+                      (ip * n)(*[ms.N for ms in meshes[sl]]), (vp * n)(*[t.data_ptr() for t in sys_[sl]]),
+                      y.data_ptr() + 4 * z0 * P, T * P, P, B, m0.n, m0.m, ptr(part[z0:]))
+        ctx.save_for_backward(*outs, *sys_)
+        ctx.meshes = meshes
+        return part
+
+    @staticmethod
+    def backward(ctx, g):
+        import ctypes
+        meshes = ctx.meshes
+        T = len(meshes)
+        outs, sys_ = ctx.saved_tensors[:T], ctx.saved_tensors[T:]
+        gouts = [torch.empty_like(o) for o in outs]
+        g1 = g.reshape(-1)[:1].contiguous()      # every partial has the same upstream gradient (they are only ever summed)
+        vp, ip = ctypes.c_void_p, ctypes.c_int
+        W = outs[0].shape[1]
+        for z0 in range(0, T, 16):
+            sl = slice(z0, min(z0 + 16, T))
+            n = sl.stop - sl.start
+            _lib.call('qt_bce_rollout_bwd', n, (vp * n)(*[o.data_ptr() for o in outs[sl]]), (ip * n)(*[o.stride(0) for o in outs[sl]]),
+                      (vp * n)(*[ms.npix.data_ptr() for ms in meshes[sl]]), (vp * n)(*[t.data_ptr() for t in sys_[sl]]),
+                      (ip * n)(*[ms.N for ms in meshes[sl]]), (vp * n)(*[ms.n_dev.data_ptr() if ms.n_dev is not None else None for ms in meshes[sl]]),
+                      ptr(g1), W, (vp * n)(*[t.data_ptr() for t in gouts[sl]]))
+        return (None, None, *gouts)
+
+
+def rollout_bce_partials(outputs, y, meshes):
+    """Partial sums of the binary cross-entropy of every output step (their total is the numerator of torch's BCELoss mean), or
+    None exactly where rollout_sse_partials returns None (per-pixel loss_mask of preset meshes, odd layouts, N == 0): the caller
+    then goes step by step through step_bce_partials.  outputs[t]: probabilities in [0, 1] (the binary head's sigmoid)."""
+    if not outputs or any(ms.loss_mask is not None or ms.N == 0 for ms in meshes):
+        return None
+    outs = [_full_rows(o) for o in outputs]
+    W = outs[0].shape[1]
+    if any(o.dtype != torch.float32 or not o.is_contiguous() or o.shape[1] != W or not o.is_cuda for o in outs):
+        return None
+    B, T = meshes[0].B, len(outs)
+    if y.dtype != torch.float32 or not y.is_contiguous() or y.numel() != B * T * meshes[0].P:
+        return None
+    return _RolloutBCE.apply(y.view(B, T, meshes[0].P), tuple(meshes), *outs)
+
+
+def step_bce_partials(out, y, mesh):
+    """One step of the binary cross-entropy where the rollout launches do not apply: the sum over the pixels that have a node and
+    are not under mesh.loss_mask of torch's BCELoss terms.  A composition of differentiable ops on gather_pixels, like
+    step_wsse_partials: NOT the tuned path."""
+    keep = mesh.labels.view(mesh.B, mesh.P) >= 0
+    if mesh.loss_mask is not None:
+        keep = keep & (mesh.loss_mask == 0).view(1, mesh.P)
+    img = gather_pixels(out[:, :1], mesh).view(mesh.B, mesh.P)
+    # (a pixel without a node gathers 0: it gets a harmless probability before the log, and weight 0 after it)
+    img = torch.where(keep, img, torch.full_like(img, 0.5))
+    terms = torch.nn.functional.binary_cross_entropy(img, y.reshape(mesh.B, mesh.P).float(), reduction='none')
+    return (terms * keep.float()).sum().view(1)
+
+
 class _RolloutWSSE(Function):
     """_RolloutSSE with a weight per pixel and per output step (qt_wsse_rollout / _bwd): partial sums of
     lam[t] w[p] (out_t[label] - y)^2, three launches per 16 steps.  w: (P,) and lam: (T,) fp32 device tensors, no gradient.
