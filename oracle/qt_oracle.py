@@ -44,7 +44,7 @@ def add_positional_encoding(x):
 
 # --------------------------------------------------------------------------- R1
 def quadtree_decompose(img, thresh=0.05, max_size=64, mask=None, high_interest_region=None,
-                       transform_func=None, condition='max_larger_than'):
+                       transform_func=None, condition='max_larger_than', return_cells=False):
     """model/graph_functions.py:145-259, restated.
 
     Depth-first traversal with an explicit LIFO stack; base cells are stacked
@@ -52,6 +52,9 @@ def quadtree_decompose(img, thresh=0.05, max_size=64, mask=None, high_interest_r
     (x,y),(x+s,y),(x,y+s),(x+s,y+s).  The split test looks at a (size+1)^2
     window whose two upper limits are BOTH clamped with the padded column
     count (:222-225), mask / high-interest windows likewise (:239-242).
+
+    return_cells: also return the (N, 3) int64 array of every leaf's (x, y, s) in label order.  The side s is not in the
+    labels: a leaf that the frame border clips owns the same pixels whatever its side.
     """
     assert max_size & (max_size - 1) == 0
     assert condition in CONDITIONS
@@ -68,6 +71,7 @@ def quadtree_decompose(img, thresh=0.05, max_size=64, mask=None, high_interest_r
     todo = [(bi * max_size, bj * max_size, max_size)
             for bi in range(n_pad // max_size) for bj in range(m_pad // max_size)]
     next_label = 0
+    cells = []
     while todo:
         x, y, s = todo.pop()
         if x >= n or y >= m:
@@ -76,6 +80,7 @@ def quadtree_decompose(img, thresh=0.05, max_size=64, mask=None, high_interest_r
             if mask is not None and mask[x, y]:
                 continue
             labels[x, y] = next_label
+            cells.append((x, y, 1))
             next_label += 1
             continue
         hi_r, hi_c = min(x + s + 1, m_pad), min(y + s + 1, m_pad)
@@ -93,7 +98,10 @@ def quadtree_decompose(img, thresh=0.05, max_size=64, mask=None, high_interest_r
             todo.extend([(x, y, h), (x + h, y, h), (x, y + h, h), (x + h, y + h, h)])
         else:
             labels[x:x + s, y:y + s] = next_label
+            cells.append((x, y, s))
             next_label += 1
+    if return_cells:
+        return labels[:n, :m], np.asarray(cells, dtype=np.int64).reshape(-1, 3)
     return labels[:n, :m]
 
 
