@@ -298,6 +298,23 @@ int qt_score_rollout(int nseg, const float* const* outs, const int* out_strides,
                      const float* base2, int64_t base2_clip_stride, int64_t base2_step_stride,
                      const uint8_t* pix_mask, float thr, int B, int n, int m, float* partial, void* stream);
 
+/* qt_reliability_rollout: probability verification of a rollout (reliability diagram, Brier score, ROC).  The arguments up to
+ * m, the sources, the counting rule and the grid (ceil(P/1024), B, nseg) are qt_score_rollout's; the forecast value f of a
+ * source is read as a probability of the event o = (y > thr) (strict, fp32) and binned into `bins` = K (2..32) equal bins of
+ * [0, 1]: t = f * (float)K in fp32 (one rounding); bin 0 if not t >= 1 (values below 1/K, negative ones, NaN), bin K-1 if
+ * t >= K (overshoot), else (int)t.  Per (step z, clip b, 1024-pixel tile), source s and bin k it writes 4 floats,
+ * partial[((((z*B + b)*ntile + tile)*S + s)*K + k)*4 + slot], over the tile's counted pixels whose value is in the bin:
+ *   slot 0  n (pixels in the bin)           slot 2  sum f
+ *   slot 1  events: sum o                   slot 3  sum (f - o)^2, f - o formed in fp32
+ * No atomics, fixed summation order (per thread its pixels p, p+256, p+512, p+768 of the tile in that order, the others' bins
+ * adding +0; 64-lane butterflies; (w0 + w1) + (w2 + w3)); the counts are ballot popcounts: the same inputs give the same bits.
+ * A NaN forecast is counted in bin 0 and makes that bin's slots 2 and 3 NaN. */
+int qt_reliability_rollout(int nseg, const float* const* outs, const int* out_strides, const int32_t* const* labels,
+                           const int* Ns, const int32_t* const* n_devs, const float* y, int64_t y_clip_stride,
+                           int64_t y_step_stride, const float* base1, int64_t base1_clip_stride, int64_t base1_step_stride,
+                           const float* base2, int64_t base2_clip_stride, int64_t base2_step_stride,
+                           const uint8_t* pix_mask, float thr, int B, int n, int m, int bins, float* partial, void* stream);
+
 /* qt_score_maps: the same eight sums kept per pixel and summed over the clips (error maps per lead time).  The arguments up
  * to m are qt_score_rollout's, with its sources, counting rule, fp32 d = f - y and strict > classes; grid (ceil(P/256), nseg),
  * one thread per pixel of a step.  Step z ACCUMULATES into maps + z*maps_step_stride, a float64 block (S, 8, P) in the slot

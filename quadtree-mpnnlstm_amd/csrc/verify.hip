@@ -1,8 +1,8 @@
 // Verification of a rollout, computed where the rollout's outputs are: the per-lead-time sums of score()
-// (k_score_multi), the per-pixel maps of score_maps() (k_score_maps) and the break-up / freeze-up dates of
-// event_dates() with the sums of their errors (k_event_scan, k_event_sums).  All of them read the head's node
-// values through every step's labels (no frame is built), none has a gradient, and the three rollout launchers
-// share one host-side setup (score_setup).  The training loss (k_sse*, k_pool_targets) is in transfer.hip.
+// (k_score_multi), the per-pixel maps of score_maps() (k_score_maps), the break-up / freeze-up dates of
+// event_dates() with the sums of their errors (k_event_scan, k_event_sums) and the per-bin probability sums of
+// reliability() (k_reliability_multi).  All of them read the head's node values through every step's labels (no
+// frame is built), none has a gradient, and the four rollout launchers share one host-side setup (score_setup).  The training loss (k_sse*, k_pool_targets) is in transfer.hip.
 #include "qt_common.h"
 
 namespace {
@@ -86,6 +86,99 @@ __global__ __launch_bounds__(256) void k_score_multi(ScoreSeg sg, const float* _
         else r = total(0) - total(v0 + 3) - total(v0 + 4) - total(v0 + 5);
         partial[((((int64_t)z * B + b) * gridDim.x + blockIdx.x) * S + s) * 8 + slot] = r;
     }
+}
+
+// Probability verification of a rollout: k_score_multi's reads, sources, counting rule and tile shape, with the forecast value
+// binned into K equal bins of [0, 1] and four sums kept per (source, bin): [n, events, sum f, sum (f - o)^2], o = (y > thr).
+// Bin of a value: t = f * (float)K (one fp32 rounding), 0 if not t >= 1 (f < 1/K, negative values and NaN), K - 1 if t >= K
+// (overshoot, +inf), else (int)t.  Every thread keeps its four pixels' values, squared errors and bins in registers and the
+// workgroup walks the bins: for (source, bin) a lane adds the terms of its pixels that fall in the bin and +0 for the others.
+// Summation order of the two float sums, fixed by pixel position: per thread its pixels p, p + 256, p + 512, p + 768 of the tile
+// in that order (starting from +0), the 64-lane butterfly (xor 32, 16, 8, 4, 2, 1), then (w0 + w1) + (w2 + w3) over the four
+// waves.  A wave none of whose pixels is in the bin skips its butterfly: every lane holds +0 there, which is what the butterfly
+// would leave.  The two counts are popcounts of wave ballots (integers <= 1024: exact in fp32).  No atomics: the same bits on
+// every run, eager or replayed.  A NaN forecast is in bin 0 and makes that bin's two float sums NaN.
+template <int S>
+__global__ __launch_bounds__(256) void k_reliability_multi(ScoreSeg sg, const float* __restrict__ y, int64_t y_clip_stride,
+                                                           int64_t y_step_stride, ScoreBase b1, ScoreBase b2,
+                                                           const uint8_t* __restrict__ pix_mask, float thr, int K, int64_t P,
+                                                           int B, float* __restrict__ partial) {
+    __shared__ float red[4][S * 32 * 4];
+    const int b = blockIdx.y, z = blockIdx.z;
+    const float* out = sg.out[z];
+    const int32_t* labels = sg.labels[z] + (int64_t)b * P;
+    const int os = sg.out_stride[z];
+    const int rows = qt_rows(sg.n_dev[z], sg.N[z]);
+    const float* yz = y + z * y_step_stride + b * y_clip_stride;
+    const float* f1 = S > 1 ? b1.f + z * b1.step_stride + b * b1.clip_stride : nullptr;
+    const float* f2 = S > 2 ? b2.f + z * b2.step_stride + b * b2.clip_stride : nullptr;
+    const float Kf = (float)K;
+    float f[S][4], e2[S][4];
+    int bin[S][4];                // -1: the pixel is not counted and matches no bin
+    bool ev[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int64_t p = (int64_t)blockIdx.x * 1024 + j * 256 + threadIdx.x;
+        bool counted = p < P;
+        int lab = -1;
+        if (counted) {
+            lab = labels[p];
+            counted = lab >= 0 && lab < rows && !(pix_mask && pix_mask[p]);
+        }
+        ev[j] = false;
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+            f[s][j] = 0.0f;
+            e2[s][j] = 0.0f;
+            bin[s][j] = -1;
+        }
+        if (!counted) continue;
+        ev[j] = yz[p] > thr;
+        const float o = ev[j] ? 1.0f : 0.0f;
+        f[0][j] = out[(int64_t)lab * os];
+        if (S > 1) f[1][j] = f1[p];
+        if (S > 2) f[2][j] = f2[p];
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+            const float d = f[s][j] - o;
+            e2[s][j] = d * d;
+            const float t = f[s][j] * Kf;
+            bin[s][j] = !(t >= 1.0f) ? 0 : t >= Kf ? K - 1 : (int)t;
+        }
+    }
+    const int w = threadIdx.x >> 6;
+    for (int k = 0; k < K; ++k) {
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+            int n = 0, e = 0;
+            float sf = 0.0f, sq = 0.0f;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const bool in = bin[s][j] == k;
+                n += __popcll(__ballot(in));
+                e += __popcll(__ballot(in && ev[j]));
+                sf += in ? f[s][j] : 0.0f;
+                sq += in ? e2[s][j] : 0.0f;
+            }
+            if (n) {              // wave-uniform: n comes from ballots
+#pragma unroll
+                for (int d = 32; d >= 1; d >>= 1) {
+                    sf += __shfl_xor(sf, d, 64);
+                    sq += __shfl_xor(sq, d, 64);
+                }
+            }
+            if ((threadIdx.x & 63) == 0) {
+                float* r = red[w] + (s * K + k) * 4;
+                r[0] = (float)n;
+                r[1] = (float)e;
+                r[2] = sf;
+                r[3] = sq;
+            }
+        }
+    }
+    __syncthreads();
+    float* dst = partial + (((int64_t)z * B + b) * gridDim.x + blockIdx.x) * (S * K * 4);
+    for (int v = threadIdx.x; v < S * K * 4; v += 256) dst[v] = (red[0][v] + red[1][v]) + (red[2][v] + red[3][v]);
 }
 
 // Per-pixel verification sums: k_score_multi's reads and counting rule, kept per pixel and summed over the clips instead of
@@ -266,7 +359,7 @@ __global__ __launch_bounds__(256) void k_event_sums(const int32_t* __restrict__ 
     }
 }
 
-// What the three rollout launchers have in common: the segment arrays of 1..16 steps into `sg`, and the dense baseline fields
+// What the four rollout launchers have in common: the segment arrays of 1..16 steps into `sg`, and the dense baseline fields
 // that are present, in order, into `bs` (`nb` of them: the kernels are instantiated per source count).  Returns the reason of a
 // refusal, or null; the entry reports it under its own name (QT_ARG).
 struct ScoreSetup {
@@ -313,6 +406,28 @@ extern "C" int qt_score_rollout(int nseg, const float* const* outs, const int* o
     auto k = st.nb == 0 ? k_score_multi<1> : st.nb == 1 ? k_score_multi<2> : k_score_multi<3>;
     hipLaunchKernelGGL(k, grid, dim3(256), 0, (hipStream_t)stream, st.sg, y, y_clip_stride, y_step_stride, st.bs[0], st.bs[1],
                        pix_mask, thr, P, B, partial);
+    QT_LAUNCHED();
+    return QT_OK;
+}
+
+extern "C" int qt_reliability_rollout(int nseg, const float* const* outs, const int* out_strides, const int32_t* const* labels,
+                                      const int* Ns, const int32_t* const* n_devs, const float* y, int64_t y_clip_stride,
+                                      int64_t y_step_stride, const float* base1, int64_t base1_clip_stride,
+                                      int64_t base1_step_stride, const float* base2, int64_t base2_clip_stride,
+                                      int64_t base2_step_stride, const uint8_t* pix_mask, float thr, int B, int n, int m,
+                                      int bins, float* partial, void* stream) {
+    ScoreSetup st;
+    const char* why = score_setup(st, nseg, outs, out_strides, labels, Ns, n_devs, y, y_clip_stride, y_step_stride,
+                                  {base1, base1_clip_stride, base1_step_stride}, {base2, base2_clip_stride, base2_step_stride});
+    QT_ARG(!why, why);
+    QT_ARG(bins >= 2 && bins <= 32, "bins must be 2..32");
+    QT_ARG(partial, "null partial");
+    QT_ARG(B > 0 && B <= 65535 && n > 0 && m > 0, "bad sizes");
+    const int64_t P = (int64_t)n * m;
+    const dim3 grid(qt_cdiv(P, 1024), B, nseg);
+    auto k = st.nb == 0 ? k_reliability_multi<1> : st.nb == 1 ? k_reliability_multi<2> : k_reliability_multi<3>;
+    hipLaunchKernelGGL(k, grid, dim3(256), 0, (hipStream_t)stream, st.sg, y, y_clip_stride, y_step_stride, st.bs[0], st.bs[1],
+                       pix_mask, thr, bins, P, B, partial);
     QT_LAUNCHED();
     return QT_OK;
 }

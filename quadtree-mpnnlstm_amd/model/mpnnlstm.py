@@ -190,6 +190,14 @@ def sums_product(threshold, maps=None):
     return reduce
 
 
+def reliability_product(threshold, bins):
+    """Bin sums: the (T_out, B, S, K, 4) float64 probability verification sums of model, persistence and (with concat)
+    climatology, K = bins (ops.rollout_reliability)."""
+    def reduce(y_hat, meshes, x, y, concat):
+        return ops.rollout_reliability(y_hat, meshes, y, threshold, bins, persistence=launch_frame(x), climatology=concat)
+    return reduce
+
+
 def events_product(threshold, kind, persist):
     """Event buffer: int32, the int64 sums (B, S1 - 1, 8) followed by the dates (B, S1, P) (split_event_buffer)."""
     def reduce(y_hat, meshes, x, y, concat):
@@ -607,6 +615,16 @@ class NextFramePredictorS2S(NextFramePredictor):
                                      high_interest_region=high_interest_region, graph_structure=graph_structure)
 
     @on_device(lambda self, *a, **k: self.device)
+    def make_graphed_reliability(self, x, y, concat_layers=None, mask=None, high_interest_region=None, graph_structure=None,
+                                 threshold=0.15, bins=10):
+        """make_graphed_scores with the per-bin probability sums in place of the verification sums: the capture holds the
+        rollout and ops.rollout_reliability (sources as make_graphed_scores), no frame gather.  Returns
+        `reliability(x, y, concat) -> (T_out, B, S, bins, 4)` float64 device tensor; `reliability.warmup` is the given batch's."""
+        ops.check_bins('make_graphed_reliability', bins)
+        return self._graphed_product(reliability_product(threshold, bins), x, y, concat_layers, mask=mask,
+                                     high_interest_region=high_interest_region, graph_structure=graph_structure)
+
+    @on_device(lambda self, *a, **k: self.device)
     def make_graphed_events(self, x, y, concat_layers=None, mask=None, high_interest_region=None, graph_structure=None,
                             threshold=0.15, kind='breakup', persist=5):
         """make_graphed_scores with the event dates in place of the verification sums: the capture holds the rollout, the
@@ -738,7 +756,7 @@ class NextFramePredictorS2S(NextFramePredictor):
         return np.stack(preds, 0)
 
     def _inference(self, loader, climatology, product, consume, use_graph, reads_y=True, begin=None, **fwd):
-        """The inference loop of predict, score, score_maps and event_dates: per batch begin(x), if given, then one no-grad
+        """The inference loop of predict, score, score_maps, reliability and event_dates: per batch begin(x), if given, then one no-grad
         rollout (teacher forcing 0, forward arguments `fwd`) reduced by a reduce(y_hat, meshes, x, y, concat), see frames_product,
         whose result goes to consume(result, x); x is the clipped batch.  product(x) makes the reduce: for every batch of an eager
         call, for every capture of a graphed one, so it must not do what every batch needs (that is begin's).  use_graph: each
@@ -834,6 +852,28 @@ class NextFramePredictorS2S(NextFramePredictor):
         if maps is not None:
             maps = ScoreMaps(maps.cpu().numpy().reshape(*maps.shape[:3], *frame), sources)
         return Scores(np.concatenate(sums, 0), sources, maps=maps)
+
+    @on_device(lambda self, *a, **k: self.device)
+    def reliability(self, loader, climatology=None, mask=None, high_interest_region=None, graph_structure=None, use_graph=False,
+                    threshold=0.15, bins=10):
+        """Probability verification over a loader -> qtmpnn.reliability.Reliability (beyond the reference): every source's value
+        is read as a forecast probability of the event `y > threshold` (strict) -- the probabilities of a binary=True head
+        (pass threshold=0.5: a 0/1 truth is then the event itself), or a concentration in [0, 1] read as a probability of ice --
+        and binned into `bins` (2..32) equal bins of [0, 1]; values below 0 and above 1 fall into the end bins.  The result
+        gives the reliability diagram, sharpness, Brier score with its decomposition, skill against climatology and the ROC.
+
+        score()'s loop, arguments and sources: every batch leaves four sums per (lead time, clip, source, bin) on the device
+        (ops.rollout_reliability: the head's outputs read through the labels, no frame is built) and makes one host copy of
+        them.  use_graph=True replays rollout + sums as one hipGraph per distinct batch shape (make_graphed_reliability)."""
+        from qtmpnn.reliability import Reliability
+        ops.check_bins('reliability', bins)
+        sources = ('model', 'persistence') + (('climatology',) if climatology is not None else ())
+        sums = []
+        reduce = reliability_product(threshold, bins)
+        self._inference(loader, climatology, lambda x: reduce,
+                        lambda part, x: sums.append(np.moveaxis(part.cpu().numpy(), 0, 1)),  # (T, B, S, K, 4) -> (B, T, S, K, 4)
+                        use_graph, mask=mask, high_interest_region=high_interest_region, graph_structure=graph_structure)
+        return Reliability(np.concatenate(sums, 0), sources, threshold)
 
     @on_device(lambda self, *a, **k: self.device)
     def event_dates(self, loader, climatology=None, mask=None, high_interest_region=None, graph_structure=None, use_graph=False,

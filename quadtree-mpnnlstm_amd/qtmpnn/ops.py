@@ -2174,6 +2174,29 @@ def rollout_scores(outputs, meshes, y, threshold=0.15, persistence=None, climato
     return part if per_tile else part.double().sum(2)
 
 
+def check_bins(who, bins):
+    """`bins` of a reliability call: an integer in 2..32 (the kernel's per-tile rows are sized by it), refused under `who`."""
+    if not (isinstance(bins, int) and not isinstance(bins, bool) and 2 <= bins <= 32):
+        raise ValueError(f'{who}: bins must be an integer in 2..32, got {bins!r}')
+    return bins
+
+
+def rollout_reliability(outputs, meshes, y, threshold=0.15, bins=10, persistence=None, climatology=None, per_tile=False):
+    """Probability verification sums of a rollout, float64 (T, B, S, K, 4) on the device (qt_reliability_rollout; bin rule and
+    slot table in include/qtmpnn.h): per output step, clip, source and bin k of K = `bins` equal bins of [0, 1] the sums
+    [n, events, sum f, sum (f - o)^2] over the counted pixels whose forecast value f falls in the bin, o = (y > threshold)
+    (strict).  Values below 0 and above 1 fall into the end bins.  Operands, sources and counting rule are rollout_scores'.
+    No autograd, no host read: capturable.  per_tile=True returns the launch's own fp32 partials (T, B, ceil(P/1024), S, K, 4)
+    instead of their float64 sum over the tiles."""
+    who = 'rollout_reliability'
+    K = check_bins(who, bins)
+    outs, y, bases, S, B, T, P = _score_args(who, outputs, meshes, y, persistence, climatology)
+    nt = -(P // -1024)
+    part = outs[0].new_empty(T, B, nt, S, K, 4)
+    _score_chunks('qt_reliability_rollout', outs, meshes, y, bases, threshold, B, T, P, lambda z0: (K, ptr(part[z0:])))
+    return part if per_tile else part.double().sum(2)
+
+
 def rollout_score_maps(outputs, meshes, y, maps, threshold=0.15, persistence=None, climatology=None):
     """rollout_scores' eight sums kept per pixel and summed over the clips: `maps`, a float64 (T, S, 8, P) tensor on the
     outputs' device, is accumulated in place (qt_score_maps) and returned.  Operands, sources, counting rule and classes are
