@@ -315,6 +315,30 @@ int qt_reliability_rollout(int nseg, const float* const* outs, const int* out_st
                            const float* base2, int64_t base2_clip_stride, int64_t base2_step_stride,
                            const uint8_t* pix_mask, float thr, int B, int n, int m, int bins, float* partial, void* stream);
 
+/* qt_fss_rollout: neighbourhood verification of a rollout (Fractions Skill Score, Roberts & Lean 2008), all in integers.  The
+ * arguments up to m, the sources and the counting rule are qt_score_rollout's; the frame is n rows of m pixels, p = r*m + c.
+ * For clip b, step z and pixel p: counted(p) = the step's label lab has 0 <= lab < rows and p is not under pix_mask;
+ * I_o(p) = counted(p) && y[p] > thr, I_s(p) = counted(p) && f_s[p] > thr for each source s (strict > in fp32: a NaN is not
+ * ice).  `scales` (host memory, read before the launch) holds nscales = K (1..8) odd window sizes in 1..33, strictly
+ * increasing.  The window count c_x(p; w) of scale w = 2h + 1 is the sum of I_x(q) over q = (r + dr, c + dc), |dr| <= h,
+ * |dc| <= h; positions outside the frame and uncounted pixels add 0 (the fraction's denominator is the fixed w^2 of the
+ * zero-padded convention, which cancels in the score).  Grid (ceil(n/32) * ceil(m/32), B, nseg): one workgroup per 32 x 32
+ * tile of centres (tile = (r / 32) * ceil(m/32) + c / 32), which reads its tile and a 16-pixel halo.  Per (step z, clip b,
+ * tile), source s and scale k it writes 5 int32,
+ * partial[((((z*B + b)*ntile + tile)*S + s)*K + k)*5 + slot], over the tile's COUNTED centres p:
+ *   slot 0  n (counted centres)             slot 2  sum (c_s - c_o)^2      slot 4  sum c_o^2
+ *   slot 1  events: sum I_o(p)              slot 3  sum c_s^2
+ * (slots 0 and 1 are the same for every s and k).  A count is <= 33^2, so a tile's slot is <= 1024 * 33^4 = 1 214 383 104
+ * < 2^31; a frame's total is not bounded so (256 x 256: 7.8e10) and is the caller's to add in int64.
+ * FSS = 1 - sum (c_s - c_o)^2 / (sum c_s^2 + sum c_o^2), undefined where the denominator is 0 (no ice in either field).  At
+ * w = 1 the slots are qt_score_rollout's table: slot 2 = over + under, slot 3 = hits + over, slot 4 = hits + under = slot 1.
+ * No atomics, integers only: the same inputs give the same bits. */
+int qt_fss_rollout(int nseg, const float* const* outs, const int* out_strides, const int32_t* const* labels, const int* Ns,
+                   const int32_t* const* n_devs, const float* y, int64_t y_clip_stride, int64_t y_step_stride,
+                   const float* base1, int64_t base1_clip_stride, int64_t base1_step_stride, const float* base2,
+                   int64_t base2_clip_stride, int64_t base2_step_stride, const uint8_t* pix_mask, float thr, int B, int n, int m,
+                   int nscales, const int* scales, int32_t* partial, void* stream);
+
 /* qt_score_maps: the same eight sums kept per pixel and summed over the clips (error maps per lead time).  The arguments up
  * to m are qt_score_rollout's, with its sources, counting rule, fp32 d = f - y and strict > classes; grid (ceil(P/256), nseg),
  * one thread per pixel of a step.  Step z ACCUMULATES into maps + z*maps_step_stride, a float64 block (S, 8, P) in the slot

@@ -1,8 +1,9 @@
 // Verification of a rollout, computed where the rollout's outputs are: the per-lead-time sums of score()
 // (k_score_multi), the per-pixel maps of score_maps() (k_score_maps), the break-up / freeze-up dates of
-// event_dates() with the sums of their errors (k_event_scan, k_event_sums) and the per-bin probability sums of
-// reliability() (k_reliability_multi).  All of them read the head's node values through every step's labels (no
-// frame is built), none has a gradient, and the four rollout launchers share one host-side setup (score_setup).  The training loss (k_sse*, k_pool_targets) is in transfer.hip.
+// event_dates() with the sums of their errors (k_event_scan, k_event_sums), the per-bin probability sums of
+// reliability() (k_reliability_multi) and the neighbourhood sums of fss() (k_fss_multi).  All of them read the head's node
+// values through every step's labels (no frame is built), none has a gradient, and the five rollout launchers share one
+// host-side setup (score_setup).  The training loss (k_sse*, k_pool_targets) is in transfer.hip.
 #include "qt_common.h"
 
 namespace {
@@ -179,6 +180,149 @@ __global__ __launch_bounds__(256) void k_reliability_multi(ScoreSeg sg, const fl
     __syncthreads();
     float* dst = partial + (((int64_t)z * B + b) * gridDim.x + blockIdx.x) * (S * K * 4);
     for (int v = threadIdx.x; v < S * K * 4; v += 256) dst[v] = (red[0][v] + red[1][v]) + (red[2][v] + red[3][v]);
+}
+
+// Neighbourhood verification of a rollout (Fractions Skill Score): k_score_multi's reads, sources and counting rule, but a
+// pixel is compared through the number of "ice" pixels in the n x n window around it, n = 2h + 1 one of K scales (h <= 16).
+// Indicators: I_o(p) = counted(p) && y[p] > thr, I_s(p) = counted(p) && f_s[p] > thr (strict, fp32: a NaN is not ice); a window
+// count c_x(p; n) is the sum of I_x over the window, positions outside the frame and uncounted pixels adding 0.  Per
+// (source, scale) the tile keeps five integers over its counted centres: [n, events = sum I_o, sum (c_s - c_o)^2, sum c_s^2,
+// sum c_o^2].
+// One workgroup per (32 x 32 tile of centres, clip, step).  It reads the 64 x 64 patch of the tile with its 16-pixel halo: wave
+// w takes patch rows 16w .. 16w + 15, lane l patch column l, and a ballot turns `counted` and every indicator of a patch row
+// into one 64-bit word (lanes outside the frame are false): the patch is 64 rows x (S + 2) words of LDS.  Thread t then owns the
+// centres (4 (t >> 5) + j, t & 31), j = 0..3 -- one column, four consecutive rows, so their windows share all but six rows --
+// and walks the scales: the window's columns are one mask of 2h + 1 bits (patch columns cc + 16 - h .. cc + 16 + h, inside the
+// word because h <= 16), a row's part of a count is popcount(word & mask), and the 2h + 4 rows the four windows cover are read
+// once each.  The 32 lanes of a half wave read the same word (an LDS broadcast), the halves two different ones.
+// Widths: a count is <= 33^2 = 1089, so a centre's term is <= 1089^2 = 33^4 and a tile's sum <= 1024 * 33^4 = 1 214 383 104
+// < 2^31: every partial (per thread: four centres; per wave; per tile) is a non-negative int32 below that, (c_s - c_o)^2
+// included since both counts are in 0..1089.  The totals over tiles are added in int64 by the caller.
+// Reduction: 64-lane butterflies, then (w0 + w1) + (w2 + w3); n and events are popcounts of the centre bits.  Integers, no
+// atomics: the same bits on every run, eager or replayed.  Neighbouring tiles (blockIdx.x, x + 1) are dealt to different XCDs, so
+// a halo is fetched by up to four L2s; a step's fields are a few tens of KB per clip, and nothing depends on the placement.
+struct FssScales {
+    int K, h[8];
+};
+
+template <int S>
+__global__ __launch_bounds__(256) void k_fss_multi(ScoreSeg sg, const float* __restrict__ y, int64_t y_clip_stride,
+                                                   int64_t y_step_stride, ScoreBase b1, ScoreBase b2,
+                                                   const uint8_t* __restrict__ pix_mask, float thr, FssScales sc, int n, int m,
+                                                   int tiles_m, int B, int32_t* __restrict__ partial) {
+    constexpr int NW = S + 2;                                  // words of a patch row: counted, I_o, I_s per source
+    __shared__ unsigned long long bits[64][NW];
+    __shared__ int red[4][2 + S * 8 * 3];
+    const int b = blockIdx.y, z = blockIdx.z;
+    const int64_t P = (int64_t)n * m;
+    const float* out = sg.out[z];
+    const int32_t* labels = sg.labels[z] + (int64_t)b * P;
+    const int os = sg.out_stride[z];
+    const int rows = qt_rows(sg.n_dev[z], sg.N[z]);
+    const float* yz = y + z * y_step_stride + b * y_clip_stride;
+    const float* f1 = S > 1 ? b1.f + z * b1.step_stride + b * b1.clip_stride : nullptr;
+    const float* f2 = S > 2 ? b2.f + z * b2.step_stride + b * b2.clip_stride : nullptr;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int r0 = (blockIdx.x / tiles_m) * 32 - 16, c0 = (blockIdx.x % tiles_m) * 32 - 16;      // frame position of patch (0, 0)
+    const int gc = c0 + lane;
+#pragma unroll 4
+    for (int i = 0; i < 16; ++i) {
+        const int pr = w * 16 + i, gr = r0 + pr;
+        const bool in = gr >= 0 && gr < n && gc >= 0 && gc < m;
+        bool counted = false, io = false, is[S];
+#pragma unroll
+        for (int s = 0; s < S; ++s) is[s] = false;
+        if (in) {
+            const int64_t p = (int64_t)gr * m + gc;
+            const int lab = labels[p];
+            counted = lab >= 0 && lab < rows && !(pix_mask && pix_mask[p]);
+            if (counted) {
+                io = yz[p] > thr;
+                is[0] = out[(int64_t)lab * os] > thr;
+                if (S > 1) is[1] = f1[p] > thr;
+                if (S > 2) is[2] = f2[p] > thr;
+            }
+        }
+        const unsigned long long wc = __ballot(counted), wo = __ballot(io);
+        unsigned long long ws[S];
+#pragma unroll
+        for (int s = 0; s < S; ++s) ws[s] = __ballot(is[s]);
+        if (lane == 0) {
+            bits[pr][0] = wc;
+            bits[pr][1] = wo;
+#pragma unroll
+            for (int s = 0; s < S; ++s) bits[pr][2 + s] = ws[s];
+        }
+    }
+    __syncthreads();
+    const int cc = (threadIdx.x & 31) + 16, rr = (threadIdx.x >> 5) * 4 + 16;       // patch column, first patch row of the centres
+    bool ctr[4], ev[4];
+    int nc = 0, ne = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        ctr[j] = (bits[rr + j][0] >> cc) & 1;
+        ev[j] = (bits[rr + j][1] >> cc) & 1;
+        nc += __popcll(__ballot(ctr[j]));
+        ne += __popcll(__ballot(ev[j]));
+    }
+    if (lane == 0) {
+        red[w][0] = nc;
+        red[w][1] = ne;
+    }
+    for (int k = 0; k < sc.K; ++k) {
+        const int h = sc.h[k];
+        const unsigned long long cmask = ((1ull << (2 * h + 1)) - 1) << (cc - h);
+        int co[4], cs[S][4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            co[j] = 0;
+#pragma unroll
+            for (int s = 0; s < S; ++s) cs[s][j] = 0;
+        }
+        for (int i = 0; i < 2 * h + 4; ++i) {                  // patch row rr - h + i is in the window of centre j iff j <= i <= j + 2h
+            const unsigned long long* row = bits[rr - h + i];
+            const int po = __popcll(row[1] & cmask);
+            int ps[S];
+#pragma unroll
+            for (int s = 0; s < S; ++s) ps[s] = __popcll(row[2 + s] & cmask);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const bool hit = i >= j && i <= j + 2 * h;
+                co[j] += hit ? po : 0;
+#pragma unroll
+                for (int s = 0; s < S; ++s) cs[s][j] += hit ? ps[s] : 0;
+            }
+        }
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+            int v[3] = {0, 0, 0};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int d = cs[s][j] - co[j];
+                v[0] += ctr[j] ? d * d : 0;
+                v[1] += ctr[j] ? cs[s][j] * cs[s][j] : 0;
+                v[2] += ctr[j] ? co[j] * co[j] : 0;
+            }
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+#pragma unroll
+                for (int d = 32; d >= 1; d >>= 1) v[q] += __shfl_xor(v[q], d, 64);
+            }
+            if (lane == 0) {
+                int* r = red[w] + 2 + (s * sc.K + k) * 3;
+                r[0] = v[0];
+                r[1] = v[1];
+                r[2] = v[2];
+            }
+        }
+    }
+    __syncthreads();
+    auto total = [&](int v) { return (red[0][v] + red[1][v]) + (red[2][v] + red[3][v]); };
+    int32_t* dst = partial + (((int64_t)z * B + b) * gridDim.x + blockIdx.x) * (S * sc.K * 5);
+    for (int v = threadIdx.x; v < S * sc.K * 5; v += 256) {
+        const int slot = v % 5;
+        dst[v] = slot < 2 ? total(slot) : total(2 + (v / 5) * 3 + slot - 2);
+    }
 }
 
 // Per-pixel verification sums: k_score_multi's reads and counting rule, kept per pixel and summed over the clips instead of
@@ -359,7 +503,7 @@ __global__ __launch_bounds__(256) void k_event_sums(const int32_t* __restrict__ 
     }
 }
 
-// What the four rollout launchers have in common: the segment arrays of 1..16 steps into `sg`, and the dense baseline fields
+// What the five rollout launchers have in common: the segment arrays of 1..16 steps into `sg`, and the dense baseline fields
 // that are present, in order, into `bs` (`nb` of them: the kernels are instantiated per source count).  Returns the reason of a
 // refusal, or null; the entry reports it under its own name (QT_ARG).
 struct ScoreSetup {
@@ -428,6 +572,39 @@ extern "C" int qt_reliability_rollout(int nseg, const float* const* outs, const 
     auto k = st.nb == 0 ? k_reliability_multi<1> : st.nb == 1 ? k_reliability_multi<2> : k_reliability_multi<3>;
     hipLaunchKernelGGL(k, grid, dim3(256), 0, (hipStream_t)stream, st.sg, y, y_clip_stride, y_step_stride, st.bs[0], st.bs[1],
                        pix_mask, thr, bins, P, B, partial);
+    QT_LAUNCHED();
+    return QT_OK;
+}
+
+extern "C" int qt_fss_rollout(int nseg, const float* const* outs, const int* out_strides, const int32_t* const* labels,
+                              const int* Ns, const int32_t* const* n_devs, const float* y, int64_t y_clip_stride,
+                              int64_t y_step_stride, const float* base1, int64_t base1_clip_stride, int64_t base1_step_stride,
+                              const float* base2, int64_t base2_clip_stride, int64_t base2_step_stride,
+                              const uint8_t* pix_mask, float thr, int B, int n, int m, int nscales, const int* scales,
+                              int32_t* partial, void* stream) {
+    ScoreSetup st;
+    const char* why = score_setup(st, nseg, outs, out_strides, labels, Ns, n_devs, y, y_clip_stride, y_step_stride,
+                                  {base1, base1_clip_stride, base1_step_stride}, {base2, base2_clip_stride, base2_step_stride});
+    QT_ARG(!why, why);
+    QT_ARG(nscales >= 1 && nscales <= 8, "nscales must be 1..8");
+    QT_ARG(scales, "null scales");
+    FssScales sc = {};
+    sc.K = nscales;
+    for (int k = 0; k < nscales; ++k) {
+        // the kernel's column mask and halo hold windows up to 33 wide and no wider
+        QT_ARG(scales[k] >= 1 && scales[k] <= 33 && (scales[k] & 1), "scales must be odd and in 1..33");
+        QT_ARG(k == 0 || scales[k] > scales[k - 1], "scales must be strictly increasing");
+        sc.h[k] = scales[k] / 2;
+    }
+    QT_ARG(partial, "null partial");
+    QT_ARG(B > 0 && B <= 65535 && n > 0 && m > 0, "bad sizes");
+    const int tiles_m = qt_cdiv(m, 32);
+    const int64_t ntile = (int64_t)qt_cdiv(n, 32) * tiles_m;
+    QT_ARG(ntile <= 0x7fffffff, "bad sizes");
+    const dim3 grid((unsigned)ntile, B, nseg);
+    auto k = st.nb == 0 ? k_fss_multi<1> : st.nb == 1 ? k_fss_multi<2> : k_fss_multi<3>;
+    hipLaunchKernelGGL(k, grid, dim3(256), 0, (hipStream_t)stream, st.sg, y, y_clip_stride, y_step_stride, st.bs[0], st.bs[1],
+                       pix_mask, thr, sc, n, m, tiles_m, B, partial);
     QT_LAUNCHED();
     return QT_OK;
 }

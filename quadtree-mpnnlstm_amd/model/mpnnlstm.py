@@ -198,6 +198,14 @@ def reliability_product(threshold, bins):
     return reduce
 
 
+def fss_product(threshold, scales):
+    """Neighbourhood sums: the (T_out, B, S, K, 5) int64 Fractions Skill Score sums of model, persistence and (with concat)
+    climatology, K = len(scales) (ops.rollout_fss)."""
+    def reduce(y_hat, meshes, x, y, concat):
+        return ops.rollout_fss(y_hat, meshes, y, threshold, scales, persistence=launch_frame(x), climatology=concat)
+    return reduce
+
+
 def events_product(threshold, kind, persist):
     """Event buffer: int32, the int64 sums (B, S1 - 1, 8) followed by the dates (B, S1, P) (split_event_buffer)."""
     def reduce(y_hat, meshes, x, y, concat):
@@ -625,6 +633,16 @@ class NextFramePredictorS2S(NextFramePredictor):
                                      high_interest_region=high_interest_region, graph_structure=graph_structure)
 
     @on_device(lambda self, *a, **k: self.device)
+    def make_graphed_fss(self, x, y, concat_layers=None, mask=None, high_interest_region=None, graph_structure=None,
+                         threshold=0.15, scales=(1, 3, 5, 9, 17, 33)):
+        """make_graphed_scores with the per-scale neighbourhood sums in place of the verification sums: the capture holds the
+        rollout and ops.rollout_fss (sources as make_graphed_scores), no frame gather.  Returns
+        `fss(x, y, concat) -> (T_out, B, S, len(scales), 5)` int64 device tensor; `fss.warmup` is the given batch's."""
+        scales = ops.check_scales('make_graphed_fss', scales)
+        return self._graphed_product(fss_product(threshold, scales), x, y, concat_layers, mask=mask,
+                                     high_interest_region=high_interest_region, graph_structure=graph_structure)
+
+    @on_device(lambda self, *a, **k: self.device)
     def make_graphed_events(self, x, y, concat_layers=None, mask=None, high_interest_region=None, graph_structure=None,
                             threshold=0.15, kind='breakup', persist=5):
         """make_graphed_scores with the event dates in place of the verification sums: the capture holds the rollout, the
@@ -756,7 +774,7 @@ class NextFramePredictorS2S(NextFramePredictor):
         return np.stack(preds, 0)
 
     def _inference(self, loader, climatology, product, consume, use_graph, reads_y=True, begin=None, **fwd):
-        """The inference loop of predict, score, score_maps, reliability and event_dates: per batch begin(x), if given, then one no-grad
+        """The inference loop of predict, score, score_maps, reliability, fss and event_dates: per batch begin(x), if given, then one no-grad
         rollout (teacher forcing 0, forward arguments `fwd`) reduced by a reduce(y_hat, meshes, x, y, concat), see frames_product,
         whose result goes to consume(result, x); x is the clipped batch.  product(x) makes the reduce: for every batch of an eager
         call, for every capture of a graphed one, so it must not do what every batch needs (that is begin's).  use_graph: each
@@ -874,6 +892,28 @@ class NextFramePredictorS2S(NextFramePredictor):
                         lambda part, x: sums.append(np.moveaxis(part.cpu().numpy(), 0, 1)),  # (T, B, S, K, 4) -> (B, T, S, K, 4)
                         use_graph, mask=mask, high_interest_region=high_interest_region, graph_structure=graph_structure)
         return Reliability(np.concatenate(sums, 0), sources, threshold)
+
+    @on_device(lambda self, *a, **k: self.device)
+    def fss(self, loader, climatology=None, mask=None, high_interest_region=None, graph_structure=None, use_graph=False,
+            threshold=0.15, scales=(1, 3, 5, 9, 17, 33)):
+        """Neighbourhood verification over a loader -> qtmpnn.fss.FSS (beyond the reference): the Fractions Skill Score
+        (Roberts & Lean 2008) of every source at every window size of `scales` (up to 8 odd sizes in 1..33, increasing).  A
+        pixel is compared through the number of ice pixels (`value > threshold`, strict) in the window around it, so an ice
+        edge that sits two pixels off is charged for those two pixels and not, as in score()'s table, as a miss and a false
+        alarm.  The result gives the score per lead time and scale, the skill against persistence and the smallest useful scale.
+
+        score()'s loop, arguments and sources: every batch leaves five integers per (lead time, clip, source, scale) on the
+        device (ops.rollout_fss: the head's outputs read through the labels, no frame is built) and makes one host copy of
+        them.  use_graph=True replays rollout + sums as one hipGraph per distinct batch shape (make_graphed_fss)."""
+        from qtmpnn.fss import FSS
+        scales = ops.check_scales('fss', scales)
+        sources = ('model', 'persistence') + (('climatology',) if climatology is not None else ())
+        sums = []
+        reduce = fss_product(threshold, scales)
+        self._inference(loader, climatology, lambda x: reduce,
+                        lambda part, x: sums.append(np.moveaxis(part.cpu().numpy(), 0, 1)),  # (T, B, S, K, 5) -> (B, T, S, K, 5)
+                        use_graph, mask=mask, high_interest_region=high_interest_region, graph_structure=graph_structure)
+        return FSS(np.concatenate(sums, 0), sources, threshold, scales)
 
     @on_device(lambda self, *a, **k: self.device)
     def event_dates(self, loader, climatology=None, mask=None, high_interest_region=None, graph_structure=None, use_graph=False,

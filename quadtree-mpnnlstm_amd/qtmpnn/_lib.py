@@ -44,6 +44,7 @@ _SIGNATURES = {
     'qt_bce_rollout_bwd': [_I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P],
     'qt_score_rollout': [_I, _P, _P, _P, _P, _P, _P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _F, _I, _I, _I, _P, _P],
     'qt_reliability_rollout': [_I, _P, _P, _P, _P, _P, _P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _F, _I, _I, _I, _I, _P, _P],
+    'qt_fss_rollout': [_I, _P, _P, _P, _P, _P, _P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _F, _I, _I, _I, _I, _P, _P, _P],
     'qt_score_maps': [_I, _P, _P, _P, _P, _P, _P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _F, _I, _I, _I, _P, _L, _P],
     'qt_event_scan': [_I, _P, _P, _P, _P, _P, _P, _L, _L, _P, _L, _L, _P, _F, _I, _I, _I, _P, _L, _I, _I, _I, _P, _P, _P],
     'qt_event_sums': [_P, _I, _I, _I, _I, _P, _P],

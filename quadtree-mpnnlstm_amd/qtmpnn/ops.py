@@ -2,6 +2,7 @@
 
 Every op runs on the GPU through libqtmpnn_hip.so; there is no CPU fallback.
 """
+import numbers
 import os
 
 import torch
@@ -2195,6 +2196,49 @@ def rollout_reliability(outputs, meshes, y, threshold=0.15, bins=10, persistence
     part = outs[0].new_empty(T, B, nt, S, K, 4)
     _score_chunks('qt_reliability_rollout', outs, meshes, y, bases, threshold, B, T, P, lambda z0: (K, ptr(part[z0:])))
     return part if per_tile else part.double().sum(2)
+
+
+def check_scales(who, scales):
+    """`scales` of an FSS call: 1..8 odd window sizes in 1..33, strictly increasing (the kernel's halo is 16 pixels and its
+    column mask one 64-bit word), refused under `who`.  -> tuple of int."""
+    try:
+        sc = tuple(scales)
+    except TypeError:
+        raise ValueError(f'{who}: scales must be a sequence of odd integers in 1..33, got {scales!r}') from None
+    if not sc:
+        raise ValueError(f'{who}: scales is empty: give 1..8 odd window sizes in 1..33')
+    if len(sc) > 8:
+        raise ValueError(f'{who}: {len(sc)} scales, at most 8 are taken: {sc!r}')
+    for v in sc:
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+            raise ValueError(f'{who}: scales must be integers, got {v!r} in {sc!r}')
+        if v % 2 == 0:
+            raise ValueError(f'{who}: scales must be odd (a window has a centre), got {v!r} in {sc!r}')
+        if not 1 <= v <= 33:
+            raise ValueError(f'{who}: scales must be in 1..33, got {v!r} in {sc!r}')
+    if any(b <= a for a, b in zip(sc, sc[1:])):
+        raise ValueError(f'{who}: scales must be strictly increasing, got {sc!r}')
+    return tuple(int(v) for v in sc)
+
+
+def rollout_fss(outputs, meshes, y, threshold=0.15, scales=(1, 3, 5, 9, 17, 33), persistence=None, climatology=None,
+                per_tile=False):
+    """Neighbourhood verification sums of a rollout (Fractions Skill Score), int64 (T, B, S, K, 5) on the device (qt_fss_rollout;
+    definition and slot table in include/qtmpnn.h): per output step, clip, source and scale k of K = len(scales) the integers
+    [n, events, sum (c_s - c_o)^2, sum c_s^2, sum c_o^2] over the counted pixels, c_x the number of counted pixels with
+    x > threshold (strict) in the scale's window around the pixel; positions outside the frame add 0.  Operands, sources and
+    counting rule are rollout_scores'.  No autograd, no host read: capturable.  per_tile=True returns the launch's own int32
+    partials (T, B, ceil(n/32) * ceil(m/32), S, K, 5) instead of their int64 sum over the tiles."""
+    import ctypes
+    who = 'rollout_fss'
+    sc = check_scales(who, scales)
+    outs, y, bases, S, B, T, P = _score_args(who, outputs, meshes, y, persistence, climatology)
+    K = len(sc)
+    nt = -(meshes[0].n // -32) * -(meshes[0].m // -32)
+    part = torch.empty(T, B, nt, S, K, 5, dtype=torch.int32, device=outs[0].device)
+    host = (ctypes.c_int * K)(*sc)
+    _score_chunks('qt_fss_rollout', outs, meshes, y, bases, threshold, B, T, P, lambda z0: (K, host, ptr(part[z0:])))
+    return part if per_tile else part.sum(2, dtype=torch.int64)
 
 
 def rollout_score_maps(outputs, meshes, y, maps, threshold=0.15, persistence=None, climatology=None):
