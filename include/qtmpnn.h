@@ -486,7 +486,8 @@ int qt_head_dgrad(const float* gU, const float* Wb2, const float* Y, const float
  *   A: Ka planes, plane k at a0 (k == 0) or a_rest + (k-1)*N*Ca, each (N, Ca)   (T_0 = Z stays in the caller's tensor)
  *   W: (Ka*Ca, Kb*Cb) row-major;  S: (N, Ks) or NULL with Ws (Ks, Kb*Cb)
  *   out: Kb planes of (N, Cb) at out + j*N*Cb
- *   act: QT_ACT_* applied to the result (only with Kb == 1); res (N) / drop (N) for QT_ACT_TANH_RES, drop may be NULL.
+ *   act: QT_ACT_* applied to the result (only with Kb == 1); res (N) for QT_ACT_TANH_RES; drop (N) or NULL: the rows' dropout
+ *   factors, applied before the activation by QT_ACT_RELU (y = max(drop * acc, 0)) and QT_ACT_TANH_RES.
  */
 int qt_dense(const float* a0, const float* a_rest, int Ka, int Ca, const float* W,
              const float* S, int Ks, const float* Ws, int Kb, int Cb, int N, const int32_t* n_dev,
@@ -666,7 +667,7 @@ int qt_spmm1(const int32_t* rowptr, const int32_t* col, const float* nrm, const 
              const float* x, int ldx, float alpha, const float* p, int ldp, float beta, const float* q, int ldq, float gamma,
              float* out, int ldo, int pad4, int act, const float* res, int ldr, const float* drop, void* stream);
 
-/* backward of the qt_dense epilogue activations: G = gY * act'(Y) (QT_ACT_RELU, QT_ACT_TANH_RES with res / drop as in
+/* backward of the qt_dense epilogue activations: G = gY * act'(Y) * drop (QT_ACT_RELU, QT_ACT_TANH_RES with res / drop as in
  * qt_dense); gres (N, res_stride) or NULL receives the gradient of the residual operand (column 0 = gY[:, 0], rest 0).
  * gY2 (optional, laid out like gY): a second gradient of Y, added to gY on load (Y with two consumers: the decoder's output goes
  * to the loss and, re-meshed, into the next step's input, model/seq2seq.py:380-398). */

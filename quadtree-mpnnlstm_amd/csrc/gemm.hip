@@ -188,7 +188,8 @@ __global__ __launch_bounds__(256, (NT == 4 && CELL != 0) ? QT_GEMM_OCC4C : (NT =
             if (i >= rows || j >= g.NB || h2 * 64 + c4 >= BNT) continue;
             float4 v = *reinterpret_cast<const float4*>(&Cs[row * 64 + c4]);
             if (g.act == QT_ACT_RELU) {
-                v.x = fmaxf(v.x, 0.0f); v.y = fmaxf(v.y, 0.0f); v.z = fmaxf(v.z, 0.0f); v.w = fmaxf(v.w, 0.0f);
+                const float d = g.drop ? g.drop[i] : 1.0f;       // (x 1.0f is exact: the same bits without a mask)
+                v.x = fmaxf(d * v.x, 0.0f); v.y = fmaxf(d * v.y, 0.0f); v.z = fmaxf(d * v.z, 0.0f); v.w = fmaxf(d * v.w, 0.0f);
             }
             if (g.act == QT_ACT_TANH_RES) {
                 const float d = g.drop ? g.drop[i] : 1.0f, rs = g.res[i * g.res_stride];
@@ -257,7 +258,8 @@ __global__ __launch_bounds__(256) void k_gemm_skinny(GemmArgs g) {
     if (!ok && !post) return;
     float4 v = acc;
     if (g.act == QT_ACT_RELU) {
-        v.x = fmaxf(v.x, 0.0f); v.y = fmaxf(v.y, 0.0f); v.z = fmaxf(v.z, 0.0f); v.w = fmaxf(v.w, 0.0f);
+        const float d = (g.drop && ok) ? g.drop[row] : 1.0f;
+        v.x = fmaxf(d * v.x, 0.0f); v.y = fmaxf(d * v.y, 0.0f); v.z = fmaxf(d * v.z, 0.0f); v.w = fmaxf(d * v.w, 0.0f);
     }
     if (g.act == QT_ACT_RELU_BWD && ok) {          // G = v * relu'(Y): k_act_bwd's arithmetic, Y = g.res (M, res_stride)
         const float4 y = *reinterpret_cast<const float4*>(g.res + row * g.res_stride + j);
@@ -349,9 +351,10 @@ __global__ __launch_bounds__(64) void k_gemm_row16(GemmArgs g) {
     }
     if (!ok) return;
     if (g.act == QT_ACT_RELU) {
+        const float d = g.drop ? g.drop[row] : 1.0f;
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-            acc[c].x = fmaxf(acc[c].x, 0.0f); acc[c].y = fmaxf(acc[c].y, 0.0f); acc[c].z = fmaxf(acc[c].z, 0.0f); acc[c].w = fmaxf(acc[c].w, 0.0f);
+            acc[c].x = fmaxf(d * acc[c].x, 0.0f); acc[c].y = fmaxf(d * acc[c].y, 0.0f); acc[c].z = fmaxf(d * acc[c].z, 0.0f); acc[c].w = fmaxf(d * acc[c].w, 0.0f);
         }
     }
     if (g.act == QT_ACT_RELU_BWD) {
@@ -573,7 +576,8 @@ __global__ __launch_bounds__(256) void k_gemm_fwd3(GemmArgs g) {
             if (i >= rows || j >= g.NB) continue;
             float4 v = *reinterpret_cast<const float4*>(&Cs[row * 64 + c4]);
             if (g.act == QT_ACT_RELU) {
-                v.x = fmaxf(v.x, 0.0f); v.y = fmaxf(v.y, 0.0f); v.z = fmaxf(v.z, 0.0f); v.w = fmaxf(v.w, 0.0f);
+                const float d = g.drop ? g.drop[i] : 1.0f;       // (x 1.0f is exact: the same bits without a mask)
+                v.x = fmaxf(d * v.x, 0.0f); v.y = fmaxf(d * v.y, 0.0f); v.z = fmaxf(d * v.z, 0.0f); v.w = fmaxf(d * v.w, 0.0f);
             }
             if (g.act == QT_ACT_TANH_RES) {
                 const float d = g.drop ? g.drop[i] : 1.0f, rs = g.res[i * g.res_stride];

@@ -171,7 +171,7 @@ __global__ void k_act_bwd(const float* __restrict__ gY, const float* __restrict_
     const float g = gY2 ? gY[idx] + gY2[idx] : gY[idx], y = Y[idx];      // (gY2: the gradient of Y's second consumer, same layout)
     float o;
     if (act == QT_ACT_RELU) {
-        o = y > 0.0f ? g : 0.0f;
+        o = y > 0.0f ? g * (drop ? drop[row] : 1.0f) : 0.0f;
     } else {
         const float t = y - res[row * rs];
         o = g * (1.0f - t * t) * (drop ? drop[row] : 1.0f);

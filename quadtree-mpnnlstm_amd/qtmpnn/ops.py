@@ -579,7 +579,7 @@ class _ChebPoly(Function):
                                     ctx.needs_input_grad[10])
             Wb2, _ = _dgrad_weight(W2, 1, [Co], [0], ctx.acc2)               # (4, Co): W2[:Co]^T
             G = Y.new_empty(N, Co)
-            fuse = act == ACT_RELU and gY is None
+            fuse = act == ACT_RELU and gY is None and drop is None      # (the fused launches know no dropout mask: qt_act_bwd does)
             need = list(ctx.needs_input_grad[:nz])
             if _HEAD_DGRAD and fuse and N > 0 and all(need) and Co == 16:
                 # both backward products of the head in ONE launch, one lane per node row (qt_head_dgrad): G = relu'(Y) (gU Wb2)
