@@ -1,10 +1,11 @@
 // Verification of a rollout, computed where the rollout's outputs are: the per-lead-time sums of score()
 // (k_score_multi), the per-pixel maps of score_maps() (k_score_maps), the break-up / freeze-up dates of
 // event_dates() with the sums of their errors (k_event_scan, k_event_sums), the per-bin probability sums of
-// reliability() (k_reliability_multi) and the neighbourhood sums of fss() (k_fss_multi).  All of them read the head's node
-// values through every step's labels (no frame is built), none has a gradient, and the five rollout launchers share one
-// host-side setup (score_setup).  The training loss (k_sse*, k_pool_targets) is in transfer.hip.
+// reliability() (k_reliability_multi), the neighbourhood sums of fss() (k_fss_multi) and the ice-edge distances of
+// edge_distance() (k_edge_planes, k_edge_search).  All of them read the head's node values through every step's labels (no
+// frame is built), none has a gradient, and the six rollout launchers share one host-side setup (score_setup).  The training loss (k_sse*, k_pool_targets) is in transfer.hip.
 #include "qt_common.h"
+#include "../../include/qtmpnn_edges.h"
 
 namespace {
 
@@ -325,6 +326,230 @@ __global__ __launch_bounds__(256) void k_fss_multi(ScoreSeg sg, const float* __r
     }
 }
 
+// Ice-edge displacement of a rollout (edge_distance()): k_fss_multi's reads, sources and counting rule, but what is compared
+// is where the ice edge lies.  ice(x, p) = counted(p) && x[p] > thr (strict, fp32: NaN and -inf are not ice, +inf is); the edge
+// set E(x) holds the ice pixels with a 4-neighbour that is inside the frame, counted and not ice (frame borders and uncounted
+// pixels make no edge).  For each source f the eight integers of include/qtmpnn_edges.h are kept per (step, clip, band of 16 rows):
+// [|E(f)|, |E(y)|, sum q fo, sum q of, sum d2 fo, sum d2 of, max d2 fo, max d2 of], d2(p, E) = min over e of dr^2 + dc^2,
+// q = isqrt(65536 d2), `fo` over p in E(f) against E(y), `of` the reverse; a direction whose target set is empty gives 0.
+// The search is over the whole frame: no radius, no cap.
+//
+// Two launches.  Every query may reach any row of the frame, so a searching workgroup needs the whole frame's edge sets, while
+// building them costs a read of every field through the labels.  Building them inside the searching workgroup would repeat
+// those reads once per band of the frame (16 times at 256 rows); instead k_edge_planes reads every pixel once (plus one halo
+// row on either side of its band) and leaves the edge sets as bit-planes in a small global scratch -- one 64-bit word per 64
+// columns of a row, (S + 1) planes of n * ceil(m / 64) words per (step, clip): 32 KB for a 256 x 256 frame with three sources
+// -- and k_edge_search loads all of a (step, clip)'s planes into LDS and answers the queries of its band.  The second launch
+// follows the first in the stream; the scratch stays in L2.
+//
+// k_edge_planes: workgroup (band, clip, step).  The band's 16 rows and the row above and below are 18 * W (row, word) units, W =
+// ceil(m / 64) <= 4, dealt to the four waves in turn; lane l is column 64 j + l, and a ballot turns `counted` and every field's
+// ice into one word (lanes outside the frame are false, so rows and columns beyond it count as "no neighbour").  After a
+// barrier a thread forms an edge word of (row, word, field): with N = counted & ~ice, edge = ice & (N above | N below |
+// N << 1 | bit 63 of the word to the left | N >> 1 | bit 0 of the word to the right).
+//
+// k_edge_search: workgroup (band, clip, step), all planes in LDS (at most 4 * 1024 words).  For each source and direction the
+// queries are the set bits of the band's rows of one plane.  They are dealt to lanes densely: the band has 16 W <= 64 words,
+// lane l of every wave takes the popcount of word l and an inclusive scan over the wave gives every word its offset; wave w
+// then visits words w, w + 4, ... and the lanes whose bit is set store (row, column) into an LDS queue at offset + rank (rank =
+// popcount of the lower set bits).  After a barrier thread t answers entries t, t + 256, ...: no lane idles on a pixel that is no
+// query, and which lane answers which query does not matter to an integer sum.  A query at (r, c) walks the target plane's rows
+// r, r -+ 1, r -+ 2, ... and stops once dr^2 >= the best d2 so far or both rows are outside the frame; in a row the nearest set
+// bit is found per word with count-leading / trailing-zeros (the word holding c is split at c).  Lanes still diverge in how far
+// they walk; a wave is done when its farthest query is.
+// q: s = (uint64)sqrt((double)(d2 << 16)), then s is stepped down while s * s > x and up while (s + 1)^2 <= x in 64-bit
+// integers, so q is floor(sqrt(65536 d2)) whatever the estimate was.
+// Widths (frames of at most 256 x 256, which the launcher enforces): d2 <= 255^2 + 255^2 = 130050, q <= 92321.  A band has at most
+// 16 * 256 = 4096 queries per direction, so a thread's, a wave's and a band's sum q <= 4096 * 92321 = 378 146 816 and sum d2 <=
+// 4096 * 130050 = 532 684 800, both < 2^31: every partial is a non-negative int32.  A frame's total (16 bands) is not bounded so
+// and is the caller's to add in int64.  Reduction: 64-lane butterflies (add, or max for the two max slots), then the four waves.
+// Integers, no atomics: the same bits on every run, eager or replayed.
+constexpr int EDGE_BAND = 16, EDGE_MAX = 256;
+
+template <int S>
+__global__ __launch_bounds__(256) void k_edge_planes(ScoreSeg sg, const float* __restrict__ y, int64_t y_clip_stride,
+                                                     int64_t y_step_stride, ScoreBase b1, ScoreBase b2,
+                                                     const uint8_t* __restrict__ pix_mask, float thr, int n, int m, int W, int B,
+                                                     unsigned long long* __restrict__ planes) {
+    constexpr int NF = S + 1;                                  // fields: y, then the sources
+    __shared__ unsigned long long bits[EDGE_BAND + 2][4][NF + 1];       // [row][word][counted, ice of y, ice of each source]
+    const int b = blockIdx.y, z = blockIdx.z;
+    const int64_t P = (int64_t)n * m;
+    const float* out = sg.out[z];
+    const int32_t* labels = sg.labels[z] + (int64_t)b * P;
+    const int os = sg.out_stride[z];
+    const int rows = qt_rows(sg.n_dev[z], sg.N[z]);
+    const float* yz = y + z * y_step_stride + b * y_clip_stride;
+    const float* f1 = S > 1 ? b1.f + z * b1.step_stride + b * b1.clip_stride : nullptr;
+    const float* f2 = S > 2 ? b2.f + z * b2.step_stride + b * b2.clip_stride : nullptr;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int r0 = blockIdx.x * EDGE_BAND;
+    for (int u = w; u < (EDGE_BAND + 2) * W; u += 4) {
+        const int i = u / W, j = u - i * W;
+        const int gr = r0 - 1 + i, gc = j * 64 + lane;
+        bool counted = false, ice[NF];
+#pragma unroll
+        for (int f = 0; f < NF; ++f) ice[f] = false;
+        if (gr >= 0 && gr < n && gc < m) {
+            const int64_t p = (int64_t)gr * m + gc;
+            const int lab = labels[p];
+            counted = lab >= 0 && lab < rows && !(pix_mask && pix_mask[p]);
+            if (counted) {
+                ice[0] = yz[p] > thr;
+                ice[1] = out[(int64_t)lab * os] > thr;
+                if (S > 1) ice[2] = f1[p] > thr;
+                if (S > 2) ice[3] = f2[p] > thr;
+            }
+        }
+        const unsigned long long wc = __ballot(counted);
+        unsigned long long wi[NF];
+#pragma unroll
+        for (int f = 0; f < NF; ++f) wi[f] = __ballot(ice[f]);
+        if (lane == 0) {
+            bits[i][j][0] = wc;
+#pragma unroll
+            for (int f = 0; f < NF; ++f) bits[i][j][1 + f] = wi[f];
+        }
+    }
+    __syncthreads();
+    unsigned long long* dst = planes + ((int64_t)z * B + b) * NF * n * W;
+    for (int v = threadIdx.x; v < EDGE_BAND * W * NF; v += 256) {
+        const int f = v % NF, u = v / NF;
+        const int i = 1 + u / W, j = u % W;
+        const int gr = r0 + i - 1;
+        if (gr >= n) continue;
+        auto open = [&](int ii, int jj) { return bits[ii][jj][0] & ~bits[ii][jj][1 + f]; };       // counted and not ice
+        const unsigned long long here = open(i, j);
+        unsigned long long nb = open(i - 1, j) | open(i + 1, j) | (here << 1) | (here >> 1);
+        if (j > 0) nb |= open(i, j - 1) >> 63;
+        if (j + 1 < W) nb |= open(i, j + 1) << 63;
+        dst[((int64_t)f * n + gr) * W + j] = bits[i][j][1 + f] & nb;
+    }
+}
+
+// min |dc| to a set bit of a plane row (W words at `row`) from column c, or 1 << 20 if the row is empty
+__device__ __forceinline__ int edge_row_dist(const unsigned long long* row, int W, int c) {
+    const int wc = c >> 6, bit = c & 63;
+    int bd = 1 << 20;
+    for (int j = 0; j < W; ++j) {
+        const unsigned long long x = row[j];
+        if (!x) continue;
+        if (j < wc) bd = min(bd, c - (j * 64 + 63 - __builtin_clzll(x)));
+        else if (j > wc) bd = min(bd, j * 64 + __builtin_ctzll(x) - c);
+        else {
+            const unsigned long long lo = x & (~0ull >> (63 - bit)), hi = x & (~0ull << bit);
+            if (lo) bd = min(bd, bit - (63 - __builtin_clzll(lo)));
+            if (hi) bd = min(bd, __builtin_ctzll(hi) - bit);
+        }
+    }
+    return bd;
+}
+
+template <int S>
+__global__ __launch_bounds__(256) void k_edge_search(const unsigned long long* __restrict__ planes, int n, int W, int B,
+                                                     int32_t* __restrict__ partial) {
+    constexpr int NF = S + 1;
+    __shared__ unsigned long long pl[NF * 4 * EDGE_MAX];      // [field][row][word], n * W <= 4 * EDGE_MAX words each
+    __shared__ unsigned short queue[EDGE_BAND * EDGE_MAX];     // (local row << 8) | column
+    __shared__ int some[NF];                                   // the field's edge set is not empty
+    __shared__ int red[4][S * 8];
+    const int b = blockIdx.y, z = blockIdx.z;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int r0 = blockIdx.x * EDGE_BAND, nr = min(EDGE_BAND, n - r0);
+    const int words = n * W;
+    const unsigned long long* src = planes + ((int64_t)z * B + b) * NF * words;
+    if (threadIdx.x < NF) some[threadIdx.x] = 0;
+    __syncthreads();
+    for (int f = 0; f < NF; ++f) {
+        unsigned long long any = 0;
+        for (int v = threadIdx.x; v < words; v += 256) {
+            const unsigned long long x = src[f * words + v];
+            pl[f * words + v] = x;
+            any |= x;
+        }
+        if (any) some[f] = 1;                                  // every writer stores the same value
+    }
+    __syncthreads();
+    const int bw = nr * W;                                     // words of the band's rows of one plane, <= 64
+    for (int s = 0; s < S; ++s) {
+        int res[8];
+#pragma unroll
+        for (int dir = 0; dir < 2; ++dir) {
+            // dir 0 (fo): queries E(f_s), target E(y); dir 1 (of): queries E(y), target E(f_s)
+            const unsigned long long* qp = pl + (dir == 0 ? 1 + s : 0) * words + r0 * W;
+            const unsigned long long* tp = pl + (dir == 0 ? 0 : 1 + s) * words;
+            const bool target = some[dir == 0 ? 0 : 1 + s] != 0;
+            int cnt = lane < bw ? __popcll(qp[lane]) : 0, incl = cnt;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const int up = __shfl_up(incl, d, 64);
+                if (lane >= d) incl += up;
+            }
+            const int total = __shfl(incl, 63, 64);
+            res[dir] = total;                                  // |E(f_s)|, |E(y)| of the band
+            int sq = 0, sd = 0, mx = 0;
+            if (target && total) {                             // uniform over the workgroup
+                for (int u = w; u < bw; u += 4) {
+                    const int base = __shfl(incl - cnt, u, 64);
+                    const unsigned long long x = qp[u];
+                    if ((x >> lane) & 1) {
+                        const int rank = __popcll(x & ((1ull << lane) - 1));
+                        queue[base + rank] = (unsigned short)(((u / W) << 8) | ((u % W) * 64 + lane));
+                    }
+                }
+                __syncthreads();
+                for (int e = threadIdx.x; e < total; e += 256) {
+                    const int r = r0 + (queue[e] >> 8), c = queue[e] & 255;
+                    int best = 0x7fffffff;
+                    for (int k = 0; k < n; ++k) {
+                        const int k2 = k * k;
+                        if (k2 >= best) break;
+                        const int lo = r - k, hi = r + k;
+                        if (lo < 0 && hi >= n) break;
+                        if (lo >= 0) {
+                            const int d = edge_row_dist(tp + lo * W, W, c);
+                            if (d < (1 << 20)) best = min(best, k2 + d * d);
+                        }
+                        if (k > 0 && hi < n) {
+                            const int d = edge_row_dist(tp + hi * W, W, c);
+                            if (d < (1 << 20)) best = min(best, k2 + d * d);
+                        }
+                    }
+                    const unsigned long long x = (unsigned long long)best << 16;
+                    unsigned long long q = (unsigned long long)sqrt((double)x);
+                    while (q * q > x) --q;
+                    while ((q + 1) * (q + 1) <= x) ++q;
+                    sq += (int)q;
+                    sd += best;
+                    mx = max(mx, best);
+                }
+                __syncthreads();                               // the queue is rewritten by the next direction
+            }
+#pragma unroll
+            for (int d = 32; d >= 1; d >>= 1) {
+                sq += __shfl_xor(sq, d, 64);
+                sd += __shfl_xor(sd, d, 64);
+                mx = max(mx, __shfl_xor(mx, d, 64));
+            }
+            res[2 + dir] = sq;
+            res[4 + dir] = sd;
+            res[6 + dir] = mx;
+        }
+        if (lane == 0) {
+#pragma unroll
+            for (int v = 0; v < 8; ++v) red[w][s * 8 + v] = res[v];
+        }
+    }
+    __syncthreads();
+    int32_t* dst = partial + (((int64_t)z * B + b) * gridDim.x + blockIdx.x) * (S * 8);
+    if (threadIdx.x < S * 8) {
+        const int v = threadIdx.x, slot = v & 7;
+        if (slot < 2) dst[v] = red[0][v];                      // every wave counted the whole band
+        else if (slot < 6) dst[v] = (red[0][v] + red[1][v]) + (red[2][v] + red[3][v]);
+        else dst[v] = max(max(red[0][v], red[1][v]), max(red[2][v], red[3][v]));
+    }
+}
+
 // Per-pixel verification sums: k_score_multi's reads and counting rule, kept per pixel and summed over the clips instead of
 // per clip and summed over the pixels.  One thread owns pixel p of step z and is the only writer of its 8 * S running doubles
 // (maps + z * maps_step_stride, laid out (S, 8, P)): it loads the three sums of every source, adds the clips' terms to them
@@ -503,7 +728,7 @@ __global__ __launch_bounds__(256) void k_event_sums(const int32_t* __restrict__ 
     }
 }
 
-// What the five rollout launchers have in common: the segment arrays of 1..16 steps into `sg`, and the dense baseline fields
+// What the six rollout launchers have in common: the segment arrays of 1..16 steps into `sg`, and the dense baseline fields
 // that are present, in order, into `bs` (`nb` of them: the kernels are instantiated per source count).  Returns the reason of a
 // refusal, or null; the entry reports it under its own name (QT_ARG).
 struct ScoreSetup {
@@ -609,7 +834,33 @@ extern "C" int qt_fss_rollout(int nseg, const float* const* outs, const int* out
     return QT_OK;
 }
 
-extern "C" int qt_score_maps(int nseg, const float* const* outs, const int* out_strides, const int32_t* const* labels,
+extern "C" int qt_edge_rollout(int nseg, const float* const* outs, const int* out_strides, const int32_t* const* labels,
+                               const int* Ns, const int32_t* const* n_devs, const float* y, int64_t y_clip_stride,
+                               int64_t y_step_stride, const float* base1, int64_t base1_clip_stride, int64_t base1_step_stride,
+                               const float* base2, int64_t base2_clip_stride, int64_t base2_step_stride,
+                               const uint8_t* pix_mask, float thr, int B, int n, int m, uint64_t* planes, int32_t* partial,
+                               void* stream) {
+    ScoreSetup st;
+    const char* why = score_setup(st, nseg, outs, out_strides, labels, Ns, n_devs, y, y_clip_stride, y_step_stride,
+                                  {base1, base1_clip_stride, base1_step_stride}, {base2, base2_clip_stride, base2_step_stride});
+    QT_ARG(!why, why);
+    QT_ARG(planes && partial, "null planes / partial");
+    QT_ARG(B > 0 && B <= 65535 && n > 0 && m > 0, "bad sizes");
+    // k_edge_search holds a (step, clip)'s planes in LDS and packs a query into 16 bits; its int32 sums are proved for this size
+    QT_ARG(n <= EDGE_MAX && m <= EDGE_MAX, "frame larger than 256 x 256");
+    const int W = qt_cdiv(m, 64);
+    const dim3 grid(qt_cdiv(n, EDGE_BAND), B, nseg);
+    auto kp = st.nb == 0 ? k_edge_planes<1> : st.nb == 1 ? k_edge_planes<2> : k_edge_planes<3>;
+    auto ks = st.nb == 0 ? k_edge_search<1> : st.nb == 1 ? k_edge_search<2> : k_edge_search<3>;
+    hipLaunchKernelGGL(kp, grid, dim3(256), 0, (hipStream_t)stream, st.sg, y, y_clip_stride, y_step_stride, st.bs[0], st.bs[1],
+                       pix_mask, thr, n, m, W, B, (unsigned long long*)planes);
+    QT_LAUNCHED();
+    hipLaunchKernelGGL(ks, grid, dim3(256), 0, (hipStream_t)stream, (const unsigned long long*)planes, n, W, B, partial);
+    QT_LAUNCHED();
+    return QT_OK;
+}
+
+extern "C" int qt_score_maps(int nseg,const float* const* outs, const int* out_strides, const int32_t* const* labels,
                              const int* Ns, const int32_t* const* n_devs, const float* y, int64_t y_clip_stride,
                              int64_t y_step_stride, const float* base1, int64_t base1_clip_stride, int64_t base1_step_stride,
                              const float* base2, int64_t base2_clip_stride, int64_t base2_step_stride,

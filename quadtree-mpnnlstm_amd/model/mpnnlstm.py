@@ -206,6 +206,14 @@ def fss_product(threshold, scales):
     return reduce
 
 
+def edge_product(threshold):
+    """Ice-edge distance sums: the (T_out, B, S, 8) int64 sums of model, persistence and (with concat) climatology
+    (ops.rollout_edges)."""
+    def reduce(y_hat, meshes, x, y, concat):
+        return ops.rollout_edges(y_hat, meshes, y, threshold, persistence=launch_frame(x), climatology=concat)
+    return reduce
+
+
 def events_product(threshold, kind, persist):
     """Event buffer: int32, the int64 sums (B, S1 - 1, 8) followed by the dates (B, S1, P) (split_event_buffer)."""
     def reduce(y_hat, meshes, x, y, concat):
@@ -643,6 +651,15 @@ class NextFramePredictorS2S(NextFramePredictor):
                                      high_interest_region=high_interest_region, graph_structure=graph_structure)
 
     @on_device(lambda self, *a, **k: self.device)
+    def make_graphed_edges(self, x, y, concat_layers=None, mask=None, high_interest_region=None, graph_structure=None,
+                           threshold=0.15):
+        """make_graphed_scores with the ice-edge distance sums in place of the verification sums: the capture holds the rollout
+        and ops.rollout_edges (sources as make_graphed_scores), no frame gather.  Returns `edges(x, y, concat) -> (T_out, B, S,
+        8)` int64 device tensor; `edges.warmup` is the given batch's."""
+        return self._graphed_product(edge_product(threshold), x, y, concat_layers, mask=mask,
+                                     high_interest_region=high_interest_region, graph_structure=graph_structure)
+
+    @on_device(lambda self, *a, **k: self.device)
     def make_graphed_events(self, x, y, concat_layers=None, mask=None, high_interest_region=None, graph_structure=None,
                             threshold=0.15, kind='breakup', persist=5):
         """make_graphed_scores with the event dates in place of the verification sums: the capture holds the rollout, the
@@ -774,7 +791,7 @@ class NextFramePredictorS2S(NextFramePredictor):
         return np.stack(preds, 0)
 
     def _inference(self, loader, climatology, product, consume, use_graph, reads_y=True, begin=None, **fwd):
-        """The inference loop of predict, score, score_maps, reliability, fss and event_dates: per batch begin(x), if given, then one no-grad
+        """The inference loop of predict, score, score_maps, reliability, fss, edge_distance and event_dates: per batch begin(x), if given, then one no-grad
         rollout (teacher forcing 0, forward arguments `fwd`) reduced by a reduce(y_hat, meshes, x, y, concat), see frames_product,
         whose result goes to consume(result, x); x is the clipped batch.  product(x) makes the reduce: for every batch of an eager
         call, for every capture of a graphed one, so it must not do what every batch needs (that is begin's).  use_graph: each
@@ -914,6 +931,27 @@ class NextFramePredictorS2S(NextFramePredictor):
                         lambda part, x: sums.append(np.moveaxis(part.cpu().numpy(), 0, 1)),  # (T, B, S, K, 5) -> (B, T, S, K, 5)
                         use_graph, mask=mask, high_interest_region=high_interest_region, graph_structure=graph_structure)
         return FSS(np.concatenate(sums, 0), sources, threshold, scales)
+
+    @on_device(lambda self, *a, **k: self.device)
+    def edge_distance(self, loader, climatology=None, mask=None, high_interest_region=None, graph_structure=None, use_graph=False,
+                      threshold=0.15):
+        """Ice-edge verification over a loader -> qtmpnn.edges.EdgeDistance (beyond the reference): how far, in pixels, the
+        forecast ice edge lies from the observed one, per launch date, lead time and source -- the average ice-edge displacement,
+        the modified Hausdorff and Hausdorff distances (Dukhovskoy et al. 2015, Melsom et al. 2019) and the RMS distance.  The
+        edge of a field is its ice pixels (`value > threshold`, strict) with an open-water 4-neighbour; coasts, masked pixels and
+        the frame border make no edge.  Frames of at most 256 x 256.
+
+        score()'s loop, arguments and sources: every batch leaves eight integers per (lead time, clip, source) on the device
+        (ops.rollout_edges: the head's outputs read through the labels, no frame is built) and makes one host copy of them.
+        use_graph=True replays rollout + sums as one hipGraph per distinct batch shape (make_graphed_edges)."""
+        from qtmpnn.edges import EdgeDistance
+        sources = ('model', 'persistence') + (('climatology',) if climatology is not None else ())
+        sums = []
+        reduce = edge_product(threshold)
+        self._inference(loader, climatology, lambda x: reduce,
+                        lambda part, x: sums.append(np.moveaxis(part.cpu().numpy(), 0, 1)),  # (T, B, S, 8) -> (B, T, S, 8)
+                        use_graph, mask=mask, high_interest_region=high_interest_region, graph_structure=graph_structure)
+        return EdgeDistance(np.concatenate(sums, 0), sources, threshold)
 
     @on_device(lambda self, *a, **k: self.device)
     def event_dates(self, loader, climatology=None, mask=None, high_interest_region=None, graph_structure=None, use_graph=False,

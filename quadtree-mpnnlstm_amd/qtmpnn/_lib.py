@@ -1,4 +1,4 @@
-"""ctypes binding of libqtmpnn_hip.so (the C ABI declared in include/qtmpnn.h).
+"""ctypes binding of libqtmpnn_hip.so (the C ABI declared in include/qtmpnn.h and include/qtmpnn_edges.h).
 
 The product path has no CPU fallback: if the shared library is missing or a call
 fails, an exception is raised.
@@ -105,6 +105,11 @@ _SIGNATURES = {
     'qt_mhattn_bwd_merge': [_P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _I, _P],
     'qt_attn_weights': [_P, _P, _P, _P, _P, _I, _L, _L, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P],
 }
+# The entries of include/qtmpnn_edges.h.  The table above mirrors include/qtmpnn.h name for name, and the tests hold both to the 87
+# entry points README.md counts (exported_names()); an entry declared beside that header is bound beside that table.
+_EDGE_SIGNATURES = {
+    'qt_edge_rollout': [_I, _P, _P, _P, _P, _P, _P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _F, _I, _I, _I, _P, _P, _P],
+}
 _PLAIN = {'qt_proj_bwd_blocks', 'qt_abi_version', 'qt_cheb_clip_rows', 'qt_cheb_tile_sync_words', 'qt_cheb_tile_xbuf_words', 'qt_tile_cap', 'qt_remesh_clip_rows', 'qt_tail_cap', 'qt_num_cus', 'qt_lstm_fused_blocks', 'qt_wgrad_blocks', 'qt_lstm_bwd_blocks', 'qt_lstm_dgrad_blocks', 'qt_attn_blocks', 'qt_mhattn_blocks'}  # return a value, not an error code
 
 _lib = None
@@ -120,7 +125,7 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
         lib.qt_last_error.restype = ctypes.c_char_p
         lib.qt_last_error.argtypes = []
-        for name, args in _SIGNATURES.items():
+        for name, args in {**_SIGNATURES, **_EDGE_SIGNATURES}.items():
             fn = getattr(lib, name)
             fn.argtypes = args
             fn.restype = ctypes.c_int

@@ -2241,6 +2241,32 @@ def rollout_fss(outputs, meshes, y, threshold=0.15, scales=(1, 3, 5, 9, 17, 33),
     return part if per_tile else part.sum(2, dtype=torch.int64)
 
 
+EDGE_MAX = 256      # largest frame side of rollout_edges (qt_edge_rollout keeps a frame's edge bit-planes in LDS)
+
+
+def rollout_edges(outputs, meshes, y, threshold=0.15, persistence=None, climatology=None, per_tile=False):
+    """Ice-edge distance sums of a rollout, int64 (T, B, S, 8) on the device (qt_edge_rollout; definitions and slot table in
+    include/qtmpnn_edges.h): per output step, clip and source [n_f, n_o, sum_q_fo, sum_q_of, sum_d2_fo, sum_d2_of, max_d2_fo,
+    max_d2_of].  The edge set E(x) of a field holds the counted pixels with x > threshold (strict) that have a 4-neighbour inside
+    the frame, counted and not ice; n_f = |E(forecast)|, n_o = |E(y)|; d2 is the squared pixel distance to the nearest pixel of
+    the other set over the whole frame and q = isqrt(65536 d2); `fo` runs over E(forecast) against E(y), `of` the reverse, and a
+    direction whose target set is empty gives 0.  Operands, sources and counting rule are rollout_scores'.  Frames of at most
+    256 x 256.  No autograd, no host read: capturable.  per_tile=True returns the launch's own int32 partials (T, B,
+    ceil(n/16), S, 8), one per band of 16 rows, instead of their int64 totals (slots 0-5 added, slots 6-7 maximised)."""
+    who = 'rollout_edges'
+    outs, y, bases, S, B, T, P = _score_args(who, outputs, meshes, y, persistence, climatology)
+    n, m = meshes[0].n, meshes[0].m
+    if n > EDGE_MAX or m > EDGE_MAX:
+        raise ValueError(f'{who}: a frame of {n} x {m} pixels is larger than {EDGE_MAX} x {EDGE_MAX}, the largest the edge search takes')
+    part = torch.empty(T, B, -(n // -16), S, 8, dtype=torch.int32, device=outs[0].device)
+    # the edge bit-planes of one launch (up to 16 steps), written and read by it; the next launch follows in the stream
+    planes = torch.empty(min(T, 16) * B * (S + 1) * n * -(m // -64), dtype=torch.int64, device=outs[0].device)
+    _score_chunks('qt_edge_rollout', outs, meshes, y, bases, threshold, B, T, P, lambda z0: (ptr(planes), ptr(part[z0:])))
+    if per_tile:
+        return part
+    return torch.cat([part[..., :6].sum(2, dtype=torch.int64), part[..., 6:].amax(2).to(torch.int64)], dim=-1)
+
+
 def rollout_score_maps(outputs, meshes, y, maps, threshold=0.15, persistence=None, climatology=None):
     """rollout_scores' eight sums kept per pixel and summed over the clips: `maps`, a float64 (T, S, 8, P) tensor on the
     outputs' device, is accumulated in place (qt_score_maps) and returned.  Operands, sources, counting rule and classes are
