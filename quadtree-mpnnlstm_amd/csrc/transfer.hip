@@ -8,7 +8,9 @@
 // builds the 2x2 / 4x4 sums in registers; 8x8 .. 64x64 sums go through a small LDS
 // pyramid.  A quadtree leaf of level L is exactly one level-L pyramid entry, so every
 // node value is written once, in a fixed order, with no atomics.
+#include <cfloat>
 #include "qt_common.h"
+#include "../../include/qtmpnn_loss.h"
 
 namespace {
 
@@ -636,6 +638,59 @@ __global__ void k_bce_bwd_multi(LossSeg sg, const float* __restrict__ g, int W) 
     sg.gout[z][idx] = v;
 }
 
+// k_bce_multi with a weight per pixel and per step and a weight pw on the positive class: partial = - sum of
+// lam[z] w[p] (pw y max(log o, -100) + (1 - y) max(log(1 - o), -100)), same grid and reduction order, the logarithms and the clamp
+// as there.  pw multiplies y before the logarithm does, so a power of two in w or lam scales every partial sum exactly.
+__global__ __launch_bounds__(256) void k_wbce_multi(LossSeg sg, const float* __restrict__ y, int64_t y_clip_stride,
+                                                    int64_t y_step_stride, const float* __restrict__ w,
+                                                    const float* __restrict__ lam, float pw, int64_t P, int B,
+                                                    float* __restrict__ partial) {
+    __shared__ float red[4];
+    const int b = blockIdx.y, z = blockIdx.z;
+    const float* out = sg.out[z];
+    const int32_t* labels = sg.labels[z];
+    const int os = sg.out_stride[z];
+    const float* yz = y + z * y_step_stride + b * y_clip_stride;
+    const float lz = lam[z];
+    float acc = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int64_t p = (int64_t)blockIdx.x * 1024 + k * 256 + threadIdx.x;
+        if (p < P) {
+            const int lab = labels[b * P + p];
+            if (lab >= 0) {
+                const float o = out[(int64_t)lab * os], t = yz[p];
+                const float l1 = fmaxf(logf(o), -100.0f), l0 = fmaxf(log1pf(-o), -100.0f);
+                acc -= lz * (w[p] * ((pw * t) * l1 + (1.0f - t) * l0));
+            }
+        }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0)
+        partial[((int64_t)z * B + b) * gridDim.x + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// gradient rows of the weighted binary cross-entropy: the per-pixel (o - y (pw + o (1 - pw))) / max(o (1 - o), 1e-12) times
+// lam w_p, summed over the node's pixels (linear in y: sg.sy[z] holds the (N, 2) rows [sum w | sum w y] of k_pool_wtargets).  The
+// factor pw + o (1 - pw) is taken as o + pw (1 - o), a sum of two non-negative terms: the first form cancels for a large pw.
+__global__ void k_wbce_bwd_multi(LossSeg sg, const float* __restrict__ g, const float* __restrict__ lam, float pw, int W) {
+    const int z = blockIdx.y;
+    const unsigned idx = blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = idx / (unsigned)W;
+    if (i >= qt_rows(sg.n_dev[z], sg.N[z])) return;
+    float v = 0.0f;
+    if ((idx - (unsigned)i * (unsigned)W) == 0) {
+        const float o = sg.out[z][i * sg.out_stride[z]];
+        const float* sw = sg.sy[z];
+        const float q = 1.0f - o;
+        v = g[0] * lam[z] * (o * sw[2 * i] - sw[2 * i + 1] * (o + pw * q)) / fmaxf(o * q, 1e-12f);
+    }
+    sg.gout[z][idx] = v;
+}
+
 __global__ void k_sse_bwd_multi(LossSeg sg, const float* __restrict__ g, int W) {
     const int z = blockIdx.y;
     const unsigned idx = blockIdx.x * blockDim.x + threadIdx.x;
@@ -794,6 +849,54 @@ extern "C" int qt_wsse_rollout_bwd(int nseg, const float* const* outs, const int
     QT_ARG((int64_t)nmax * W + 256 < ((int64_t)1 << 31), "N * W too large for 32-bit thread indices");
     if (nmax <= 0) return QT_OK;
     hipLaunchKernelGGL(k_wsse_bwd_multi, dim3(qt_cdiv((int64_t)nmax * W, 256), nseg), dim3(256), 0, (hipStream_t)stream, sg, g, lam, W);
+    QT_LAUNCHED();
+    return QT_OK;
+}
+
+extern "C" int qt_wbce_rollout(int nseg, const float* const* outs, const int* out_strides, const int32_t* const* labels,
+                               const uint8_t* const* levels, const int* Ns, float* const* swys, const float* y,
+                               int64_t y_clip_stride, int64_t y_step_stride, const float* w, const float* lam, int B, int n, int m,
+                               float* partial, float pos_weight, void* stream) {
+    QT_ARG(nseg >= 1 && nseg <= 16 && outs && out_strides && labels && levels && Ns && swys && y && partial && B > 0, "bad arguments");
+    QT_ARG(w && lam, "null weights: w (n*m) and lam (nseg) are device arrays");
+    QT_ARG(pos_weight > 0.0f && pos_weight <= FLT_MAX, "pos_weight must be finite and > 0");
+    QT_ARG(n > 0 && m > 0 && y_clip_stride >= 0 && y_step_stride >= 0, "bad sizes");
+    LossSeg sg = {};
+    for (int z = 0; z < nseg; ++z) {
+        QT_ARG(outs[z] && labels[z] && levels[z] && swys[z] && out_strides[z] >= 1 && Ns[z] >= 0, "null segment pointer");
+        sg.out[z] = outs[z]; sg.out_stride[z] = out_strides[z]; sg.labels[z] = labels[z]; sg.level[z] = levels[z];
+        sg.N[z] = Ns[z]; sg.sy[z] = swys[z];
+    }
+    const int64_t P = (int64_t)n * m;
+    hipLaunchKernelGGL(k_wbce_multi, dim3(qt_cdiv(P, 1024), B, nseg), dim3(256), 0, (hipStream_t)stream, sg, y, y_clip_stride,
+                       y_step_stride, w, lam, pos_weight, P, B, partial);
+    QT_LAUNCHED();
+    PoolArgs a = {};
+    a.img = y; a.S = 1; a.img_clip_stride = y_clip_stride; a.C = 2; a.mean = 0; a.B = B; a.n = n; a.m = m;
+    a.out_stride = 2; a.out_coff = 0; a.tiles_r = qt_cdiv(n, 64); a.tiles_c = qt_cdiv(m, 64);
+    hipLaunchKernelGGL(k_pool_wtargets, dim3(B * a.tiles_r * a.tiles_c, 1, nseg), dim3(256), 0, (hipStream_t)stream, a, sg,
+                       y_step_stride, w);
+    QT_LAUNCHED();
+    return QT_OK;
+}
+
+extern "C" int qt_wbce_rollout_bwd(int nseg, const float* const* outs, const int* out_strides, const float* const* swys,
+                                   const int* Ns, const int32_t* const* n_devs, const float* g, const float* lam, int W,
+                                   float* const* gouts, float pos_weight, void* stream) {
+    QT_ARG(nseg >= 1 && nseg <= 16 && outs && out_strides && swys && Ns && n_devs && g && lam && gouts && W >= 1, "bad arguments");
+    QT_ARG(pos_weight > 0.0f && pos_weight <= FLT_MAX, "pos_weight must be finite and > 0");
+    LossSeg sg = {};
+    int nmax = 0;
+    for (int z = 0; z < nseg; ++z) {
+        QT_ARG(outs[z] && swys[z] && gouts[z] && out_strides[z] >= 1, "null segment pointer");
+        sg.out[z] = outs[z]; sg.out_stride[z] = out_strides[z]; sg.sy[z] = (float*)swys[z];
+        sg.N[z] = Ns[z]; sg.n_dev[z] = n_devs[z]; sg.gout[z] = gouts[z];
+        nmax = Ns[z] > nmax ? Ns[z] : nmax;
+    }
+    QT_ARG((int64_t)nmax * W + 256 < ((int64_t)1 << 31), "N * W too large for 32-bit thread indices");
+    if (nmax <= 0) return QT_OK;
+    hipLaunchKernelGGL(k_wbce_bwd_multi, dim3(qt_cdiv((int64_t)nmax * W, 256), nseg), dim3(256), 0, (hipStream_t)stream, sg, g, lam,
+                       pos_weight, W);
     QT_LAUNCHED();
     return QT_OK;
 }

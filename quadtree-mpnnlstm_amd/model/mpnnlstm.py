@@ -42,10 +42,13 @@ class LossWeights:
     `lead_weights` (T_out,), non-negative weights of the output steps (None: ones).  Everything is checked here, on the host and
     before any launch -- shape, finite, non-negative, a positive sum (of the pixel weights over the pixels `mask` leaves) -- and
     each refusal is a ValueError that names the argument.  The sums of the divisor are float64 sums of the float32 values the
-    kernels read.  to(device) uploads the two arrays once; chunk(steps) is the view of a truncated-BPTT chunk."""
+    kernels read.  to(device) uploads the two arrays once; chunk(steps) is the view of a truncated-BPTT chunk.
+    `pos_weight` (binary predictors only; None: 1) is the positive-class weight of masked_bce, carried beside the two arrays so
+    that one object holds everything a trainer method was given; it is checked like them and does not enter the divisor."""
 
-    def __init__(self, weights, lead_weights, shape, T_out, mask=None):
+    def __init__(self, weights, lead_weights, shape, T_out, mask=None, pos_weight=None):
         shape, self.T = tuple(int(v) for v in shape), int(T_out)
+        self.pos_weight = 1.0 if pos_weight is None else ops.check_pos_weight(pos_weight)
         mask = host_mask(mask)
         if mask is not None and tuple(mask.shape) != shape:
             raise ValueError(f'mask: shape {tuple(mask.shape)} for frames of {shape}')
@@ -99,14 +102,34 @@ def loss_weights_of(weights, lead_weights, shape, T_out, mask=None, binary=False
     if weights is None and lead_weights is None:
         return None
     if binary:
-        raise ValueError('loss_weights / lead_weights: the weighted loss is the squared error; binary=True (BCE) takes no weights')
+        raise ValueError('loss_weights / lead_weights: the weighted loss of masked_mse is the squared error; binary=True (BCE) takes '
+                         'no weights here: the weighted binary cross-entropy is masked_bce')
+    return _checked_weights(weights, lead_weights, shape, T_out, mask)
+
+
+def _checked_weights(weights, lead_weights, shape, T_out, mask=None, pos_weight=None):
+    """A LossWeights as it is (held to the frame shape and step count; with pos_weight given, a copy that carries it), else the
+    checked weights, a missing array being ones."""
     if isinstance(weights, LossWeights):
         if lead_weights is not None:
             raise ValueError('lead_weights: already part of the LossWeights passed as the pixel weights')
         if weights.shape != tuple(shape) or weights.T != T_out:
             raise ValueError(f'loss_weights: prepared for {weights.T} steps of {weights.shape} frames, not {T_out} of {tuple(shape)}')
+        if pos_weight is not None:
+            pos_weight, lw = ops.check_pos_weight(pos_weight), weights
+            weights = object.__new__(LossWeights)
+            weights.__dict__.update(lw.__dict__)
+            weights.pos_weight = pos_weight
         return weights
-    return LossWeights(weights, lead_weights, shape, T_out, mask)
+    return LossWeights(weights, lead_weights, shape, T_out, mask, pos_weight)
+
+
+def bce_weights_of(weights, lead_weights, pos_weight, shape, T_out, mask=None):
+    """The loss of a binary=True predictor: None when no weight of any kind is given (the unweighted BCE paths, untouched), else the
+    checked LossWeights of masked_bce with its pos_weight (a missing array is ones, a missing pos_weight 1)."""
+    if weights is None and lead_weights is None and pos_weight is None:
+        return None
+    return _checked_weights(weights, lead_weights, shape, T_out, mask, pos_weight)
 
 
 def masked_mse(outputs, meshes, y, mask=None, binary=False, weights=None, lead_weights=None, fused=False):
@@ -158,6 +181,36 @@ def masked_mse(outputs, meshes, y, mask=None, binary=False, weights=None, lead_w
     if part is None:
         part = torch.cat([ops.step_sse_partials(out, y[:, t], mesh) for t, (out, mesh) in enumerate(zip(outputs, meshes))])
     return part.sum() / float(mesh0.B * len(outputs) * n_valid)        # one reduction for all steps
+
+
+def masked_bce(outputs, meshes, y, mask=None, weights=None, lead_weights=None, pos_weight=1.0):
+    """The weighted binary cross-entropy of a binary=True rollout (beyond the reference): over the pixels masked_mse counts,
+
+        term(b, t, p) = -(pos_weight y L1 + (1 - y) L0),  L1 = max(log o, -100),  L0 = max(log(1 - o), -100)   (torch's clamp)
+        loss          = sum lam_t w_p term / (B sum_t lam_t sum_{p unmasked} w_p)
+
+    weights (W, H) >= 0 and lead_weights (T_out,) >= 0 as in masked_mse (a missing one is ones; or one LossWeights as `weights`),
+    the divisor formed on the host in float64; pos_weight, one finite number > 0, weighs the y = 1 side and does not enter the
+    divisor (the convention of torch's BCEWithLogitsLoss(pos_weight=)).  Unit weights and pos_weight = 1 are
+    masked_mse(binary=True, fused=True).  Always the rollout launches (ops.rollout_wbce_partials; ops.step_wbce_partials for
+    loss_mask meshes and odd layouts): no frames, no host read, capturable, the same bits on every run.  Every refusal is a
+    ValueError that names the argument, before any launch."""
+    if y.dim() == 4:
+        y = y.unsqueeze(0)
+    mesh0 = meshes[0]
+    want = (mesh0.B, len(outputs), mesh0.n, mesh0.m, 1)
+    if tuple(y.shape) != want:      # (the loss kernels read B x P targets per step straight from this buffer)
+        raise ValueError(f'targets of shape {tuple(y.shape)} for {mesh0.B} clip(s) x {len(outputs)} output steps of {mesh0.n} x {mesh0.m} '
+                         f'frames: expected (T_out, W, H, 1) or (B, T_out, W, H, 1) = {want}')
+    lw = _checked_weights(weights, lead_weights, (mesh0.n, mesh0.m), len(outputs), mask)
+    pos_weight = ops.check_pos_weight(pos_weight)
+    y = y.to(outputs[0].device)
+    lw.to(y.device)
+    part = ops.rollout_wbce_partials(outputs, y, meshes, lw.w, lw.lam, pos_weight) if y.shape[1] == len(outputs) else None
+    if part is None:        # loss_mask meshes, odd layouts: step by step, composed (ops.step_wbce_partials)
+        part = torch.cat([ops.step_wbce_partials(out, y[:, t], mesh, lw.w, lw.lam[t], pos_weight)
+                          for t, (out, mesh) in enumerate(zip(outputs, meshes))])
+    return part.sum() / float(mesh0.B * lw.sum_lam * lw.sum_w)
 
 
 def launch_frame(x):
@@ -316,22 +369,36 @@ class NextFramePredictorS2S(NextFramePredictor):
 
     # -- the measured unit -----------------------------------------------------------
     def forward_loss(self, x, y, concat_layers=None, mask=None, high_interest_region=None, graph_structure=None,
-                     fused=False, loss_weights=None, lead_weights=None):
+                     fused=False, pos_weight=None, loss_weights=None, lead_weights=None):
         """loss_weights (W, H) / lead_weights (T_out,): the weighted loss of masked_mse (checked before the rollout starts).
-        fused=True (binary predictors only): the fused binary cross-entropy of masked_mse."""
+        fused=True (binary predictors only): the fused binary cross-entropy of masked_mse.  On a binary=True predictor any of
+        loss_weights / lead_weights / pos_weight (the positive-class weight) selects masked_bce, which is always fused."""
         if fused and not self.binary:
             raise ValueError('fused: fused=True selects the fused binary cross-entropy and needs a binary=True predictor')
-        lw = self._loss_weights(x, mask, loss_weights, lead_weights)
+        lw = self._loss_weights(x, mask, loss_weights, lead_weights, pos_weight)
         y_hat, meshes = self.model(x, y, concat_layers, teacher_forcing_ratio=0, mask=mask,
                                    high_interest_region=high_interest_region, graph_structure=graph_structure)
         if lw is None:
             return masked_mse(y_hat, meshes, y, mask, self.binary, fused=fused)
-        return masked_mse(y_hat, meshes, y, mask, self.binary, weights=lw)
+        return self._weighted_loss(y_hat, meshes, y, mask, lw)
 
-    def _loss_weights(self, x, mask, loss_weights, lead_weights):
-        """The checked, uploaded weights of this predictor's loss for batches shaped like x (None: unweighted)."""
-        lw = loss_weights_of(loss_weights, lead_weights, tuple(x.shape[-3:-1]), self.output_timesteps, mask, self.binary)
-        return lw if lw is None else lw.to(self.device if self.device is not None else x.device)
+    def _loss_weights(self, x, mask, loss_weights, lead_weights, pos_weight=None, shape=None):
+        """The checked, uploaded weights of this predictor's loss for batches shaped like x, or of frames of `shape` (None:
+        unweighted).  A binary=True predictor takes pos_weight beside them (masked_bce); any other refuses it by name."""
+        shape = tuple(x.shape[-3:-1]) if shape is None else tuple(shape)
+        if self.binary:
+            lw = bce_weights_of(loss_weights, lead_weights, pos_weight, shape, self.output_timesteps, mask)
+        elif pos_weight is not None:
+            raise ValueError('pos_weight: the positive-class weight belongs to the binary cross-entropy and needs a binary=True predictor')
+        else:
+            lw = loss_weights_of(loss_weights, lead_weights, shape, self.output_timesteps, mask)
+        return lw if lw is None else lw.to(self.device if self.device is not None else ('cpu' if x is None else x.device))
+
+    def _weighted_loss(self, y_hat, meshes, y, mask, lw):
+        """The weighted loss of this predictor's head: masked_bce on a binary=True one, else masked_mse."""
+        if self.binary:
+            return masked_bce(y_hat, meshes, y, mask, weights=lw, pos_weight=lw.pos_weight)
+        return masked_mse(y_hat, meshes, y, mask, weights=lw)
 
     def zero_grad(self):
         """Drop all gradients (set to None, like optimizer.zero_grad(set_to_none=True) on the reference's per-tensor optimizer)."""
@@ -376,12 +443,13 @@ class NextFramePredictorS2S(NextFramePredictor):
 
     @on_device(lambda self, *a, **k: self.device)
     def train_step(self, x, y, concat_layers=None, mask=None, high_interest_region=None, graph_structure=None,
-                   max_norm=10.0, fused=False, loss_weights=None, lead_weights=None):
+                   max_norm=10.0, fused=False, pos_weight=None, loss_weights=None, lead_weights=None):
         """zero_grad -> forward -> masked MSE -> backward -> [all-reduce] -> clip_grad_norm_(10) -> Adam
         (mpnnlstm.py:229-257).  x: (T_in, W, H, C) or (B, T_in, W, H, C).  Returns the loss tensor.
         loss_weights / lead_weights: the weighted loss (masked_mse).  fused=True (binary predictors only): the fused binary
-        cross-entropy of masked_mse, the loss a captured step runs."""
-        lw = self._loss_weights(x, mask, loss_weights, lead_weights)
+        cross-entropy of masked_mse, the loss a captured step runs.  On a binary=True predictor the weights, and pos_weight, the
+        weight of the positive class, select the weighted binary cross-entropy (masked_bce)."""
+        lw = self._loss_weights(x, mask, loss_weights, lead_weights, pos_weight)
         self.zero_grad()
         loss = self.forward_loss(x, y, concat_layers, mask, high_interest_region, graph_structure, fused=fused, loss_weights=lw)
         loss.backward()
@@ -391,7 +459,7 @@ class NextFramePredictorS2S(NextFramePredictor):
 
     @on_device(lambda self, *a, **k: self.device)
     def truncated_backward(self, x, y, concat_layers, mask, high_interest_region=None, graph_structure=None,
-                           truncated_backprop=45, loss_weights=None, lead_weights=None):
+                           truncated_backprop=45, pos_weight=None, loss_weights=None, lead_weights=None):
         """The reference's truncated-BPTT loop (mpnnlstm.py:281-315), quirks included: every chunk re-runs the encoder
         and unrolls ITS steps from the encoder state, `zero_grad` runs per chunk (so only the last chunk's gradient
         survives to optimizer.step()), and the chunk bound is min(start + tb, T_out + 1).  Returns the chunk losses.
@@ -402,11 +470,11 @@ class NextFramePredictorS2S(NextFramePredictor):
         Where HEAD runs (tb divides T_out: ice_exp.py exp 5 / 6) the clamp changes nothing.
 
         loss_weights / lead_weights: the weighted loss; a chunk takes lead_weights[steps] and divides by that slice's sum (every
-        chunk's slice is checked before the first one runs)."""
+        chunk's slice is checked before the first one runs).  pos_weight (binary=True predictors): as in train_step."""
         losses, step = [], 0
         if y.dim() == 4:
             y = y.unsqueeze(0)
-        lw = self._loss_weights(x, mask, loss_weights, lead_weights)
+        lw = self._loss_weights(x, mask, loss_weights, lead_weights, pos_weight)
         chunks = []
         while step < self.output_timesteps:
             step = min(step + truncated_backprop, self.output_timesteps + 1)
@@ -420,14 +488,15 @@ class NextFramePredictorS2S(NextFramePredictor):
             if lwc is None:
                 loss = masked_mse(y_hat, meshes, y[:, steps.start:steps.stop], mask, self.binary)
             else:
-                loss = masked_mse(y_hat, meshes, y[:, steps.start:steps.stop], mask, self.binary, weights=lwc)
+                loss = self._weighted_loss(y_hat, meshes, y[:, steps.start:steps.stop], mask, lwc)
             loss.backward()
             losses.append(loss.detach())
         return losses
 
     @on_device(lambda self, *a, **k: self.device)
     def make_graphed_step(self, x, y, concat_layers=None, mask=None, high_interest_region=None, max_norm=10.0,
-                          warmup=2, graph_structure=None, force_multi=False, loss_weights=None, lead_weights=None):
+                          warmup=2, graph_structure=None, force_multi=False, pos_weight=None, loss_weights=None,
+                          lead_weights=None):
         """Capture one whole training step in hipGraphs and return `step(x, y, concat) -> loss`.
 
         The rollout is data dependent (every decoder step re-meshes on its own output), so the capture runs in
@@ -443,7 +512,9 @@ class NextFramePredictorS2S(NextFramePredictor):
         loss_weights / lead_weights: the weighted loss (masked_mse); checked and uploaded once, here, and the captured step reads
         the two device arrays -- step(x, y, concat) keeps its signature.
         A binary=True predictor runs the fused binary cross-entropy (masked_mse(fused=True)) in the warm-up steps and in the
-        capture alike: torch's BCELoss path indexes with a host mask and cannot be captured.
+        capture alike: torch's BCELoss path indexes with a host mask and cannot be captured.  Given weights or pos_weight it runs
+        the weighted binary cross-entropy (masked_bce) instead; pos_weight goes to the kernels by value, so the captured graph
+        keeps the value it was captured with -- it is constant for the life of the step object.
         """
         import torch.distributed as dist
         if force_multi and not (dist.is_available() and dist.is_initialized()):
@@ -457,7 +528,7 @@ class NextFramePredictorS2S(NextFramePredictor):
             self.initiate_training(float(lr), self.scheduler.gamma, capturable=True)
         sx, sy = x.clone(), y.clone()
         sc = concat_layers.clone() if concat_layers is not None else None
-        lw = self._loss_weights(x, mask, loss_weights, lead_weights)
+        lw = self._loss_weights(x, mask, loss_weights, lead_weights, pos_weight)
 
         def fwd_bwd():
             self.zero_grad()
@@ -672,8 +743,8 @@ class NextFramePredictorS2S(NextFramePredictor):
 
     @on_device(lambda self, *a, **k: self.device)
     def train(self, loader_train, loader_test, climatology=None, n_epochs=200, lr=0.01, lr_decay=0.95, mask=None,
-              high_interest_region=None, truncated_backprop=45, graph_structure=None, use_graph=False, loss_weights=None,
-              lead_weights=None):
+              high_interest_region=None, truncated_backprop=45, graph_structure=None, use_graph=False, pos_weight=None,
+              loss_weights=None, lead_weights=None):
         """The reference's training loop (mpnnlstm.py:186-387).  use_graph=True (beyond the reference) replays the whole training
         step as a hipGraph: one graph is captured per distinct batch shape on first sight (that batch's own update runs eagerly just
         before the capture) and the learning-rate schedule keeps working because the capturable optimizer holds lr in a device
@@ -681,7 +752,8 @@ class NextFramePredictorS2S(NextFramePredictor):
         length that covers all output steps (the default 45 with the notebook's 10: the truncated loop is then a single chunk over
         the whole rollout, without gradient clipping -- mpnnlstm.py:311 is commented out -- and that is what is captured).
         loss_weights (W, H) / lead_weights (T_out,) (beyond the reference): the weighted loss of masked_mse, for the training
-        steps and for the test pass alike; checked and uploaded once."""
+        steps and for the test pass alike; checked and uploaded once.  On a binary=True predictor they, and pos_weight (the weight
+        of the positive class), select the weighted binary cross-entropy of masked_bce, for the test pass too."""
         image_shape = loader_train.dataset.image_shape
         truncate_ = truncated_backprop not in (0, None)
         single_chunk = truncate_ and truncated_backprop >= self.output_timesteps
@@ -695,9 +767,7 @@ class NextFramePredictorS2S(NextFramePredictor):
             mshape = tuple(host_mask(mask).shape) if not hasattr(mask, 'shape') else tuple(mask.shape)
             assert mshape == tuple(image_shape), f'Mask and image shapes do not match. Got {mshape} and {image_shape}'
         truncate = truncate_ and not (use_graph and single_chunk)
-        lw = loss_weights_of(loss_weights, lead_weights, tuple(image_shape), self.output_timesteps, mask, self.binary)
-        if lw is not None:
-            lw.to(self.device if self.device is not None else 'cpu')
+        lw = self._loss_weights(None, mask, loss_weights, lead_weights, pos_weight, shape=image_shape)
         st = time.time()
         batch_step = 0
         for epoch in range(n_epochs):

@@ -1,4 +1,5 @@
-"""ctypes binding of libqtmpnn_hip.so (the C ABI declared in include/qtmpnn.h and include/qtmpnn_edges.h).
+"""ctypes binding of libqtmpnn_hip.so (the C ABI declared in include/qtmpnn.h, include/qtmpnn_edges.h and
+include/qtmpnn_loss.h).
 
 The product path has no CPU fallback: if the shared library is missing or a call
 fails, an exception is raised.
@@ -110,6 +111,11 @@ _SIGNATURES = {
 _EDGE_SIGNATURES = {
     'qt_edge_rollout': [_I, _P, _P, _P, _P, _P, _P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _F, _I, _I, _I, _P, _P, _P],
 }
+# The entries of include/qtmpnn_loss.h, bound the same way: qt_wsse_rollout's / _bwd's arguments and pos_weight by value.
+_LOSS_SIGNATURES = {
+    'qt_wbce_rollout': _SIGNATURES['qt_wsse_rollout'][:-1] + [_F, _P],
+    'qt_wbce_rollout_bwd': _SIGNATURES['qt_wsse_rollout_bwd'][:-1] + [_F, _P],
+}
 _PLAIN = {'qt_proj_bwd_blocks', 'qt_abi_version', 'qt_cheb_clip_rows', 'qt_cheb_tile_sync_words', 'qt_cheb_tile_xbuf_words', 'qt_tile_cap', 'qt_remesh_clip_rows', 'qt_tail_cap', 'qt_num_cus', 'qt_lstm_fused_blocks', 'qt_wgrad_blocks', 'qt_lstm_bwd_blocks', 'qt_lstm_dgrad_blocks', 'qt_attn_blocks', 'qt_mhattn_blocks'}  # return a value, not an error code
 
 _lib = None
@@ -125,7 +131,7 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
         lib.qt_last_error.restype = ctypes.c_char_p
         lib.qt_last_error.argtypes = []
-        for name, args in {**_SIGNATURES, **_EDGE_SIGNATURES}.items():
+        for name, args in {**_SIGNATURES, **_EDGE_SIGNATURES, **_LOSS_SIGNATURES}.items():
             fn = getattr(lib, name)
             fn.argtypes = args
             fn.restype = ctypes.c_int

@@ -2116,6 +2116,103 @@ def step_wsse_partials(out, y, mesh, w, lam_t):
     return (lam_t * (keep * (d * d)).sum()).view(1)
 
 
+class _RolloutWBCE(Function):
+    """_RolloutWSSE for the binary head (qt_wbce_rollout / _bwd): partial sums of
+    -lam[t] w[p] (pos_weight y max(log o, -100) + (1 - y) max(log(1 - o), -100)), o = column 0 of outs[t], three launches per 16
+    steps.  w: (P,) and lam: (T,) fp32 device tensors, no gradient; pos_weight: a Python float > 0, passed by value (a captured
+    graph keeps it).  The backward reads the same per-node [sum w | sum w y] (N_t, 2) as _RolloutWSSE's."""
+
+    @staticmethod
+    def forward(ctx, y, meshes, w, lam, pos_weight, *outs):
+        import ctypes
+        B, T, P = y.shape
+        m0 = meshes[0]
+        nt = -(P // -1024)
+        part = outs[0].new_empty(T, B * nt)
+        swys = [o.new_empty(ms.N, 2) for o, ms in zip(outs, meshes)]
+        vp, ip = ctypes.c_void_p, ctypes.c_int
+        for z0 in range(0, T, 16):
+            sl = slice(z0, min(z0 + 16, T))
+            n = sl.stop - sl.start
+            _lib.call('qt_wbce_rollout', n, (vp * n)(*[o.data_ptr() for o in outs[sl]]), (ip * n)(*[o.stride(0) for o in outs[sl]]),
+                      (vp * n)(*[ms.labels.data_ptr() for ms in meshes[sl]]), (vp * n)(*[ms.level.data_ptr() for ms in meshes[sl]]),
+                      (ip * n)(*[ms.N for ms in meshes[sl]]), (vp * n)(*[t.data_ptr() for t in swys[sl]]),
+                      y.data_ptr() + 4 * z0 * P, T * P, P, ptr(w), lam.data_ptr() + 4 * z0, B, m0.n, m0.m, ptr(part[z0:]), pos_weight)
+        ctx.save_for_backward(lam, *outs, *swys)
+        ctx.meshes, ctx.pos_weight = meshes, pos_weight
+        return part
+
+    @staticmethod
+    def backward(ctx, g):
+        import ctypes
+        meshes = ctx.meshes
+        T = len(meshes)
+        lam, outs, swys = ctx.saved_tensors[0], ctx.saved_tensors[1:1 + T], ctx.saved_tensors[1 + T:]
+        gouts = [torch.empty_like(o) for o in outs]
+        g1 = g.reshape(-1)[:1].contiguous()      # every partial has the same upstream gradient (they are only ever summed)
+        vp, ip = ctypes.c_void_p, ctypes.c_int
+        W = outs[0].shape[1]
+        for z0 in range(0, T, 16):
+            sl = slice(z0, min(z0 + 16, T))
+            n = sl.stop - sl.start
+            _lib.call('qt_wbce_rollout_bwd', n, (vp * n)(*[o.data_ptr() for o in outs[sl]]), (ip * n)(*[o.stride(0) for o in outs[sl]]),
+                      (vp * n)(*[t.data_ptr() for t in swys[sl]]), (ip * n)(*[ms.N for ms in meshes[sl]]),
+                      (vp * n)(*[ms.n_dev.data_ptr() if ms.n_dev is not None else None for ms in meshes[sl]]),
+                      ptr(g1), lam.data_ptr() + 4 * z0, W, (vp * n)(*[t.data_ptr() for t in gouts[sl]]), ctx.pos_weight)
+        return (None, None, None, None, None, *gouts)
+
+
+def check_pos_weight(pos_weight):
+    """pos_weight as a Python float; anything but one real number that is finite and > 0 as a float32 (the kernels take it by value
+    in that format) is refused by name."""
+    if isinstance(pos_weight, bool) or not isinstance(pos_weight, numbers.Real):
+        raise ValueError(f'pos_weight: one real number > 0 is needed, got {type(pos_weight).__name__}')
+    pw = float(pos_weight)
+    if not 2.0 ** -126 <= pw <= 3.4028234e38:       # (NaN fails both comparisons)
+        raise ValueError(f'pos_weight: a finite number > 0 (a normal float32) is needed, got {pos_weight!r}')
+    return pw
+
+
+def rollout_wbce_partials(outputs, y, meshes, w, lam, pos_weight=1.0):
+    """Partial sums of lam[t] * w[p] * (the binary cross-entropy term with pos_weight on the y = 1 side) of every output step
+    (their total is the numerator of the weighted loss), or None exactly where rollout_wsse_partials returns None (per-pixel
+    loss_mask of preset meshes, odd layouts): the caller then goes step by step through step_wbce_partials.  outputs[t]:
+    probabilities in [0, 1]; w: (W, H) or (P,) pixel weights, lam: (T,) step weights, both fp32 on the outputs' device and already
+    checked (non-negative, finite), no gradient; pos_weight: a finite number > 0."""
+    pos_weight = check_pos_weight(pos_weight)
+    if not outputs or any(ms.loss_mask is not None or ms.N == 0 for ms in meshes):
+        return None
+    outs = [_full_rows(o) for o in outputs]
+    W = outs[0].shape[1]
+    if any(o.dtype != torch.float32 or not o.is_contiguous() or o.shape[1] != W or not o.is_cuda for o in outs):
+        return None
+    B, T = meshes[0].B, len(outs)
+    if y.dtype != torch.float32 or not y.is_contiguous() or y.numel() != B * T * meshes[0].P:
+        return None
+    _check_loss_weights(w, lam, meshes[0], T)
+    return _RolloutWBCE.apply(y.view(B, T, meshes[0].P), tuple(meshes), w.view(-1), lam, pos_weight, *outs)
+
+
+def step_wbce_partials(out, y, mesh, w, lam_t, pos_weight=1.0):
+    """One step of the weighted binary cross-entropy where the rollout launches do not apply: lam_t * sum of keep * w * term with
+    keep = the pixel has a node and is not under mesh.loss_mask and term = -(pos_weight y L1 + (1 - y) L0), the logarithms clamped
+    at -100 before the products.  A composition of differentiable ops on gather_pixels, like step_wsse_partials /
+    step_bce_partials: NOT the tuned path.  w: (P,) fp32 device tensor, lam_t: 0-dim device tensor."""
+    pos_weight = check_pos_weight(pos_weight)
+    keep = mesh.labels.view(mesh.B, mesh.P) >= 0
+    if mesh.loss_mask is not None:
+        keep = keep & (mesh.loss_mask == 0).view(1, mesh.P)
+    img = gather_pixels(out[:, :1], mesh).view(mesh.B, mesh.P)
+    # (a pixel without a node gathers 0: it gets a harmless probability before the log, and weight 0 after it)
+    img = torch.where(keep, img, torch.full_like(img, 0.5))
+    yt = y.reshape(mesh.B, mesh.P).float()
+    # torch's binary_cross_entropy with the target's own weight pos_weight y + (1 - y) on each side: its clamp, and its backward
+    bce = torch.nn.functional.binary_cross_entropy
+    terms = pos_weight * bce(img, torch.ones_like(img), weight=yt, reduction='none') \
+        + bce(img, torch.zeros_like(img), weight=1.0 - yt, reduction='none')
+    return (lam_t * (terms * (keep.float() * w.view(1, mesh.P))).sum()).view(1)
+
+
 def _score_args(who, outputs, meshes, y, persistence, climatology):
     """The checked operands rollout_scores and rollout_score_maps share: (outs, y, bases, S, B, T, P), bases = two
     (field or None, clip stride, step stride).  Refusals carry `who`."""
