@@ -1,7 +1,7 @@
 // Mesh <-> image transfers by label map: flatten / unflatten
 // (model/graph_functions.py:391-419, 451-458) without the dense (N, P) mapping, the fused
 // remesh transfer of seq2seq.py:440-442 + 474-477, and the masked squared error of
-// mpnnlstm.py:243-246 (the training loss: k_sse*, k_pool_targets).  The verification
+// mpnnlstm.py:243-246 (the training loss: k_sse, k_loss_multi, k_pool_targets).  The verification
 // kernels that read a rollout the same way (scores, maps, event dates) are in verify.hip.
 //
 // k_pool: one workgroup per 64x64 image tile.  Each thread owns a 4x4 pixel block and
@@ -87,7 +87,7 @@ __device__ __forceinline__ void vstore(float* p, const Vec<VEC>& r, float scale)
 // (experiment switches: the node kernel takes nodes up to QT_NODE_MAX_Z pixels wide, the tile kernel those from level QT_TILE_MIN_LV)
 static constexpr int QT_TILE_MIN_LV = 3;
 static constexpr int QT_NODE_MAX_Z = 4;
-// WY (compile time; the weighted loss, k_pool_wtargets): the image is one channel y and the two "channels" summed are the pixel
+// WY (compile time; the weighted losses, k_pool_targets<true>): the image is one channel y and the two "channels" summed are the pixel
 // weight and its product with y, (w_p, w_p y_p), formed in registers at the load: VEC = 2, rows [sum w | sum w y] of `out`.
 template <int VEC, bool WY = false>
 __device__ __forceinline__ void tile_body(const PoolArgs& a, int bx, int by, int ny, float* pyr, const float* wmap = nullptr) {
@@ -257,8 +257,11 @@ struct LossSeg {
     int out_stride[16], N[16];
 };
 
-__global__ __launch_bounds__(256) void k_pool_targets(PoolArgs a, LossSeg sg, int64_t y_step_stride) {
-    __shared__ float pyr[256 + 64 + 16 + 4 + 1];
+// Per node the sum of the target over its pixels, sg.sy[z] (N floats).  WGT (the weighted losses): per node
+// [sum of w_p | sum of w_p y_p], rows of 2 floats in sg.sy[z], by the same tree; the unweighted instantiation does not read w.
+template <bool WGT>
+__global__ __launch_bounds__(256) void k_pool_targets(PoolArgs a, LossSeg sg, int64_t y_step_stride, const float* __restrict__ w) {
+    __shared__ float pyr[(256 + 64 + 16 + 4 + 1) * (WGT ? 2 : 1)];
     const int z = blockIdx.z;
     a.img = a.img + z * y_step_stride;
     a.labels = sg.labels[z];
@@ -266,20 +269,10 @@ __global__ __launch_bounds__(256) void k_pool_targets(PoolArgs a, LossSeg sg, in
     a.npix = sg.npix[z];
     a.N = sg.N[z];
     a.out = sg.sy[z];
-    tile_body<1>(a, blockIdx.x, 0, 1, pyr);
-}
-
-// The weighted loss: per node [sum of w_p | sum of w_p y_p] over its pixels, rows of 2 floats in sg.sy[z], by the same tree.
-__global__ __launch_bounds__(256) void k_pool_wtargets(PoolArgs a, LossSeg sg, int64_t y_step_stride, const float* __restrict__ w) {
-    __shared__ float pyr[(256 + 64 + 16 + 4 + 1) * 2];
-    const int z = blockIdx.z;
-    a.img = a.img + z * y_step_stride;
-    a.labels = sg.labels[z];
-    a.level = sg.level[z];
-    a.npix = sg.npix[z];
-    a.N = sg.N[z];
-    a.out = sg.sy[z];
-    tile_body<2, true>(a, blockIdx.x, 0, 1, pyr, w);
+    if constexpr (WGT)
+        tile_body<2, true>(a, blockIdx.x, 0, 1, pyr, w);
+    else
+        tile_body<1>(a, blockIdx.x, 0, 1, pyr);
 }
 
 // Node-centric transfer for nodes of 1x1 .. 4x4 pixels: thread = (node, float4 chunk of its row), chunk fastest, so the
@@ -519,129 +512,20 @@ __global__ __launch_bounds__(256) void k_sse(const float* __restrict__ out, int 
     if (threadIdx.x == 0) partial[(int64_t)b * gridDim.x + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-__global__ __launch_bounds__(256) void k_sse_multi(LossSeg sg, const float* __restrict__ y, int64_t y_clip_stride,
-                                                   int64_t y_step_stride, int64_t P, int B, float* __restrict__ partial) {
-    __shared__ float red[4];
-    const int b = blockIdx.y, z = blockIdx.z;
-    const float* out = sg.out[z];
-    const int32_t* labels = sg.labels[z];
-    const int os = sg.out_stride[z];
-    const float* yz = y + z * y_step_stride + b * y_clip_stride;
-    float acc = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int64_t p = (int64_t)blockIdx.x * 1024 + k * 256 + threadIdx.x;
-        if (p < P) {
-            const int lab = labels[b * P + p];
-            if (lab >= 0) {
-                const float d = out[(int64_t)lab * os] - yz[p];
-                acc += d * d;
-            }
-        }
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0)
-        partial[((int64_t)z * B + b) * gridDim.x + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
-}
+// The loss of up to 16 output steps in one launch: per-block partial sums of the per-pixel term over clip b of step z, one
+// workgroup per 1024 pixels, a butterfly per wave and the four waves in a fixed order (no atomics).  KIND and WGT select the term:
+//   LOSS_SSE         (out[label] - y)^2
+//   LOSS_SSE, WGT    lam[z] w[p] (out[label] - y)^2
+//   LOSS_BCE         -(y max(log o, -100) + (1 - y) max(log(1 - o), -100)), o = out[label]: torch's BCELoss with its clamp
+//   LOSS_BCE, WGT    -lam[z] w[p] (pw y max(log o, -100) + (1 - y) max(log(1 - o), -100)), pw the weight of the positive class
+// The unweighted instantiations do not read w, lam or pw.  logf / log1pf are the accurate library functions: log(1 - o) is taken
+// as log1pf(-o), because the rounding of 1 - o alone is an error of 2^-25 / (1 - o) in the logarithm, 25 units in the last place
+// of log(1 - o) at o = 0.02.  The clamp comes before the product, so y = 0 beside o = 0 gives 0 and not 0 * -inf.  pw multiplies
+// y before the logarithm does, so a power of two in w or lam scales every partial sum exactly.
+enum { LOSS_SSE = 0, LOSS_BCE = 1 };
 
-// k_sse_multi with a weight per pixel and per step: partial = sum of lam[z] w[p] (out[label] - y)^2, same reduction order
-__global__ __launch_bounds__(256) void k_wsse_multi(LossSeg sg, const float* __restrict__ y, int64_t y_clip_stride,
-                                                    int64_t y_step_stride, const float* __restrict__ w,
-                                                    const float* __restrict__ lam, int64_t P, int B, float* __restrict__ partial) {
-    __shared__ float red[4];
-    const int b = blockIdx.y, z = blockIdx.z;
-    const float* out = sg.out[z];
-    const int32_t* labels = sg.labels[z];
-    const int os = sg.out_stride[z];
-    const float* yz = y + z * y_step_stride + b * y_clip_stride;
-    const float lz = lam[z];
-    float acc = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int64_t p = (int64_t)blockIdx.x * 1024 + k * 256 + threadIdx.x;
-        if (p < P) {
-            const int lab = labels[b * P + p];
-            if (lab >= 0) {
-                const float d = out[(int64_t)lab * os] - yz[p];
-                acc += lz * (w[p] * (d * d));
-            }
-        }
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0)
-        partial[((int64_t)z * B + b) * gridDim.x + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-// gradient rows of the weighted loss: sg.sy[z] holds the (N, 2) rows [sum w | sum w y] of k_pool_wtargets
-__global__ void k_wsse_bwd_multi(LossSeg sg, const float* __restrict__ g, const float* __restrict__ lam, int W) {
-    const int z = blockIdx.y;
-    const unsigned idx = blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t i = idx / (unsigned)W;
-    if (i >= qt_rows(sg.n_dev[z], sg.N[z])) return;
-    const float* out = sg.out[z];
-    const float* sw = sg.sy[z];
-    sg.gout[z][idx] = (idx - (unsigned)i * (unsigned)W) == 0
-                          ? 2.0f * g[0] * lam[z] * (sw[2 * i] * out[i * sg.out_stride[z]] - sw[2 * i + 1]) : 0.0f;
-}
-
-// k_sse_multi for the binary head: partial = - sum of y max(log o, -100) + (1 - y) max(log(1 - o), -100) (torch's BCELoss with
-// its clamp), same grid and reduction order.  logf / log1pf are the accurate library functions: log(1 - o) is taken as
-// log1pf(-o), because the rounding of 1 - o alone is an error of 2^-25 / (1 - o) in the logarithm, 25 units in the last place of
-// log(1 - o) at o = 0.02.  The clamp comes before the product, so y = 0 beside o = 0 gives 0 and not 0 * -inf.
-__global__ __launch_bounds__(256) void k_bce_multi(LossSeg sg, const float* __restrict__ y, int64_t y_clip_stride,
-                                                   int64_t y_step_stride, int64_t P, int B, float* __restrict__ partial) {
-    __shared__ float red[4];
-    const int b = blockIdx.y, z = blockIdx.z;
-    const float* out = sg.out[z];
-    const int32_t* labels = sg.labels[z];
-    const int os = sg.out_stride[z];
-    const float* yz = y + z * y_step_stride + b * y_clip_stride;
-    float acc = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int64_t p = (int64_t)blockIdx.x * 1024 + k * 256 + threadIdx.x;
-        if (p < P) {
-            const int lab = labels[b * P + p];
-            if (lab >= 0) {
-                const float o = out[(int64_t)lab * os], t = yz[p];
-                const float l1 = fmaxf(logf(o), -100.0f), l0 = fmaxf(log1pf(-o), -100.0f);
-                acc -= t * l1 + (1.0f - t) * l0;
-            }
-        }
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0)
-        partial[((int64_t)z * B + b) * gridDim.x + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-// gradient rows of the binary cross-entropy: torch's (o - y) / max(o (1 - o), 1e-12) summed over the node's pixels (linear in y,
-// so the node sums npix and sy suffice); the clamped product keeps the row finite at o = 0 and o = 1
-__global__ void k_bce_bwd_multi(LossSeg sg, const float* __restrict__ g, int W) {
-    const int z = blockIdx.y;
-    const unsigned idx = blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t i = idx / (unsigned)W;
-    if (i >= qt_rows(sg.n_dev[z], sg.N[z])) return;
-    float v = 0.0f;
-    if ((idx - (unsigned)i * (unsigned)W) == 0) {
-        const float o = sg.out[z][i * sg.out_stride[z]];
-        v = g[0] * (sg.npix[z][i] * o - sg.sy[z][i]) / fmaxf(o * (1.0f - o), 1e-12f);
-    }
-    sg.gout[z][idx] = v;
-}
-
-// k_bce_multi with a weight per pixel and per step and a weight pw on the positive class: partial = - sum of
-// lam[z] w[p] (pw y max(log o, -100) + (1 - y) max(log(1 - o), -100)), same grid and reduction order, the logarithms and the clamp
-// as there.  pw multiplies y before the logarithm does, so a power of two in w or lam scales every partial sum exactly.
-__global__ __launch_bounds__(256) void k_wbce_multi(LossSeg sg, const float* __restrict__ y, int64_t y_clip_stride,
+template <int KIND, bool WGT>
+__global__ __launch_bounds__(256) void k_loss_multi(LossSeg sg, const float* __restrict__ y, int64_t y_clip_stride,
                                                     int64_t y_step_stride, const float* __restrict__ w,
                                                     const float* __restrict__ lam, float pw, int64_t P, int B,
                                                     float* __restrict__ partial) {
@@ -651,7 +535,8 @@ __global__ __launch_bounds__(256) void k_wbce_multi(LossSeg sg, const float* __r
     const int32_t* labels = sg.labels[z];
     const int os = sg.out_stride[z];
     const float* yz = y + z * y_step_stride + b * y_clip_stride;
-    const float lz = lam[z];
+    float lz = 1.0f;
+    if constexpr (WGT) lz = lam[z];
     float acc = 0.0f;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -660,8 +545,19 @@ __global__ __launch_bounds__(256) void k_wbce_multi(LossSeg sg, const float* __r
             const int lab = labels[b * P + p];
             if (lab >= 0) {
                 const float o = out[(int64_t)lab * os], t = yz[p];
-                const float l1 = fmaxf(logf(o), -100.0f), l0 = fmaxf(log1pf(-o), -100.0f);
-                acc -= lz * (w[p] * ((pw * t) * l1 + (1.0f - t) * l0));
+                if constexpr (KIND == LOSS_SSE) {
+                    const float d = o - t;
+                    if constexpr (WGT)
+                        acc += lz * (w[p] * (d * d));
+                    else
+                        acc += d * d;
+                } else {
+                    const float l1 = fmaxf(logf(o), -100.0f), l0 = fmaxf(log1pf(-o), -100.0f);
+                    if constexpr (WGT)
+                        acc -= lz * (w[p] * ((pw * t) * l1 + (1.0f - t) * l0));
+                    else
+                        acc -= t * l1 + (1.0f - t) * l0;
+                }
             }
         }
     }
@@ -673,10 +569,15 @@ __global__ __launch_bounds__(256) void k_wbce_multi(LossSeg sg, const float* __r
         partial[((int64_t)z * B + b) * gridDim.x + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-// gradient rows of the weighted binary cross-entropy: the per-pixel (o - y (pw + o (1 - pw))) / max(o (1 - o), 1e-12) times
-// lam w_p, summed over the node's pixels (linear in y: sg.sy[z] holds the (N, 2) rows [sum w | sum w y] of k_pool_wtargets).  The
-// factor pw + o (1 - pw) is taken as o + pw (1 - o), a sum of two non-negative terms: the first form cancels for a large pw.
-__global__ void k_wbce_bwd_multi(LossSeg sg, const float* __restrict__ g, const float* __restrict__ lam, float pw, int W) {
+// Gradient rows of k_loss_multi's sum: column 0 of row i gets the derivative with respect to node i's value o, summed over the
+// node's pixels, the other W - 1 columns 0.  Every term is linear in y, so the node sums of k_pool_targets suffice: npix and sy
+// (sum of y), or with WGT the (N, 2) rows sw = [sum w | sum w y] in sg.sy[z].
+//   LOSS_SSE         2 (npix o - sy)
+//   LOSS_BCE         torch's (o - y) / max(o (1 - o), 1e-12): the clamped product keeps the row finite at o = 0 and o = 1
+//   LOSS_BCE, WGT    (o - y (pw + o (1 - pw))) / max(o (1 - o), 1e-12) times lam w_p.  The factor pw + o (1 - pw) is taken as
+//                    o + pw (1 - o), a sum of two non-negative terms: the first form cancels for a large pw.
+template <int KIND, bool WGT>
+__global__ void k_loss_bwd_multi(LossSeg sg, const float* __restrict__ g, const float* __restrict__ lam, float pw, int W) {
     const int z = blockIdx.y;
     const unsigned idx = blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t i = idx / (unsigned)W;
@@ -686,19 +587,13 @@ __global__ void k_wbce_bwd_multi(LossSeg sg, const float* __restrict__ g, const 
         const float o = sg.out[z][i * sg.out_stride[z]];
         const float* sw = sg.sy[z];
         const float q = 1.0f - o;
-        v = g[0] * lam[z] * (o * sw[2 * i] - sw[2 * i + 1] * (o + pw * q)) / fmaxf(o * q, 1e-12f);
+        if constexpr (KIND == LOSS_SSE && !WGT) v = 2.0f * g[0] * (sg.npix[z][i] * o - sg.sy[z][i]);
+        if constexpr (KIND == LOSS_SSE && WGT) v = 2.0f * g[0] * lam[z] * (sw[2 * i] * o - sw[2 * i + 1]);
+        if constexpr (KIND == LOSS_BCE && !WGT) v = g[0] * (sg.npix[z][i] * o - sg.sy[z][i]) / fmaxf(o * q, 1e-12f);
+        if constexpr (KIND == LOSS_BCE && WGT)
+            v = g[0] * lam[z] * (o * sw[2 * i] - sw[2 * i + 1] * (o + pw * q)) / fmaxf(o * q, 1e-12f);
     }
     sg.gout[z][idx] = v;
-}
-
-__global__ void k_sse_bwd_multi(LossSeg sg, const float* __restrict__ g, int W) {
-    const int z = blockIdx.y;
-    const unsigned idx = blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t i = idx / (unsigned)W;
-    if (i >= qt_rows(sg.n_dev[z], sg.N[z])) return;
-    const float* out = sg.out[z];
-    sg.gout[z][idx] = (idx - (unsigned)i * (unsigned)W) == 0
-                          ? 2.0f * g[0] * (sg.npix[z][i] * out[i * sg.out_stride[z]] - sg.sy[z][i]) : 0.0f;
 }
 
 __global__ void k_sse_bwd(const float* __restrict__ out, int out_stride, const float* __restrict__ npix,
@@ -723,182 +618,132 @@ extern "C" int qt_sse_bwd(const float* out, int out_stride, const float* npix, c
     return QT_OK;
 }
 
-extern "C" int qt_sse_rollout(int nseg, const float* const* outs, const int* out_strides, const int32_t* const* labels,
-                              const uint8_t* const* levels, const int* Ns, float* const* sys, const float* y,
-                              int64_t y_clip_stride, int64_t y_step_stride, int B, int n, int m, float* partial, void* stream) {
-    QT_ARG(nseg >= 1 && nseg <= 16 && outs && out_strides && labels && levels && Ns && sys && y && partial && B > 0, "bad arguments");
+// QT_ARG / QT_LAUNCHED for the two launchers that the eight rollout-loss entry points share: the error names the entry `fn`
+#define LOSS_ARG(cond, msg)                         \
+    do {                                            \
+        if (!(cond)) {                              \
+            qt_set_error("%s: %s", fn, msg);        \
+            return QT_E_ARG;                        \
+        }                                           \
+    } while (0)
+
+#define LOSS_LAUNCHED()                                             \
+    do {                                                            \
+        hipError_t qt_e_ = hipGetLastError();                       \
+        if (qt_e_ != hipSuccess) {                                  \
+            qt_set_error("%s: %s", fn, hipGetErrorString(qt_e_));   \
+            return QT_E_LAUNCH;                                     \
+        }                                                           \
+    } while (0)
+
+// Forward of every rollout loss: the partial sums (k_loss_multi) and the per-node target sums the backward reads
+// (k_pool_targets), one launch each over the nseg steps.  wgt: w (n*m) and lam (nseg) are given and sys[z] are (N, 2) rows.
+static int loss_fwd(const char* fn, int kind, bool wgt, int nseg, const float* const* outs, const int* out_strides,
+                    const int32_t* const* labels, const uint8_t* const* levels, const int* Ns, float* const* sys, const float* y,
+                    int64_t y_clip_stride, int64_t y_step_stride, const float* w, const float* lam, float pos_weight, int B, int n,
+                    int m, float* partial, void* stream) {
+    LOSS_ARG(nseg >= 1 && nseg <= 16 && outs && out_strides && labels && levels && Ns && sys && y && partial && B > 0, "bad arguments");
+    LOSS_ARG(!wgt || (w && lam), "null weights: w (n*m) and lam (nseg) are device arrays");
+    LOSS_ARG(pos_weight > 0.0f && pos_weight <= FLT_MAX, "pos_weight must be finite and > 0");
+    LOSS_ARG(n > 0 && m > 0 && y_clip_stride >= 0 && y_step_stride >= 0, "bad sizes");
     LossSeg sg = {};
     for (int z = 0; z < nseg; ++z) {
-        QT_ARG(outs[z] && labels[z] && levels[z] && sys[z] && out_strides[z] >= 1, "null segment pointer");
+        LOSS_ARG(outs[z] && labels[z] && levels[z] && sys[z] && out_strides[z] >= 1 && Ns[z] >= 0, "null segment pointer");
         sg.out[z] = outs[z]; sg.out_stride[z] = out_strides[z]; sg.labels[z] = labels[z]; sg.level[z] = levels[z];
         sg.N[z] = Ns[z]; sg.sy[z] = sys[z];
     }
     const int64_t P = (int64_t)n * m;
-    hipLaunchKernelGGL(k_sse_multi, dim3(qt_cdiv(P, 1024), B, nseg), dim3(256), 0, (hipStream_t)stream, sg, y, y_clip_stride,
-                       y_step_stride, P, B, partial);
-    QT_LAUNCHED();
+    const auto loss = kind == LOSS_SSE ? (wgt ? k_loss_multi<LOSS_SSE, true> : k_loss_multi<LOSS_SSE, false>)
+                                       : (wgt ? k_loss_multi<LOSS_BCE, true> : k_loss_multi<LOSS_BCE, false>);
+    hipLaunchKernelGGL(loss, dim3(qt_cdiv(P, 1024), B, nseg), dim3(256), 0, (hipStream_t)stream, sg, y, y_clip_stride,
+                       y_step_stride, w, lam, pos_weight, P, B, partial);
+    LOSS_LAUNCHED();
     PoolArgs a = {};
-    a.img = y; a.S = 1; a.img_clip_stride = y_clip_stride; a.C = 1; a.mean = 0; a.B = B; a.n = n; a.m = m;
-    a.out_stride = 1; a.out_coff = 0; a.tiles_r = qt_cdiv(n, 64); a.tiles_c = qt_cdiv(m, 64);
-    hipLaunchKernelGGL(k_pool_targets, dim3(B * a.tiles_r * a.tiles_c, 1, nseg), dim3(256), 0, (hipStream_t)stream, a, sg,
-                       y_step_stride);
-    QT_LAUNCHED();
+    a.img = y; a.S = 1; a.img_clip_stride = y_clip_stride; a.C = wgt ? 2 : 1; a.mean = 0; a.B = B; a.n = n; a.m = m;
+    a.out_stride = a.C; a.out_coff = 0; a.tiles_r = qt_cdiv(n, 64); a.tiles_c = qt_cdiv(m, 64);
+    hipLaunchKernelGGL(wgt ? k_pool_targets<true> : k_pool_targets<false>, dim3(B * a.tiles_r * a.tiles_c, 1, nseg), dim3(256), 0,
+                       (hipStream_t)stream, a, sg, y_step_stride, w);
+    LOSS_LAUNCHED();
     return QT_OK;
+}
+
+// Backward of every rollout loss: the gradient rows (k_loss_bwd_multi), one launch over the nseg steps.  The node sums are
+// npixs[z] and sys[z] (N), or with wgt the (N, 2) rows sys[z] alone, and lam (nseg) is given.
+static int loss_bwd(const char* fn, int kind, bool wgt, int nseg, const float* const* outs, const int* out_strides,
+                    const float* const* npixs, const float* const* sys, const int* Ns, const int32_t* const* n_devs, const float* g,
+                    const float* lam, float pos_weight, int W, float* const* gouts, void* stream) {
+    LOSS_ARG(nseg >= 1 && nseg <= 16 && outs && out_strides && (wgt ? lam != nullptr : npixs != nullptr) && sys && Ns && n_devs && g &&
+             gouts && W >= 1, "bad arguments");
+    LOSS_ARG(pos_weight > 0.0f && pos_weight <= FLT_MAX, "pos_weight must be finite and > 0");
+    LossSeg sg = {};
+    int nmax = 0;
+    for (int z = 0; z < nseg; ++z) {
+        LOSS_ARG(outs[z] && (wgt || npixs[z]) && sys[z] && gouts[z] && out_strides[z] >= 1, "null segment pointer");
+        sg.out[z] = outs[z]; sg.out_stride[z] = out_strides[z]; sg.npix[z] = wgt ? nullptr : npixs[z]; sg.sy[z] = (float*)sys[z];
+        sg.N[z] = Ns[z]; sg.n_dev[z] = n_devs[z]; sg.gout[z] = gouts[z];
+        nmax = Ns[z] > nmax ? Ns[z] : nmax;
+    }
+    LOSS_ARG((int64_t)nmax * W + 256 < ((int64_t)1 << 31), "N * W too large for 32-bit thread indices");
+    if (nmax <= 0) return QT_OK;
+    const auto rows = kind == LOSS_SSE ? (wgt ? k_loss_bwd_multi<LOSS_SSE, true> : k_loss_bwd_multi<LOSS_SSE, false>)
+                                       : (wgt ? k_loss_bwd_multi<LOSS_BCE, true> : k_loss_bwd_multi<LOSS_BCE, false>);
+    hipLaunchKernelGGL(rows, dim3(qt_cdiv((int64_t)nmax * W, 256), nseg), dim3(256), 0, (hipStream_t)stream, sg, g, lam, pos_weight, W);
+    LOSS_LAUNCHED();
+    return QT_OK;
+}
+
+extern "C" int qt_sse_rollout(int nseg, const float* const* outs, const int* out_strides, const int32_t* const* labels,
+                              const uint8_t* const* levels, const int* Ns, float* const* sys, const float* y,
+                              int64_t y_clip_stride, int64_t y_step_stride, int B, int n, int m, float* partial, void* stream) {
+    return loss_fwd(__func__, LOSS_SSE, false, nseg, outs, out_strides, labels, levels, Ns, sys, y, y_clip_stride, y_step_stride,
+                    nullptr, nullptr, 1.0f, B, n, m, partial, stream);
 }
 
 extern "C" int qt_sse_rollout_bwd(int nseg, const float* const* outs, const int* out_strides, const float* const* npixs,
                                   const float* const* sys, const int* Ns, const int32_t* const* n_devs, const float* g, int W,
                                   float* const* gouts, void* stream) {
-    QT_ARG(nseg >= 1 && nseg <= 16 && outs && out_strides && npixs && sys && Ns && n_devs && g && gouts && W >= 1, "bad arguments");
-    LossSeg sg = {};
-    int nmax = 0;
-    for (int z = 0; z < nseg; ++z) {
-        QT_ARG(outs[z] && npixs[z] && sys[z] && gouts[z] && out_strides[z] >= 1, "null segment pointer");
-        sg.out[z] = outs[z]; sg.out_stride[z] = out_strides[z]; sg.npix[z] = npixs[z]; sg.sy[z] = (float*)sys[z];
-        sg.N[z] = Ns[z]; sg.n_dev[z] = n_devs[z]; sg.gout[z] = gouts[z];
-        nmax = Ns[z] > nmax ? Ns[z] : nmax;
-    }
-    QT_ARG((int64_t)nmax * W + 256 < ((int64_t)1 << 31), "N * W too large for 32-bit thread indices");
-    if (nmax <= 0) return QT_OK;
-    hipLaunchKernelGGL(k_sse_bwd_multi, dim3(qt_cdiv((int64_t)nmax * W, 256), nseg), dim3(256), 0, (hipStream_t)stream, sg, g, W);
-    QT_LAUNCHED();
-    return QT_OK;
+    return loss_bwd(__func__, LOSS_SSE, false, nseg, outs, out_strides, npixs, sys, Ns, n_devs, g, nullptr, 1.0f, W, gouts, stream);
 }
 
 extern "C" int qt_bce_rollout(int nseg, const float* const* outs, const int* out_strides, const int32_t* const* labels,
                               const uint8_t* const* levels, const int* Ns, float* const* sys, const float* y,
                               int64_t y_clip_stride, int64_t y_step_stride, int B, int n, int m, float* partial, void* stream) {
-    QT_ARG(nseg >= 1 && nseg <= 16 && outs && out_strides && labels && levels && Ns && sys && y && partial && B > 0, "bad arguments");
-    QT_ARG(n > 0 && m > 0 && y_clip_stride >= 0 && y_step_stride >= 0, "bad sizes");
-    LossSeg sg = {};
-    for (int z = 0; z < nseg; ++z) {
-        QT_ARG(outs[z] && labels[z] && levels[z] && sys[z] && out_strides[z] >= 1 && Ns[z] >= 0, "null segment pointer");
-        sg.out[z] = outs[z]; sg.out_stride[z] = out_strides[z]; sg.labels[z] = labels[z]; sg.level[z] = levels[z];
-        sg.N[z] = Ns[z]; sg.sy[z] = sys[z];
-    }
-    const int64_t P = (int64_t)n * m;
-    hipLaunchKernelGGL(k_bce_multi, dim3(qt_cdiv(P, 1024), B, nseg), dim3(256), 0, (hipStream_t)stream, sg, y, y_clip_stride,
-                       y_step_stride, P, B, partial);
-    QT_LAUNCHED();
-    PoolArgs a = {};
-    a.img = y; a.S = 1; a.img_clip_stride = y_clip_stride; a.C = 1; a.mean = 0; a.B = B; a.n = n; a.m = m;
-    a.out_stride = 1; a.out_coff = 0; a.tiles_r = qt_cdiv(n, 64); a.tiles_c = qt_cdiv(m, 64);
-    hipLaunchKernelGGL(k_pool_targets, dim3(B * a.tiles_r * a.tiles_c, 1, nseg), dim3(256), 0, (hipStream_t)stream, a, sg,
-                       y_step_stride);
-    QT_LAUNCHED();
-    return QT_OK;
+    return loss_fwd(__func__, LOSS_BCE, false, nseg, outs, out_strides, labels, levels, Ns, sys, y, y_clip_stride, y_step_stride,
+                    nullptr, nullptr, 1.0f, B, n, m, partial, stream);
 }
 
 extern "C" int qt_bce_rollout_bwd(int nseg, const float* const* outs, const int* out_strides, const float* const* npixs,
                                   const float* const* sys, const int* Ns, const int32_t* const* n_devs, const float* g, int W,
                                   float* const* gouts, void* stream) {
-    QT_ARG(nseg >= 1 && nseg <= 16 && outs && out_strides && npixs && sys && Ns && n_devs && g && gouts && W >= 1, "bad arguments");
-    LossSeg sg = {};
-    int nmax = 0;
-    for (int z = 0; z < nseg; ++z) {
-        QT_ARG(outs[z] && npixs[z] && sys[z] && gouts[z] && out_strides[z] >= 1, "null segment pointer");
-        sg.out[z] = outs[z]; sg.out_stride[z] = out_strides[z]; sg.npix[z] = npixs[z]; sg.sy[z] = (float*)sys[z];
-        sg.N[z] = Ns[z]; sg.n_dev[z] = n_devs[z]; sg.gout[z] = gouts[z];
-        nmax = Ns[z] > nmax ? Ns[z] : nmax;
-    }
-    QT_ARG((int64_t)nmax * W + 256 < ((int64_t)1 << 31), "N * W too large for 32-bit thread indices");
-    if (nmax <= 0) return QT_OK;
-    hipLaunchKernelGGL(k_bce_bwd_multi, dim3(qt_cdiv((int64_t)nmax * W, 256), nseg), dim3(256), 0, (hipStream_t)stream, sg, g, W);
-    QT_LAUNCHED();
-    return QT_OK;
+    return loss_bwd(__func__, LOSS_BCE, false, nseg, outs, out_strides, npixs, sys, Ns, n_devs, g, nullptr, 1.0f, W, gouts, stream);
 }
 
 extern "C" int qt_wsse_rollout(int nseg, const float* const* outs, const int* out_strides, const int32_t* const* labels,
                                const uint8_t* const* levels, const int* Ns, float* const* swys, const float* y,
                                int64_t y_clip_stride, int64_t y_step_stride, const float* w, const float* lam, int B, int n, int m,
                                float* partial, void* stream) {
-    QT_ARG(nseg >= 1 && nseg <= 16 && outs && out_strides && labels && levels && Ns && swys && y && partial && B > 0, "bad arguments");
-    QT_ARG(w && lam, "null weights: w (n*m) and lam (nseg) are device arrays");
-    QT_ARG(n > 0 && m > 0 && y_clip_stride >= 0 && y_step_stride >= 0, "bad sizes");
-    LossSeg sg = {};
-    for (int z = 0; z < nseg; ++z) {
-        QT_ARG(outs[z] && labels[z] && levels[z] && swys[z] && out_strides[z] >= 1 && Ns[z] >= 0, "null segment pointer");
-        sg.out[z] = outs[z]; sg.out_stride[z] = out_strides[z]; sg.labels[z] = labels[z]; sg.level[z] = levels[z];
-        sg.N[z] = Ns[z]; sg.sy[z] = swys[z];
-    }
-    const int64_t P = (int64_t)n * m;
-    hipLaunchKernelGGL(k_wsse_multi, dim3(qt_cdiv(P, 1024), B, nseg), dim3(256), 0, (hipStream_t)stream, sg, y, y_clip_stride,
-                       y_step_stride, w, lam, P, B, partial);
-    QT_LAUNCHED();
-    PoolArgs a = {};
-    a.img = y; a.S = 1; a.img_clip_stride = y_clip_stride; a.C = 2; a.mean = 0; a.B = B; a.n = n; a.m = m;
-    a.out_stride = 2; a.out_coff = 0; a.tiles_r = qt_cdiv(n, 64); a.tiles_c = qt_cdiv(m, 64);
-    hipLaunchKernelGGL(k_pool_wtargets, dim3(B * a.tiles_r * a.tiles_c, 1, nseg), dim3(256), 0, (hipStream_t)stream, a, sg,
-                       y_step_stride, w);
-    QT_LAUNCHED();
-    return QT_OK;
+    return loss_fwd(__func__, LOSS_SSE, true, nseg, outs, out_strides, labels, levels, Ns, swys, y, y_clip_stride, y_step_stride, w,
+                    lam, 1.0f, B, n, m, partial, stream);
 }
 
 extern "C" int qt_wsse_rollout_bwd(int nseg, const float* const* outs, const int* out_strides, const float* const* swys,
                                    const int* Ns, const int32_t* const* n_devs, const float* g, const float* lam, int W,
                                    float* const* gouts, void* stream) {
-    QT_ARG(nseg >= 1 && nseg <= 16 && outs && out_strides && swys && Ns && n_devs && g && lam && gouts && W >= 1, "bad arguments");
-    LossSeg sg = {};
-    int nmax = 0;
-    for (int z = 0; z < nseg; ++z) {
-        QT_ARG(outs[z] && swys[z] && gouts[z] && out_strides[z] >= 1, "null segment pointer");
-        sg.out[z] = outs[z]; sg.out_stride[z] = out_strides[z]; sg.sy[z] = (float*)swys[z];
-        sg.N[z] = Ns[z]; sg.n_dev[z] = n_devs[z]; sg.gout[z] = gouts[z];
-        nmax = Ns[z] > nmax ? Ns[z] : nmax;
-    }
-    QT_ARG((int64_t)nmax * W + 256 < ((int64_t)1 << 31), "N * W too large for 32-bit thread indices");
-    if (nmax <= 0) return QT_OK;
-    hipLaunchKernelGGL(k_wsse_bwd_multi, dim3(qt_cdiv((int64_t)nmax * W, 256), nseg), dim3(256), 0, (hipStream_t)stream, sg, g, lam, W);
-    QT_LAUNCHED();
-    return QT_OK;
+    return loss_bwd(__func__, LOSS_SSE, true, nseg, outs, out_strides, nullptr, swys, Ns, n_devs, g, lam, 1.0f, W, gouts, stream);
 }
 
 extern "C" int qt_wbce_rollout(int nseg, const float* const* outs, const int* out_strides, const int32_t* const* labels,
                                const uint8_t* const* levels, const int* Ns, float* const* swys, const float* y,
                                int64_t y_clip_stride, int64_t y_step_stride, const float* w, const float* lam, int B, int n, int m,
                                float* partial, float pos_weight, void* stream) {
-    QT_ARG(nseg >= 1 && nseg <= 16 && outs && out_strides && labels && levels && Ns && swys && y && partial && B > 0, "bad arguments");
-    QT_ARG(w && lam, "null weights: w (n*m) and lam (nseg) are device arrays");
-    QT_ARG(pos_weight > 0.0f && pos_weight <= FLT_MAX, "pos_weight must be finite and > 0");
-    QT_ARG(n > 0 && m > 0 && y_clip_stride >= 0 && y_step_stride >= 0, "bad sizes");
-    LossSeg sg = {};
-    for (int z = 0; z < nseg; ++z) {
-        QT_ARG(outs[z] && labels[z] && levels[z] && swys[z] && out_strides[z] >= 1 && Ns[z] >= 0, "null segment pointer");
-        sg.out[z] = outs[z]; sg.out_stride[z] = out_strides[z]; sg.labels[z] = labels[z]; sg.level[z] = levels[z];
-        sg.N[z] = Ns[z]; sg.sy[z] = swys[z];
-    }
-    const int64_t P = (int64_t)n * m;
-    hipLaunchKernelGGL(k_wbce_multi, dim3(qt_cdiv(P, 1024), B, nseg), dim3(256), 0, (hipStream_t)stream, sg, y, y_clip_stride,
-                       y_step_stride, w, lam, pos_weight, P, B, partial);
-    QT_LAUNCHED();
-    PoolArgs a = {};
-    a.img = y; a.S = 1; a.img_clip_stride = y_clip_stride; a.C = 2; a.mean = 0; a.B = B; a.n = n; a.m = m;
-    a.out_stride = 2; a.out_coff = 0; a.tiles_r = qt_cdiv(n, 64); a.tiles_c = qt_cdiv(m, 64);
-    hipLaunchKernelGGL(k_pool_wtargets, dim3(B * a.tiles_r * a.tiles_c, 1, nseg), dim3(256), 0, (hipStream_t)stream, a, sg,
-                       y_step_stride, w);
-    QT_LAUNCHED();
-    return QT_OK;
+    return loss_fwd(__func__, LOSS_BCE, true, nseg, outs, out_strides, labels, levels, Ns, swys, y, y_clip_stride, y_step_stride, w,
+                    lam, pos_weight, B, n, m, partial, stream);
 }
 
 extern "C" int qt_wbce_rollout_bwd(int nseg, const float* const* outs, const int* out_strides, const float* const* swys,
                                    const int* Ns, const int32_t* const* n_devs, const float* g, const float* lam, int W,
                                    float* const* gouts, float pos_weight, void* stream) {
-    QT_ARG(nseg >= 1 && nseg <= 16 && outs && out_strides && swys && Ns && n_devs && g && lam && gouts && W >= 1, "bad arguments");
-    QT_ARG(pos_weight > 0.0f && pos_weight <= FLT_MAX, "pos_weight must be finite and > 0");
-    LossSeg sg = {};
-    int nmax = 0;
-    for (int z = 0; z < nseg; ++z) {
-        QT_ARG(outs[z] && swys[z] && gouts[z] && out_strides[z] >= 1, "null segment pointer");
-        sg.out[z] = outs[z]; sg.out_stride[z] = out_strides[z]; sg.sy[z] = (float*)swys[z];
-        sg.N[z] = Ns[z]; sg.n_dev[z] = n_devs[z]; sg.gout[z] = gouts[z];
-        nmax = Ns[z] > nmax ? Ns[z] : nmax;
-    }
-    QT_ARG((int64_t)nmax * W + 256 < ((int64_t)1 << 31), "N * W too large for 32-bit thread indices");
-    if (nmax <= 0) return QT_OK;
-    hipLaunchKernelGGL(k_wbce_bwd_multi, dim3(qt_cdiv((int64_t)nmax * W, 256), nseg), dim3(256), 0, (hipStream_t)stream, sg, g, lam,
-                       pos_weight, W);
-    QT_LAUNCHED();
-    return QT_OK;
+    return loss_bwd(__func__, LOSS_BCE, true, nseg, outs, out_strides, nullptr, swys, Ns, n_devs, g, lam, pos_weight, W, gouts, stream);
 }
 
 static int pool_launch(PoolArgs& a, bool v4, const int32_t* cell, const int32_t* n_dev, hipStream_t stream) {

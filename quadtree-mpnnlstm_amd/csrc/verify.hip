@@ -3,13 +3,13 @@
 // event_dates() with the sums of their errors (k_event_scan, k_event_sums), the per-bin probability sums of
 // reliability() (k_reliability_multi), the neighbourhood sums of fss() (k_fss_multi) and the ice-edge distances of
 // edge_distance() (k_edge_planes, k_edge_search).  All of them read the head's node values through every step's labels (no
-// frame is built), none has a gradient, and the six rollout launchers share one host-side setup (score_setup).  The training loss (k_sse*, k_pool_targets) is in transfer.hip.
+// frame is built), none has a gradient, and the six rollout launchers share one host-side setup (score_setup).  The training loss (k_sse, k_loss_multi, k_pool_targets) is in transfer.hip.
 #include "qt_common.h"
 #include "../../include/qtmpnn_edges.h"
 
 namespace {
 
-// Forecast verification of a rollout: k_sse_multi's reads with more accumulators, kept per (step, clip, tile) and per
+// Forecast verification of a rollout: k_loss_multi's reads with more accumulators, kept per (step, clip, tile) and per
 // source (the model's node values through the labels, then up to two dense baseline fields), no gradient.
 struct ScoreSeg {
     const float* out[16];         // node values of the step (column 0 of rows of out_stride floats)

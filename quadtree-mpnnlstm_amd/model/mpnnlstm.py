@@ -132,6 +132,31 @@ def bce_weights_of(weights, lead_weights, pos_weight, shape, T_out, mask=None):
     return _checked_weights(weights, lead_weights, shape, T_out, mask, pos_weight)
 
 
+def _rollout_targets(outputs, meshes, y):
+    """y as (B, T_out, W, H, 1), refused unless it is the targets of this rollout."""
+    if y.dim() == 4:
+        y = y.unsqueeze(0)
+    mesh0 = meshes[0]
+    want = (mesh0.B, len(outputs), mesh0.n, mesh0.m, 1)
+    if tuple(y.shape) != want:      # (the loss kernels read B x P targets per step straight from this buffer)
+        raise ValueError(f'targets of shape {tuple(y.shape)} for {mesh0.B} clip(s) x {len(outputs)} output steps of {mesh0.n} x {mesh0.m} '
+                         f'frames: expected (T_out, W, H, 1) or (B, T_out, W, H, 1) = {want}')
+    return y
+
+
+def _summed_loss(outputs, meshes, y, divisor, rollout, step, lw=None, *tail):
+    """The sum of a rollout's loss terms / divisor, in one reduction for all steps.  rollout: ops.rollout_*_partials, all steps in
+    one launch per kernel; where it returns None (loss_mask meshes, odd layouts) step: ops.step_*_partials, step by step,
+    composed.  lw: the LossWeights of the weighted losses; tail: what follows the weights (pos_weight)."""
+    y = y.to(outputs[0].device)
+    w, lam = (lw.to(y.device).w, lw.lam) if lw is not None else (None, None)
+    part = rollout(outputs, y, meshes, *(() if lw is None else (w, lam)), *tail)
+    if part is None:
+        part = torch.cat([step(out, y[:, t], mesh, *(() if lw is None else (w, lam[t])), *tail)
+                          for t, (out, mesh) in enumerate(zip(outputs, meshes))])
+    return part.sum() / float(divisor)
+
+
 def masked_mse(outputs, meshes, y, mask=None, binary=False, weights=None, lead_weights=None, fused=False):
     """MSELoss(y_hat[:, ~mask], y[:, ~mask]) of mpnnlstm.py:243-246 without building y_hat:
     sum over steps of the per-mesh squared error, divided by (clips x steps x unmasked pixels).
@@ -148,39 +173,19 @@ def masked_mse(outputs, meshes, y, mask=None, binary=False, weights=None, lead_w
     if fused and not binary:
         raise ValueError('fused: fused=True selects the fused binary cross-entropy and needs binary=True (the squared error always '
                          'runs through the rollout launches)')
-    if y.dim() == 4:
-        y = y.unsqueeze(0)
+    y = _rollout_targets(outputs, meshes, y)
     mesh0 = meshes[0]
-    want = (mesh0.B, len(outputs), mesh0.n, mesh0.m, 1)
-    if tuple(y.shape) != want:      # (the loss kernels read B x P targets per step straight from this buffer)
-        raise ValueError(f'targets of shape {tuple(y.shape)} for {mesh0.B} clip(s) x {len(outputs)} output steps of {mesh0.n} x {mesh0.m} '
-                         f'frames: expected (T_out, W, H, 1) or (B, T_out, W, H, 1) = {want}')
     lw = loss_weights_of(weights, lead_weights, (mesh0.n, mesh0.m), len(outputs), mask, binary)
     if lw is not None:
-        y = y.to(outputs[0].device)
-        lw.to(y.device)
-        part = ops.rollout_wsse_partials(outputs, y, meshes, lw.w, lw.lam) if y.shape[1] == len(outputs) else None
-        if part is None:        # loss_mask meshes, odd layouts: step by step, composed (ops.step_wsse_partials)
-            part = torch.cat([ops.step_wsse_partials(out, y[:, t], mesh, lw.w, lw.lam[t])
-                              for t, (out, mesh) in enumerate(zip(outputs, meshes))])
-        return part.sum() / float(mesh0.B * lw.sum_lam * lw.sum_w)
+        return _summed_loss(outputs, meshes, y, mesh0.B * lw.sum_lam * lw.sum_w, ops.rollout_wsse_partials, ops.step_wsse_partials, lw)
     mask = host_mask(mask)
     n_valid = mesh0.P if mask is None else int((~mask).sum())
-    if binary and fused:
-        y = y.to(outputs[0].device)
-        part = ops.rollout_bce_partials(outputs, y, meshes) if y.shape[1] == len(outputs) else None
-        if part is None:        # loss_mask meshes, odd layouts: step by step, composed (ops.step_bce_partials)
-            part = torch.cat([ops.step_bce_partials(out, y[:, t], mesh) for t, (out, mesh) in enumerate(zip(outputs, meshes))])
-        return part.sum() / float(mesh0.B * len(outputs) * n_valid)
-    if binary:
+    if binary and not fused:
         y_hat = torch.stack([unflatten(o, ms, (ms.n, ms.m)).reshape(ms.B, ms.n, ms.m, 1) for o, ms in zip(outputs, meshes)], 1)
         keep = torch.ones(mesh0.n, mesh0.m, dtype=torch.bool) if mask is None else ~torch.as_tensor(mask)
         return torch.nn.functional.binary_cross_entropy(y_hat[:, :, keep], y.to(y_hat.device)[:, :, keep])
-    y = y.to(outputs[0].device)
-    part = ops.rollout_sse_partials(outputs, y, meshes) if y.shape[1] == len(outputs) else None     # all steps in one launch
-    if part is None:
-        part = torch.cat([ops.step_sse_partials(out, y[:, t], mesh) for t, (out, mesh) in enumerate(zip(outputs, meshes))])
-    return part.sum() / float(mesh0.B * len(outputs) * n_valid)        # one reduction for all steps
+    loss = (ops.rollout_bce_partials, ops.step_bce_partials) if binary else (ops.rollout_sse_partials, ops.step_sse_partials)
+    return _summed_loss(outputs, meshes, y, mesh0.B * len(outputs) * n_valid, *loss)
 
 
 def masked_bce(outputs, meshes, y, mask=None, weights=None, lead_weights=None, pos_weight=1.0):
@@ -195,22 +200,12 @@ def masked_bce(outputs, meshes, y, mask=None, weights=None, lead_weights=None, p
     masked_mse(binary=True, fused=True).  Always the rollout launches (ops.rollout_wbce_partials; ops.step_wbce_partials for
     loss_mask meshes and odd layouts): no frames, no host read, capturable, the same bits on every run.  Every refusal is a
     ValueError that names the argument, before any launch."""
-    if y.dim() == 4:
-        y = y.unsqueeze(0)
+    y = _rollout_targets(outputs, meshes, y)
     mesh0 = meshes[0]
-    want = (mesh0.B, len(outputs), mesh0.n, mesh0.m, 1)
-    if tuple(y.shape) != want:      # (the loss kernels read B x P targets per step straight from this buffer)
-        raise ValueError(f'targets of shape {tuple(y.shape)} for {mesh0.B} clip(s) x {len(outputs)} output steps of {mesh0.n} x {mesh0.m} '
-                         f'frames: expected (T_out, W, H, 1) or (B, T_out, W, H, 1) = {want}')
     lw = _checked_weights(weights, lead_weights, (mesh0.n, mesh0.m), len(outputs), mask)
     pos_weight = ops.check_pos_weight(pos_weight)
-    y = y.to(outputs[0].device)
-    lw.to(y.device)
-    part = ops.rollout_wbce_partials(outputs, y, meshes, lw.w, lw.lam, pos_weight) if y.shape[1] == len(outputs) else None
-    if part is None:        # loss_mask meshes, odd layouts: step by step, composed (ops.step_wbce_partials)
-        part = torch.cat([ops.step_wbce_partials(out, y[:, t], mesh, lw.w, lw.lam[t], pos_weight)
-                          for t, (out, mesh) in enumerate(zip(outputs, meshes))])
-    return part.sum() / float(mesh0.B * lw.sum_lam * lw.sum_w)
+    return _summed_loss(outputs, meshes, y, mesh0.B * lw.sum_lam * lw.sum_w, ops.rollout_wbce_partials, ops.step_wbce_partials, lw,
+                        pos_weight)
 
 
 def launch_frame(x):

@@ -1898,185 +1898,62 @@ def _full_rows(out):
     return out
 
 
-class _RolloutSSE(Function):
-    """_StepSSE for all output steps of a rollout in one launch per kernel (qt_sse_rollout / _bwd): the loss touches every
-    step once, after the last one, so the 3 x T_out small launches (squared error, per-node target sums for the gradient,
-    the gradient rows) become 3 per 16 steps.  y: (B, T, P) contiguous fp32; outs[t]: contiguous (N_t, W) matrices whose
-    column 0 is the prediction."""
+def _loss_slices(T):
+    """The launches of a rollout loss over T steps, 16 steps each: (z0, n, seg) with seg(values of all T steps) -> the ctypes
+    array of the n steps from z0, ints as they are and tensors (or None) as addresses."""
+    import ctypes
+    for z0 in range(0, T, 16):
+        n = min(16, T - z0)
+
+        def seg(vals, z0=z0, n=n):
+            vals = list(vals)[z0:z0 + n]
+            if isinstance(vals[0], int):
+                return (ctypes.c_int * n)(*vals)
+            return (ctypes.c_void_p * n)(*[None if v is None else v.data_ptr() for v in vals])
+        yield z0, n, seg
+
+
+class _RolloutLoss(Function):
+    """_StepSSE for all output steps of a rollout in one launch per kernel (qt_{sse,bce,wsse,wbce}_rollout / _bwd): the loss
+    touches every step once, after the last one, so the 3 x T_out small launches (the partial sums, per-node target sums for the
+    gradient, the gradient rows) become 3 per 16 steps.  y: (B, T, P) contiguous fp32; outs[t]: contiguous (N_t, W) matrices
+    whose column 0 is the prediction.  kind: 'sse', partial sums of (out_t[label] - y)^2, or 'bce', those of torch's BCELoss
+    numerator -(y max(log o, -100) + (1 - y) max(log(1 - o), -100)), o = column 0 of outs[t] (the binary head's probabilities).
+    weighted: each term times lam[t] w[p], w: (P,) and lam: (T,) fp32 device tensors, no gradient; the weighted 'bce' has
+    pos_weight on its y = 1 side, a Python float > 0, passed by value (a captured graph keeps it).  The backward reads per node
+    the target sum (N_t), or weighted [sum w | sum w y] (N_t, 2), summed by the same pooling tree."""
 
     @staticmethod
-    def forward(ctx, y, meshes, *outs):
-        import ctypes
+    def forward(ctx, kind, weighted, y, meshes, w, lam, pos_weight, *outs):
         B, T, P = y.shape
         m0 = meshes[0]
         nt = -(P // -1024)
         part = outs[0].new_empty(T, B * nt)
-        sys_ = [o.new_empty(ms.N) for o, ms in zip(outs, meshes)]
-        vp, ip = ctypes.c_void_p, ctypes.c_int
-        for z0 in range(0, T, 16):
-            sl = slice(z0, min(z0 + 16, T))
-            n = sl.stop - sl.start
-            _lib.call('qt_sse_rollout', n, (vp * n)(*[o.data_ptr() for o in outs[sl]]), (ip * n)(*[o.stride(0) for o in outs[sl]]),
-                      (vp * n)(*[ms.labels.data_ptr() for ms in meshes[sl]]), (vp * n)(*[ms.level.data_ptr() for ms in meshes[sl]]),
-                      (ip * n)(*[ms.N for ms in meshes[sl]]), (vp * n)(*[t.data_ptr() for t in sys_[sl]]),
-                      y.data_ptr() + 4 * z0 * P, T * P, P, B, m0.n, m0.m, ptr(part[z0:]))
-        ctx.save_for_backward(*outs, *sys_)
-        ctx.meshes = meshes
+        sums = [o.new_empty(ms.N, 2) if weighted else o.new_empty(ms.N) for o, ms in zip(outs, meshes)]
+        entry = 'qt_' + ('w' if weighted else '') + kind + '_rollout'
+        pw = () if pos_weight is None else (pos_weight,)
+        for z0, n, seg in _loss_slices(T):
+            wl = (ptr(w), lam.data_ptr() + 4 * z0) if weighted else ()
+            _lib.call(entry, n, seg(outs), seg(o.stride(0) for o in outs), seg(ms.labels for ms in meshes),
+                      seg(ms.level for ms in meshes), seg(ms.N for ms in meshes), seg(sums), y.data_ptr() + 4 * z0 * P, T * P, P,
+                      *wl, B, m0.n, m0.m, ptr(part[z0:]), *pw)
+        ctx.save_for_backward(*outs, *sums, *((lam,) if weighted else ()))
+        ctx.entry, ctx.meshes, ctx.pw = entry + '_bwd', meshes, pw
         return part
 
     @staticmethod
     def backward(ctx, g):
-        import ctypes
         meshes = ctx.meshes
         T = len(meshes)
-        outs, sys_ = ctx.saved_tensors[:T], ctx.saved_tensors[T:]
+        outs, sums, lam = ctx.saved_tensors[:T], ctx.saved_tensors[T:2 * T], ctx.saved_tensors[2 * T:]      # lam: weighted only
         gouts = [torch.empty_like(o) for o in outs]
         g1 = g.reshape(-1)[:1].contiguous()      # every partial has the same upstream gradient (they are only ever summed)
-        vp, ip = ctypes.c_void_p, ctypes.c_int
         W = outs[0].shape[1]
-        for z0 in range(0, T, 16):
-            sl = slice(z0, min(z0 + 16, T))
-            n = sl.stop - sl.start
-            _lib.call('qt_sse_rollout_bwd', n, (vp * n)(*[o.data_ptr() for o in outs[sl]]), (ip * n)(*[o.stride(0) for o in outs[sl]]),
-                      (vp * n)(*[ms.npix.data_ptr() for ms in meshes[sl]]), (vp * n)(*[t.data_ptr() for t in sys_[sl]]),
-                      (ip * n)(*[ms.N for ms in meshes[sl]]), (vp * n)(*[ms.n_dev.data_ptr() if ms.n_dev is not None else None for ms in meshes[sl]]),
-                      ptr(g1), W, (vp * n)(*[t.data_ptr() for t in gouts[sl]]))
-        return (None, None, *gouts)
-
-
-def rollout_sse_partials(outputs, y, meshes):
-    """Partial sums of the squared error of every output step (their total is the MSE numerator), or None when the steps
-    cannot share the launches (masked-per-pixel preset meshes, odd layouts): the caller then goes step by step."""
-    if not outputs or any(ms.loss_mask is not None or ms.N == 0 for ms in meshes):
-        return None
-    outs = [_full_rows(o) for o in outputs]
-    W = outs[0].shape[1]
-    if any(o.dtype != torch.float32 or not o.is_contiguous() or o.shape[1] != W or not o.is_cuda for o in outs):
-        return None
-    B, T = meshes[0].B, len(outs)
-    if y.dtype != torch.float32 or not y.is_contiguous() or y.numel() != B * T * meshes[0].P:
-        return None
-    return _RolloutSSE.apply(y.view(B, T, meshes[0].P), tuple(meshes), *outs)
-
-
-class _RolloutBCE(Function):
-    """_RolloutSSE for the binary head (qt_bce_rollout / _bwd): partial sums of torch's BCELoss numerator,
-    -(y max(log o, -100) + (1 - y) max(log(1 - o), -100)), o = column 0 of outs[t], three launches per 16 steps.  The backward
-    reads the same per-node target sums as _RolloutSSE's."""
-
-    @staticmethod
-    def forward(ctx, y, meshes, *outs):
-        import ctypes
-        B, T, P = y.shape
-        m0 = meshes[0]
-        nt = -(P // -1024)
-        part = outs[0].new_empty(T, B * nt)
-        sys_ = [o.new_empty(ms.N) for o, ms in zip(outs, meshes)]
-        vp, ip = ctypes.c_void_p, ctypes.c_int
-        for z0 in range(0, T, 16):
-            sl = slice(z0, min(z0 + 16, T))
-            n = sl.stop - sl.start
-            _lib.call('qt_bce_rollout', n, (vp * n)(*[o.data_ptr() for o in outs[sl]]), (ip * n)(*[o.stride(0) for o in outs[sl]]),
-                      (vp * n)(*[ms.labels.data_ptr() for ms in meshes[sl]]), (vp * n)(*[ms.level.data_ptr() for ms in meshes[sl]]),
-                      (ip * n)(*[ms.N for ms in meshes[sl]]), (vp * n)(*[t.data_ptr() for t in sys_[sl]]),
-                      y.data_ptr() + 4 * z0 * P, T * P, P, B, m0.n, m0.m, ptr(part[z0:]))
-        ctx.save_for_backward(*outs, *sys_)
-        ctx.meshes = meshes
-        return part
-
-    @staticmethod
-    def backward(ctx, g):
-        import ctypes
-        meshes = ctx.meshes
-        T = len(meshes)
-        outs, sys_ = ctx.saved_tensors[:T], ctx.saved_tensors[T:]
-        gouts = [torch.empty_like(o) for o in outs]
-        g1 = g.reshape(-1)[:1].contiguous()      # every partial has the same upstream gradient (they are only ever summed)
-        vp, ip = ctypes.c_void_p, ctypes.c_int
-        W = outs[0].shape[1]
-        for z0 in range(0, T, 16):
-            sl = slice(z0, min(z0 + 16, T))
-            n = sl.stop - sl.start
-            _lib.call('qt_bce_rollout_bwd', n, (vp * n)(*[o.data_ptr() for o in outs[sl]]), (ip * n)(*[o.stride(0) for o in outs[sl]]),
-                      (vp * n)(*[ms.npix.data_ptr() for ms in meshes[sl]]), (vp * n)(*[t.data_ptr() for t in sys_[sl]]),
-                      (ip * n)(*[ms.N for ms in meshes[sl]]), (vp * n)(*[ms.n_dev.data_ptr() if ms.n_dev is not None else None for ms in meshes[sl]]),
-                      ptr(g1), W, (vp * n)(*[t.data_ptr() for t in gouts[sl]]))
-        return (None, None, *gouts)
-
-
-def rollout_bce_partials(outputs, y, meshes):
-    """Partial sums of the binary cross-entropy of every output step (their total is the numerator of torch's BCELoss mean), or
-    None exactly where rollout_sse_partials returns None (per-pixel loss_mask of preset meshes, odd layouts, N == 0): the caller
-    then goes step by step through step_bce_partials.  outputs[t]: probabilities in [0, 1] (the binary head's sigmoid)."""
-    if not outputs or any(ms.loss_mask is not None or ms.N == 0 for ms in meshes):
-        return None
-    outs = [_full_rows(o) for o in outputs]
-    W = outs[0].shape[1]
-    if any(o.dtype != torch.float32 or not o.is_contiguous() or o.shape[1] != W or not o.is_cuda for o in outs):
-        return None
-    B, T = meshes[0].B, len(outs)
-    if y.dtype != torch.float32 or not y.is_contiguous() or y.numel() != B * T * meshes[0].P:
-        return None
-    return _RolloutBCE.apply(y.view(B, T, meshes[0].P), tuple(meshes), *outs)
-
-
-def step_bce_partials(out, y, mesh):
-    """One step of the binary cross-entropy where the rollout launches do not apply: the sum over the pixels that have a node and
-    are not under mesh.loss_mask of torch's BCELoss terms.  A composition of differentiable ops on gather_pixels, like
-    step_wsse_partials: NOT the tuned path."""
-    keep = mesh.labels.view(mesh.B, mesh.P) >= 0
-    if mesh.loss_mask is not None:
-        keep = keep & (mesh.loss_mask == 0).view(1, mesh.P)
-    img = gather_pixels(out[:, :1], mesh).view(mesh.B, mesh.P)
-    # (a pixel without a node gathers 0: it gets a harmless probability before the log, and weight 0 after it)
-    img = torch.where(keep, img, torch.full_like(img, 0.5))
-    terms = torch.nn.functional.binary_cross_entropy(img, y.reshape(mesh.B, mesh.P).float(), reduction='none')
-    return (terms * keep.float()).sum().view(1)
-
-
-class _RolloutWSSE(Function):
-    """_RolloutSSE with a weight per pixel and per output step (qt_wsse_rollout / _bwd): partial sums of
-    lam[t] w[p] (out_t[label] - y)^2, three launches per 16 steps.  w: (P,) and lam: (T,) fp32 device tensors, no gradient.
-    The backward reads per node [sum w | sum w y] (N_t, 2), summed by the pooling tree of the unweighted target sums."""
-
-    @staticmethod
-    def forward(ctx, y, meshes, w, lam, *outs):
-        import ctypes
-        B, T, P = y.shape
-        m0 = meshes[0]
-        nt = -(P // -1024)
-        part = outs[0].new_empty(T, B * nt)
-        swys = [o.new_empty(ms.N, 2) for o, ms in zip(outs, meshes)]
-        vp, ip = ctypes.c_void_p, ctypes.c_int
-        for z0 in range(0, T, 16):
-            sl = slice(z0, min(z0 + 16, T))
-            n = sl.stop - sl.start
-            _lib.call('qt_wsse_rollout', n, (vp * n)(*[o.data_ptr() for o in outs[sl]]), (ip * n)(*[o.stride(0) for o in outs[sl]]),
-                      (vp * n)(*[ms.labels.data_ptr() for ms in meshes[sl]]), (vp * n)(*[ms.level.data_ptr() for ms in meshes[sl]]),
-                      (ip * n)(*[ms.N for ms in meshes[sl]]), (vp * n)(*[t.data_ptr() for t in swys[sl]]),
-                      y.data_ptr() + 4 * z0 * P, T * P, P, ptr(w), lam.data_ptr() + 4 * z0, B, m0.n, m0.m, ptr(part[z0:]))
-        ctx.save_for_backward(lam, *outs, *swys)
-        ctx.meshes = meshes
-        return part
-
-    @staticmethod
-    def backward(ctx, g):
-        import ctypes
-        meshes = ctx.meshes
-        T = len(meshes)
-        lam, outs, swys = ctx.saved_tensors[0], ctx.saved_tensors[1:1 + T], ctx.saved_tensors[1 + T:]
-        gouts = [torch.empty_like(o) for o in outs]
-        g1 = g.reshape(-1)[:1].contiguous()      # every partial has the same upstream gradient (they are only ever summed)
-        vp, ip = ctypes.c_void_p, ctypes.c_int
-        W = outs[0].shape[1]
-        for z0 in range(0, T, 16):
-            sl = slice(z0, min(z0 + 16, T))
-            n = sl.stop - sl.start
-            _lib.call('qt_wsse_rollout_bwd', n, (vp * n)(*[o.data_ptr() for o in outs[sl]]), (ip * n)(*[o.stride(0) for o in outs[sl]]),
-                      (vp * n)(*[t.data_ptr() for t in swys[sl]]), (ip * n)(*[ms.N for ms in meshes[sl]]),
-                      (vp * n)(*[ms.n_dev.data_ptr() if ms.n_dev is not None else None for ms in meshes[sl]]),
-                      ptr(g1), lam.data_ptr() + 4 * z0, W, (vp * n)(*[t.data_ptr() for t in gouts[sl]]))
-        return (None, None, None, None, *gouts)
+        for z0, n, seg in _loss_slices(T):
+            node_sums = (seg(sums),) if lam else (seg(ms.npix for ms in meshes), seg(sums))
+            _lib.call(ctx.entry, n, seg(outs), seg(o.stride(0) for o in outs), *node_sums, seg(ms.N for ms in meshes),
+                      seg(ms.n_dev for ms in meshes), ptr(g1), *(t.data_ptr() + 4 * z0 for t in lam), W, seg(gouts), *ctx.pw)
+        return (None,) * 7 + (*gouts,)
 
 
 def _check_loss_weights(w, lam, mesh, T):
@@ -2085,11 +1962,9 @@ def _check_loss_weights(w, lam, mesh, T):
             raise ValueError(f'{what}: a contiguous fp32 device tensor of {count} entries is needed')
 
 
-def rollout_wsse_partials(outputs, y, meshes, w, lam):
-    """Partial sums of lam[t] * w[p] * (squared error) of every output step (their total is the numerator of the weighted
-    loss), or None exactly where rollout_sse_partials returns None (per-pixel loss_mask of preset meshes, odd layouts): the
-    caller then goes step by step through step_wsse_partials.  w: (W, H) or (P,) pixel weights, lam: (T,) step weights, both
-    fp32 on the outputs' device and already checked (non-negative, finite); they carry no gradient."""
+def _rollout_partials(kind, outputs, y, meshes, weights=None, pos_weight=None):
+    """The partial sums of _RolloutLoss, or None when the steps cannot share the launches (masked-per-pixel preset meshes, odd
+    layouts, N == 0).  weights: None or (w, lam), checked once the launches are known to apply."""
     if not outputs or any(ms.loss_mask is not None or ms.N == 0 for ms in meshes):
         return None
     outs = [_full_rows(o) for o in outputs]
@@ -2099,67 +1974,32 @@ def rollout_wsse_partials(outputs, y, meshes, w, lam):
     B, T = meshes[0].B, len(outs)
     if y.dtype != torch.float32 or not y.is_contiguous() or y.numel() != B * T * meshes[0].P:
         return None
-    _check_loss_weights(w, lam, meshes[0], T)
-    return _RolloutWSSE.apply(y.view(B, T, meshes[0].P), tuple(meshes), w.view(-1), lam, *outs)
+    w, lam = weights or (None, None)
+    if weights is not None:
+        _check_loss_weights(w, lam, meshes[0], T)
+        w = w.view(-1)
+    return _RolloutLoss.apply(kind, weights is not None, y.view(B, T, meshes[0].P), tuple(meshes), w, lam, pos_weight, *outs)
 
 
-def step_wsse_partials(out, y, mesh, w, lam_t):
-    """One step of the weighted squared error where the rollout launches do not apply: lam_t * sum of keep * w * d^2 with
-    keep = the pixel has a node and is not under mesh.loss_mask.  A composition of differentiable ops (the counted weights,
-    gather_pixels, then the step's weight), like the loss_mask branch of step_sse_partials: NOT the tuned path.  w: (P,)
-    fp32 device tensor, lam_t: 0-dim device tensor."""
-    keep = (mesh.labels.view(mesh.B, mesh.P) >= 0).float() * w.view(1, mesh.P)
-    if mesh.loss_mask is not None:
-        keep = keep * (mesh.loss_mask == 0).float().view(1, mesh.P)
-    img = gather_pixels(out[:, :1], mesh).view(mesh.B, mesh.P)
-    d = img - y.reshape(mesh.B, mesh.P).float()
-    return (lam_t * (keep * (d * d)).sum()).view(1)
+def rollout_sse_partials(outputs, y, meshes):
+    """Partial sums of the squared error of every output step (their total is the MSE numerator), or None when the steps
+    cannot share the launches (masked-per-pixel preset meshes, odd layouts): the caller then goes step by step."""
+    return _rollout_partials('sse', outputs, y, meshes)
 
 
-class _RolloutWBCE(Function):
-    """_RolloutWSSE for the binary head (qt_wbce_rollout / _bwd): partial sums of
-    -lam[t] w[p] (pos_weight y max(log o, -100) + (1 - y) max(log(1 - o), -100)), o = column 0 of outs[t], three launches per 16
-    steps.  w: (P,) and lam: (T,) fp32 device tensors, no gradient; pos_weight: a Python float > 0, passed by value (a captured
-    graph keeps it).  The backward reads the same per-node [sum w | sum w y] (N_t, 2) as _RolloutWSSE's."""
+def rollout_bce_partials(outputs, y, meshes):
+    """Partial sums of the binary cross-entropy of every output step (their total is the numerator of torch's BCELoss mean), or
+    None exactly where rollout_sse_partials returns None (per-pixel loss_mask of preset meshes, odd layouts, N == 0): the caller
+    then goes step by step through step_bce_partials.  outputs[t]: probabilities in [0, 1] (the binary head's sigmoid)."""
+    return _rollout_partials('bce', outputs, y, meshes)
 
-    @staticmethod
-    def forward(ctx, y, meshes, w, lam, pos_weight, *outs):
-        import ctypes
-        B, T, P = y.shape
-        m0 = meshes[0]
-        nt = -(P // -1024)
-        part = outs[0].new_empty(T, B * nt)
-        swys = [o.new_empty(ms.N, 2) for o, ms in zip(outs, meshes)]
-        vp, ip = ctypes.c_void_p, ctypes.c_int
-        for z0 in range(0, T, 16):
-            sl = slice(z0, min(z0 + 16, T))
-            n = sl.stop - sl.start
-            _lib.call('qt_wbce_rollout', n, (vp * n)(*[o.data_ptr() for o in outs[sl]]), (ip * n)(*[o.stride(0) for o in outs[sl]]),
-                      (vp * n)(*[ms.labels.data_ptr() for ms in meshes[sl]]), (vp * n)(*[ms.level.data_ptr() for ms in meshes[sl]]),
-                      (ip * n)(*[ms.N for ms in meshes[sl]]), (vp * n)(*[t.data_ptr() for t in swys[sl]]),
-                      y.data_ptr() + 4 * z0 * P, T * P, P, ptr(w), lam.data_ptr() + 4 * z0, B, m0.n, m0.m, ptr(part[z0:]), pos_weight)
-        ctx.save_for_backward(lam, *outs, *swys)
-        ctx.meshes, ctx.pos_weight = meshes, pos_weight
-        return part
 
-    @staticmethod
-    def backward(ctx, g):
-        import ctypes
-        meshes = ctx.meshes
-        T = len(meshes)
-        lam, outs, swys = ctx.saved_tensors[0], ctx.saved_tensors[1:1 + T], ctx.saved_tensors[1 + T:]
-        gouts = [torch.empty_like(o) for o in outs]
-        g1 = g.reshape(-1)[:1].contiguous()      # every partial has the same upstream gradient (they are only ever summed)
-        vp, ip = ctypes.c_void_p, ctypes.c_int
-        W = outs[0].shape[1]
-        for z0 in range(0, T, 16):
-            sl = slice(z0, min(z0 + 16, T))
-            n = sl.stop - sl.start
-            _lib.call('qt_wbce_rollout_bwd', n, (vp * n)(*[o.data_ptr() for o in outs[sl]]), (ip * n)(*[o.stride(0) for o in outs[sl]]),
-                      (vp * n)(*[t.data_ptr() for t in swys[sl]]), (ip * n)(*[ms.N for ms in meshes[sl]]),
-                      (vp * n)(*[ms.n_dev.data_ptr() if ms.n_dev is not None else None for ms in meshes[sl]]),
-                      ptr(g1), lam.data_ptr() + 4 * z0, W, (vp * n)(*[t.data_ptr() for t in gouts[sl]]), ctx.pos_weight)
-        return (None, None, None, None, None, *gouts)
+def rollout_wsse_partials(outputs, y, meshes, w, lam):
+    """Partial sums of lam[t] * w[p] * (squared error) of every output step (their total is the numerator of the weighted
+    loss), or None exactly where rollout_sse_partials returns None (per-pixel loss_mask of preset meshes, odd layouts): the
+    caller then goes step by step through step_wsse_partials.  w: (W, H) or (P,) pixel weights, lam: (T,) step weights, both
+    fp32 on the outputs' device and already checked (non-negative, finite); they carry no gradient."""
+    return _rollout_partials('sse', outputs, y, meshes, (w, lam))
 
 
 def check_pos_weight(pos_weight):
@@ -2179,18 +2019,47 @@ def rollout_wbce_partials(outputs, y, meshes, w, lam, pos_weight=1.0):
     loss_mask of preset meshes, odd layouts): the caller then goes step by step through step_wbce_partials.  outputs[t]:
     probabilities in [0, 1]; w: (W, H) or (P,) pixel weights, lam: (T,) step weights, both fp32 on the outputs' device and already
     checked (non-negative, finite), no gradient; pos_weight: a finite number > 0."""
-    pos_weight = check_pos_weight(pos_weight)
-    if not outputs or any(ms.loss_mask is not None or ms.N == 0 for ms in meshes):
-        return None
-    outs = [_full_rows(o) for o in outputs]
-    W = outs[0].shape[1]
-    if any(o.dtype != torch.float32 or not o.is_contiguous() or o.shape[1] != W or not o.is_cuda for o in outs):
-        return None
-    B, T = meshes[0].B, len(outs)
-    if y.dtype != torch.float32 or not y.is_contiguous() or y.numel() != B * T * meshes[0].P:
-        return None
-    _check_loss_weights(w, lam, meshes[0], T)
-    return _RolloutWBCE.apply(y.view(B, T, meshes[0].P), tuple(meshes), w.view(-1), lam, pos_weight, *outs)
+    return _rollout_partials('bce', outputs, y, meshes, (w, lam), check_pos_weight(pos_weight))
+
+
+def _step_keep(mesh):
+    """(B, P) bool: the pixel has a node and is not under mesh.loss_mask."""
+    keep = mesh.labels.view(mesh.B, mesh.P) >= 0
+    if mesh.loss_mask is not None:
+        keep = keep & (mesh.loss_mask == 0).view(1, mesh.P)
+    return keep
+
+
+def _step_pixels(out, y, mesh, keep=None):
+    """One step as pixels, (B, P) each: column 0 of `out` gathered through the mesh, and the target in fp32.  keep (the binary
+    losses): a pixel without a node gathers 0: it gets a harmless probability before the log, and weight 0 after it."""
+    img = gather_pixels(out[:, :1], mesh).view(mesh.B, mesh.P)
+    if keep is not None:
+        img = torch.where(keep, img, torch.full_like(img, 0.5))
+    return img, y.reshape(mesh.B, mesh.P).float()
+
+
+def step_bce_partials(out, y, mesh):
+    """One step of the binary cross-entropy where the rollout launches do not apply: the sum over the pixels that have a node and
+    are not under mesh.loss_mask of torch's BCELoss terms.  A composition of differentiable ops on gather_pixels, like
+    step_wsse_partials: NOT the tuned path."""
+    keep = _step_keep(mesh)
+    img, yt = _step_pixels(out, y, mesh, keep)
+    terms = torch.nn.functional.binary_cross_entropy(img, yt, reduction='none')
+    return (terms * keep.float()).sum().view(1)
+
+
+def step_wsse_partials(out, y, mesh, w, lam_t):
+    """One step of the weighted squared error where the rollout launches do not apply: lam_t * sum of keep * w * d^2 with
+    keep = the pixel has a node and is not under mesh.loss_mask.  A composition of differentiable ops (the counted weights,
+    gather_pixels, then the step's weight), like the loss_mask branch of step_sse_partials: NOT the tuned path.  w: (P,)
+    fp32 device tensor, lam_t: 0-dim device tensor."""
+    keep = (mesh.labels.view(mesh.B, mesh.P) >= 0).float() * w.view(1, mesh.P)
+    if mesh.loss_mask is not None:
+        keep = keep * (mesh.loss_mask == 0).float().view(1, mesh.P)
+    img, yt = _step_pixels(out, y, mesh)
+    d = img - yt
+    return (lam_t * (keep * (d * d)).sum()).view(1)
 
 
 def step_wbce_partials(out, y, mesh, w, lam_t, pos_weight=1.0):
@@ -2199,13 +2068,8 @@ def step_wbce_partials(out, y, mesh, w, lam_t, pos_weight=1.0):
     at -100 before the products.  A composition of differentiable ops on gather_pixels, like step_wsse_partials /
     step_bce_partials: NOT the tuned path.  w: (P,) fp32 device tensor, lam_t: 0-dim device tensor."""
     pos_weight = check_pos_weight(pos_weight)
-    keep = mesh.labels.view(mesh.B, mesh.P) >= 0
-    if mesh.loss_mask is not None:
-        keep = keep & (mesh.loss_mask == 0).view(1, mesh.P)
-    img = gather_pixels(out[:, :1], mesh).view(mesh.B, mesh.P)
-    # (a pixel without a node gathers 0: it gets a harmless probability before the log, and weight 0 after it)
-    img = torch.where(keep, img, torch.full_like(img, 0.5))
-    yt = y.reshape(mesh.B, mesh.P).float()
+    keep = _step_keep(mesh)
+    img, yt = _step_pixels(out, y, mesh, keep)
     # torch's binary_cross_entropy with the target's own weight pos_weight y + (1 - y) on each side: its clamp, and its backward
     bce = torch.nn.functional.binary_cross_entropy
     terms = pos_weight * bce(img, torch.ones_like(img), weight=yt, reduction='none') \
@@ -2427,15 +2291,10 @@ def step_sse_partials(out, y, mesh):
         # homogeneous preset mesh: partly masked cells keep all their pixels, so the mask is applied per pixel
         # (composition of differentiable ops; this preset-mesh path is not the tuned one)
         keep = (mesh.loss_mask == 0).float().view(1, mesh.P)
-        img = gather_pixels(out[:, :1], mesh).view(mesh.B, mesh.P)
-        d = (img - y.reshape(mesh.B, mesh.P).float()) * keep
+        img, yt = _step_pixels(out, y, mesh)
+        d = (img - yt) * keep
         return (d * d).sum().view(1)
-    base = out._base
-    if (base is not None and base.dim() == 2 and out.dim() == 2 and out.shape[1] == 1 and base.is_contiguous()
-            and base.shape[0] == out.shape[0] and out.storage_offset() == base.storage_offset()
-            and out.stride(0) == base.shape[1] and base.dtype == torch.float32):
-        out = base
-    return _StepSSE.apply(out, y, mesh)
+    return _StepSSE.apply(_full_rows(out), y, mesh)
 
 
 def step_sse(out, y, mesh):

@@ -491,7 +491,7 @@ def _step_meshes(tag, T, static):
 @pytest.mark.parametrize('static', [False, True])
 @pytest.mark.parametrize('tag', ['M', 'D'])
 def test_rollout_sse_over_two_launches(tag, static):
-    """_RolloutSSE (qt_sse_rollout / _bwd) over T_out = 18 steps = two launches (16 + 2), a different mesh at every step, outputs
+    """_RolloutLoss 'sse' (qt_sse_rollout / _bwd) over T_out = 18 steps = two launches (16 + 2), a different mesh at every step, outputs
     (N_t, 4): the total, every step's own partial sums (a step that wrote into another step's slots shows there) and every step's
     gradient rows.  M: B = 2, P = 15000 = 14 * 1024 + 664; D: B = 3.  Static: capacity rows of the outputs hold NaN."""
     from qtmpnn import ops

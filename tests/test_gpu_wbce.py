@@ -7,11 +7,13 @@ partial sum lam w times the terms pw y L1, L0 and -y L0 of every pixel; for a gr
 |g| lam (|o| sw + (pw + o (1 - pw)) sum w |y|) / max(o (1 - o), 1e-12)); an entry with mag = 0 -- a step of lead weight 0, a node
 whose pixels all have weight 0, columns 1.. -- is exactly 0.  LIMIT = 50 is derived, not measured: 25 roundings, doubled, and both
 kernels as written reach 25.
-  A partial sum (k_wbce_multi) is k_bce_multi's chain of 22 with three more products: the logarithm (logf for L1, log1pf(-o) for
+  A partial sum (k_loss_multi, the weighted term) is the unweighted term's chain of 22 with three more products: the logarithm
+  (logf for L1, log1pf(-o) for
   L0; the device library follows the OpenCL accuracy table, log <= 3 ulp and log1p <= 2 ulp, and 3 ulp are 6 units of 2^-24), the
   difference 1 - y, the product pw y, the two products with the logarithms and their sum (5), the factors w and lam (2), four
   serial adds per thread (4), six butterfly steps (6), two adds of the four wave sums (2): 6 + 5 + 2 + 12 = 25.
-  A gradient row of a 64 x 64 cell (k_pool_wtargets, then k_wbce_bwd_multi): the product w y at the load (1), the 2 x 2 sum (2),
+  A gradient row of a 64 x 64 cell (k_pool_targets<true>, then k_loss_bwd_multi): the product w y at the load (1), the 2 x 2 sum
+  (2),
   the four serial adds of the 4 x 4 sum (4), four pyramid levels of a 4-way sum each (8); the factor o + pw (1 - o), which is
   pw + o (1 - pw) as a sum of two non-negative terms (3), its product with swy (1), the subtraction from o sw (1; o sw is the
   shorter branch), 1 - o and the product o (1 - o) of the denominator (2), the factors g and lam and the division (3): 25.
