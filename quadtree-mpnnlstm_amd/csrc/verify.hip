@@ -3,14 +3,15 @@
 // event_dates() with the sums of their errors (k_event_scan, k_event_sums), the per-bin probability sums of
 // reliability() (k_reliability_multi), the neighbourhood sums of fss() (k_fss_multi) and the ice-edge distances of
 // edge_distance() (k_edge_planes, k_edge_search).  All of them read the head's node values through every step's labels (no
-// frame is built), none has a gradient, and the six rollout launchers share one host-side setup (score_setup).  The training loss (k_sse, k_loss_multi, k_pool_targets) is in transfer.hip.
+// frame is built) and none has a gradient.  What they share is written once: ScoreArgs, the by-value kernel argument that the
+// six rollout launchers fill in one host-side setup (score_setup); PixelReader, which says which pixels count and how a
+// pixel's values are read; wave_sum / wave_max, the 64-lane butterflies.  A further product is a kernel body over the reader
+// and an entry.  The training loss (k_sse, k_loss_multi, k_pool_targets) is in transfer.hip.
 #include "qt_common.h"
 #include "../../include/qtmpnn_edges.h"
 
 namespace {
 
-// Forecast verification of a rollout: k_loss_multi's reads with more accumulators, kept per (step, clip, tile) and per
-// source (the model's node values through the labels, then up to two dense baseline fields), no gradient.
 struct ScoreSeg {
     const float* out[16];         // node values of the step (column 0 of rows of out_stride floats)
     const int32_t* labels[16];
@@ -21,24 +22,97 @@ struct ScoreBase {
     const float* f;               // dense field: step z of clip b starts at f + b*clip_stride + z*step_stride
     int64_t clip_stride, step_stride;
 };
+// What every rollout kernel is given, by value (about 600 bytes of kernel arguments), followed by the kernel's own extras.
+struct ScoreArgs {
+    ScoreSeg sg;
+    ScoreBase y;                  // the truth
+    ScoreBase bs[2];              // the dense baseline fields that are present, in order
+    int nb;                       // how many: the kernels are instantiated per source count S = 1 + nb
+    const uint8_t* pix_mask;      // (P) or null: a non-zero byte takes the pixel out of every clip and step
+    float thr;
+    __device__ bool masked(int64_t p) const { return pix_mask && pix_mask[p]; }
+};
 
+// The pixels of step z of clip b as every product reads them.  A pixel p COUNTS iff its label is a node of the step (0 <= lab <
+// rows, rows = the step's node count on the device capped by its capacity) and the pixel mask does not cover it: counted().
+// An uncounted pixel is read no further and adds nothing anywhere.  A counted pixel has the truth y[p] and S sources: the
+// model's node value through the label, then the dense fields at p (load(): in that order).  A kernel that walks the clips at
+// a fixed pixel constructs the reader at clip 0 and steps it with next_clip(); one that walks the steps constructs one per step.
+template <int S>
+struct PixelReader {
+    const ScoreArgs& a;
+    const int64_t P;
+    const float* out;             // node values of the step
+    const int32_t* labels;
+    const float *yz, *dense[2];
+    int os, rows;
+    __device__ PixelReader(const ScoreArgs& a, int64_t P, int b, int z)
+        : a(a), P(P), out(a.sg.out[z]), labels(a.sg.labels[z] + (int64_t)b * P),
+          yz(a.y.f + z * a.y.step_stride + b * a.y.clip_stride), os(a.sg.out_stride[z]), rows(qt_rows(a.sg.n_dev[z], a.sg.N[z])) {
+#pragma unroll
+        for (int s = 1; s < S; ++s) dense[s - 1] = a.bs[s - 1].f + z * a.bs[s - 1].step_stride + b * a.bs[s - 1].clip_stride;
+    }
+    __device__ void next_clip() {
+        labels += P;
+        yz += a.y.clip_stride;
+#pragma unroll
+        for (int s = 1; s < S; ++s) dense[s - 1] += a.bs[s - 1].clip_stride;
+    }
+    __device__ int label(int64_t p) const { return labels[p]; }
+    __device__ bool node(int lab) const { return lab >= 0 && lab < rows; }
+    __device__ bool counted(int64_t p, int lab) const { return node(lab) && !a.masked(p); }
+    __device__ float truth(int64_t p) const { return yz[p]; }
+    __device__ void load(int64_t p, int lab, float* f) const {
+        f[0] = out[(int64_t)lab * os];
+#pragma unroll
+        for (int s = 1; s < S; ++s) f[s] = dense[s - 1][p];
+    }
+    // The wave's 64 pixels (this lane's is p, or none if !in) as S + 2 ballot words: counted, then ice = counted && value > thr
+    // (strict, fp32: a NaN is not ice) of the truth and of every source
+    __device__ void ice_words(bool in, int64_t p, unsigned long long* w) const {
+        bool c = false, ice[S + 1];
+#pragma unroll
+        for (int s = 0; s <= S; ++s) ice[s] = false;
+        if (in) {
+            const int lab = label(p);
+            c = counted(p, lab);
+            if (c) {
+                float f[S];
+                ice[0] = truth(p) > a.thr;
+                load(p, lab, f);
+#pragma unroll
+                for (int s = 0; s < S; ++s) ice[1 + s] = f[s] > a.thr;
+            }
+        }
+        w[0] = __ballot(c);
+#pragma unroll
+        for (int s = 0; s <= S; ++s) w[1 + s] = __ballot(ice[s]);
+    }
+};
+
+// Sum / maximum over the 64 lanes of a wave, left in every lane: the butterfly xor 32, 16, 8, 4, 2, 1, in that order (for a
+// float sum the order is part of the result).
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+__device__ __forceinline__ int wave_max(int v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v = max(v, __shfl_xor(v, d, 64));
+    return v;
+}
+
+// Forecast verification of a rollout: the reader's pixels, summed per (step, clip, tile of 1024 pixels) and per source.
 // Per tile: n, then per source [sum d, sum |d|, sum d^2, hits, over, under]; the correct negatives are n - hits - over - under
 // (every counted pixel falls in exactly one of the four classes, and the counts are integers <= 1024: exact in fp32).
 template <int S>
-__global__ __launch_bounds__(256) void k_score_multi(ScoreSeg sg, const float* __restrict__ y, int64_t y_clip_stride,
-                                                     int64_t y_step_stride, ScoreBase b1, ScoreBase b2,
-                                                     const uint8_t* __restrict__ pix_mask, float thr, int64_t P, int B,
-                                                     float* __restrict__ partial) {
+__global__ __launch_bounds__(256) void k_score_multi(ScoreArgs a, int64_t P, int B, float* __restrict__ partial) {
     constexpr int NV = 1 + 6 * S;
     __shared__ float red[4][NV];
     const int b = blockIdx.y, z = blockIdx.z;
-    const float* out = sg.out[z];
-    const int32_t* labels = sg.labels[z] + (int64_t)b * P;
-    const int os = sg.out_stride[z];
-    const int rows = qt_rows(sg.n_dev[z], sg.N[z]);
-    const float* yz = y + z * y_step_stride + b * y_clip_stride;
-    const float* f1 = S > 1 ? b1.f + z * b1.step_stride + b * b1.clip_stride : nullptr;
-    const float* f2 = S > 2 ? b2.f + z * b2.step_stride + b * b2.clip_stride : nullptr;
+    const PixelReader<S> rd(a, P, b, z);
     float acc[NV];
 #pragma unroll
     for (int v = 0; v < NV; ++v) acc[v] = 0.0f;
@@ -46,33 +120,28 @@ __global__ __launch_bounds__(256) void k_score_multi(ScoreSeg sg, const float* _
     for (int k = 0; k < 4; ++k) {
         const int64_t p = (int64_t)blockIdx.x * 1024 + k * 256 + threadIdx.x;
         if (p >= P) continue;
-        const int lab = labels[p];
-        if (lab < 0 || lab >= rows || (pix_mask && pix_mask[p])) continue;
-        const float t = yz[p];
-        const bool ty = t > thr;
+        const int lab = rd.label(p);
+        if (!rd.counted(p, lab)) continue;
+        const float t = rd.truth(p);
+        const bool ty = t > a.thr;
         float f[S];
-        f[0] = out[(int64_t)lab * os];
-        if (S > 1) f[1] = f1[p];
-        if (S > 2) f[2] = f2[p];
+        rd.load(p, lab, f);
         acc[0] += 1.0f;
 #pragma unroll
         for (int s = 0; s < S; ++s) {
-            float* a = acc + 1 + 6 * s;
+            float* as = acc + 1 + 6 * s;
             const float d = f[s] - t;
-            const bool tf = f[s] > thr;
-            a[0] += d;
-            a[1] += fabsf(d);
-            a[2] += d * d;
-            a[3] += (tf && ty) ? 1.0f : 0.0f;
-            a[4] += (tf && !ty) ? 1.0f : 0.0f;
-            a[5] += (!tf && ty) ? 1.0f : 0.0f;
+            const bool tf = f[s] > a.thr;
+            as[0] += d;
+            as[1] += fabsf(d);
+            as[2] += d * d;
+            as[3] += (tf && ty) ? 1.0f : 0.0f;
+            as[4] += (tf && !ty) ? 1.0f : 0.0f;
+            as[5] += (!tf && ty) ? 1.0f : 0.0f;
         }
     }
 #pragma unroll
-    for (int v = 0; v < NV; ++v) {
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) acc[v] += __shfl_xor(acc[v], d, 64);
-    }
+    for (int v = 0; v < NV; ++v) acc[v] = wave_sum(acc[v]);
     if ((threadIdx.x & 63) == 0) {
 #pragma unroll
         for (int v = 0; v < NV; ++v) red[threadIdx.x >> 6][v] = acc[v];
@@ -90,7 +159,7 @@ __global__ __launch_bounds__(256) void k_score_multi(ScoreSeg sg, const float* _
     }
 }
 
-// Probability verification of a rollout: k_score_multi's reads, sources, counting rule and tile shape, with the forecast value
+// Probability verification of a rollout: k_score_multi's reads (PixelReader) and tile shape, with the forecast value
 // binned into K equal bins of [0, 1] and four sums kept per (source, bin): [n, events, sum f, sum (f - o)^2], o = (y > thr).
 // Bin of a value: t = f * (float)K (one fp32 rounding), 0 if not t >= 1 (f < 1/K, negative values and NaN), K - 1 if t >= K
 // (overshoot, +inf), else (int)t.  Every thread keeps its four pixels' values, squared errors and bins in registers and the
@@ -101,19 +170,10 @@ __global__ __launch_bounds__(256) void k_score_multi(ScoreSeg sg, const float* _
 // would leave.  The two counts are popcounts of wave ballots (integers <= 1024: exact in fp32).  No atomics: the same bits on
 // every run, eager or replayed.  A NaN forecast is in bin 0 and makes that bin's two float sums NaN.
 template <int S>
-__global__ __launch_bounds__(256) void k_reliability_multi(ScoreSeg sg, const float* __restrict__ y, int64_t y_clip_stride,
-                                                           int64_t y_step_stride, ScoreBase b1, ScoreBase b2,
-                                                           const uint8_t* __restrict__ pix_mask, float thr, int K, int64_t P,
-                                                           int B, float* __restrict__ partial) {
+__global__ __launch_bounds__(256) void k_reliability_multi(ScoreArgs a, int K, int64_t P, int B, float* __restrict__ partial) {
     __shared__ float red[4][S * 32 * 4];
     const int b = blockIdx.y, z = blockIdx.z;
-    const float* out = sg.out[z];
-    const int32_t* labels = sg.labels[z] + (int64_t)b * P;
-    const int os = sg.out_stride[z];
-    const int rows = qt_rows(sg.n_dev[z], sg.N[z]);
-    const float* yz = y + z * y_step_stride + b * y_clip_stride;
-    const float* f1 = S > 1 ? b1.f + z * b1.step_stride + b * b1.clip_stride : nullptr;
-    const float* f2 = S > 2 ? b2.f + z * b2.step_stride + b * b2.clip_stride : nullptr;
+    const PixelReader<S> rd(a, P, b, z);
     const float Kf = (float)K;
     float f[S][4], e2[S][4];
     int bin[S][4];                // -1: the pixel is not counted and matches no bin
@@ -124,8 +184,8 @@ __global__ __launch_bounds__(256) void k_reliability_multi(ScoreSeg sg, const fl
         bool counted = p < P;
         int lab = -1;
         if (counted) {
-            lab = labels[p];
-            counted = lab >= 0 && lab < rows && !(pix_mask && pix_mask[p]);
+            lab = rd.label(p);
+            counted = rd.counted(p, lab);
         }
         ev[j] = false;
 #pragma unroll
@@ -135,13 +195,13 @@ __global__ __launch_bounds__(256) void k_reliability_multi(ScoreSeg sg, const fl
             bin[s][j] = -1;
         }
         if (!counted) continue;
-        ev[j] = yz[p] > thr;
+        ev[j] = rd.truth(p) > a.thr;
         const float o = ev[j] ? 1.0f : 0.0f;
-        f[0][j] = out[(int64_t)lab * os];
-        if (S > 1) f[1][j] = f1[p];
-        if (S > 2) f[2][j] = f2[p];
+        float v[S];
+        rd.load(p, lab, v);
 #pragma unroll
         for (int s = 0; s < S; ++s) {
+            f[s][j] = v[s];
             const float d = f[s][j] - o;
             e2[s][j] = d * d;
             const float t = f[s][j] * Kf;
@@ -163,11 +223,8 @@ __global__ __launch_bounds__(256) void k_reliability_multi(ScoreSeg sg, const fl
                 sq += in ? e2[s][j] : 0.0f;
             }
             if (n) {              // wave-uniform: n comes from ballots
-#pragma unroll
-                for (int d = 32; d >= 1; d >>= 1) {
-                    sf += __shfl_xor(sf, d, 64);
-                    sq += __shfl_xor(sq, d, 64);
-                }
+                sf = wave_sum(sf);
+                sq = wave_sum(sq);
             }
             if ((threadIdx.x & 63) == 0) {
                 float* r = red[w] + (s * K + k) * 4;
@@ -183,7 +240,7 @@ __global__ __launch_bounds__(256) void k_reliability_multi(ScoreSeg sg, const fl
     for (int v = threadIdx.x; v < S * K * 4; v += 256) dst[v] = (red[0][v] + red[1][v]) + (red[2][v] + red[3][v]);
 }
 
-// Neighbourhood verification of a rollout (Fractions Skill Score): k_score_multi's reads, sources and counting rule, but a
+// Neighbourhood verification of a rollout (Fractions Skill Score): k_score_multi's reads (PixelReader), but a
 // pixel is compared through the number of "ice" pixels in the n x n window around it, n = 2h + 1 one of K scales (h <= 16).
 // Indicators: I_o(p) = counted(p) && y[p] > thr, I_s(p) = counted(p) && f_s[p] > thr (strict, fp32: a NaN is not ice); a window
 // count c_x(p; n) is the sum of I_x over the window, positions outside the frame and uncounted pixels adding 0.  Per
@@ -207,52 +264,24 @@ struct FssScales {
 };
 
 template <int S>
-__global__ __launch_bounds__(256) void k_fss_multi(ScoreSeg sg, const float* __restrict__ y, int64_t y_clip_stride,
-                                                   int64_t y_step_stride, ScoreBase b1, ScoreBase b2,
-                                                   const uint8_t* __restrict__ pix_mask, float thr, FssScales sc, int n, int m,
-                                                   int tiles_m, int B, int32_t* __restrict__ partial) {
+__global__ __launch_bounds__(256) void k_fss_multi(ScoreArgs a, FssScales sc, int n, int m, int tiles_m, int B,
+                                                   int32_t* __restrict__ partial) {
     constexpr int NW = S + 2;                                  // words of a patch row: counted, I_o, I_s per source
     __shared__ unsigned long long bits[64][NW];
     __shared__ int red[4][2 + S * 8 * 3];
     const int b = blockIdx.y, z = blockIdx.z;
-    const int64_t P = (int64_t)n * m;
-    const float* out = sg.out[z];
-    const int32_t* labels = sg.labels[z] + (int64_t)b * P;
-    const int os = sg.out_stride[z];
-    const int rows = qt_rows(sg.n_dev[z], sg.N[z]);
-    const float* yz = y + z * y_step_stride + b * y_clip_stride;
-    const float* f1 = S > 1 ? b1.f + z * b1.step_stride + b * b1.clip_stride : nullptr;
-    const float* f2 = S > 2 ? b2.f + z * b2.step_stride + b * b2.clip_stride : nullptr;
+    const PixelReader<S> rd(a, (int64_t)n * m, b, z);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int r0 = (blockIdx.x / tiles_m) * 32 - 16, c0 = (blockIdx.x % tiles_m) * 32 - 16;      // frame position of patch (0, 0)
     const int gc = c0 + lane;
 #pragma unroll 4
     for (int i = 0; i < 16; ++i) {
         const int pr = w * 16 + i, gr = r0 + pr;
-        const bool in = gr >= 0 && gr < n && gc >= 0 && gc < m;
-        bool counted = false, io = false, is[S];
-#pragma unroll
-        for (int s = 0; s < S; ++s) is[s] = false;
-        if (in) {
-            const int64_t p = (int64_t)gr * m + gc;
-            const int lab = labels[p];
-            counted = lab >= 0 && lab < rows && !(pix_mask && pix_mask[p]);
-            if (counted) {
-                io = yz[p] > thr;
-                is[0] = out[(int64_t)lab * os] > thr;
-                if (S > 1) is[1] = f1[p] > thr;
-                if (S > 2) is[2] = f2[p] > thr;
-            }
-        }
-        const unsigned long long wc = __ballot(counted), wo = __ballot(io);
-        unsigned long long ws[S];
-#pragma unroll
-        for (int s = 0; s < S; ++s) ws[s] = __ballot(is[s]);
+        unsigned long long w[NW];
+        rd.ice_words(gr >= 0 && gr < n && gc >= 0 && gc < m, (int64_t)gr * m + gc, w);
         if (lane == 0) {
-            bits[pr][0] = wc;
-            bits[pr][1] = wo;
 #pragma unroll
-            for (int s = 0; s < S; ++s) bits[pr][2 + s] = ws[s];
+            for (int q = 0; q < NW; ++q) bits[pr][q] = w[q];
         }
     }
     __syncthreads();
@@ -305,10 +334,7 @@ __global__ __launch_bounds__(256) void k_fss_multi(ScoreSeg sg, const float* __r
                 v[2] += ctr[j] ? co[j] * co[j] : 0;
             }
 #pragma unroll
-            for (int q = 0; q < 3; ++q) {
-#pragma unroll
-                for (int d = 32; d >= 1; d >>= 1) v[q] += __shfl_xor(v[q], d, 64);
-            }
+            for (int q = 0; q < 3; ++q) v[q] = wave_sum(v[q]);
             if (lane == 0) {
                 int* r = red[w] + 2 + (s * sc.K + k) * 3;
                 r[0] = v[0];
@@ -326,7 +352,7 @@ __global__ __launch_bounds__(256) void k_fss_multi(ScoreSeg sg, const float* __r
     }
 }
 
-// Ice-edge displacement of a rollout (edge_distance()): k_fss_multi's reads, sources and counting rule, but what is compared
+// Ice-edge displacement of a rollout (edge_distance()): k_fss_multi's reads (PixelReader), but what is compared
 // is where the ice edge lies.  ice(x, p) = counted(p) && x[p] > thr (strict, fp32: NaN and -inf are not ice, +inf is); the edge
 // set E(x) holds the ice pixels with a 4-neighbour that is inside the frame, counted and not ice (frame borders and uncounted
 // pixels make no edge).  For each source f the eight integers of include/qtmpnn_edges.h are kept per (step, clip, band of 16 rows):
@@ -367,48 +393,22 @@ __global__ __launch_bounds__(256) void k_fss_multi(ScoreSeg sg, const float* __r
 constexpr int EDGE_BAND = 16, EDGE_MAX = 256;
 
 template <int S>
-__global__ __launch_bounds__(256) void k_edge_planes(ScoreSeg sg, const float* __restrict__ y, int64_t y_clip_stride,
-                                                     int64_t y_step_stride, ScoreBase b1, ScoreBase b2,
-                                                     const uint8_t* __restrict__ pix_mask, float thr, int n, int m, int W, int B,
+__global__ __launch_bounds__(256) void k_edge_planes(ScoreArgs a, int n, int m, int W, int B,
                                                      unsigned long long* __restrict__ planes) {
     constexpr int NF = S + 1;                                  // fields: y, then the sources
     __shared__ unsigned long long bits[EDGE_BAND + 2][4][NF + 1];       // [row][word][counted, ice of y, ice of each source]
     const int b = blockIdx.y, z = blockIdx.z;
-    const int64_t P = (int64_t)n * m;
-    const float* out = sg.out[z];
-    const int32_t* labels = sg.labels[z] + (int64_t)b * P;
-    const int os = sg.out_stride[z];
-    const int rows = qt_rows(sg.n_dev[z], sg.N[z]);
-    const float* yz = y + z * y_step_stride + b * y_clip_stride;
-    const float* f1 = S > 1 ? b1.f + z * b1.step_stride + b * b1.clip_stride : nullptr;
-    const float* f2 = S > 2 ? b2.f + z * b2.step_stride + b * b2.clip_stride : nullptr;
+    const PixelReader<S> rd(a, (int64_t)n * m, b, z);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int r0 = blockIdx.x * EDGE_BAND;
     for (int u = w; u < (EDGE_BAND + 2) * W; u += 4) {
         const int i = u / W, j = u - i * W;
         const int gr = r0 - 1 + i, gc = j * 64 + lane;
-        bool counted = false, ice[NF];
-#pragma unroll
-        for (int f = 0; f < NF; ++f) ice[f] = false;
-        if (gr >= 0 && gr < n && gc < m) {
-            const int64_t p = (int64_t)gr * m + gc;
-            const int lab = labels[p];
-            counted = lab >= 0 && lab < rows && !(pix_mask && pix_mask[p]);
-            if (counted) {
-                ice[0] = yz[p] > thr;
-                ice[1] = out[(int64_t)lab * os] > thr;
-                if (S > 1) ice[2] = f1[p] > thr;
-                if (S > 2) ice[3] = f2[p] > thr;
-            }
-        }
-        const unsigned long long wc = __ballot(counted);
-        unsigned long long wi[NF];
-#pragma unroll
-        for (int f = 0; f < NF; ++f) wi[f] = __ballot(ice[f]);
+        unsigned long long w[NF + 1];
+        rd.ice_words(gr >= 0 && gr < n && gc < m, (int64_t)gr * m + gc, w);
         if (lane == 0) {
-            bits[i][j][0] = wc;
 #pragma unroll
-            for (int f = 0; f < NF; ++f) bits[i][j][1 + f] = wi[f];
+            for (int q = 0; q <= NF; ++q) bits[i][j][q] = w[q];
         }
     }
     __syncthreads();
@@ -525,15 +525,9 @@ __global__ __launch_bounds__(256) void k_edge_search(const unsigned long long* _
                 }
                 __syncthreads();                               // the queue is rewritten by the next direction
             }
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) {
-                sq += __shfl_xor(sq, d, 64);
-                sd += __shfl_xor(sd, d, 64);
-                mx = max(mx, __shfl_xor(mx, d, 64));
-            }
-            res[2 + dir] = sq;
-            res[4 + dir] = sd;
-            res[6 + dir] = mx;
+            res[2 + dir] = wave_sum(sq);
+            res[4 + dir] = wave_sum(sd);
+            res[6 + dir] = wave_max(mx);
         }
         if (lane == 0) {
 #pragma unroll
@@ -550,8 +544,8 @@ __global__ __launch_bounds__(256) void k_edge_search(const unsigned long long* _
     }
 }
 
-// Per-pixel verification sums: k_score_multi's reads and counting rule, kept per pixel and summed over the clips instead of
-// per clip and summed over the pixels.  One thread owns pixel p of step z and is the only writer of its 8 * S running doubles
+// Per-pixel verification sums: k_score_multi's reads (one PixelReader stepped over the clips), kept per pixel and summed over
+// the clips instead of per clip and summed over the pixels.  One thread owns pixel p of step z and is the only writer of its 8 * S running doubles
 // (maps + z * maps_step_stride, laid out (S, 8, P)): it loads the three sums of every source, adds the clips' terms to them
 // one by one in clip order in double, and stores them; the class counts are integers (exact in any order) and are added to
 // their running values at the end.  d = f - y is formed in fp32 as in k_score_multi and then widened; d * d of a widened fp32
@@ -559,20 +553,12 @@ __global__ __launch_bounds__(256) void k_edge_search(const unsigned long long* _
 // clip that was ever added, however the clips were batched.  No atomics, no LDS, no cross-thread step; launches that share
 // `maps` are ordered by their stream.
 template <int S>
-__global__ __launch_bounds__(256) void k_score_maps(ScoreSeg sg, const float* __restrict__ y, int64_t y_clip_stride,
-                                                    int64_t y_step_stride, ScoreBase b1, ScoreBase b2,
-                                                    const uint8_t* __restrict__ pix_mask, float thr, int64_t P, int B,
-                                                    double* __restrict__ maps, int64_t maps_step_stride) {
+__global__ __launch_bounds__(256) void k_score_maps(ScoreArgs a, int64_t P, int B, double* __restrict__ maps,
+                                                    int64_t maps_step_stride) {
     const int z = blockIdx.y;
     const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (p >= P || (pix_mask && pix_mask[p])) return;         // a masked pixel counts in no clip: its doubles stay as they are
-    const float* out = sg.out[z];
-    const int32_t* labels = sg.labels[z] + p;
-    const int os = sg.out_stride[z];
-    const int rows = qt_rows(sg.n_dev[z], sg.N[z]);
-    const float* yz = y + z * y_step_stride + p;
-    const float* f1 = S > 1 ? b1.f + z * b1.step_stride + p : nullptr;
-    const float* f2 = S > 2 ? b2.f + z * b2.step_stride + p : nullptr;
+    if (p >= P || a.masked(p)) return;                        // a masked pixel counts in no clip: its doubles stay as they are
+    PixelReader<S> rd(a, P, 0, z);
     double* mz = maps + z * maps_step_stride + p;             // slot k of source s: mz[(s * 8 + k) * P]
     double sum[S][3];
     int cls[S][3], n = 0;
@@ -584,21 +570,19 @@ __global__ __launch_bounds__(256) void k_score_maps(ScoreSeg sg, const float* __
             cls[s][k] = 0;
         }
     }
-    for (int b = 0; b < B; ++b) {
-        const int lab = labels[b * P];
-        if (lab < 0 || lab >= rows) continue;
-        const float t = yz[b * y_clip_stride];
-        const bool ty = t > thr;
+    for (int b = 0; b < B; ++b, rd.next_clip()) {
+        const int lab = rd.label(p);
+        if (!rd.node(lab)) continue;                          // with the mask test above: counted()
+        const float t = rd.truth(p);
+        const bool ty = t > a.thr;
         float f[S];
-        f[0] = out[(int64_t)lab * os];
-        if (S > 1) f[1] = f1[b * b1.clip_stride];
-        if (S > 2) f[2] = f2[b * b2.clip_stride];
+        rd.load(p, lab, f);
         ++n;
 #pragma unroll
         for (int s = 0; s < S; ++s) {
             const float d32 = f[s] - t;
             const double d = (double)d32;
-            const bool tf = f[s] > thr;
+            const bool tf = f[s] > a.thr;
             sum[s][0] += d;
             sum[s][1] += fabs(d);
             sum[s][2] += d * d;
@@ -622,19 +606,18 @@ __global__ __launch_bounds__(256) void k_score_maps(ScoreSeg sg, const float* __
 }
 
 // Event dates of a rollout (break-up / freeze-up): the first output step from which a pixel stays in the target state g for k
-// consecutive steps, per source (observed, model, optionally one dense field).  k_score_maps' reads and counting rule, but along
-// the time axis: one thread owns pixel p of clip b, reads its label once per step and serves every source from it, and carries
+// consecutive steps, per source (observed, model, optionally one dense field).  k_score_maps' reads, but along the time axis
+// (a PixelReader per step; the truth is source 0 here): one thread owns pixel p of clip b, reads its label once per step and
+// serves every source from it, and carries
 // per source the current run length and the date in registers over the chunk's steps.  A launch with z0 == 0 initialises the
 // state (date -2 under the mask, else -1; run 0, or -1 where the launch frame is already in the target state: such a pixel has
 // no event, and a negative run is never advanced), a launch with z0 > 0 loads what the previous chunk stored.  A pixel without
 // a valid node at any step ends as -2 for every source.  No atomics, no LDS, no cross-thread step; chunks are ordered by their
 // stream.
 template <int S1>
-__global__ __launch_bounds__(256) void k_event_scan(ScoreSeg sg, int nseg, const float* __restrict__ y, int64_t y_clip_stride,
-                                                    int64_t y_step_stride, ScoreBase b1, const uint8_t* __restrict__ pix_mask,
-                                                    const float* __restrict__ launch, int64_t launch_clip_stride, float thr,
-                                                    int target, int k, int z0, int64_t P, int32_t* __restrict__ dates,
-                                                    int32_t* __restrict__ runs) {
+__global__ __launch_bounds__(256) void k_event_scan(ScoreArgs a, int nseg, const float* __restrict__ launch,
+                                                    int64_t launch_clip_stride, int target, int k, int z0, int64_t P,
+                                                    int32_t* __restrict__ dates, int32_t* __restrict__ runs) {
     const int b = blockIdx.y;
     const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (p >= P) return;
@@ -642,8 +625,8 @@ __global__ __launch_bounds__(256) void k_event_scan(ScoreSeg sg, int nseg, const
     const int64_t st = ((int64_t)b * S1) * P + p;             // source s of this pixel: st + s * P
     int date[S1], run[S1];
     if (z0 == 0) {
-        const int d0 = (pix_mask && pix_mask[p]) ? -2 : -1;
-        const int r0 = ((launch[b * launch_clip_stride + p] > thr) == g) ? -1 : 0;
+        const int d0 = a.masked(p) ? -2 : -1;
+        const int r0 = ((launch[b * launch_clip_stride + p] > a.thr) == g) ? -1 : 0;
 #pragma unroll
         for (int s = 0; s < S1; ++s) {
             date[s] = d0;
@@ -657,22 +640,20 @@ __global__ __launch_bounds__(256) void k_event_scan(ScoreSeg sg, int nseg, const
         }
     }
     bool dead = date[0] == -2;                                // masked, or without a node at an earlier step
-    const float* yp = y + b * y_clip_stride + p;
-    const float* fp = S1 > 2 ? b1.f + b * b1.clip_stride + p : nullptr;
     for (int z = 0; z < nseg && !dead; ++z) {
-        const int lab = sg.labels[z][(int64_t)b * P + p];
-        if (lab < 0 || lab >= qt_rows(sg.n_dev[z], sg.N[z])) {
+        const PixelReader<S1 - 1> rd(a, P, b, z);
+        const int lab = rd.label(p);
+        if (!rd.node(lab)) {                                  // the mask made the pixel dead before the first step
             dead = true;
             break;
         }
         float f[S1];
-        f[0] = yp[z * y_step_stride];
-        f[1] = sg.out[z][(int64_t)lab * sg.out_stride[z]];
-        if (S1 > 2) f[2] = fp[z * b1.step_stride];
+        f[0] = rd.truth(p);
+        rd.load(p, lab, f + 1);
 #pragma unroll
         for (int s = 0; s < S1; ++s) {
             if (run[s] < 0) continue;
-            run[s] = ((f[s] > thr) == g) ? run[s] + 1 : 0;
+            run[s] = ((f[s] > a.thr) == g) ? run[s] + 1 : 0;
             if (run[s] >= k && date[s] == -1) date[s] = z0 + z - k + 1;
         }
     }
@@ -713,10 +694,7 @@ __global__ __launch_bounds__(256) void k_event_sums(const int32_t* __restrict__ 
         }
     }
 #pragma unroll
-    for (int v = 0; v < 8; ++v) {
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) acc[v] += __shfl_xor(acc[v], d, 64);
-    }
+    for (int v = 0; v < 8; ++v) acc[v] = wave_sum(acc[v]);
     if ((threadIdx.x & 63) == 0) {
 #pragma unroll
         for (int v = 0; v < 8; ++v) red[threadIdx.x >> 6][v] = acc[v];
@@ -728,32 +706,53 @@ __global__ __launch_bounds__(256) void k_event_sums(const int32_t* __restrict__ 
     }
 }
 
-// What the six rollout launchers have in common: the segment arrays of 1..16 steps into `sg`, and the dense baseline fields
-// that are present, in order, into `bs` (`nb` of them: the kernels are instantiated per source count).  Returns the reason of a
-// refusal, or null; the entry reports it under its own name (QT_ARG).
-struct ScoreSetup {
-    ScoreSeg sg;
-    ScoreBase bs[2];
-    int nb;
-};
-
-const char* score_setup(ScoreSetup& st, int nseg, const float* const* outs, const int* out_strides, const int32_t* const* labels,
-                        const int* Ns, const int32_t* const* n_devs, const float* y, int64_t y_clip_stride, int64_t y_step_stride,
-                        ScoreBase base1, ScoreBase base2) {
+// What the six rollout launchers have in common, in the order every one of them refuses: the segment arrays of 1..16 steps, the
+// truth and the dense baseline fields that are present into `a`; then `own`, the reason of the entry's own first checks if
+// one of them failed (else null); then the sizes, where B is at most `B_max` (a grid dimension for all but qt_score_maps).
+// Returns the reason of a refusal, or null; the entry reports it under its own name (QT_ARG).
+const char* score_setup(ScoreArgs& a, int nseg, const float* const* outs, const int* out_strides, const int32_t* const* labels,
+                        const int* Ns, const int32_t* const* n_devs, ScoreBase y, ScoreBase base1, ScoreBase base2,
+                        const uint8_t* pix_mask, float thr, const char* own, int B, int n, int m, int B_max = 65535) {
     if (!(nseg >= 1 && nseg <= 16)) return "nseg must be 1..16";
-    if (!(outs && out_strides && labels && Ns && n_devs && y)) return "null pointer";
-    if (!(y_clip_stride >= 0 && y_step_stride >= 0 && base1.clip_stride >= 0 && base1.step_stride >= 0 &&
+    if (!(outs && out_strides && labels && Ns && n_devs && y.f)) return "null pointer";
+    if (!(y.clip_stride >= 0 && y.step_stride >= 0 && base1.clip_stride >= 0 && base1.step_stride >= 0 &&
           base2.clip_stride >= 0 && base2.step_stride >= 0))
         return "negative stride";
-    st = {};
-    ScoreSeg& sg = st.sg;
+    a = {};
+    ScoreSeg& sg = a.sg;
     for (int z = 0; z < nseg; ++z) {
         if (!(labels[z] && Ns[z] >= 0 && (outs[z] || Ns[z] == 0) && out_strides[z] >= 1)) return "bad segment";
         sg.out[z] = outs[z]; sg.out_stride[z] = out_strides[z]; sg.labels[z] = labels[z]; sg.N[z] = Ns[z]; sg.n_dev[z] = n_devs[z];
     }
-    if (base1.f) st.bs[st.nb++] = base1;
-    if (base2.f) st.bs[st.nb++] = base2;
+    a.y = y;
+    if (base1.f) a.bs[a.nb++] = base1;
+    if (base2.f) a.bs[a.nb++] = base2;
+    a.pix_mask = pix_mask;
+    a.thr = thr;
+    if (own) return own;
+    if (!(B > 0 && B <= B_max && n > 0 && m > 0)) return "bad sizes";
     return nullptr;
+}
+
+// The instantiation of a kernel template for the sources present: the model and `nb` dense fields
+template <typename K>
+K by_sources(int nb, K k1, K k2, K k3) {
+    return nb == 0 ? k1 : nb == 1 ? k2 : k3;
+}
+
+// The first of qt_fss_rollout's own refusals, or null with the half widths in `sc`
+const char* fss_scales(FssScales& sc, int nscales, const int* scales, const int32_t* partial) {
+    if (!(nscales >= 1 && nscales <= 8)) return "nscales must be 1..8";
+    if (!scales) return "null scales";
+    sc = {};
+    sc.K = nscales;
+    for (int k = 0; k < nscales; ++k) {
+        // the kernel's column mask and halo hold windows up to 33 wide and no wider
+        if (!(scales[k] >= 1 && scales[k] <= 33 && (scales[k] & 1))) return "scales must be odd and in 1..33";
+        if (!(k == 0 || scales[k] > scales[k - 1])) return "scales must be strictly increasing";
+        sc.h[k] = scales[k] / 2;
+    }
+    return partial ? nullptr : "null partial";
 }
 
 }  // namespace
@@ -763,18 +762,15 @@ extern "C" int qt_score_rollout(int nseg, const float* const* outs, const int* o
                                 int64_t y_step_stride, const float* base1, int64_t base1_clip_stride, int64_t base1_step_stride,
                                 const float* base2, int64_t base2_clip_stride, int64_t base2_step_stride,
                                 const uint8_t* pix_mask, float thr, int B, int n, int m, float* partial, void* stream) {
-    ScoreSetup st;
-    const char* why = score_setup(st, nseg, outs, out_strides, labels, Ns, n_devs, y, y_clip_stride, y_step_stride,
-                                  {base1, base1_clip_stride, base1_step_stride}, {base2, base2_clip_stride, base2_step_stride});
+    ScoreArgs a;
+    const char* why = score_setup(a, nseg, outs, out_strides, labels, Ns, n_devs, {y, y_clip_stride, y_step_stride},
+                                  {base1, base1_clip_stride, base1_step_stride}, {base2, base2_clip_stride, base2_step_stride},
+                                  pix_mask, thr, partial ? nullptr : "null pointer", B, n, m);
     QT_ARG(!why, why);
-    QT_ARG(partial, "null pointer");
-    QT_ARG(B > 0 && B <= 65535 && n > 0 && m > 0, "bad sizes");
     const int64_t P = (int64_t)n * m;
-    const dim3 grid(qt_cdiv(P, 1024), B, nseg);
     // the kernel's partial rows are sized for the sources present
-    auto k = st.nb == 0 ? k_score_multi<1> : st.nb == 1 ? k_score_multi<2> : k_score_multi<3>;
-    hipLaunchKernelGGL(k, grid, dim3(256), 0, (hipStream_t)stream, st.sg, y, y_clip_stride, y_step_stride, st.bs[0], st.bs[1],
-                       pix_mask, thr, P, B, partial);
+    hipLaunchKernelGGL(by_sources(a.nb, k_score_multi<1>, k_score_multi<2>, k_score_multi<3>), dim3(qt_cdiv(P, 1024), B, nseg),
+                       dim3(256), 0, (hipStream_t)stream, a, P, B, partial);
     QT_LAUNCHED();
     return QT_OK;
 }
@@ -785,18 +781,15 @@ extern "C" int qt_reliability_rollout(int nseg, const float* const* outs, const 
                                       int64_t base1_step_stride, const float* base2, int64_t base2_clip_stride,
                                       int64_t base2_step_stride, const uint8_t* pix_mask, float thr, int B, int n, int m,
                                       int bins, float* partial, void* stream) {
-    ScoreSetup st;
-    const char* why = score_setup(st, nseg, outs, out_strides, labels, Ns, n_devs, y, y_clip_stride, y_step_stride,
-                                  {base1, base1_clip_stride, base1_step_stride}, {base2, base2_clip_stride, base2_step_stride});
+    ScoreArgs a;
+    const char* own = !(bins >= 2 && bins <= 32) ? "bins must be 2..32" : !partial ? "null partial" : nullptr;
+    const char* why = score_setup(a, nseg, outs, out_strides, labels, Ns, n_devs, {y, y_clip_stride, y_step_stride},
+                                  {base1, base1_clip_stride, base1_step_stride}, {base2, base2_clip_stride, base2_step_stride},
+                                  pix_mask, thr, own, B, n, m);
     QT_ARG(!why, why);
-    QT_ARG(bins >= 2 && bins <= 32, "bins must be 2..32");
-    QT_ARG(partial, "null partial");
-    QT_ARG(B > 0 && B <= 65535 && n > 0 && m > 0, "bad sizes");
     const int64_t P = (int64_t)n * m;
-    const dim3 grid(qt_cdiv(P, 1024), B, nseg);
-    auto k = st.nb == 0 ? k_reliability_multi<1> : st.nb == 1 ? k_reliability_multi<2> : k_reliability_multi<3>;
-    hipLaunchKernelGGL(k, grid, dim3(256), 0, (hipStream_t)stream, st.sg, y, y_clip_stride, y_step_stride, st.bs[0], st.bs[1],
-                       pix_mask, thr, bins, P, B, partial);
+    hipLaunchKernelGGL(by_sources(a.nb, k_reliability_multi<1>, k_reliability_multi<2>, k_reliability_multi<3>),
+                       dim3(qt_cdiv(P, 1024), B, nseg), dim3(256), 0, (hipStream_t)stream, a, bins, P, B, partial);
     QT_LAUNCHED();
     return QT_OK;
 }
@@ -807,29 +800,18 @@ extern "C" int qt_fss_rollout(int nseg, const float* const* outs, const int* out
                               const float* base2, int64_t base2_clip_stride, int64_t base2_step_stride,
                               const uint8_t* pix_mask, float thr, int B, int n, int m, int nscales, const int* scales,
                               int32_t* partial, void* stream) {
-    ScoreSetup st;
-    const char* why = score_setup(st, nseg, outs, out_strides, labels, Ns, n_devs, y, y_clip_stride, y_step_stride,
-                                  {base1, base1_clip_stride, base1_step_stride}, {base2, base2_clip_stride, base2_step_stride});
+    ScoreArgs a;
+    FssScales sc;
+    const char* own = fss_scales(sc, nscales, scales, partial);
+    const char* why = score_setup(a, nseg, outs, out_strides, labels, Ns, n_devs, {y, y_clip_stride, y_step_stride},
+                                  {base1, base1_clip_stride, base1_step_stride}, {base2, base2_clip_stride, base2_step_stride},
+                                  pix_mask, thr, own, B, n, m);
     QT_ARG(!why, why);
-    QT_ARG(nscales >= 1 && nscales <= 8, "nscales must be 1..8");
-    QT_ARG(scales, "null scales");
-    FssScales sc = {};
-    sc.K = nscales;
-    for (int k = 0; k < nscales; ++k) {
-        // the kernel's column mask and halo hold windows up to 33 wide and no wider
-        QT_ARG(scales[k] >= 1 && scales[k] <= 33 && (scales[k] & 1), "scales must be odd and in 1..33");
-        QT_ARG(k == 0 || scales[k] > scales[k - 1], "scales must be strictly increasing");
-        sc.h[k] = scales[k] / 2;
-    }
-    QT_ARG(partial, "null partial");
-    QT_ARG(B > 0 && B <= 65535 && n > 0 && m > 0, "bad sizes");
     const int tiles_m = qt_cdiv(m, 32);
     const int64_t ntile = (int64_t)qt_cdiv(n, 32) * tiles_m;
     QT_ARG(ntile <= 0x7fffffff, "bad sizes");
-    const dim3 grid((unsigned)ntile, B, nseg);
-    auto k = st.nb == 0 ? k_fss_multi<1> : st.nb == 1 ? k_fss_multi<2> : k_fss_multi<3>;
-    hipLaunchKernelGGL(k, grid, dim3(256), 0, (hipStream_t)stream, st.sg, y, y_clip_stride, y_step_stride, st.bs[0], st.bs[1],
-                       pix_mask, thr, sc, n, m, tiles_m, B, partial);
+    hipLaunchKernelGGL(by_sources(a.nb, k_fss_multi<1>, k_fss_multi<2>, k_fss_multi<3>), dim3((unsigned)ntile, B, nseg),
+                       dim3(256), 0, (hipStream_t)stream, a, sc, n, m, tiles_m, B, partial);
     QT_LAUNCHED();
     return QT_OK;
 }
@@ -840,22 +822,20 @@ extern "C" int qt_edge_rollout(int nseg, const float* const* outs, const int* ou
                                const float* base2, int64_t base2_clip_stride, int64_t base2_step_stride,
                                const uint8_t* pix_mask, float thr, int B, int n, int m, uint64_t* planes, int32_t* partial,
                                void* stream) {
-    ScoreSetup st;
-    const char* why = score_setup(st, nseg, outs, out_strides, labels, Ns, n_devs, y, y_clip_stride, y_step_stride,
-                                  {base1, base1_clip_stride, base1_step_stride}, {base2, base2_clip_stride, base2_step_stride});
+    ScoreArgs a;
+    const char* why = score_setup(a, nseg, outs, out_strides, labels, Ns, n_devs, {y, y_clip_stride, y_step_stride},
+                                  {base1, base1_clip_stride, base1_step_stride}, {base2, base2_clip_stride, base2_step_stride},
+                                  pix_mask, thr, planes && partial ? nullptr : "null planes / partial", B, n, m);
     QT_ARG(!why, why);
-    QT_ARG(planes && partial, "null planes / partial");
-    QT_ARG(B > 0 && B <= 65535 && n > 0 && m > 0, "bad sizes");
     // k_edge_search holds a (step, clip)'s planes in LDS and packs a query into 16 bits; its int32 sums are proved for this size
     QT_ARG(n <= EDGE_MAX && m <= EDGE_MAX, "frame larger than 256 x 256");
     const int W = qt_cdiv(m, 64);
     const dim3 grid(qt_cdiv(n, EDGE_BAND), B, nseg);
-    auto kp = st.nb == 0 ? k_edge_planes<1> : st.nb == 1 ? k_edge_planes<2> : k_edge_planes<3>;
-    auto ks = st.nb == 0 ? k_edge_search<1> : st.nb == 1 ? k_edge_search<2> : k_edge_search<3>;
-    hipLaunchKernelGGL(kp, grid, dim3(256), 0, (hipStream_t)stream, st.sg, y, y_clip_stride, y_step_stride, st.bs[0], st.bs[1],
-                       pix_mask, thr, n, m, W, B, (unsigned long long*)planes);
+    hipLaunchKernelGGL(by_sources(a.nb, k_edge_planes<1>, k_edge_planes<2>, k_edge_planes<3>), grid, dim3(256), 0,
+                       (hipStream_t)stream, a, n, m, W, B, (unsigned long long*)planes);
     QT_LAUNCHED();
-    hipLaunchKernelGGL(ks, grid, dim3(256), 0, (hipStream_t)stream, (const unsigned long long*)planes, n, W, B, partial);
+    hipLaunchKernelGGL(by_sources(a.nb, k_edge_search<1>, k_edge_search<2>, k_edge_search<3>), grid, dim3(256), 0,
+                       (hipStream_t)stream, (const unsigned long long*)planes, n, W, B, partial);
     QT_LAUNCHED();
     return QT_OK;
 }
@@ -866,18 +846,17 @@ extern "C" int qt_score_maps(int nseg,const float* const* outs, const int* out_s
                              const float* base2, int64_t base2_clip_stride, int64_t base2_step_stride,
                              const uint8_t* pix_mask, float thr, int B, int n, int m, double* maps, int64_t maps_step_stride,
                              void* stream) {
-    ScoreSetup st;
-    const char* why = score_setup(st, nseg, outs, out_strides, labels, Ns, n_devs, y, y_clip_stride, y_step_stride,
-                                  {base1, base1_clip_stride, base1_step_stride}, {base2, base2_clip_stride, base2_step_stride});
+    ScoreArgs a;
+    // the clips are a loop in the kernel and no grid dimension: B has no upper bound
+    const char* why = score_setup(a, nseg, outs, out_strides, labels, Ns, n_devs, {y, y_clip_stride, y_step_stride},
+                                  {base1, base1_clip_stride, base1_step_stride}, {base2, base2_clip_stride, base2_step_stride},
+                                  pix_mask, thr, maps ? nullptr : "null pointer", B, n, m, 0x7fffffff);
     QT_ARG(!why, why);
-    QT_ARG(maps, "null pointer");
-    QT_ARG(B > 0 && n > 0 && m > 0, "bad sizes");
     const int64_t P = (int64_t)n * m;
     // a step's (S, 8, P) block must fit its stride, or step z would write into step z + 1
-    QT_ARG(maps_step_stride >= (int64_t)(1 + st.nb) * 8 * P, "maps_step_stride is smaller than S*8*n*m");
-    auto k = st.nb == 0 ? k_score_maps<1> : st.nb == 1 ? k_score_maps<2> : k_score_maps<3>;
-    hipLaunchKernelGGL(k, dim3(qt_cdiv(P, 256), nseg), dim3(256), 0, (hipStream_t)stream, st.sg, y, y_clip_stride, y_step_stride,
-                       st.bs[0], st.bs[1], pix_mask, thr, P, B, maps, maps_step_stride);
+    QT_ARG(maps_step_stride >= (int64_t)(1 + a.nb) * 8 * P, "maps_step_stride is smaller than S*8*n*m");
+    hipLaunchKernelGGL(by_sources(a.nb, k_score_maps<1>, k_score_maps<2>, k_score_maps<3>), dim3(qt_cdiv(P, 256), nseg),
+                       dim3(256), 0, (hipStream_t)stream, a, P, B, maps, maps_step_stride);
     QT_LAUNCHED();
     return QT_OK;
 }
@@ -888,21 +867,18 @@ extern "C" int qt_event_scan(int nseg, const float* const* outs, const int* out_
                              const uint8_t* pix_mask, float thr, int B, int n, int m, const float* launch,
                              int64_t launch_clip_stride, int target, int k, int z0, int32_t* dates, int32_t* runs,
                              void* stream) {
-    ScoreSetup st;
-    const char* why = score_setup(st, nseg, outs, out_strides, labels, Ns, n_devs, y, y_clip_stride, y_step_stride,
-                                  {base, base_clip_stride, base_step_stride}, {});
+    ScoreArgs a;
+    const char* own = !launch ? "null pointer" : !(dates && runs) ? "null dates / runs" : nullptr;
+    const char* why = score_setup(a, nseg, outs, out_strides, labels, Ns, n_devs, {y, y_clip_stride, y_step_stride},
+                                  {base, base_clip_stride, base_step_stride}, {}, pix_mask, thr, own, B, n, m);
     QT_ARG(!why, why);
-    QT_ARG(launch, "null pointer");
-    QT_ARG(dates && runs, "null dates / runs");
-    QT_ARG(B > 0 && B <= 65535 && n > 0 && m > 0, "bad sizes");
     QT_ARG(launch_clip_stride >= 0, "negative stride");
     QT_ARG(target == 0 || target == 1, "target must be 0 (no ice: break-up) or 1 (ice: freeze-up)");
     QT_ARG(k >= 1, "k (persist) must be >= 1");
     QT_ARG(z0 >= 0, "z0 must be >= 0");
     const int64_t P = (int64_t)n * m;
-    auto kern = st.nb ? k_event_scan<3> : k_event_scan<2>;
-    hipLaunchKernelGGL(kern, dim3(qt_cdiv(P, 256), B), dim3(256), 0, (hipStream_t)stream, st.sg, nseg, y, y_clip_stride,
-                       y_step_stride, st.bs[0], pix_mask, launch, launch_clip_stride, thr, target, k, z0, P, dates, runs);
+    hipLaunchKernelGGL(a.nb ? k_event_scan<3> : k_event_scan<2>, dim3(qt_cdiv(P, 256), B), dim3(256), 0, (hipStream_t)stream, a,
+                       nseg, launch, launch_clip_stride, target, k, z0, P, dates, runs);
     QT_LAUNCHED();
     return QT_OK;
 }

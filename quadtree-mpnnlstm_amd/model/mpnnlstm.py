@@ -930,28 +930,34 @@ class NextFramePredictorS2S(NextFramePredictor):
         Every batch must have the first one's frame shape."""
         return self._score(loader, climatology, mask, high_interest_region, graph_structure, use_graph, threshold, True)
 
+    def _rollout_sums(self, loader, climatology, product, use_graph, begin=None, **fwd):
+        """_inference with a reduce that leaves (T, B, ...) sums per batch (sums_product, reliability_product, fss_product,
+        edge_product) -> (the loader's (B_total, T, ...) array, one host copy per batch; the names of its sources)."""
+        sums = []
+        self._inference(loader, climatology, product, lambda part, x: sums.append(np.moveaxis(part.cpu().numpy(), 0, 1)),
+                        use_graph, begin=begin, **fwd)
+        return np.concatenate(sums, 0), ('model', 'persistence') + (('climatology',) if climatology is not None else ())
+
     def _score(self, loader, climatology, mask, high_interest_region, graph_structure, use_graph, threshold, with_maps):
         from qtmpnn.score import ScoreMaps, Scores
-        sources = ('model', 'persistence') + (('climatology',) if climatology is not None else ())
-        sums, maps, frame = [], None, None
+        maps, frame = None, None
 
         def begin(x):           # the maps buffer exists, zeroed, before the first batch's forward; every batch has its grid
             nonlocal maps, frame
             if maps is None:
                 frame = tuple(x.shape[-3:-1])
-                maps = torch.zeros(self.output_timesteps, len(sources), 8, frame[0] * frame[1], dtype=torch.float64,
-                                   device=x.device)
+                maps = torch.zeros(self.output_timesteps, 2 + (climatology is not None), 8, frame[0] * frame[1],    # per source
+                                   dtype=torch.float64, device=x.device)
             elif tuple(x.shape[-3:-1]) != frame:
                 raise ValueError(f'score_maps: a batch of {tuple(x.shape[-3:-1])} frames after {frame} ones: maps need '
                                  'one grid (use one loader per grid)')
 
-        self._inference(loader, climatology, lambda x: sums_product(threshold, maps),
-                        lambda part, x: sums.append(np.moveaxis(part.cpu().numpy(), 0, 1)),      # (T, B, S, 8) -> (B, T, S, 8)
-                        use_graph, begin=begin if with_maps else None, mask=mask, high_interest_region=high_interest_region,
-                        graph_structure=graph_structure)
+        sums, sources = self._rollout_sums(loader, climatology, lambda x: sums_product(threshold, maps), use_graph,
+                                           begin=begin if with_maps else None, mask=mask,
+                                           high_interest_region=high_interest_region, graph_structure=graph_structure)
         if maps is not None:
             maps = ScoreMaps(maps.cpu().numpy().reshape(*maps.shape[:3], *frame), sources)
-        return Scores(np.concatenate(sums, 0), sources, maps=maps)
+        return Scores(sums, sources, maps=maps)
 
     @on_device(lambda self, *a, **k: self.device)
     def reliability(self, loader, climatology=None, mask=None, high_interest_region=None, graph_structure=None, use_graph=False,
@@ -967,13 +973,10 @@ class NextFramePredictorS2S(NextFramePredictor):
         them.  use_graph=True replays rollout + sums as one hipGraph per distinct batch shape (make_graphed_reliability)."""
         from qtmpnn.reliability import Reliability
         ops.check_bins('reliability', bins)
-        sources = ('model', 'persistence') + (('climatology',) if climatology is not None else ())
-        sums = []
         reduce = reliability_product(threshold, bins)
-        self._inference(loader, climatology, lambda x: reduce,
-                        lambda part, x: sums.append(np.moveaxis(part.cpu().numpy(), 0, 1)),  # (T, B, S, K, 4) -> (B, T, S, K, 4)
-                        use_graph, mask=mask, high_interest_region=high_interest_region, graph_structure=graph_structure)
-        return Reliability(np.concatenate(sums, 0), sources, threshold)
+        sums, sources = self._rollout_sums(loader, climatology, lambda x: reduce, use_graph, mask=mask,      # (B, T, S, K, 4)
+                                           high_interest_region=high_interest_region, graph_structure=graph_structure)
+        return Reliability(sums, sources, threshold)
 
     @on_device(lambda self, *a, **k: self.device)
     def fss(self, loader, climatology=None, mask=None, high_interest_region=None, graph_structure=None, use_graph=False,
@@ -989,13 +992,10 @@ class NextFramePredictorS2S(NextFramePredictor):
         them.  use_graph=True replays rollout + sums as one hipGraph per distinct batch shape (make_graphed_fss)."""
         from qtmpnn.fss import FSS
         scales = ops.check_scales('fss', scales)
-        sources = ('model', 'persistence') + (('climatology',) if climatology is not None else ())
-        sums = []
         reduce = fss_product(threshold, scales)
-        self._inference(loader, climatology, lambda x: reduce,
-                        lambda part, x: sums.append(np.moveaxis(part.cpu().numpy(), 0, 1)),  # (T, B, S, K, 5) -> (B, T, S, K, 5)
-                        use_graph, mask=mask, high_interest_region=high_interest_region, graph_structure=graph_structure)
-        return FSS(np.concatenate(sums, 0), sources, threshold, scales)
+        sums, sources = self._rollout_sums(loader, climatology, lambda x: reduce, use_graph, mask=mask,      # (B, T, S, K, 5)
+                                           high_interest_region=high_interest_region, graph_structure=graph_structure)
+        return FSS(sums, sources, threshold, scales)
 
     @on_device(lambda self, *a, **k: self.device)
     def edge_distance(self, loader, climatology=None, mask=None, high_interest_region=None, graph_structure=None, use_graph=False,
@@ -1010,13 +1010,10 @@ class NextFramePredictorS2S(NextFramePredictor):
         (ops.rollout_edges: the head's outputs read through the labels, no frame is built) and makes one host copy of them.
         use_graph=True replays rollout + sums as one hipGraph per distinct batch shape (make_graphed_edges)."""
         from qtmpnn.edges import EdgeDistance
-        sources = ('model', 'persistence') + (('climatology',) if climatology is not None else ())
-        sums = []
         reduce = edge_product(threshold)
-        self._inference(loader, climatology, lambda x: reduce,
-                        lambda part, x: sums.append(np.moveaxis(part.cpu().numpy(), 0, 1)),  # (T, B, S, 8) -> (B, T, S, 8)
-                        use_graph, mask=mask, high_interest_region=high_interest_region, graph_structure=graph_structure)
-        return EdgeDistance(np.concatenate(sums, 0), sources, threshold)
+        sums, sources = self._rollout_sums(loader, climatology, lambda x: reduce, use_graph, mask=mask,      # (B, T, S, 8)
+                                           high_interest_region=high_interest_region, graph_structure=graph_structure)
+        return EdgeDistance(sums, sources, threshold)
 
     @on_device(lambda self, *a, **k: self.device)
     def event_dates(self, loader, climatology=None, mask=None, high_interest_region=None, graph_structure=None, use_graph=False,
