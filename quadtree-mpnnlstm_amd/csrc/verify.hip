@@ -1,14 +1,16 @@
 // Verification of a rollout, computed where the rollout's outputs are: the per-lead-time sums of score()
 // (k_score_multi), the per-pixel maps of score_maps() (k_score_maps), the break-up / freeze-up dates of
 // event_dates() with the sums of their errors (k_event_scan, k_event_sums), the per-bin probability sums of
-// reliability() (k_reliability_multi), the neighbourhood sums of fss() (k_fss_multi) and the ice-edge distances of
-// edge_distance() (k_edge_planes, k_edge_search).  All of them read the head's node values through every step's labels (no
+// reliability() (k_reliability_multi), the neighbourhood sums of fss() (k_fss_multi), the ice-edge distances of
+// edge_distance() (k_edge_planes, k_edge_search) and the regional area sums of extent() (k_extent_multi).  All of them read the
+// head's node values through every step's labels (no
 // frame is built) and none has a gradient.  What they share is written once: ScoreArgs, the by-value kernel argument that the
-// six rollout launchers fill in one host-side setup (score_setup); PixelReader, which says which pixels count and how a
+// rollout launchers fill in one host-side setup (score_setup); PixelReader, which says which pixels count and how a
 // pixel's values are read; wave_sum / wave_max, the 64-lane butterflies.  A further product is a kernel body over the reader
 // and an entry.  The training loss (k_sse, k_loss_multi, k_pool_targets) is in transfer.hip.
 #include "qt_common.h"
 #include "../../include/qtmpnn_edges.h"
+#include "../../include/qtmpnn_extent.h"
 
 namespace {
 
@@ -238,6 +240,98 @@ __global__ __launch_bounds__(256) void k_reliability_multi(ScoreArgs a, int K, i
     __syncthreads();
     float* dst = partial + (((int64_t)z * B + b) * gridDim.x + blockIdx.x) * (S * K * 4);
     for (int v = threadIdx.x; v < S * K * 4; v += 256) dst[v] = (red[0][v] + red[1][v]) + (red[2][v] + red[3][v]);
+}
+
+// Regional ice extent, ice area and the over- / under-forecast areas of a rollout (extent(); slot table in
+// include/qtmpnn_extent.h): k_score_multi's reads (PixelReader) and tile shape, with two per-pixel maps shared by all clips and
+// steps: region[p] (int8; 0 <= r < R places the pixel in region r, any other value in none: such a pixel is read no further and
+// adds nothing; null: every pixel is in region 0) and area[p] (the pixel's weight a; null: 1).  With I_o = y > thr and I_s =
+// f_s > thr (strict, fp32) every (region, tile) keeps row 0 [n, A = sum a, E_o = sum a I_o, SIA_o = sum a y] and per source
+// row 1 + s [E_s = sum a I_s, SIA_s = sum a f_s, O_s = sum a I_s (1 - I_o), U_s = sum a (1 - I_s) I_o] over its counted pixels.
+// k_reliability_multi's order: every thread keeps its four pixels' region, a, a * y, a * f_s (one fp32 rounding each) and
+// indicators in registers and the workgroup walks the regions; for region r a lane adds the terms of its pixels that lie in r
+// and +0 for the others, its pixels p, p + 256, p + 512, p + 768 of the tile in that order (starting from +0), then the 64-lane
+// butterfly (xor 32, 16, 8, 4, 2, 1), then (w0 + w1) + (w2 + w3) over the four waves.  A wave none of whose pixels is in the
+// region skips its butterflies: every lane holds +0 there, which is what they would leave.  n is a popcount of wave ballots.  A
+// term is selected, never multiplied by an indicator, so a NaN stays where it is: a NaN forecast is not ice (it is `under`
+// where the truth is ice) and makes SIA_s of its own region, tile and source NaN and nothing else; a NaN truth likewise SIA_o.
+// No atomics: the same bits on every run, eager or replayed.  LDS: 4 waves x R <= 32 regions x (1 + S) <= 4 rows x 4 floats <= 8 KB.
+template <int S>
+__global__ __launch_bounds__(256) void k_extent_multi(ScoreArgs a, const int8_t* __restrict__ region,
+                                                      const float* __restrict__ area, int R, int64_t P, int B,
+                                                      float* __restrict__ partial) {
+    constexpr int NR = 1 + S;
+    __shared__ float red[4][32 * NR * 4];
+    const int b = blockIdx.y, z = blockIdx.z;
+    const PixelReader<S> rd(a, P, b, z);
+    int reg[4];                   // -1: the pixel is not counted or in no region, and matches none
+    float w[4], wy[4], wf[S][4];
+    bool io[4], is[S][4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int64_t p = (int64_t)blockIdx.x * 1024 + j * 256 + threadIdx.x;
+        reg[j] = -1;
+        w[j] = 0.0f;
+        wy[j] = 0.0f;
+        io[j] = false;
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+            wf[s][j] = 0.0f;
+            is[s][j] = false;
+        }
+        if (p >= P) continue;
+        const int r = region ? (int)region[p] : 0;
+        if (!(r >= 0 && r < R)) continue;
+        const int lab = rd.label(p);
+        if (!rd.counted(p, lab)) continue;
+        reg[j] = r;
+        w[j] = area ? area[p] : 1.0f;
+        const float t = rd.truth(p);
+        float f[S];
+        rd.load(p, lab, f);
+        io[j] = t > a.thr;
+        wy[j] = __fmul_rn(w[j], t);
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+            is[s][j] = f[s] > a.thr;
+            wf[s][j] = __fmul_rn(w[j], f[s]);
+        }
+    }
+    const int wv = threadIdx.x >> 6;
+    for (int r = 0; r < R; ++r) {
+        int n = 0;
+        float v[NR * 4];
+#pragma unroll
+        for (int q = 0; q < NR * 4; ++q) v[q] = 0.0f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const bool in = reg[j] == r;
+            n += __popcll(__ballot(in));
+            v[1] += in ? w[j] : 0.0f;
+            v[2] += in && io[j] ? w[j] : 0.0f;
+            v[3] += in ? wy[j] : 0.0f;
+#pragma unroll
+            for (int s = 0; s < S; ++s) {
+                float* vs = v + 4 * (1 + s);
+                vs[0] += in && is[s][j] ? w[j] : 0.0f;
+                vs[1] += in ? wf[s][j] : 0.0f;
+                vs[2] += in && is[s][j] && !io[j] ? w[j] : 0.0f;
+                vs[3] += in && !is[s][j] && io[j] ? w[j] : 0.0f;
+            }
+        }
+        if (n) {                  // wave-uniform: n comes from ballots
+#pragma unroll
+            for (int q = 1; q < NR * 4; ++q) v[q] = wave_sum(v[q]);
+        }
+        v[0] = (float)n;
+        if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+            for (int q = 0; q < NR * 4; ++q) red[wv][r * NR * 4 + q] = v[q];
+        }
+    }
+    __syncthreads();
+    float* dst = partial + (((int64_t)z * B + b) * gridDim.x + blockIdx.x) * ((int64_t)R * NR * 4);
+    for (int q = threadIdx.x; q < R * NR * 4; q += 256) dst[q] = (red[0][q] + red[1][q]) + (red[2][q] + red[3][q]);
 }
 
 // Neighbourhood verification of a rollout (Fractions Skill Score): k_score_multi's reads (PixelReader), but a
@@ -706,7 +800,7 @@ __global__ __launch_bounds__(256) void k_event_sums(const int32_t* __restrict__ 
     }
 }
 
-// What the six rollout launchers have in common, in the order every one of them refuses: the segment arrays of 1..16 steps, the
+// What the rollout launchers have in common, in the order every one of them refuses: the segment arrays of 1..16 steps, the
 // truth and the dense baseline fields that are present into `a`; then `own`, the reason of the entry's own first checks if
 // one of them failed (else null); then the sizes, where B is at most `B_max` (a grid dimension for all but qt_score_maps).
 // Returns the reason of a refusal, or null; the entry reports it under its own name (QT_ARG).
@@ -790,6 +884,26 @@ extern "C" int qt_reliability_rollout(int nseg, const float* const* outs, const 
     const int64_t P = (int64_t)n * m;
     hipLaunchKernelGGL(by_sources(a.nb, k_reliability_multi<1>, k_reliability_multi<2>, k_reliability_multi<3>),
                        dim3(qt_cdiv(P, 1024), B, nseg), dim3(256), 0, (hipStream_t)stream, a, bins, P, B, partial);
+    QT_LAUNCHED();
+    return QT_OK;
+}
+
+extern "C" int qt_extent_rollout(int nseg, const float* const* outs, const int* out_strides, const int32_t* const* labels,
+                                 const int* Ns, const int32_t* const* n_devs, const float* y, int64_t y_clip_stride,
+                                 int64_t y_step_stride, const float* base1, int64_t base1_clip_stride, int64_t base1_step_stride,
+                                 const float* base2, int64_t base2_clip_stride, int64_t base2_step_stride,
+                                 const uint8_t* pix_mask, float thr, int B, int n, int m, const int8_t* region,
+                                 const float* area, int R, float* partial, void* stream) {
+    ScoreArgs a;
+    // the kernel's LDS rows are sized for 32 regions
+    const char* own = !(R >= 1 && R <= 32) ? "R must be 1..32" : !partial ? "null partial" : nullptr;
+    const char* why = score_setup(a, nseg, outs, out_strides, labels, Ns, n_devs, {y, y_clip_stride, y_step_stride},
+                                  {base1, base1_clip_stride, base1_step_stride}, {base2, base2_clip_stride, base2_step_stride},
+                                  pix_mask, thr, own, B, n, m);
+    QT_ARG(!why, why);
+    const int64_t P = (int64_t)n * m;
+    hipLaunchKernelGGL(by_sources(a.nb, k_extent_multi<1>, k_extent_multi<2>, k_extent_multi<3>),
+                       dim3(qt_cdiv(P, 1024), B, nseg), dim3(256), 0, (hipStream_t)stream, a, region, area, R, P, B, partial);
     QT_LAUNCHED();
     return QT_OK;
 }

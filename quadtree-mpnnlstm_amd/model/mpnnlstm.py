@@ -262,6 +262,26 @@ def edge_product(threshold):
     return reduce
 
 
+def extent_product(threshold, region_dev, area_dev, R):
+    """Regional extent sums: the (T_out, B, R, 1 + S, 4) float64 sums of the truth (row 0) and of model, persistence and (with
+    concat) climatology (ops.rollout_extent); region_dev / area_dev: the device maps of ops.rollout_extent, or None."""
+    def reduce(y_hat, meshes, x, y, concat):
+        return ops.rollout_extent(y_hat, meshes, y, threshold, region_dev, area_dev, R, persistence=launch_frame(x),
+                                  climatology=concat)
+    return reduce
+
+
+def _extent_maps(who, regions, areas, shape, device, region_names=None):
+    """ops.check_regions, the names of the regions checked against R, and the two maps uploaded once -> (region_dev, area_dev,
+    R, names)."""
+    region, area, R = ops.check_regions(who, regions, areas, shape)
+    names = tuple(f'region{r}' for r in range(R)) if region_names is None else tuple(region_names)
+    if len(names) != R or len(set(names)) != R:
+        raise ValueError(f'{who}: region_names must be {R} distinct names (the regions map has indices 0..{R - 1}), got {names}')
+    up = lambda a: None if a is None else torch.from_numpy(a).to(device).view(-1)
+    return up(region), up(area), R, names
+
+
 def events_product(threshold, kind, persist):
     """Event buffer: int32, the int64 sums (B, S1 - 1, 8) followed by the dates (B, S1, P) (split_event_buffer)."""
     def reduce(y_hat, meshes, x, y, concat):
@@ -726,6 +746,17 @@ class NextFramePredictorS2S(NextFramePredictor):
                                      high_interest_region=high_interest_region, graph_structure=graph_structure)
 
     @on_device(lambda self, *a, **k: self.device)
+    def make_graphed_extent(self, x, y, concat_layers=None, mask=None, high_interest_region=None, graph_structure=None,
+                            threshold=0.15, regions=None, areas=None):
+        """make_graphed_scores with the regional extent sums in place of the verification sums: the capture holds the rollout
+        and ops.rollout_extent (sources as make_graphed_scores), no frame gather.  regions / areas: the (W, H) host maps of
+        extent(), checked (ops.check_regions) and uploaded here, once.  Returns `extent(x, y, concat) -> (T_out, B, R, 1 + S, 4)`
+        float64 device tensor; `extent.warmup` is the given batch's."""
+        region_dev, area_dev, R, _ = _extent_maps('make_graphed_extent', regions, areas, x.shape[-3:-1], x.device)
+        return self._graphed_product(extent_product(threshold, region_dev, area_dev, R), x, y, concat_layers, mask=mask,
+                                     high_interest_region=high_interest_region, graph_structure=graph_structure)
+
+    @on_device(lambda self, *a, **k: self.device)
     def make_graphed_events(self, x, y, concat_layers=None, mask=None, high_interest_region=None, graph_structure=None,
                             threshold=0.15, kind='breakup', persist=5):
         """make_graphed_scores with the event dates in place of the verification sums: the capture holds the rollout, the
@@ -856,7 +887,7 @@ class NextFramePredictorS2S(NextFramePredictor):
         return np.stack(preds, 0)
 
     def _inference(self, loader, climatology, product, consume, use_graph, reads_y=True, begin=None, **fwd):
-        """The inference loop of predict, score, score_maps, reliability, fss, edge_distance and event_dates: per batch begin(x), if given, then one no-grad
+        """The inference loop of predict, score, score_maps, reliability, fss, edge_distance, extent and event_dates: per batch begin(x), if given, then one no-grad
         rollout (teacher forcing 0, forward arguments `fwd`) reduced by a reduce(y_hat, meshes, x, y, concat), see frames_product,
         whose result goes to consume(result, x); x is the clipped batch.  product(x) makes the reduce: for every batch of an eager
         call, for every capture of a graphed one, so it must not do what every batch needs (that is begin's).  use_graph: each
@@ -932,7 +963,7 @@ class NextFramePredictorS2S(NextFramePredictor):
 
     def _rollout_sums(self, loader, climatology, product, use_graph, begin=None, **fwd):
         """_inference with a reduce that leaves (T, B, ...) sums per batch (sums_product, reliability_product, fss_product,
-        edge_product) -> (the loader's (B_total, T, ...) array, one host copy per batch; the names of its sources)."""
+        edge_product, extent_product) ->(the loader's (B_total, T, ...) array, one host copy per batch; the names of its sources)."""
         sums = []
         self._inference(loader, climatology, product, lambda part, x: sums.append(np.moveaxis(part.cpu().numpy(), 0, 1)),
                         use_graph, begin=begin, **fwd)
@@ -1014,6 +1045,29 @@ class NextFramePredictorS2S(NextFramePredictor):
         sums, sources = self._rollout_sums(loader, climatology, lambda x: reduce, use_graph, mask=mask,      # (B, T, S, 8)
                                            high_interest_region=high_interest_region, graph_structure=graph_structure)
         return EdgeDistance(sums, sources, threshold)
+
+    @on_device(lambda self, *a, **k: self.device)
+    def extent(self, loader, climatology=None, mask=None, high_interest_region=None, graph_structure=None, use_graph=False,
+               threshold=0.15, regions=None, areas=None, region_names=None):
+        """Sea-ice extent, sea-ice area and the integrated ice-edge error over a loader -> qtmpnn.extent.Extent (beyond the
+        reference): per launch date, lead time and region the observed and forecast extent (the area of the pixels with `value >
+        threshold`, strict) and ice area (the area-weighted sum of the values), and the over- and under-forecast areas O and U
+        from which the result forms IIEE = O + U, the absolute extent error |O - U| and the misplacement error 2 min(O, U)
+        (Goessling et al. 2016) per forecast.  regions: a (W, H) integer map, region index per pixel, negative for none, at most
+        32 regions (None: one region of every pixel); areas: a (W, H) map of cell areas, finite and non-negative, in whose
+        unit the results are (model.utils.cell_area_weights for a latitude-longitude grid; None: 1, i.e. pixel counts);
+        region_names: a name per region index.  The maps are checked and uploaded once, before the first batch.
+
+        score()'s loop, arguments and sources: every batch leaves (1 + S) * 4 sums per (lead time, clip, region) on the device
+        (ops.rollout_extent: the head's outputs read through the labels, no frame is built) and makes one host copy of them.
+        use_graph=True replays rollout + sums as one hipGraph per distinct batch shape (make_graphed_extent)."""
+        from qtmpnn.extent import Extent
+        region_dev, area_dev, R, names = _extent_maps('extent', regions, areas, loader.dataset.image_shape, self.device,
+                                                      region_names)
+        reduce = extent_product(threshold, region_dev, area_dev, R)
+        sums, sources = self._rollout_sums(loader, climatology, lambda x: reduce, use_graph, mask=mask,      # (B, T, R, 1 + S, 4)
+                                           high_interest_region=high_interest_region, graph_structure=graph_structure)
+        return Extent(sums, sources, threshold, names)
 
     @on_device(lambda self, *a, **k: self.device)
     def event_dates(self, loader, climatology=None, mask=None, high_interest_region=None, graph_structure=None, use_graph=False,

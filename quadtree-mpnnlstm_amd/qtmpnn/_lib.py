@@ -1,5 +1,5 @@
-"""ctypes binding of libqtmpnn_hip.so (the C ABI declared in include/qtmpnn.h, include/qtmpnn_edges.h and
-include/qtmpnn_loss.h).
+"""ctypes binding of libqtmpnn_hip.so (the C ABI declared in include/qtmpnn.h, include/qtmpnn_edges.h,
+include/qtmpnn_loss.h and include/qtmpnn_extent.h).
 
 The product path has no CPU fallback: if the shared library is missing or a call
 fails, an exception is raised.
@@ -116,6 +116,10 @@ _LOSS_SIGNATURES = {
     'qt_wbce_rollout': _SIGNATURES['qt_wsse_rollout'][:-1] + [_F, _P],
     'qt_wbce_rollout_bwd': _SIGNATURES['qt_wsse_rollout_bwd'][:-1] + [_F, _P],
 }
+# The entry of include/qtmpnn_extent.h, bound the same way: qt_score_rollout's arguments up to m, then region, area, R, partial.
+_EXTENT_SIGNATURES = {
+    'qt_extent_rollout': _SIGNATURES['qt_score_rollout'][:20] + [_P, _P, _I, _P, _P],
+}
 _PLAIN = {'qt_proj_bwd_blocks', 'qt_abi_version', 'qt_cheb_clip_rows', 'qt_cheb_tile_sync_words', 'qt_cheb_tile_xbuf_words', 'qt_tile_cap', 'qt_remesh_clip_rows', 'qt_tail_cap', 'qt_num_cus', 'qt_lstm_fused_blocks', 'qt_wgrad_blocks', 'qt_lstm_bwd_blocks', 'qt_lstm_dgrad_blocks', 'qt_attn_blocks', 'qt_mhattn_blocks'}  # return a value, not an error code
 
 _lib = None
@@ -131,7 +135,7 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
         lib.qt_last_error.restype = ctypes.c_char_p
         lib.qt_last_error.argtypes = []
-        for name, args in {**_SIGNATURES, **_EDGE_SIGNATURES, **_LOSS_SIGNATURES}.items():
+        for name, args in {**_SIGNATURES, **_EDGE_SIGNATURES, **_LOSS_SIGNATURES, **_EXTENT_SIGNATURES}.items():
             fn = getattr(lib, name)
             fn.argtypes = args
             fn.restype = ctypes.c_int

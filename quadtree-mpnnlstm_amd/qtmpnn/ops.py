@@ -2159,6 +2159,75 @@ def rollout_reliability(outputs, meshes, y, threshold=0.15, bins=10, persistence
     return part if per_tile else part.double().sum(2)
 
 
+EXTENT_MAX_REGIONS = 32      # qt_extent_rollout keeps a tile's rows of every region in LDS
+
+
+def check_regions(who, regions, areas, shape):
+    """The maps of an extent call on the host, refused under `who` -> (region int8 (W, H) or None, area float32 (W, H) or None,
+    R).  regions: an integer array of `shape` = (W, H); a value r >= 0 places the pixel in region r, a negative one in none;
+    R = max + 1 (1 if no pixel is in a region), at most 32.  None: one region of every pixel.  areas: finite, non-negative
+    values of `shape` (cell areas, e.g. model.utils.cell_area_weights); None: 1 everywhere."""
+    import numpy as np
+    shape = tuple(int(v) for v in shape)
+    region, area, R = None, None, 1
+    if regions is not None:
+        r = regions.detach().cpu().numpy() if isinstance(regions, torch.Tensor) else np.asarray(regions)
+        if tuple(r.shape) != shape:
+            raise ValueError(f'{who}: regions of shape {tuple(r.shape)} for frames of {shape}')
+        if r.dtype.kind == 'f':
+            if not (np.isfinite(r).all() and (r == np.floor(r)).all()):
+                raise ValueError(f'{who}: regions must hold integers (a region index per pixel, negative for none)')
+        elif r.dtype.kind not in 'iu':
+            raise ValueError(f'{who}: regions must hold integers (a region index per pixel, negative for none), got {r.dtype}')
+        top = int(r.max()) if r.size else -1
+        R = max(top, 0) + 1
+        if R > EXTENT_MAX_REGIONS:
+            raise ValueError(f'{who}: regions name {R} regions (largest index {top}), at most {EXTENT_MAX_REGIONS} are taken')
+        region = np.ascontiguousarray(np.where(r < 0, -1, r).astype(np.int8))
+    if areas is not None:
+        a = areas.detach().cpu().numpy() if isinstance(areas, torch.Tensor) else np.asarray(areas)
+        if tuple(a.shape) != shape:
+            raise ValueError(f'{who}: areas of shape {tuple(a.shape)} for frames of {shape}')
+        if a.dtype.kind not in 'fiu':
+            raise ValueError(f'{who}: areas must be numbers, got {a.dtype}')
+        a = a.astype(np.float64)
+        if not np.isfinite(a).all():
+            raise ValueError(f'{who}: areas must be finite')
+        if (a < 0).any():
+            raise ValueError(f'{who}: areas must not be negative (lowest {float(a.min())!r})')
+        with np.errstate(over='ignore'):
+            area = np.ascontiguousarray(a.astype(np.float32))
+        if not np.isfinite(area).all():
+            raise ValueError(f'{who}: areas must be finite in fp32')
+    return region, area, R
+
+
+def rollout_extent(outputs, meshes, y, threshold=0.15, regions=None, areas=None, R=1, persistence=None, climatology=None,
+                   per_tile=False):
+    """Regional extent sums of a rollout, float64 (T, B, R, 1 + S, 4) on the device (qt_extent_rollout; slot table in
+    include/qtmpnn_extent.h): per output step, clip and region, over the region's counted pixels with weight a, row 0 (the truth)
+    [n, A = sum a, E_o = sum a I_o, SIA_o = sum a y] and per source row 1 + s [E_s = sum a I_s, SIA_s = sum a f_s, O_s = sum a
+    I_s (1 - I_o), U_s = sum a (1 - I_s) I_o], I = value > threshold (strict).  regions: an int8 device tensor of P entries
+    (0 <= r < R: region r; any other value: none) or None (every pixel in region 0); areas: a float32 device tensor of P
+    entries or None (1); both as check_regions leaves them, uploaded once by the caller.  Operands, sources and counting rule
+    are rollout_scores'.  No autograd, no host read: capturable.  per_tile=True returns the launch's own fp32 partials
+    (T, B, ceil(P/1024), R, 1 + S, 4) instead of their float64 sum over the tiles."""
+    who = 'rollout_extent'
+    if not (isinstance(R, int) and not isinstance(R, bool) and 1 <= R <= EXTENT_MAX_REGIONS):
+        raise ValueError(f'{who}: R must be an integer in 1..{EXTENT_MAX_REGIONS}, got {R!r}')
+    outs, y, bases, S, B, T, P = _score_args(who, outputs, meshes, y, persistence, climatology)
+    for t, name, dtype in ((regions, 'regions', torch.int8), (areas, 'areas', torch.float32)):
+        if t is not None and not (isinstance(t, torch.Tensor) and t.dtype == dtype and t.device == outs[0].device
+                                  and t.numel() == P and t.is_contiguous()):
+            got = f'{t.dtype} {tuple(t.shape)} on {t.device}' if isinstance(t, torch.Tensor) else type(t).__name__
+            raise ValueError(f'{who}: {name} must be a contiguous {dtype} tensor of {P} pixels on {outs[0].device}, got {got}')
+    nt = -(P // -1024)
+    part = outs[0].new_empty(T, B, nt, R, 1 + S, 4)
+    _score_chunks('qt_extent_rollout', outs, meshes, y, bases, threshold, B, T, P,
+                  lambda z0: (ptr(regions), ptr(areas), R, ptr(part[z0:])))
+    return part if per_tile else part.double().sum(2)
+
+
 def check_scales(who, scales):
     """`scales` of an FSS call: 1..8 odd window sizes in 1..33, strictly increasing (the kernel's halo is 16 pixels and its
     column mask one 64-bit word), refused under `who`.  -> tuple of int."""
