@@ -279,6 +279,24 @@ int qt_bce_rollout_bwd(int nseg, const float* const* outs, const int* out_stride
                        const float* const* sys, const int* Ns, const int32_t* const* n_devs, const float* g, int W,
                        float* const* gouts, void* stream);
 
+/* The binary cross-entropy of qt_bce_rollout with the weights of qt_wsse_rollout and a weight on the positive class.  The
+ * arguments are qt_wsse_rollout's / qt_wsse_rollout_bwd's (w (n*m) pixel weights and lam (nseg) step weights, fp32 device arrays,
+ * non-negative; the caller forms the divisor) followed by pos_weight, passed by value, finite and > 0 (a captured graph keeps
+ * the value it was captured with).  With o = outs[z][labels[p]*stride], L1 = max(log o, -100), L0 = max(log(1 - o), -100):
+ *   partial[z][b*ntile + tile] = - sum over the tile's pixels with a node of lam[z] w[p] (pos_weight y L1 + (1 - y) L0)
+ * and swys[z] (N_z, 2) receives per node [sum of w | sum of w*y] over the node's pixels.  qt_wbce_rollout_bwd writes
+ *   gouts[z][i, 0] = g lam[z] (o_i sw_i - swy_i (pos_weight + o_i (1 - pos_weight))) / max(o_i (1 - o_i), 1e-12),
+ * the per-pixel derivative (o - y (pos_weight + o (1 - pos_weight))) / (o (1 - o)) summed over the node with its weights (finite
+ * at o = 0 and o = 1), zeros in columns 1..W-1, rows up to n_devs[z] where given.  Unit weights and pos_weight = 1 give
+ * qt_bce_rollout's sums.  No atomics: the same bits on every run. */
+int qt_wbce_rollout(int nseg, const float* const* outs, const int* out_strides, const int32_t* const* labels,
+                    const uint8_t* const* levels, const int* Ns, float* const* swys, const float* y, int64_t y_clip_stride,
+                    int64_t y_step_stride, const float* w, const float* lam, int B, int n, int m, float* partial,
+                    float pos_weight, void* stream);
+int qt_wbce_rollout_bwd(int nseg, const float* const* outs, const int* out_strides, const float* const* swys,
+                        const int* Ns, const int32_t* const* n_devs, const float* g, const float* lam, int W,
+                        float* const* gouts, float pos_weight, void* stream);
+
 /* qt_score_rollout: forecast verification of a rollout (no gradient), shaped like qt_sse_rollout: up to 16 output steps per
  * call, one mesh per step, grid (ceil(P/1024), B, nseg).  Per (step z, clip b, 1024-pixel tile) and per source s it writes
  * 8 floats, partial[(((z*B + b)*ntile + tile)*S + s)*8 + slot], over the tile's counted pixels:
@@ -315,6 +333,33 @@ int qt_reliability_rollout(int nseg, const float* const* outs, const int* out_st
                            const float* base2, int64_t base2_clip_stride, int64_t base2_step_stride,
                            const uint8_t* pix_mask, float thr, int B, int n, int m, int bins, float* partial, void* stream);
 
+/* qt_extent_rollout: sea-ice extent, sea-ice area and the over- / under-forecast areas of a rollout per region, the sums behind
+ * the integrated ice-edge error and its decomposition (Goessling et al. 2016: IIEE = O + U, AEE = |O - U|, ME = 2 min(O, U), all
+ * three formed by the caller per forecast).  The arguments up to m, the sources (model: column 0 of the step's output through
+ * the step's labels; then the dense baselines present, S = 1 + their number) and the counting rule are qt_score_rollout's.
+ * Two per-pixel maps of n*m entries, shared by all clips and steps:
+ *   region   int8 or NULL.  0 <= region[p] < R places pixel p in that region; any other value places it in none, and it adds
+ *            nothing anywhere.  NULL: every pixel is in region 0.  R is in 1..32.
+ *   area     float or NULL: the weight a of pixel p (a cell area).  NULL: 1.
+ * With I_o = y > thr and I_s = f_s > thr (strict, fp32) the launch writes, per (step z, clip b, tile of 1024 pixels, region r),
+ * 1 + S rows of 4 floats over the counted pixels of the region, partial[((((z*B + b)*ntile + tile)*R + r)*(1 + S) + row)*4 + slot]:
+ *   row 0      the truth     slot 0  n (a count)      slot 1  A = sum a           slot 2  E_o = sum a I_o      slot 3  SIA_o = sum a y
+ *   row 1 + s  source s      slot 0  E_s = sum a I_s  slot 1  SIA_s = sum a f_s   slot 2  O_s = sum a I_s (1 - I_o)
+ *                                                                                 slot 3  U_s = sum a (1 - I_s) I_o
+ * Grid (ceil(n*m/1024), B, nseg), 256 threads, one launch.  Summation order, fixed by pixel position: a thread adds its pixels p,
+ * p + 256, p + 512, p + 768 of the tile that lie in the region in that order (a * y and a * f_s are rounded to fp32 once), then
+ * the 64-lane butterfly (xor 32 .. 1), then (w0 + w1) + (w2 + w3) over the four waves; n is a popcount.  No atomics: the same
+ * inputs give the same bits.  The caller adds the tiles (in float64: ops.rollout_extent).
+ * NaN: a NaN forecast value is not ice (it counts as under-forecast where the truth is ice) and makes SIA_s of its own region,
+ * tile and source NaN; it touches no count, no other slot, no other region and no other source.  A NaN truth is not ice and
+ * makes SIA_o of its region and tile NaN, likewise.  The areas are the caller's to keep finite (ops.check_regions).
+ * Refused with qt_last_error(): whatever qt_reliability_rollout refuses, an R outside 1..32 and a null partial. */
+int qt_extent_rollout(int nseg, const float* const* outs, const int* out_strides, const int32_t* const* labels, const int* Ns,
+                      const int32_t* const* n_devs, const float* y, int64_t y_clip_stride, int64_t y_step_stride,
+                      const float* base1, int64_t base1_clip_stride, int64_t base1_step_stride, const float* base2,
+                      int64_t base2_clip_stride, int64_t base2_step_stride, const uint8_t* pix_mask, float thr, int B, int n, int m,
+                      const int8_t* region, const float* area, int R, float* partial, void* stream);
+
 /* qt_fss_rollout: neighbourhood verification of a rollout (Fractions Skill Score, Roberts & Lean 2008), all in integers.  The
  * arguments up to m, the sources and the counting rule are qt_score_rollout's; the frame is n rows of m pixels, p = r*m + c.
  * For clip b, step z and pixel p: counted(p) = the step's label lab has 0 <= lab < rows and p is not under pix_mask;
@@ -338,6 +383,31 @@ int qt_fss_rollout(int nseg, const float* const* outs, const int* out_strides, c
                    const float* base1, int64_t base1_clip_stride, int64_t base1_step_stride, const float* base2,
                    int64_t base2_clip_stride, int64_t base2_step_stride, const uint8_t* pix_mask, float thr, int B, int n, int m,
                    int nscales, const int* scales, int32_t* partial, void* stream);
+
+/* qt_edge_rollout: ice-edge displacement of a rollout (average ice-edge displacement and Hausdorff distances, Dukhovskoy et
+ * al. 2015, Melsom et al. 2019), all in integers.  The arguments up to m, the sources (model: column 0 of the step's output
+ * through the step's labels; then the dense baselines present) and the counting rule are qt_score_rollout's; the frame is n rows
+ * of m pixels, p = r*m + c, at most 256 x 256 (a larger frame is refused: the search keeps a frame's edge sets in LDS).
+ *   counted(p)   the step's label lab has 0 <= lab < rows and p is not under pix_mask.
+ *   ice(x, p)    counted(p) && x[p] > thr, strict, fp32: NaN and -inf are not ice, +inf is.
+ *   E(x)         the edge set of field x: the pixels p with ice(x, p) that have at least one 4-neighbour which is inside the
+ *                frame, counted, and not ice.  Frame borders and uncounted pixels (land, mask, no node) make no edge.
+ *   d2(p, E)     for a non-empty set E, min over e in E of dr^2 + dc^2: exact over the whole frame, no search radius.
+ *   q(p, E)      isqrt(65536 * d2(p, E)): the distance in 1/256 pixel, rounded down, exact (fixed up in 64-bit integers).
+ * Grid (ceil(n/16), B, nseg), two launches: the first leaves E(y) and E(f_s) as bit-planes in `planes`, scratch of
+ * nseg * B * (S + 1) * n * ceil(m/64) 64-bit words that the caller provides and need not initialise; the second searches them.
+ * Per (step z, clip b, band of 16 rows) and source s it writes 8 int32, partial[(((z*B + b)*nband + band)*S + s)*8 + slot]:
+ *   slot 0  n_f = |E(f_s)| in the band         slot 1  n_o = |E(y)| in the band
+ *   slot 2  sum_q_fo    slot 4  sum_d2_fo    slot 6  max_d2_fo    over p in E(f_s), rows of the band, against all of E(y)
+ *   slot 3  sum_q_of    slot 5  sum_d2_of    slot 7  max_d2_of    over p in E(y), rows of the band, against all of E(f_s)
+ * A direction whose target set is empty has sum and max 0.  Over the bands slots 0-5 add and slots 6-7 are maximised (the
+ * caller's, in int64: d2 <= 130050 and q <= 92321, so a band of <= 4096 queries stays below 2^31 and a frame need not).
+ * No atomics, integers only: the same inputs give the same bits. */
+int qt_edge_rollout(int nseg, const float* const* outs, const int* out_strides, const int32_t* const* labels, const int* Ns,
+                    const int32_t* const* n_devs, const float* y, int64_t y_clip_stride, int64_t y_step_stride,
+                    const float* base1, int64_t base1_clip_stride, int64_t base1_step_stride, const float* base2,
+                    int64_t base2_clip_stride, int64_t base2_step_stride, const uint8_t* pix_mask, float thr, int B, int n, int m,
+                    uint64_t* planes, int32_t* partial, void* stream);
 
 /* qt_score_maps: the same eight sums kept per pixel and summed over the clips (error maps per lead time).  The arguments up
  * to m are qt_score_rollout's, with its sources, counting rule, fp32 d = f - y and strict > classes; grid (ceil(P/256), nseg),

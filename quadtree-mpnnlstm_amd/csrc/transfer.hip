@@ -10,7 +10,6 @@
 // node value is written once, in a fixed order, with no atomics.
 #include <cfloat>
 #include "qt_common.h"
-#include "../../include/qtmpnn_loss.h"
 
 namespace {
 

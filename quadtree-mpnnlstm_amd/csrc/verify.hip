@@ -9,8 +9,6 @@
 // pixel's values are read; wave_sum / wave_max, the 64-lane butterflies.  A further product is a kernel body over the reader
 // and an entry.  The training loss (k_sse, k_loss_multi, k_pool_targets) is in transfer.hip.
 #include "qt_common.h"
-#include "../../include/qtmpnn_edges.h"
-#include "../../include/qtmpnn_extent.h"
 
 namespace {
 
@@ -243,7 +241,7 @@ __global__ __launch_bounds__(256) void k_reliability_multi(ScoreArgs a, int K, i
 }
 
 // Regional ice extent, ice area and the over- / under-forecast areas of a rollout (extent(); slot table in
-// include/qtmpnn_extent.h): k_score_multi's reads (PixelReader) and tile shape, with two per-pixel maps shared by all clips and
+// include/qtmpnn.h, qt_extent_rollout): k_score_multi's reads (PixelReader) and tile shape, with two per-pixel maps shared by all clips and
 // steps: region[p] (int8; 0 <= r < R places the pixel in region r, any other value in none: such a pixel is read no further and
 // adds nothing; null: every pixel is in region 0) and area[p] (the pixel's weight a; null: 1).  With I_o = y > thr and I_s =
 // f_s > thr (strict, fp32) every (region, tile) keeps row 0 [n, A = sum a, E_o = sum a I_o, SIA_o = sum a y] and per source
@@ -449,7 +447,7 @@ __global__ __launch_bounds__(256) void k_fss_multi(ScoreArgs a, FssScales sc, in
 // Ice-edge displacement of a rollout (edge_distance()): k_fss_multi's reads (PixelReader), but what is compared
 // is where the ice edge lies.  ice(x, p) = counted(p) && x[p] > thr (strict, fp32: NaN and -inf are not ice, +inf is); the edge
 // set E(x) holds the ice pixels with a 4-neighbour that is inside the frame, counted and not ice (frame borders and uncounted
-// pixels make no edge).  For each source f the eight integers of include/qtmpnn_edges.h are kept per (step, clip, band of 16 rows):
+// pixels make no edge).  For each source f the eight integers of qt_edge_rollout (include/qtmpnn.h) are kept per (step, clip, band of 16 rows):
 // [|E(f)|, |E(y)|, sum q fo, sum q of, sum d2 fo, sum d2 of, max d2 fo, max d2 of], d2(p, E) = min over e of dr^2 + dc^2,
 // q = isqrt(65536 d2), `fo` over p in E(f) against E(y), `of` the reverse; a direction whose target set is empty gives 0.
 // The search is over the whole frame: no radius, no cap.

@@ -1,5 +1,4 @@
-"""ctypes binding of libqtmpnn_hip.so (the C ABI declared in include/qtmpnn.h, include/qtmpnn_edges.h,
-include/qtmpnn_loss.h and include/qtmpnn_extent.h).
+"""ctypes binding of libqtmpnn_hip.so (the C ABI declared in include/qtmpnn.h).
 
 The product path has no CPU fallback: if the shared library is missing or a call
 fails, an exception is raised.
@@ -15,7 +14,14 @@ LIB_PATH = os.environ.get('QT_LIB_PATH') or os.path.join(_HERE, 'libqtmpnn_hip.s
 
 _P, _I, _L, _F = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
 
-# name -> argument types (return type is int unless listed in _RESTYPE)
+# The operands every rollout-verification entry starts with (qt_score_rollout's up to m): nseg, outs, out_strides, labels, Ns,
+# n_devs, y + 2 strides, base1 + 2 strides, base2 + 2 strides, pix_mask, thr, B, n, m
+_ROLLOUT = [_I, _P, _P, _P, _P, _P, _P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _F, _I, _I, _I]
+# qt_wsse_rollout / _bwd, whose arguments qt_wbce_rollout / _bwd extend
+_WSSE = [_I, _P, _P, _P, _P, _P, _P, _P, _L, _L, _P, _P, _I, _I, _I, _P, _P]
+_WSSE_BWD = [_I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P]
+
+# name -> argument types: every entry include/qtmpnn.h declares but qt_last_error (bound in load()); all return int
 _SIGNATURES = {
     'qt_abi_version': [],
     'qt_quadtree_stage1': [_P, _I, _I, _P, _I, _P, _I, _I, _I, _I, _F, _I, _P, _P, _P, _P, _P, _I, _P, _I, _P],
@@ -39,15 +45,20 @@ _SIGNATURES = {
     'qt_pool': [_P, _I, _L, _P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _I, _I, _P],
     'qt_sse_rollout': [_I, _P, _P, _P, _P, _P, _P, _P, ctypes.c_int64, ctypes.c_int64, _I, _I, _I, _P, _P],
     'qt_sse_rollout_bwd': [_I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P],
-    'qt_wsse_rollout': [_I, _P, _P, _P, _P, _P, _P, _P, _L, _L, _P, _P, _I, _I, _I, _P, _P],
-    'qt_wsse_rollout_bwd': [_I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P],
+    'qt_wsse_rollout': _WSSE,
+    'qt_wsse_rollout_bwd': _WSSE_BWD,
     'qt_bce_rollout': [_I, _P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _I, _I, _P, _P],
     'qt_bce_rollout_bwd': [_I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P],
-    'qt_score_rollout': [_I, _P, _P, _P, _P, _P, _P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _F, _I, _I, _I, _P, _P],
-    'qt_reliability_rollout': [_I, _P, _P, _P, _P, _P, _P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _F, _I, _I, _I, _I, _P, _P],
-    'qt_fss_rollout': [_I, _P, _P, _P, _P, _P, _P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _F, _I, _I, _I, _I, _P, _P, _P],
-    'qt_score_maps': [_I, _P, _P, _P, _P, _P, _P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _F, _I, _I, _I, _P, _L, _P],
-    'qt_event_scan': [_I, _P, _P, _P, _P, _P, _P, _L, _L, _P, _L, _L, _P, _F, _I, _I, _I, _P, _L, _I, _I, _I, _P, _P, _P],
+    # qt_wsse_rollout's / _bwd's arguments, then pos_weight by value and the stream
+    'qt_wbce_rollout': _WSSE[:-1] + [_F, _P],
+    'qt_wbce_rollout_bwd': _WSSE_BWD[:-1] + [_F, _P],
+    'qt_score_rollout': _ROLLOUT + [_P, _P],
+    'qt_reliability_rollout': _ROLLOUT + [_I, _P, _P],
+    'qt_extent_rollout': _ROLLOUT + [_P, _P, _I, _P, _P],
+    'qt_fss_rollout': _ROLLOUT + [_I, _P, _P, _P],
+    'qt_edge_rollout': _ROLLOUT + [_P, _P, _P],
+    'qt_score_maps': _ROLLOUT + [_P, _L, _P],
+    'qt_event_scan': _ROLLOUT[:12] + _ROLLOUT[15:20] + [_P, _L, _I, _I, _I, _P, _P, _P],         # (one dense baseline, not two)
     'qt_event_sums': [_P, _I, _I, _I, _I, _P, _P],
     'qt_remesh': [_P, _P, _P, _I, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P],
     'qt_remesh_clip_rows': [],
@@ -106,20 +117,6 @@ _SIGNATURES = {
     'qt_mhattn_bwd_merge': [_P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _I, _P],
     'qt_attn_weights': [_P, _P, _P, _P, _P, _I, _L, _L, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P],
 }
-# The entries of include/qtmpnn_edges.h.  The table above mirrors include/qtmpnn.h name for name, and the tests hold both to the 87
-# entry points README.md counts (exported_names()); an entry declared beside that header is bound beside that table.
-_EDGE_SIGNATURES = {
-    'qt_edge_rollout': [_I, _P, _P, _P, _P, _P, _P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _F, _I, _I, _I, _P, _P, _P],
-}
-# The entries of include/qtmpnn_loss.h, bound the same way: qt_wsse_rollout's / _bwd's arguments and pos_weight by value.
-_LOSS_SIGNATURES = {
-    'qt_wbce_rollout': _SIGNATURES['qt_wsse_rollout'][:-1] + [_F, _P],
-    'qt_wbce_rollout_bwd': _SIGNATURES['qt_wsse_rollout_bwd'][:-1] + [_F, _P],
-}
-# The entry of include/qtmpnn_extent.h, bound the same way: qt_score_rollout's arguments up to m, then region, area, R, partial.
-_EXTENT_SIGNATURES = {
-    'qt_extent_rollout': _SIGNATURES['qt_score_rollout'][:20] + [_P, _P, _I, _P, _P],
-}
 _PLAIN = {'qt_proj_bwd_blocks', 'qt_abi_version', 'qt_cheb_clip_rows', 'qt_cheb_tile_sync_words', 'qt_cheb_tile_xbuf_words', 'qt_tile_cap', 'qt_remesh_clip_rows', 'qt_tail_cap', 'qt_num_cus', 'qt_lstm_fused_blocks', 'qt_wgrad_blocks', 'qt_lstm_bwd_blocks', 'qt_lstm_dgrad_blocks', 'qt_attn_blocks', 'qt_mhattn_blocks'}  # return a value, not an error code
 
 _lib = None
@@ -135,7 +132,7 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
         lib.qt_last_error.restype = ctypes.c_char_p
         lib.qt_last_error.argtypes = []
-        for name, args in {**_SIGNATURES, **_EDGE_SIGNATURES, **_LOSS_SIGNATURES, **_EXTENT_SIGNATURES}.items():
+        for name, args in _SIGNATURES.items():
             fn = getattr(lib, name)
             fn.argtypes = args
             fn.restype = ctypes.c_int

@@ -2205,7 +2205,7 @@ def check_regions(who, regions, areas, shape):
 def rollout_extent(outputs, meshes, y, threshold=0.15, regions=None, areas=None, R=1, persistence=None, climatology=None,
                    per_tile=False):
     """Regional extent sums of a rollout, float64 (T, B, R, 1 + S, 4) on the device (qt_extent_rollout; slot table in
-    include/qtmpnn_extent.h): per output step, clip and region, over the region's counted pixels with weight a, row 0 (the truth)
+    include/qtmpnn.h): per output step, clip and region, over the region's counted pixels with weight a, row 0 (the truth)
     [n, A = sum a, E_o = sum a I_o, SIA_o = sum a y] and per source row 1 + s [E_s = sum a I_s, SIA_s = sum a f_s, O_s = sum a
     I_s (1 - I_o), U_s = sum a (1 - I_s) I_o], I = value > threshold (strict).  regions: an int8 device tensor of P entries
     (0 <= r < R: region r; any other value: none) or None (every pixel in region 0); areas: a float32 device tensor of P
@@ -2276,7 +2276,7 @@ EDGE_MAX = 256      # largest frame side of rollout_edges (qt_edge_rollout keeps
 
 def rollout_edges(outputs, meshes, y, threshold=0.15, persistence=None, climatology=None, per_tile=False):
     """Ice-edge distance sums of a rollout, int64 (T, B, S, 8) on the device (qt_edge_rollout; definitions and slot table in
-    include/qtmpnn_edges.h): per output step, clip and source [n_f, n_o, sum_q_fo, sum_q_of, sum_d2_fo, sum_d2_of, max_d2_fo,
+    include/qtmpnn.h): per output step, clip and source [n_f, n_o, sum_q_fo, sum_q_of, sum_d2_fo, sum_d2_of, max_d2_fo,
     max_d2_of].  The edge set E(x) of a field holds the counted pixels with x > threshold (strict) that have a 4-neighbour inside
     the frame, counted and not ice; n_f = |E(forecast)|, n_o = |E(y)|; d2 is the squared pixel distance to the nearest pixel of
     the other set over the whole frame and q = isqrt(65536 d2); `fo` runs over E(forecast) against E(y), `of` the reverse, and a

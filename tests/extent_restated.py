@@ -1,5 +1,5 @@
 """Regional ice extent, ice area and over- / under-forecast areas restated in numpy from dense frames, written from the slot
-table of include/qtmpnn_extent.h.  The checker of qt_extent_rollout, ops.rollout_extent and NextFramePredictorS2S.extent()
+table of qt_extent_rollout in include/qtmpnn.h.  The checker of qt_extent_rollout, ops.rollout_extent and NextFramePredictorS2S.extent()
 (tests only; no code shared with qtmpnn).
 
 What decides an integer or an indicator is done as the device does it: ice on the fp32 value with the threshold rounded to fp32

@@ -1,11 +1,42 @@
-"""Shared helpers for the GPU parity tests (oracle = checker only)."""
+"""Shared helpers for the GPU parity tests (oracle = checker only) and the one parser of the C header for the host tests."""
+import collections
+import ctypes
 import os
+import re
 
 import numpy as np
 import torch
 
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
 RTOL, ATOL = 1e-4, 1e-5          # north_star: 1e-4 rel fp32
+
+HEADER = os.path.join(ROOT, 'include', 'qtmpnn.h')
+Decl = collections.namedtuple('Decl', 'params kinds text times')
+
+
+def header_decls():
+    """The declarations of include/qtmpnn.h, comments stripped: {name: Decl} for every qt_* function.  params: the parameter
+    strings, runs of white space as one blank ([] for `(void)`); kinds: a letter per parameter, p a pointer, f a float, u a uint32_t,
+    l an int64_t, i anything else (int); text: the declaration from its return type to the closing parenthesis as written;
+    times: how often the header declares the name (1, unless something is wrong)."""
+    bare = re.sub(r'/\*.*?\*/', ' ', open(HEADER).read(), flags=re.S)
+    found = re.findall(r'\b((?:int|const\s+char\s*\*)\s+(qt_[a-z0-9_]+)\s*\(([^;{]*?)\))\s*;', bare, flags=re.S)
+    mentions = re.findall(r'\b(qt_[a-z0-9_]+)\s*\(', bare)
+    assert {name for _, name, _ in found} == set(mentions), 'a qt_* declaration that this parser cannot read'
+    kind = lambda p: 'p' if '*' in p else 'f' if p.startswith('float') else 'u' if p.startswith('uint32_t') else \
+        'l' if p.startswith('int64_t') else 'i'
+    decls = {}
+    for text, name, args in found:
+        params = [re.sub(r'\s+', ' ', p.strip()) for p in args.split(',')] if args.strip() not in ('', 'void') else []
+        decls[name] = Decl(params, ''.join(kind(p) for p in params), text, mentions.count(name))
+    return decls
+
+
+def binding_kinds(argtypes):
+    """The kind string of a ctypes argument list, in header_decls()'s letters."""
+    letter = {ctypes.c_void_p: 'p', ctypes.c_int: 'i', ctypes.c_int64: 'l', ctypes.c_float: 'f', ctypes.c_uint32: 'u'}
+    return ''.join(letter[t] for t in argtypes)
 
 
 def golden(name):

@@ -97,11 +97,12 @@ def test_fused_refuses_wrong_target_shapes_before_any_launch(shape):
 
 
 def test_bce_entries_are_declared_exported_and_bound():
+    from helpers import header_decls
     from qtmpnn import _lib
-    header = open(os.path.join(ROOT, 'include', 'qtmpnn.h')).read()
+    decls = header_decls()
     lib = ctypes.CDLL(_lib.LIB_PATH)
     for name in ('qt_bce_rollout', 'qt_bce_rollout_bwd'):
-        assert re.search(r'\bint\s+%s\s*\(' % name, header), name
+        assert re.match(r'int\s+%s\s*\(' % name, decls[name].text) and decls[name].times == 1, name
         assert hasattr(lib, name) and name in _lib._SIGNATURES and name in _lib.exported_names(), name
     # the arguments of the squared-error pair
     assert _lib._SIGNATURES['qt_bce_rollout'] == _lib._SIGNATURES['qt_sse_rollout']

@@ -175,29 +175,27 @@ def test_edge_distance_refuses_by_name():
 
 
 def test_edge_entry_is_declared_exported_and_bound():
+    from helpers import binding_kinds, header_decls
     from qtmpnn import _lib
-    header = open(os.path.join(ROOT, 'include', 'qtmpnn_edges.h')).read()
-    assert re.search(r'\bint\s+qt_edge_rollout\s*\(', header)
-    # the entry's own header and table hold each other as qtmpnn.h and _SIGNATURES do (tests/test_host_cpu.py): the same names,
-    # and per argument a pointer, an int, an int64 or a float in the same place
-    bare = re.sub(r'/\*.*?\*/', ' ', header, flags=re.S)
-    assert set(re.findall(r'\b(qt_[a-z0-9_]+)\s*\(', bare)) == set(_lib._EDGE_SIGNATURES)
-    params = [p.strip() for p in re.search(r'\bqt_edge_rollout\s*\(([^;{]*?)\)\s*;', bare, flags=re.S).group(1).split(',')]
-    kind = lambda p: 'p' if '*' in p else 'l' if p.startswith('int64_t') else 'f' if p.startswith('float') else 'i'
-    kinds = {ctypes.c_void_p: 'p', ctypes.c_int: 'i', ctypes.c_float: 'f', ctypes.c_int64: 'l'}
-    assert [kind(p) for p in params] == [kinds[t] for t in _lib._EDGE_SIGNATURES['qt_edge_rollout']]
-    assert re.search(r'int\s+m\s*,\s*uint64_t\s*\*\s*planes\s*,\s*int32_t\s*\*\s*partial\s*,\s*void\s*\*\s*stream\s*\)', header)
-    lib = ctypes.CDLL(_lib.LIB_PATH)
     name = 'qt_edge_rollout'
-    # declared beside qtmpnn.h and bound beside _SIGNATURES, which the suite holds to the README's 87 entry points
-    assert hasattr(lib, name) and name in _lib._EDGE_SIGNATURES and name not in _lib._SIGNATURES
-    edge = _lib._EDGE_SIGNATURES[name]
+    decls = header_decls()
+    decl = decls[name]
+    assert re.match(r'int\s+qt_edge_rollout\s*\(', decl.text) and decl.times == 1
+    # header and table hold each other (tests/test_host_cpu.py does so for every entry): per argument a pointer, an int, an
+    # int64 or a float in the same place
+    edge = _lib._SIGNATURES[name]
+    assert decl.kinds == binding_kinds(edge)
+    assert re.search(r'int\s+m\s*,\s*uint64_t\s*\*\s*planes\s*,\s*int32_t\s*\*\s*partial\s*,\s*void\s*\*\s*stream\s*\)', decl.text)
+    lib = ctypes.CDLL(_lib.LIB_PATH)
+    assert hasattr(lib, name) and name in _lib._SIGNATURES and name in _lib.exported_names()
     assert _lib.load().qt_edge_rollout.argtypes == edge and _lib.load().qt_edge_rollout.restype is ctypes.c_int
+    # the 20 leading arguments are qt_score_rollout's, in the binding and in the header's text
     assert edge[:20] == _lib._SIGNATURES['qt_score_rollout'][:20] == _lib._SIGNATURES['qt_fss_rollout'][:20]
+    assert decl.params[:20] == decls['qt_score_rollout'].params[:20]
     assert edge[20:] == [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     assert lib.qt_abi_version() == 1
     readme = open(os.path.join(ROOT, 'README.md')).read()
-    assert f'({len(_lib.exported_names())} entry points)' in readme and '`include/qtmpnn_edges.h`' in readme
+    assert f'({len(_lib.exported_names())} entry points)' in readme and not re.search(r'qtmpnn_\w+\.h', readme)
 
 
 def _buf():

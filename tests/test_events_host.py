@@ -15,17 +15,22 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_event_entries_are_declared_exported_and_bound():
+    from helpers import header_decls
     from qtmpnn import _lib
-    header = open(os.path.join(ROOT, 'include', 'qtmpnn.h')).read()
-    assert re.search(r'\bint\s+qt_event_scan\s*\(', header) and re.search(r'\bint\s+qt_event_sums\s*\(', header)
-    assert re.search(r'int32_t\s*\*\s*dates\s*,\s*int32_t\s*\*\s*runs', header)
-    assert re.search(r'int64_t\s*\*\s*sums', header)
+    decls = header_decls()
+    scan, sums = decls['qt_event_scan'], decls['qt_event_sums']
+    assert re.match(r'int\s+qt_event_scan\s*\(', scan.text) and re.match(r'int\s+qt_event_sums\s*\(', sums.text)
+    assert scan.times == sums.times == 1
+    assert re.search(r'int32_t\s*\*\s*dates\s*,\s*int32_t\s*\*\s*runs', scan.text)
+    assert re.search(r'int64_t\s*\*\s*sums', sums.text)
     lib = ctypes.CDLL(_lib.LIB_PATH)
     for name in ('qt_event_scan', 'qt_event_sums'):
         assert hasattr(lib, name) and name in _lib._SIGNATURES and name in _lib.exported_names(), name
     # the head of qt_event_scan is qt_score_rollout's with one dense base: (nseg .. y, strides), (base, strides), mask, thr, B, n, m
     score = _lib._SIGNATURES['qt_score_rollout']
     assert _lib._SIGNATURES['qt_event_scan'][:17] == score[:12] + score[15:20]
+    score_params = [p.replace('base1', 'base') for p in decls['qt_score_rollout'].params]
+    assert scan.params[:17] == score_params[:12] + score_params[15:20]
     assert lib.qt_abi_version() == 1
     readme = open(os.path.join(ROOT, 'README.md')).read()
     assert f'({len(_lib.exported_names())} entry points)' in readme

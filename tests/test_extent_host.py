@@ -216,42 +216,34 @@ def test_check_regions():
 
 
 def test_extent_entry_is_declared_exported_and_bound():
+    from helpers import HEADER, binding_kinds, header_decls
     from qtmpnn import _lib
-    header = open(os.path.join(ROOT, 'include', 'qtmpnn_extent.h')).read()
-    assert re.search(r'\bint\s+qt_extent_rollout\s*\(', header)
-    bare = re.sub(r'/\*.*?\*/', ' ', header, flags=re.S)
-    assert set(re.findall(r'\b(qt_[a-z0-9_]+)\s*\(', bare)) == set(_lib._EXTENT_SIGNATURES) == {'qt_extent_rollout'}
-    split = lambda text, name: [p.strip() for p in
-                                re.search(r'\b%s\s*\(([^;{]*?)\)\s*;' % name, text, flags=re.S).group(1).split(',')]
-    params = split(bare, 'qt_extent_rollout')
-    kind = lambda p: 'p' if '*' in p else 'l' if p.startswith('int64_t') else 'f' if p.startswith('float') else 'i'
-    kinds = {ctypes.c_void_p: 'p', ctypes.c_int: 'i', ctypes.c_float: 'f', ctypes.c_int64: 'l'}
-    ext = _lib._EXTENT_SIGNATURES['qt_extent_rollout']
-    assert [kind(p) for p in params] == [kinds[t] for t in ext]
+    name = 'qt_extent_rollout'
+    decls = header_decls()
+    decl = decls[name]
+    assert re.match(r'int\s+qt_extent_rollout\s*\(', decl.text)
+    ext = _lib._SIGNATURES[name]
+    assert decl.kinds == binding_kinds(ext)
     # the 20 leading arguments are qt_score_rollout's, unchanged
-    main = re.sub(r'/\*.*?\*/', ' ', open(os.path.join(ROOT, 'include', 'qtmpnn.h')).read(), flags=re.S)
-    squeeze = lambda ps: [re.sub(r'\s+', ' ', p) for p in ps]
-    assert squeeze(params[:20]) == squeeze(split(main, 'qt_score_rollout')[:20])
+    assert decl.params[:20] == decls['qt_score_rollout'].params[:20]
     assert ext[:20] == _lib._SIGNATURES['qt_score_rollout'][:20] == _lib._SIGNATURES['qt_reliability_rollout'][:20]
     assert re.search(r'int\s+m\s*,\s*const\s+int8_t\s*\*\s*region\s*,\s*const\s+float\s*\*\s*area\s*,\s*int\s+R\s*,\s*'
-                     r'float\s*\*\s*partial\s*,\s*void\s*\*\s*stream\s*\)', header)
+                     r'float\s*\*\s*partial\s*,\s*void\s*\*\s*stream\s*\)', decl.text)
     assert ext[20:] == [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
-    # declared in the new header only, bound in its own table only
-    name = 'qt_extent_rollout'
-    for other in ('qtmpnn.h', 'qtmpnn_edges.h', 'qtmpnn_loss.h'):
-        assert name not in open(os.path.join(ROOT, 'include', other)).read(), other
-    assert name not in _lib._SIGNATURES and name not in _lib._EDGE_SIGNATURES and name not in _lib._LOSS_SIGNATURES
+    # declared once in the one header, bound in the one table
+    assert decl.times == 1
     lib = ctypes.CDLL(_lib.LIB_PATH)
-    assert hasattr(lib, name) and name not in _lib.exported_names()
+    assert hasattr(lib, name) and name in _lib._SIGNATURES and name in _lib.exported_names()
     assert _lib.load().qt_extent_rollout.argtypes == ext and _lib.load().qt_extent_rollout.restype is ctypes.c_int
     assert lib.qt_abi_version() == 1
     readme = open(os.path.join(ROOT, 'README.md')).read()
-    assert len(_lib.exported_names()) == 87 and '(87 entry points)' in readme and '`include/qtmpnn_extent.h`' in readme
-    mk = open(os.path.join(ROOT, 'quadtree-mpnnlstm_amd', 'csrc', 'Makefile')).read()
-    assert mk.count('../../include/qtmpnn_extent.h') == 2
-    # the slot table and the NaN rule are stated where the entry is declared
+    assert len(_lib.exported_names()) == 91 and '(91 entry points)' in readme and not re.search(r'qtmpnn_\w+\.h', readme)
+    # the slot table and the NaN rule are stated where the entry is declared: in the comment that ends at the declaration
+    header = open(HEADER).read()
+    doc = header[:header.index(decl.text)].rsplit('/*', 1)[1]
+    assert doc.startswith(' qt_extent_rollout:') and doc.rstrip().endswith('*/')
     for word in ('E_o', 'SIA_o', 'O_s', 'U_s', 'NaN'):
-        assert word in header, word
+        assert word in doc, word
 
 
 def _buf():

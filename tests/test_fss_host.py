@@ -185,21 +185,24 @@ def test_scales_are_checked_on_the_host_by_name():
 
 
 def test_fss_entry_is_declared_exported_and_bound():
+    from helpers import header_decls
     from qtmpnn import _lib
-    header = open(os.path.join(ROOT, 'include', 'qtmpnn.h')).read()
-    assert re.search(r'\bint\s+qt_fss_rollout\s*\(', header)
-    assert re.search(r'int\s+m\s*,\s*int\s+nscales\s*,\s*const\s+int\s*\*\s*scales\s*,\s*int32_t\s*\*\s*partial\s*,\s*void\s*\*\s*stream\s*\)',
-                     header)
-    lib = ctypes.CDLL(_lib.LIB_PATH)
     name = 'qt_fss_rollout'
+    decls = header_decls()
+    decl = decls[name]
+    assert re.match(r'int\s+qt_fss_rollout\s*\(', decl.text) and decl.times == 1
+    assert re.search(r'int\s+m\s*,\s*int\s+nscales\s*,\s*const\s+int\s*\*\s*scales\s*,\s*int32_t\s*\*\s*partial\s*,\s*void\s*\*\s*stream\s*\)',
+                     decl.text)
+    lib = ctypes.CDLL(_lib.LIB_PATH)
     assert hasattr(lib, name) and name in _lib._SIGNATURES and name in _lib.exported_names()
     # the arguments up to m are qt_reliability_rollout's (and qt_score_rollout's); then nscales, scales, partial, stream
     rel, fss = _lib._SIGNATURES['qt_reliability_rollout'], _lib._SIGNATURES[name]
     assert fss[:20] == rel[:20] == _lib._SIGNATURES['qt_score_rollout'][:20]
+    assert decl.params[:20] == decls['qt_score_rollout'].params[:20]
     assert fss[20:] == [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     assert lib.qt_abi_version() == 1
     readme = open(os.path.join(ROOT, 'README.md')).read()
-    assert len(_lib.exported_names()) == 87 and '(87 entry points)' in readme
+    assert len(_lib.exported_names()) == 91 and '(91 entry points)' in readme
 
 
 def _buf():

@@ -11,44 +11,54 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def _exported_qt_symbols(path):
+    """The qt_* names in the dynamic symbol table of a shared library (nm, which every host that built the library has)."""
+    import subprocess
+    out = subprocess.run(['nm', '-D', '--defined-only', path], check=True, capture_output=True, text=True).stdout
+    return {line.split()[-1] for line in out.splitlines() if line.split()[-1].startswith('qt_')}
+
+
 def test_library_exports_every_declared_symbol():
+    """One ABI, stated three times: what include/qtmpnn.h declares == what the library exports under qt_ == what _lib binds."""
+    from helpers import header_decls
     from qtmpnn import _lib
-    header = open(os.path.join(ROOT, 'include', 'qtmpnn.h')).read()
-    declared = set(re.findall(r'\b(qt_[a-z0-9_]+)\s*\(', header))
+    declared = set(header_decls())
     assert declared, 'no declarations parsed'
     lib = ctypes.CDLL(_lib.LIB_PATH)
     for name in sorted(declared):
         assert hasattr(lib, name), f'{name} is declared in include/qtmpnn.h but not exported'
+    assert declared == _exported_qt_symbols(_lib.LIB_PATH), declared ^ _exported_qt_symbols(_lib.LIB_PATH)
     assert declared == set(_lib.exported_names()), declared ^ set(_lib.exported_names())
+    assert len(_lib.exported_names()) == len(declared) == 91
     assert lib.qt_abi_version() == 1
+
+
+def test_the_abi_has_one_header():
+    """include/ holds qtmpnn.h alone, it declares every name once, and both pattern rules of the Makefile (the product's objects and
+    the small-caps test build's) rebuild on it and on nothing else under include/."""
+    from helpers import header_decls
+    assert os.listdir(os.path.join(ROOT, 'include')) == ['qtmpnn.h']
+    assert [n for n, d in header_decls().items() if d.times != 1] == []
+    mk = open(os.path.join(ROOT, 'quadtree-mpnnlstm_amd', 'csrc', 'Makefile')).read()
+    rules = [line for line in mk.splitlines() if re.match(r'%\.(small\.)?o\s*:', line)]
+    assert len(rules) == 2 and all('../../include/qtmpnn.h' in r.split() for r in rules), rules
+    assert set(re.findall(r'\.\./\.\./include/\S*', mk)) == {'../../include/qtmpnn.h'}
 
 
 def test_ctypes_signatures_match_the_header():
     """Every binding in qtmpnn._lib lists exactly as many arguments as the header declares, pointer / int / float in the
     same places (a short list makes ctypes push garbage for the rest: a host-side crash, not an error code)."""
+    from helpers import binding_kinds, header_decls
     from qtmpnn import _lib
-    header = re.sub(r'/\*.*?\*/', ' ', open(os.path.join(ROOT, 'include', 'qtmpnn.h')).read(), flags=re.S)
-    decls = dict(re.findall(r'\b(qt_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;', header, flags=re.S))
-    kinds = {ctypes.c_void_p: 'p', ctypes.c_int: 'i', ctypes.c_float: 'f', ctypes.c_uint32: 'u', ctypes.c_int64: 'l'}
+    decls = header_decls()
+    assert set(decls) == set(_lib._SIGNATURES) | {'qt_last_error'} and decls['qt_last_error'].params == []
     checked = 0
     for name, sig in _lib._SIGNATURES.items():
-        params = [p.strip() for p in decls[name].split(',')] if decls[name].strip() not in ('', 'void') else []
-        want = ''
-        for p_ in params:
-            if '*' in p_:
-                want += 'p'
-            elif p_.startswith('float'):
-                want += 'f'
-            elif p_.startswith('uint32_t'):
-                want += 'u'
-            elif p_.startswith('int64_t'):
-                want += 'l'
-            else:
-                want += 'i'
-        got = ''.join(kinds[t] for t in sig)
+        got, want = binding_kinds(sig), decls[name].kinds
         assert got == want, f'{name}: binding {got} vs header {want}'
+        assert getattr(_lib.load(), name).argtypes == sig, name
         checked += 1
-    assert checked >= 35
+    assert checked == len(_lib._SIGNATURES)
 
 
 def test_bad_arguments_fail_loudly_without_gpu():

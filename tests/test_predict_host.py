@@ -12,10 +12,12 @@ def test_predict_has_use_graph_off_by_default():
 
 
 def test_inference_entries_are_exported():
+    from helpers import header_decls
     from qtmpnn import _lib
+    decls = header_decls()
     lib = ctypes.CDLL(_lib.LIB_PATH)
     for name in ('qt_lstm_infer', 'qt_gather_frame'):
-        assert hasattr(lib, name) and name in _lib.exported_names(), name
+        assert hasattr(lib, name) and name in _lib.exported_names() and decls[name].times == 1, name
 
 
 def _buf():

@@ -16,15 +16,18 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_reliability_entry_is_declared_exported_and_bound():
+    from helpers import header_decls
     from qtmpnn import _lib
-    header = open(os.path.join(ROOT, 'include', 'qtmpnn.h')).read()
-    assert re.search(r'\bint\s+qt_reliability_rollout\s*\(', header)
-    assert re.search(r'int\s+m\s*,\s*int\s+bins\s*,\s*float\s*\*\s*partial\s*,\s*void\s*\*\s*stream\s*\)', header)
-    lib = ctypes.CDLL(_lib.LIB_PATH)
     name = 'qt_reliability_rollout'
+    decls = header_decls()
+    decl = decls[name]
+    assert re.match(r'int\s+qt_reliability_rollout\s*\(', decl.text) and decl.times == 1
+    assert re.search(r'int\s+m\s*,\s*int\s+bins\s*,\s*float\s*\*\s*partial\s*,\s*void\s*\*\s*stream\s*\)', decl.text)
+    lib = ctypes.CDLL(_lib.LIB_PATH)
     assert hasattr(lib, name) and name in _lib._SIGNATURES and name in _lib.exported_names()
     # the arguments up to m are qt_score_rollout's; then bins, partial, stream
     score, rel = _lib._SIGNATURES['qt_score_rollout'], _lib._SIGNATURES[name]
+    assert decl.params[:20] == decls['qt_score_rollout'].params[:20]
     assert rel[:20] == score[:20] and rel[20:] == [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
     assert score[20:] == [ctypes.c_void_p, ctypes.c_void_p]
     assert lib.qt_abi_version() == 1

@@ -27,9 +27,11 @@ def test_score_signature():
 
 
 def test_score_entry_is_declared_exported_and_bound():
+    from helpers import HEADER, header_decls
     from qtmpnn import _lib
-    header = open(os.path.join(ROOT, 'include', 'qtmpnn.h')).read()
-    assert re.search(r'\bint\s+qt_score_rollout\s*\(', header)
+    decl = header_decls()['qt_score_rollout']
+    assert re.match(r'int\s+qt_score_rollout\s*\(', decl.text) and decl.times == 1
+    header = open(HEADER).read()
     for slot in ('hits', 'over', 'under', 'correct negatives'):         # the header comment states the slot table
         assert slot in header
     lib = ctypes.CDLL(_lib.LIB_PATH)

@@ -15,10 +15,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_score_maps_entry_is_declared_exported_and_bound():
+    from helpers import header_decls
     from qtmpnn import _lib
-    header = open(os.path.join(ROOT, 'include', 'qtmpnn.h')).read()
-    assert re.search(r'\bint\s+qt_score_maps\s*\(', header)
-    assert re.search(r'double\s*\*\s*maps\s*,\s*int64_t\s+maps_step_stride', header)
+    decls = header_decls()
+    decl = decls['qt_score_maps']
+    assert re.match(r'int\s+qt_score_maps\s*\(', decl.text) and decl.times == 1
+    assert re.search(r'double\s*\*\s*maps\s*,\s*int64_t\s+maps_step_stride', decl.text)
+    assert decl.params[:20] == decls['qt_score_rollout'].params[:20]
     lib = ctypes.CDLL(_lib.LIB_PATH)
     assert hasattr(lib, 'qt_score_maps')
     assert 'qt_score_maps' in _lib._SIGNATURES and 'qt_score_maps' in _lib.exported_names()

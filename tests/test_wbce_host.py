@@ -231,29 +231,24 @@ def test_loss_weights_carry_pos_weight_through_chunks():
 
 # ---- the two entry points ----
 def test_wbce_entries_are_declared_exported_and_bound():
+    from helpers import binding_kinds, header_decls
     from qtmpnn import _lib
-    header = open(os.path.join(ROOT, 'include', 'qtmpnn_loss.h')).read()
-    bare = re.sub(r'/\*.*?\*/', ' ', header, flags=re.S)
-    assert set(re.findall(r'\b(qt_[a-z0-9_]+)\s*\(', bare)) == set(_lib._LOSS_SIGNATURES) == {'qt_wbce_rollout', 'qt_wbce_rollout_bwd'}
-    kind = lambda p: 'p' if '*' in p else 'l' if p.startswith('int64_t') else 'f' if p.startswith('float') else 'i'
-    kinds = {ctypes.c_void_p: 'p', ctypes.c_int: 'i', ctypes.c_float: 'f', ctypes.c_int64: 'l'}
+    decls = header_decls()
+    assert {n for n in decls if 'wbce' in n} == {n for n in _lib._SIGNATURES if 'wbce' in n} == {'qt_wbce_rollout', 'qt_wbce_rollout_bwd'}
     lib, bound = ctypes.CDLL(_lib.LIB_PATH), _lib.load()
-    main = open(os.path.join(ROOT, 'include', 'qtmpnn.h')).read()
     for name, like in (('qt_wbce_rollout', 'qt_wsse_rollout'), ('qt_wbce_rollout_bwd', 'qt_wsse_rollout_bwd')):
-        assert re.search(r'\bint\s+%s\s*\(' % name, bare), name
-        params = [p.strip() for p in re.search(r'\b%s\s*\(([^;{]*?)\)\s*;' % name, bare, flags=re.S).group(1).split(',')]
-        sig = _lib._LOSS_SIGNATURES[name]
-        assert [kind(p) for p in params] == [kinds[t] for t in sig], name
-        assert re.match(r'float\s+pos_weight$', params[-2]) and re.match(r'void\s*\*\s*stream$', params[-1]), params[-2:]
+        decl = decls[name]
+        assert re.match(r'int\s+%s\s*\(' % name, decl.text) and decl.times == 1, name
+        sig = _lib._SIGNATURES[name]
+        assert decl.kinds == binding_kinds(sig), name
+        assert re.match(r'float\s+pos_weight$', decl.params[-2]) and re.match(r'void\s*\*\s*stream$', decl.params[-1]), decl.params[-2:]
         # the arguments of the weighted squared-error pair, then pos_weight by value, then the stream
         assert sig == _lib._SIGNATURES[like][:-1] + [ctypes.c_float, ctypes.c_void_p]
-        assert hasattr(lib, name) and name not in _lib._SIGNATURES and name not in _lib._EDGE_SIGNATURES
-        assert name not in _lib.exported_names() and not re.search(r'\b%s\b' % name, main)
+        assert decl.params[:-2] == decls[like].params[:-1], name
+        assert hasattr(lib, name) and name in _lib._SIGNATURES and name in _lib.exported_names()
         assert getattr(bound, name).argtypes == sig and getattr(bound, name).restype is ctypes.c_int
     readme = open(os.path.join(ROOT, 'README.md')).read()
-    assert f'({len(_lib.exported_names())} entry points)' in readme and '`include/qtmpnn_loss.h`' in readme
-    mk = open(os.path.join(ROOT, 'quadtree-mpnnlstm_amd', 'csrc', 'Makefile')).read()
-    assert mk.count('../../include/qtmpnn_loss.h') == 2
+    assert f'({len(_lib.exported_names())} entry points)' in readme and not re.search(r'qtmpnn_\w+\.h', readme)
 
 
 def test_wbce_entries_refuse_bad_arguments():

@@ -143,13 +143,14 @@ def test_cell_area_weights():
 
 
 def test_wsse_entries_are_declared_exported_and_bound():
+    from helpers import header_decls
     from qtmpnn import _lib
-    header = open(os.path.join(ROOT, 'include', 'qtmpnn.h')).read()
+    decls = header_decls()
     lib = ctypes.CDLL(_lib.LIB_PATH)
     for name in ('qt_wsse_rollout', 'qt_wsse_rollout_bwd'):
-        assert re.search(r'\bint\s+%s\s*\(' % name, header), name
+        assert re.match(r'int\s+%s\s*\(' % name, decls[name].text) and decls[name].times == 1, name
         assert hasattr(lib, name) and name in _lib._SIGNATURES and name in _lib.exported_names(), name
-    assert re.search(r'const float\s*\*\s*w\s*,\s*const float\s*\*\s*lam', header)
+    assert re.search(r'const float\s*\*\s*w\s*,\s*const float\s*\*\s*lam', decls['qt_wsse_rollout'].text)
     sse, wsse = _lib._SIGNATURES['qt_sse_rollout'], _lib._SIGNATURES['qt_wsse_rollout']
     assert wsse == sse[:10] + [ctypes.c_void_p, ctypes.c_void_p] + sse[10:]            # qt_sse_rollout's with (w, lam) after the strides
     readme = open(os.path.join(ROOT, 'README.md')).read()
