@@ -19,9 +19,11 @@ from model.seq2seq import Seq2Seq
 from model.utils import add_positional_encoding, get_n_params, int_to_datetime
 from qtmpnn import ops
 from qtmpnn.dist import all_reduce_sum, allreduce_gradients
-from qtmpnn.flat import flat_params
+from qtmpnn.flat import flat_params, name_table
 from qtmpnn._lib import on_device
 from qtmpnn.mesh import check_tile_errors, host_mask
+
+CHECKPOINT_FORMAT = 1       # of save_checkpoint(); load_checkpoint() refuses a newer one
 
 try:                                        # pragma: no cover - optional dependency
     from torch.utils.tensorboard import SummaryWriter
@@ -341,6 +343,143 @@ class NextFramePredictorS2S(NextFramePredictor):
     def load(self, directory):
         path = os.path.join(directory, f'{self.experiment_name}.pth')
         self.model.load_state_dict(torch.load(path, map_location=self.device or 'cpu', weights_only=True))
+
+    # -- checkpoints: everything a resumed run needs to continue bit for bit (beyond the reference) ------------------------------
+    def _description(self):
+        """What a checkpoint must agree with before it is loaded: the settings that fix the parameter set, and the set itself."""
+        m = self.model
+        return {'convolution_type': m.convolution_type, 'hidden_size': int(m.hidden_size), 'n_layers': int(m.n_layers),
+                'n_conv_layers': int(m.encoder.rnns[0].n_conv_layers), 'input_features': int(self.input_features),
+                'input_timesteps': int(self.input_timesteps), 'output_timesteps': int(self.output_timesteps),
+                'binary': bool(self.binary), 'parameters': [[name, list(shape)] for name, _, shape in name_table(m)]}
+
+    def save_checkpoint(self, path):
+        """Write the whole training state to the file `path` (torch.save of a dict of host tensors and plain Python values: it
+        loads with torch.load(path, weights_only=True)), so that load_checkpoint + train(n_epochs=k) continues this run bit for bit:
+
+            format        1
+            description   convolution_type, hidden_size, n_layers, n_conv_layers, input_features, input_timesteps,
+                          output_timesteps, binary, parameters [[name, shape], ...] in module order
+            state_dict    model.state_dict(), the keys and values save() writes
+            optimizer     exp_avg / exp_avg_sq {name: tensor in the parameter's shape}, step (one integer), lr (float), betas, eps:
+                          one layout for FlatAdam and torch's Adam (qtmpnn.optim.adam_state), so either loads the other's file
+            scheduler     StepLR.state_dict(), learning rates as floats
+            train_loss, test_loss, capturable
+            rng           torch (torch.get_rng_state()), cuda (torch.cuda.get_rng_state(device), None on the CPU), attention
+                          (ops.dropout_state: the call counter and device step counter the attention kernels' seeds are made of)
+
+        The file is written under a temporary name beside `path` and moved there by os.replace: an interrupted save leaves
+        whatever was under `path` as it was.  Under torch.distributed the ranks hold the same state: one rank saves."""
+        if not self.training_initiated:
+            raise ValueError('save_checkpoint: nothing to resume yet (no initiate_training() / train()); save() stores the weights')
+        from qtmpnn.optim import adam_state
+        group = self.optimizer.param_groups[0]
+        dev = next(self.model.parameters()).device
+        host = lambda v: float(v) if torch.is_tensor(v) else [host(e) for e in v] if isinstance(v, (list, tuple)) else v
+        ckpt = {'format': CHECKPOINT_FORMAT, 'description': self._description(),
+                'state_dict': {k: v.detach().cpu().clone() for k, v in self.model.state_dict().items()},
+                'optimizer': adam_state(self.optimizer, self.model),
+                'scheduler': {k: host(v) for k, v in self.scheduler.state_dict().items()},
+                'train_loss': [float(v) for v in self.train_loss], 'test_loss': [float(v) for v in self.test_loss],
+                'capturable': bool(group.get('capturable', False)),
+                'rng': {'torch': torch.get_rng_state(), 'cuda': torch.cuda.get_rng_state(dev) if dev.type == 'cuda' else None,
+                        'attention': ops.dropout_state(dev)}}
+        path = os.fspath(path)
+        tmp = f'{path}.tmp{os.getpid()}'
+        try:
+            torch.save(ckpt, tmp)
+            os.replace(tmp, path)
+        except BaseException:
+            if os.path.exists(tmp):
+                os.remove(tmp)
+            raise
+
+    def _checked_checkpoint(self, path):
+        """The checkpoint under `path`, host tensors, or a ValueError that names the field that does not fit this predictor.
+        Reads the file and this predictor, changes neither."""
+        from qtmpnn.optim import check_adam_state
+        ckpt = torch.load(path, map_location='cpu', weights_only=True)
+        if not isinstance(ckpt, dict) or 'format' not in ckpt:
+            raise ValueError(f"format: {path} is no checkpoint of save_checkpoint() (no 'format' entry; load() reads the weights of save())")
+        if not isinstance(ckpt['format'], int) or ckpt['format'] > CHECKPOINT_FORMAT or ckpt['format'] < 1:
+            raise ValueError(f"format: the file has format {ckpt['format']!r}, this version reads up to {CHECKPOINT_FORMAT}")
+        for k in ('description', 'state_dict', 'optimizer', 'scheduler', 'train_loss', 'test_loss', 'capturable', 'rng'):
+            if k not in ckpt:
+                raise ValueError(f'{k}: missing in the file')
+        here, there = self._description(), ckpt['description']
+        for k, v in here.items():
+            if k != 'parameters' and there.get(k) != v:
+                raise ValueError(f'{k}={there.get(k)!r} in the file, {v!r} here')
+        mine, theirs = {n: tuple(s) for n, s in here['parameters']}, {n: tuple(s) for n, s in there.get('parameters', [])}
+        missing, extra = [n for n in mine if n not in theirs], [n for n in theirs if n not in mine]
+        if missing or extra or list(mine) != list(theirs):
+            raise ValueError(f'parameters: the names differ: missing in the file {missing}, not in this model {extra}'
+                             + ('' if missing or extra else ' (same names, another order)'))
+        for n, s in mine.items():
+            if theirs[n] != s:
+                raise ValueError(f'parameters[{n!r}]: shape {theirs[n]} in the file, {s} here')
+        sd, own = ckpt['state_dict'], self.model.state_dict()
+        missing, extra = [k for k in own if k not in sd], [k for k in sd if k not in own]
+        if missing or extra:
+            raise ValueError(f'state_dict: the keys differ: missing in the file {missing}, not in this model {extra}')
+        for k, v in own.items():
+            if not torch.is_tensor(sd[k]) or tuple(sd[k].shape) != tuple(v.shape):
+                raise ValueError(f'state_dict[{k!r}]: shape {tuple(sd[k].shape) if torch.is_tensor(sd[k]) else None} in the file, '
+                                 f'{tuple(v.shape)} here')
+        check_adam_state(ckpt['optimizer'], name_table(self.model))
+        sched = ckpt['scheduler']
+        for k in ('last_epoch', '_last_lr', 'step_size', 'gamma', 'base_lrs'):
+            if not isinstance(sched, dict) or k not in sched:
+                raise ValueError(f'scheduler: no {k!r}')
+        if len(ckpt['train_loss']) != len(ckpt['test_loss']):
+            raise ValueError(f"train_loss: {len(ckpt['train_loss'])} epochs, test_loss has {len(ckpt['test_loss'])}")
+        rng = ckpt['rng']
+        for k in ('torch', 'cuda', 'attention'):
+            if not isinstance(rng, dict) or k not in rng:
+                raise ValueError(f'rng: no {k!r}')
+        return ckpt
+
+    @on_device(lambda self, *a, **k: self.device)
+    def load_checkpoint(self, path, capturable=None):
+        """Restore what save_checkpoint(path) wrote into this predictor; `train(n_epochs=k)` then continues that run: the same
+        parameters and losses, bit for bit, as the run that was never interrupted, and `self.loss` covers the restored epochs and
+        the new ones.
+
+        A predictor that has not trained yet gets initiate_training() first.  capturable: None takes the mode the file was
+        written in; True / False converts (the learning rate becomes a device tensor or a float, the step counter moves with
+        it), so an eager run resumes with train(use_graph=True) and the other way round.  A predictor whose optimiser is in
+        the other mode than the one asked for is initiated again; its captured steps, if any, are void then.
+
+        Otherwise EVERYTHING IS RESTORED IN PLACE: parameters (load_state_dict copies into them; the flat buffer keeps its views
+        and its zero pad tail), Adam moments, step counters, a device learning rate and the attention-dropout counter by copy_ /
+        fill_ into the storage that is there.  A make_graphed_step object captured before the load holds pointers into
+        exactly these buffers: it keeps working and its next replay continues from the loaded state.  The weight packing reads
+        the parameters in every forward pass, so nothing else has to be told.
+
+        A file that does not fit is refused with a ValueError that names the field -- no checkpoint, a newer format, another
+        description (`convolution_type='ChebConv' in the file, 'GCNConv' here`), parameter names, shapes, non-finite moments,
+        negative exp_avg_sq, step < 0 -- after reading the file on the host and before anything here changes.  Every rank of a
+        torch.distributed run loads the same file; there is no collective."""
+        from qtmpnn.optim import load_adam_state, set_lr
+        ckpt = self._checked_checkpoint(path)
+        opt, sched = ckpt['optimizer'], dict(ckpt['scheduler'])
+        want = bool(ckpt['capturable']) if capturable is None else bool(capturable)
+        if not self.training_initiated or bool(self.optimizer.param_groups[0].get('capturable', False)) != want:
+            self.initiate_training(opt['lr'], sched['gamma'], capturable=want)
+        self.model.load_state_dict(ckpt['state_dict'])          # (copy_ into the parameters, as load() does)
+        if self.flat is not None and not self.flat.intact(self.model):
+            raise RuntimeError('the model parameters were moved or replaced after initiate_training(): call it again')
+        load_adam_state(self.optimizer, self.model, opt)
+        group = self.optimizer.param_groups[0]
+        set_lr(group, 'initial_lr', sched['base_lrs'][0])
+        sched['base_lrs'], sched['_last_lr'] = [group['initial_lr']], [group['lr']]     # (the scheduler's own aliases)
+        self.scheduler.load_state_dict(sched)
+        self.train_loss, self.test_loss = list(ckpt['train_loss']), list(ckpt['test_loss'])
+        rng, dev = ckpt['rng'], next(self.model.parameters()).device
+        torch.set_rng_state(rng['torch'])
+        if dev.type == 'cuda' and rng['cuda'] is not None:
+            torch.cuda.set_rng_state(rng['cuda'], dev)
+        ops.set_dropout_state(rng['attention'], dev)
 
     def test_threshold(self, x, thresh, mask=None, high_interest_region=None, contours=True):
         import matplotlib.pyplot as plt

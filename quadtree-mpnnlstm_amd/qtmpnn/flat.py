@@ -81,6 +81,41 @@ class FlatParams:
         self.last_grad = None
 
 
+def name_table(module):
+    """[(name, offset, shape)] of module.named_parameters(): the offsets of FlatParams (same order, same sizes), under the
+    state-dict names.  It is what a checkpoint's per-name optimiser state is sliced by."""
+    table, off = [], 0
+    for name, p in module.named_parameters():
+        table.append((name, off, tuple(p.shape)))
+        off += p.numel()
+    return table
+
+
+def split_flat(vec, table):
+    """Flat -> per name: {name: a copy of vec[offset:offset + numel] in the parameter's shape}.  What lies behind the last
+    entry (FlatParams' pad tail) belongs to no name and is not returned."""
+    out = {}
+    for name, off, shape in table:
+        n = 1
+        for s in shape:
+            n *= s
+        out[name] = vec[off:off + n].detach().clone().reshape(shape)
+    return out
+
+
+def join_flat(named, table, out):
+    """Per name -> flat, IN PLACE: out[offset:offset + numel] = named[name] for every entry of the table (copy_, so `out` keeps its
+    storage and whoever holds a pointer into it sees the values).  Elements behind the last entry are not touched: a pad tail
+    stays what it was (zero).  Returns out."""
+    with torch.no_grad():
+        for name, off, shape in table:
+            t = named[name]
+            if tuple(t.shape) != tuple(shape):
+                raise ValueError(f'{name}: shape {tuple(t.shape)}, the table has {tuple(shape)}')
+            out[off:off + t.numel()].copy_(t.reshape(-1))
+    return out
+
+
 def flat_params(module):
     """The module's FlatParams (made on first use, remade when the parameters were moved or replaced), or None when the
     parameters are not fp32 (model.double() / .half(): the packing gather and qt_flat_adam are fp32 kernels -- the callers

@@ -898,6 +898,23 @@ def advance_dropout_epoch(device):
         ep.add_(1)
 
 
+def dropout_state(device):
+    """What the next attention-dropout seeds are made of besides torch.initial_seed(): {'calls': the host-side call counter,
+    'epoch': the device's step counter, None while no attention convolution with dropout has run there}.  One device read."""
+    ep = _ATTN_EPOCH.get(str(device))
+    return {'calls': int(_ATTN_CALLS[0]), 'epoch': None if ep is None else int(ep.item())}
+
+
+def set_dropout_state(state, device):
+    """Put dropout_state() back.  The device counter keeps its storage (fill_): a captured step reads it through the pointer it
+    was captured with.  'epoch' None: a counter that exists here restarts at 0."""
+    _ATTN_CALLS[0] = int(state['calls'])
+    if state['epoch'] is not None:
+        dropout_epoch(device).fill_(int(state['epoch']))
+    elif str(device) in _ATTN_EPOCH:
+        _ATTN_EPOCH[str(device)].zero_()
+
+
 class _Attention(Function):
     """out = edge-softmax attention over the mesh adjacency + skip, from the fused projection proj = [q | k | v | skip]
     (N, 4C) and the edge-feature weight We (C, 2)  (PyG TransformerConv as configured by model/model.py:51).
