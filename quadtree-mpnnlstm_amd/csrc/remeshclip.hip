@@ -5,22 +5,31 @@
 //
 // The general kernels (transfer.hip: k_pool_nodes for nodes up to 4 x 4 pixels, k_pool for the bigger ones) walk
 // index -> label -> row chains through L2 / HBM for every node and channel chunk, 41 - 52 us per transfer of the benchmark's
-// 68 state channels.  The transfer of one 64 x 64 tile (= base cell) of a clip and one 4-channel column slice fits a
-// workgroup's LDS -- a base cell's nodes are one contiguous label range of the DFS order, so its source rows are a range too
-// (frames of several tiles: both meshes decomposed with max_size 64; frames up to 64 x 64: any mesh, the clip is the tile):
-//   * the source slice of the clip (<= 4096 rows x 16 B = 64 KB) is staged once (pre-scaled by 1 / src_npix for the backward);
-//   * every thread owns one 2 x 2 pixel block (Morton order): pixel value = staged row of the pixel's source node, an LDS gather;
-//   * a sum pyramid over the 64 x 64 frame (level-1 sums in registers, levels 2 .. 6 through 22 KB of LDS) -- a quadtree leaf
-//     of level L is exactly one level-L entry, so every destination node is written once, deterministically, by the thread
-//     that owns its head pixel.
+// 68 state channels.  Here one workgroup owns one 32 x 32 pixel QUADRANT of one 64 x 64 tile (= base cell) of a clip and one
+// COLUMN GROUP: up to four consecutive float4 chunks (64 bytes) that lie in one source part and in one output part -- for the
+// dense 16-wide state parts (H and C of a layer) a group is the whole 64-byte row, so four neighbouring lanes load / store one
+// row and a wave instruction moves 16 whole rows (1 KB, contiguous while staging):
+//   * lane t & 3 owns one float4 chunk of the group, lanes t >> 2 enumerate the quadrant's 256 2 x 2 pixel blocks (Morton order);
+//   * the source rows of the quadrant's pixels are found by the workgroup itself (min / max of its valid source labels); labels
+//     are in depth-first order, so for quadtree meshes that range has at most 1024 rows = 64 KB of LDS and is staged once
+//     (pre-scaled by 1 / src_npix for the backward).  Any other mesh (preset order, pixelwise: the range can be the whole clip)
+//     is walked in windows of 1024 rows: a pixel takes its value in the window that holds its source row -- an assignment, not
+//     a sum, so the bits do not depend on the windows;
+//   * a sum pyramid over the quadrant: level 1 in registers, levels 2 and 3 by lane shuffles (a wave is one 8 x 8 entry),
+//     levels 4 and 5 from the 16 waves' level-3 sums through 1 KB of LDS -- a quadtree leaf of level L is exactly one level-L
+//     entry, so every destination node is written once, deterministically, by the lanes that own its head pixel.  A node of
+//     level 6 (a whole tile) is formed by the tile's quadrant-0 workgroup, which walks all four quadrants.
 // No per-node cell record, no direct-index side array, no pixel loops of data-dependent length, no atomics.  Summation order:
 // (top-left + top-right) + (bottom-left + bottom-right) at every level.
 #include "qt_common.h"
+#include <type_traits>
 
 namespace {
 
-constexpr int RC_T = 1024;          // threads = 2 x 2 pixel blocks of a 64 x 64 frame
-constexpr int RC_ROWS = 4096;       // source rows of a clip that fit
+constexpr int RC_T = 1024;          // threads of a workgroup: 256 2 x 2 pixel blocks of a quadrant x 4 float4 chunks
+constexpr int RC_ROWS = 4096;       // source rows of a clip that fit (qt_remesh_clip_rows: a 64 x 64 frame's pixels)
+constexpr int RC_WIN = 1024;        // source rows staged at a time (64 bytes each)
+constexpr int RC_GROUPS = 256;      // column groups of one launch
 
 struct RcArgs {
     const float* part[8];           // source state as up to 8 matrices side by side (row strides part_ld, float4 prefix part_end)
@@ -29,7 +38,6 @@ struct RcArgs {
     int opart_w[8], opart_end[8];
     const int32_t* src_labels;      // (B, n, m) source mesh
     const float* src_npix;
-    const int32_t* src_off;         // (B * tiles + 1) first source node of every 64 x 64 tile, label order (slot b*T + (T-1-tile))
     const int32_t* labels;          // (B, n, m) destination mesh
     const uint8_t* level;
     const float* npix;
@@ -40,7 +48,9 @@ struct RcArgs {
     const float* posfeat;
     int src_first_only;
     int ride;                       // 1: chunk 0 is the decoder input's scalar (posfeat or src_first_only, and more chunks follow): it has no
-                                    // workgroups of its own, the workgroups of chunk 1 carry its column 0 along
+                                    // column group of its own, the workgroups of the first group carry its column 0 along
+    int ngroups;
+    unsigned grp[RC_GROUPS];        // column group g = float4 chunks [grp & 0xffff, + (grp >> 16)), 1 .. 4 of them
 };
 
 __device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
@@ -55,9 +65,9 @@ __device__ __forceinline__ unsigned compact_bits(unsigned v) {       // even bit
 // Workgroup barrier that waits for this wave's LDS traffic only (not for its global loads / stores)
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-// Pairwise sums over lane groups of four, in the pyramid's order: lane 4j holds child 0 .. lane 4j+3 child 3 of entry j (Morton
-// order, child = row bit | col bit << 1) -> every lane of the group gets (c0 + c2) + (c1 + c3) (a + b = b + a bit for bit, so
-// the four lanes hold the same bits).  sh = log2 of the distance between the children: 0, 2, 4 for levels 2, 3, 4.
+// Pairwise sums over four lanes, in the pyramid's order: the lanes hold child 0 .. child 3 of an entry (Morton order, child =
+// row bit | col bit << 1) 1 << sh lanes apart -> every one of them gets (c0 + c2) + (c1 + c3) (a + b = b + a bit for bit, so the
+// four lanes hold the same bits).  sh = log2 of the distance between the children: 2 and 4 for levels 2 and 3.
 __device__ __forceinline__ float quad_sum(float v, int sh) {
     const float a = v + __shfl_xor(v, 2 << sh, 64);
     return a + __shfl_xor(a, 1 << sh, 64);
@@ -66,72 +76,42 @@ __device__ __forceinline__ float4 quad_sum4(float4 v, int sh) {
     return make_float4(quad_sum(v.x, sh), quad_sum(v.y, sh), quad_sum(v.z, sh), quad_sum(v.w, sh));
 }
 
-// 64 KB + 16 KB of LDS and <= 64 registers: TWO workgroups per CU.  The first version kept the whole pyramid in LDS (86 KB, one
-// workgroup per CU, seven barriers) and the benchmark's 17 chunks x 32 clips = 544 workgroups ran in three rounds over the 256
-// CUs; now levels 1 .. 4 are lane-group sums in registers (a wave's 64 threads are exactly one level-4 entry), levels 5 and 6
-// are formed from the sixteen level-4 entries by the few threads that need them, and the decoder input's scalar chunk RIDES with
-// chunk 1 (ride): 16 x 32 = 512 workgroups, all resident at once.
-__global__ __launch_bounds__(RC_T, 2) void k_remesh_clip(RcArgs a) {
-    __shared__ float4 A[RC_ROWS];                 // the clip's source slice; after the gathers its first 16 entries = the level-4 sums
-    __shared__ float A0[RC_ROWS];                 // the rider: column 0 of chunk 0; likewise
+// 64 KB + 4 KB + 1.5 KB of LDS and <= 64 registers: TWO workgroups per CU; the benchmark's 32 clips x 4 quadrants x 4 groups
+// (H0, C0, H1, C1; the decoder input's scalar chunk RIDES with the first: ride) = 512 workgroups, all resident at once.
+__global__ __launch_bounds__(RC_T, 8) void k_remesh_clip(RcArgs a) {
+    __shared__ float4 A[RC_WIN * 4];              // a window of source rows of the group: row r, chunk k at A[4 r + k]
+    __shared__ float A0[RC_WIN];                  // the rider: column 0 of chunk 0 of the same rows
+    __shared__ float4 S3[16 * 4];                 // the 16 waves' level-3 sums (8 x 8 pixels), per chunk
+    __shared__ float S30[16];
+    __shared__ float4 S5[4 * 4];                  // level-6 walk: the four quadrants' level-5 sums (read back by their writers)
+    __shared__ float S50[4];
+    __shared__ int smin[16], smax[16];
     const int t = threadIdx.x;
+    const int k = t & 3, j = t >> 2, w = t >> 6;
     const int b = (int)blockIdx.x % a.B;
-    const int rest = (int)blockIdx.x / a.B;
+    int rest = (int)blockIdx.x / a.B;
     const int tile = rest % a.tiles;
-    const int ch = rest / a.tiles + a.ride;
-    const bool ride = a.ride && ch == 1;          // (workgroup-uniform) this workgroup also transfers column 0 of chunk 0
+    rest /= a.tiles;
+    const int qd = rest & 3, g = rest >> 2;
+    const unsigned grp = a.grp[g];
+    const int ch0 = (int)(grp & 0xffffu), nch = (int)(grp >> 16);
+    const int ch = ch0 + k;                       // this lane's float4 chunk
+    const bool mine = k < nch;                    // (groups narrower than four chunks: the spare lanes move nothing)
+    const bool ride = a.ride && g == 0;           // (workgroup-uniform) this workgroup also transfers column 0 of chunk 0
     const int R0 = (tile / a.tiles_c) * 64, C0 = (tile % a.tiles_c) * 64;
-    const int slot = b * a.tiles + (a.tiles - 1 - tile);
-    int sp = 0, op = 0;
-    while (ch >= a.part_end[sp]) ++sp;
-    while (ch >= a.opart_end[op]) ++op;
-    const float* src = a.part[sp] + (ch - (sp ? a.part_end[sp - 1] : 0)) * 4;
-    const int lds = a.part_ld[sp];
-    float* dst = a.opart[op] + (ch - (op ? a.opart_end[op - 1] : 0)) * 4;
-    const int ldd = a.opart_w[op];
-    const int r0s = a.src_off[slot];
-    const int nrs = min(a.src_off[slot + 1] - r0s, RC_ROWS);
     const int P = a.n * a.m;
-
-    // ---- one memory phase: the source slice (4 rows per thread) and the labels / levels of this thread's 2 x 2 pixels
-    float4 x[4];
-    float x0[4], sc[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        const int lr = min(t + RC_T * u, nrs - 1);
-        x[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-        x0[u] = 0.0f;
-        sc[u] = 1.0f;
-        if (nrs > 0) {
-            x[u] = *reinterpret_cast<const float4*>(src + (int64_t)(r0s + lr) * lds);
-            if (ride) x0[u] = a.part[0][(int64_t)(r0s + lr) * a.part_ld[0]];
-            if (a.src_inv) sc[u] = a.src_npix[r0s + lr];
-        }
-    }
-    const int br = (int)compact_bits((unsigned)t), bc = (int)compact_bits((unsigned)t >> 1);     // t = spread(br) | spread(bc) << 1
-    int lab[4], sl[4], lv[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int r = R0 + 2 * br + (q >> 1), c = C0 + 2 * bc + (q & 1);
-        lab[q] = sl[q] = -1;
-        lv[q] = 0;
-        if (r < a.n && c < a.m) {
-            const int64_t p = (int64_t)b * P + (int64_t)r * a.m + c;
-            lab[q] = a.labels[p];
-            sl[q] = a.src_labels[p];
-            lv[q] = a.level[p];
-        }
-    }
+    int sp = 0, op = 0;
+    while (ch0 >= a.part_end[sp]) ++sp;
+    while (ch0 >= a.opart_end[op]) ++op;
+    const int lds = a.part_ld[sp];
+    // (uniform base + a small per-lane offset: the spare lanes of a narrow group read its last chunk again)
+    const float* src = a.part[sp] + (ch0 - (sp ? a.part_end[sp - 1] : 0)) * 4;
+    const int ksrc = 4 * min(k, nch - 1);
+    const int ldd = a.opart_w[op];
+    float* dst = a.opart[op] + (ch0 - (op ? a.opart_end[op - 1] : 0)) * 4;          // (uniform; + 4 k per lane)
+    const float* src0 = a.part[0];
+    const int lds0 = a.part_ld[0];
     const bool first_only = a.src_first_only && ch == 0;       // (the scalar chunk on its own: a transfer of that chunk alone)
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        if (first_only) x[u].y = x[u].z = x[u].w = 0.0f;
-        if (t + RC_T * u < nrs) {
-            const float inv = a.src_inv ? 1.0f / sc[u] : 1.0f;
-            A[t + RC_T * u] = a.src_inv ? mul4(x[u], inv) : x[u];
-            if (ride) A0[t + RC_T * u] = a.src_inv ? x0[u] * inv : x0[u];
-        }
-    }
     const bool dec = a.posfeat != nullptr;          // chunk 0 of the result = [value | position, size] of the node
     float* dst0 = a.opart[0];
     const int ldd0 = a.opart_w[0];
@@ -140,7 +120,7 @@ __global__ __launch_bounds__(RC_T, 2) void k_remesh_clip(RcArgs a) {
             const float* pf = a.posfeat + 3 * (int64_t)node;
             v.y = pf[0]; v.z = pf[1]; v.w = pf[2];
         }
-        *reinterpret_cast<float4*>(dst + (int64_t)node * ldd) = v;
+        *reinterpret_cast<float4*>(dst + ((int64_t)node * ldd + 4 * k)) = v;
     };
     auto put0 = [&](int node, float v) {            // the rider's result row: (value, position, size) or (gradient, 0, 0, 0)
         float4 o = make_float4(v, 0.0f, 0.0f, 0.0f);
@@ -150,64 +130,205 @@ __global__ __launch_bounds__(RC_T, 2) void k_remesh_clip(RcArgs a) {
         }
         *reinterpret_cast<float4*>(dst0 + (int64_t)node * ldd0) = o;
     };
-    lds_barrier();
+    // a tile that is ONE destination node (level 6; its head pixel is the tile's first): the quadrant-0 workgroup walks the four
+    // quadrants, the other three have nothing to write
+    bool walk = false;
+    {
+        const int64_t p0 = (int64_t)b * P + (int64_t)R0 * a.m + C0;
+        walk = a.labels[p0] >= 0 && a.level[p0] >= 6;
+    }
+    if (walk && qd != 0) return;
+    int node6 = -1;
+    float oscale6 = 1.0f;
 
-    // ---- pixel values, single-pixel nodes, 2 x 2 sums
-    float4 v[4];
-    float v0[4];
+    // one quadrant: WALK = it is one of the four of a level-6 node (nothing is written, its level-5 sum is kept)
+    auto quadrant = [&](int qq, auto walk_c) {
+        constexpr bool WALK = decltype(walk_c)::value;
+        int jq = j, wq = w;
+        if (WALK) asm volatile("" : "+v"(jq), "+v"(wq));      // (the walk recomputes its per-lane indices in every quadrant: nothing held across)
+        const int br = (int)compact_bits((unsigned)jq), bc = (int)compact_bits((unsigned)jq >> 1);     // jq = spread(br) | spread(bc) << 1
+        const int rq = 32 * (qq & 1) + 2 * br, cq = 32 * (qq >> 1) + 2 * bc;     // this block's first pixel inside the tile
+        // ---- the labels / levels of this lane's 2 x 2 pixels, and the range of the quadrant's source rows
+        int lab[4], sl[4];
+        unsigned lv = 0;                            // the four pixels' levels, one byte each
+        int lo = 0x7fffffff, hi = -1;
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const bool ok = lab[q] >= 0 && sl[q] >= 0;
-        const int row = ok ? ((sl[q] - r0s) & (RC_ROWS - 1)) : 0;
-        v[q] = A[row];
-        v0[q] = ride ? A0[row] : 0.0f;
-        if (!ok) {
-            v[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-            v0[q] = 0.0f;
+        for (int q = 0; q < 4; ++q) {
+            const int r = R0 + rq + (q >> 1), c = C0 + cq + (q & 1);
+            lab[q] = sl[q] = -1;
+            if (r < a.n && c < a.m) {
+                const int64_t p = (int64_t)b * P + (int64_t)r * a.m + c;
+                lab[q] = a.labels[p];
+                sl[q] = a.src_labels[p];
+                lv |= (unsigned)a.level[p] << (8 * q);
+            }
+            if (lab[q] < 0) sl[q] = -1;           // (a pixel counts when both meshes hold it)
+            if (sl[q] >= 0) {
+                lo = min(lo, sl[q]);
+                hi = max(hi, sl[q]);
+            }
         }
-    }
+        const int L = lab[0] >= 0 ? (int)(lv & 255u) : 0;      // a node of level >= 1 has its head at a block's first pixel
+        float oscale = 1.0f;
+        if (L >= 1 && a.mean) oscale = 1.0f / a.npix[lab[0]];          // (requested before the pyramid, used after it)
 #pragma unroll
-    for (int q = 0; q < 4; ++q)
-        if (lab[q] >= 0 && lv[q] == 0) {
-            put(lab[q], v[q]);
-            if (ride) put0(lab[q], v0[q]);
+        for (int d = 4; d < 64; d <<= 1) {          // (the four lanes of a block hold the same labels)
+            lo = min(lo, __shfl_xor(lo, d, 64));
+            hi = max(hi, __shfl_xor(hi, d, 64));
         }
-    const int L = lab[0] >= 0 ? lv[0] : 0;          // a node of level >= 1 has its head at a block's first pixel
-    float oscale = 1.0f;
-    if (L >= 1 && a.mean) oscale = 1.0f / a.npix[lab[0]];          // (requested before the pyramid, used after it)
-    // ---- sum pyramid, (top-left + bottom-left) + (top-right + bottom-right) at every level as before: levels 1 .. 4 in registers
-    const float4 s1 = add4(add4(v[0], v[1]), add4(v[2], v[3]));
-    const float4 s2 = quad_sum4(s1, 0), s3 = quad_sum4(s2, 2), s4 = quad_sum4(s3, 4);
-    float r1 = 0.0f, r2 = 0.0f, r3 = 0.0f, r4 = 0.0f;
-    if (ride) {
-        r1 = (v0[0] + v0[1]) + (v0[2] + v0[3]);
-        r2 = quad_sum(r1, 0); r3 = quad_sum(r2, 2); r4 = quad_sum(r3, 4);
-    }
-    lds_barrier();                                  // every gather done: A / A0 are free
-    if ((t & 63) == 0) {
-        A[t >> 6] = s4;
-        A0[t >> 6] = r4;
-    }
-    lds_barrier();
-    // ---- every node of level >= 1 is written by the thread that owns its head pixel (the block's first pixel, aligned to 2^L)
-    if (L >= 1 && ((2 * br) & ((1 << L) - 1)) == 0 && ((2 * bc) & ((1 << L) - 1)) == 0) {
-        float4 s;
-        float r;
-        auto l5 = [&](int j) { return add4(add4(A[4 * j], A[4 * j + 2]), add4(A[4 * j + 1], A[4 * j + 3])); };
-        auto l50 = [&](int j) { return (A0[4 * j] + A0[4 * j + 2]) + (A0[4 * j + 1] + A0[4 * j + 3]); };
-        switch (L) {
-            case 1: s = s1; r = r1; break;
-            case 2: s = s2; r = r2; break;
-            case 3: s = s3; r = r3; break;
-            case 4: s = s4; r = r4; break;
-            case 5: s = l5(t >> 8); r = ride ? l50(t >> 8) : 0.0f; break;
-            default:
-                s = add4(add4(l5(0), l5(2)), add4(l5(1), l5(3)));
-                r = ride ? (l50(0) + l50(2)) + (l50(1) + l50(3)) : 0.0f;
-                break;
+        if ((t & 63) == 0) {
+            smin[wq] = lo;
+            smax[wq] = hi;
         }
-        put(lab[0], mul4(s, oscale));
-        if (ride) put0(lab[0], r * oscale);
+        lds_barrier();                              // (also: the previous quadrant's gathers and S3 reads are done)
+        lo = smin[t & 15];
+        hi = smax[t & 15];
+#pragma unroll
+        for (int d = 1; d < 16; d <<= 1) {
+            lo = min(lo, __shfl_xor(lo, d, 64));
+            hi = max(hi, __shfl_xor(hi, d, 64));
+        }
+        lo = __builtin_amdgcn_readfirstlane(lo);    // (the same in every lane: the window loop is uniform)
+        hi = __builtin_amdgcn_readfirstlane(hi);
+        // ---- pixel values: stage a window of source rows, gather.  Quadtree meshes: the first window is the whole range
+        // (4 rows per lane, loads first); the windows after it (any other mesh) go row by row
+        float4 v[4];
+        float v0[4];
+        auto stage = [&](int wb, int nr, int u0, int u1, float4* x, float* x0, float* sc) {
+            const float* srcw = src + (int64_t)wb * lds;           // (uniform)
+            const float* srcw0 = src0 + (int64_t)wb * lds0;
+            const float* npixw = a.src_npix + wb;
+            for (int u = u0; u < u1; ++u) {
+                const int lr = min(jq + 256 * u, nr - 1);          // (rows past the window: its last row again, not kept)
+                x[u - u0] = *reinterpret_cast<const float4*>(srcw + (unsigned)(lr * lds + ksrc));
+                x0[u - u0] = 0.0f;
+                sc[u - u0] = 1.0f;
+                if (ride) x0[u - u0] = srcw0[(unsigned)(lr * lds0)];
+                if (a.src_inv) sc[u - u0] = npixw[(unsigned)lr];
+            }
+            for (int u = u0; u < u1; ++u) {
+                float4 xx = x[u - u0];
+                if (first_only) xx.y = xx.z = xx.w = 0.0f;
+                const int lr = jq + 256 * u;
+                if (lr < nr) {
+                    const float inv = a.src_inv ? 1.0f / sc[u - u0] : 1.0f;
+                    A[4 * lr + k] = a.src_inv ? mul4(xx, inv) : xx;
+                    if (ride) A0[lr] = a.src_inv ? x0[u - u0] * inv : x0[u - u0];          // (four lanes, one value)
+                }
+            }
+        };
+        const bool any = lo <= hi;                  // (uniform; no valid pixel, e.g. a masked quadrant: nothing to stage, no window)
+        const int wb0 = any ? lo & ~1 : 0;          // (even first row: whole 128-byte lines)
+        if (any) {
+            float4 x[4];
+            float x0[4], sc[4];
+            stage(wb0, min(hi - wb0 + 1, RC_WIN), 0, 4, x, x0, sc);
+        }
+        lds_barrier();
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const unsigned lr = (unsigned)(sl[q] - wb0);
+            const bool in = sl[q] >= 0 && lr < (unsigned)RC_WIN;
+            v[q] = A[in ? 4 * lr + k : k];
+            v0[q] = ride ? A0[in ? lr : 0] : 0.0f;
+            if (!in) {
+                v[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+                v0[q] = 0.0f;
+            }
+        }
+#pragma nounroll
+        for (int wb = wb0 + RC_WIN; any && wb <= hi; wb += RC_WIN) {
+            const int nr = min(hi - wb + 1, RC_WIN);
+            lds_barrier();                          // the previous window's gathers are done
+#pragma nounroll
+            for (int u = 0; u < 4; ++u) {
+                float4 x[1];
+                float x0[1], sc[1];
+                stage(wb, nr, u, u + 1, x, x0, sc);
+            }
+            lds_barrier();
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const unsigned lr = (unsigned)(sl[q] - wb);
+                if (sl[q] >= 0 && lr < (unsigned)RC_WIN) {        // (every pixel has one source row: it is in one window)
+                    v[q] = A[4 * lr + k];
+                    if (ride) v0[q] = A0[lr];
+                }
+            }
+        }
+        // ---- single-pixel nodes
+        if (!WALK) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                if (lab[q] >= 0 && ((lv >> (8 * q)) & 255u) == 0) {
+                    if (mine) put(lab[q], v[q]);
+                    if (ride && k == 0) put0(lab[q], v0[q]);
+                }
+        }
+        // ---- sum pyramid, (top-left + top-right) + (bottom-left + bottom-right) at every level: level 1 in registers, levels 2
+        // and 3 between lanes 4 / 8 and 16 / 32 apart, the waves' level-3 sums through LDS
+        const float4 s1 = add4(add4(v[0], v[1]), add4(v[2], v[3]));
+        const float4 s2 = quad_sum4(s1, 2), s3 = quad_sum4(s2, 4);
+        float r1 = 0.0f, r2 = 0.0f, r3 = 0.0f;
+        if (ride) {
+            r1 = (v0[0] + v0[1]) + (v0[2] + v0[3]);
+            r2 = quad_sum(r1, 2); r3 = quad_sum(r2, 4);
+        }
+        if ((t & 63) < 4) {
+            S3[4 * wq + k] = s3;
+            if (k == 0) S30[wq] = r3;
+        }
+        lds_barrier();
+        // levels 4 and 5: the first wave of every level-4 entry sums its four waves' entries (wave 0: lanes 4 e + k take entry e,
+        // so that its lanes 0 .. 15 hold the quadrant's four level-4 sums and two more shuffles give level 5)
+        float4 s4 = s3, s5 = s3;
+        float r4 = r3, r5 = r3;
+        if ((w & 3) == 0) {                         // (wave-uniform)
+            const int e = w == 0 ? (j & 3) : w >> 2;
+            s4 = add4(add4(S3[16 * e + k], S3[16 * e + 8 + k]), add4(S3[16 * e + 4 + k], S3[16 * e + 12 + k]));
+            if (ride) r4 = (S30[4 * e] + S30[4 * e + 2]) + (S30[4 * e + 1] + S30[4 * e + 3]);
+            if (w == 0) {
+                s5 = quad_sum4(s4, 2);
+                if (ride) r5 = quad_sum(r4, 2);
+            }
+        }
+        if (WALK) {
+            // the quadrant's level-5 sum, kept by the four lanes that write the node in the end
+            if (t < 4) {
+                S5[4 * qq + k] = s5;
+                if (ride && k == 0) S50[qq] = r5;
+                if (qq == 0) {
+                    node6 = lab[0];
+                    oscale6 = oscale;
+                }
+            }
+            return;
+        }
+        // ---- every node of level >= 1 is written by the lanes that own its head pixel (the block's first pixel, aligned to 2^L)
+        if (L >= 1 && (rq & ((1 << L) - 1)) == 0 && (cq & ((1 << L) - 1)) == 0) {
+            float4 s;
+            float r;
+            switch (L) {
+                case 1: s = s1; r = r1; break;
+                case 2: s = s2; r = r2; break;
+                case 3: s = s3; r = r3; break;
+                case 4: s = s4; r = r4; break;
+                default: s = s5; r = r5; break;     // (level 5: the quadrant)
+            }
+            if (mine) put(lab[0], mul4(s, oscale));
+            if (ride && k == 0) put0(lab[0], r * oscale);
+        }
+    };
+    if (!walk) {
+        quadrant(qd, std::false_type());
+        return;
+    }
+#pragma nounroll
+    for (int qq = 0; qq < 4; ++qq) quadrant(qq, std::true_type());
+    if (t < 4 && node6 >= 0) {
+        const float4 s = add4(add4(S5[k], S5[8 + k]), add4(S5[4 + k], S5[12 + k]));
+        if (mine) put(node6, mul4(s, oscale6));
+        if (ride && k == 0) put0(node6, ((S50[0] + S50[2]) + (S50[1] + S50[3])) * oscale6);
     }
 }
 
@@ -326,9 +447,9 @@ extern "C" int qt_remesh_clip(const float* const* src_parts, const int* widths, 
     }
     for (int i = nout; i < 8; ++i) { a.opart[i] = nullptr; a.opart_w[i] = 0; a.opart_end[i] = 1 << 30; }
     QT_ARG(o4 == c4, "the output parts must add up to the source width");
+    QT_ARG(c4 < (1 << 16), "state too wide");
     a.src_labels = src_labels;
     a.src_npix = src_npix;
-    a.src_off = src_cell_off;
     a.tiles_c = qt_cdiv(m, 64);
     a.tiles = qt_cdiv(n, 64) * a.tiles_c;
     a.labels = labels;
@@ -342,8 +463,18 @@ extern "C" int qt_remesh_clip(const float* const* src_parts, const int* widths, 
     a.posfeat = posfeat;
     a.src_first_only = src_first_only;
     a.ride = (posfeat || src_first_only) && c4 > 1 && widths[0] == 4 && out_widths[0] == 4 ? 1 : 0;
-    QT_ARG((int64_t)B * a.tiles * c4 < ((int64_t)1 << 31), "grid too large");
-    hipLaunchKernelGGL(k_remesh_clip, dim3(B * a.tiles * (c4 - a.ride)), dim3(RC_T), 0, (hipStream_t)stream, a);
+    // column groups: runs of up to four chunks inside one source part and one output part (the rider's chunk 0 has none)
+    int sp = 0, op = 0;
+    for (int c = a.ride; c < c4;) {
+        while (c >= a.part_end[sp]) ++sp;
+        while (c >= a.opart_end[op]) ++op;
+        const int e = std::min(std::min(a.part_end[sp], a.opart_end[op]), c + 4);
+        QT_ARG(a.ngroups < RC_GROUPS, "too many column groups for one launch");
+        a.grp[a.ngroups++] = (unsigned)c | (unsigned)(e - c) << 16;
+        c = e;
+    }
+    QT_ARG((int64_t)B * a.tiles * 4 * a.ngroups < ((int64_t)1 << 31), "grid too large");
+    hipLaunchKernelGGL(k_remesh_clip, dim3(B * a.tiles * 4 * a.ngroups), dim3(RC_T), 0, (hipStream_t)stream, a);
     QT_LAUNCHED();
     return QT_OK;
 }
