@@ -4,7 +4,10 @@ Same constructor / train / predict / save / load surface; the train step (mpnnls
 `train_step` below and additionally accepts batches of clips and a torch.distributed process group
 (one flat gradient all-reduce per step).  tensorboard is optional (absent -> no-op writer).
 """
+import collections
+import collections.abc
 import datetime
+import inspect
 import os
 import time
 from abc import ABC, abstractmethod
@@ -218,6 +221,16 @@ def launch_frame(x):
 
 # The products of one inference rollout.  Each is reduce(y_hat, meshes, x, y, concat) -> one device tensor, written once: the
 # eager branch of the inference loop and the captured body (NextFramePredictorS2S._graphed_product) call the same function.
+# None writes what another reads, so any of them may follow one rollout in any order (PRODUCTS, below the trainer).
+def reference_frames(image_shape, mask):
+    """Frames by the reference's path (`unflatten` per step, in the caller's mode, one host copy per step): what an eager predict
+    returns.  The only reduce whose result is a host array, (B, T_out, W, H, 1); it cannot be captured."""
+    def reduce(y_hat, meshes, x, y, concat):
+        frames = [unflatten(o, ms, image_shape, mask).cpu().numpy() for o, ms in zip(y_hat, meshes)]
+        return np.stack(frames, axis=0)[None] if x.dim() == 4 else np.stack(frames, axis=1)
+    return reduce
+
+
 def frames_product(x, T_out):
     """Frames: every step gathered by one launch into its slot of a (B, T_out, W, H, 1) stack for batches shaped like x."""
     out = torch.empty(1 if x.dim() == 4 else x.shape[0], T_out, x.shape[-3], x.shape[-2], 1, device=x.device)
@@ -289,6 +302,213 @@ def events_product(threshold, kind, persist):
     def reduce(y_hat, meshes, x, y, concat):
         return ops._event_buffer(y_hat, meshes, y, launch_frame(x), threshold, kind, persist, concat)[0]
     return reduce
+
+
+def split_event_buffer(buf, B, S1, frame):
+    """Host copy of ops.rollout_event_dates' buffer -> (dates (B, S1, W, H) int32, sums (B, S1 - 1, 8) int64)."""
+    nsum = 2 * B * (S1 - 1) * 8
+    return buf[nsum:].reshape(B, S1, *frame), buf[:nsum].view(np.int64).reshape(B, S1 - 1, 8)
+
+
+# The product table: what each method of the inference loop is, stated once.  NextFramePredictorS2S.verify and the product's own
+# method (predict, score, ...) both read it.
+ProductCall = collections.namedtuple('ProductCall', 'T_out shape device with_clim graphed mask')
+ProductCall.__doc__ = """What a product is told about the call it is part of: the output steps, the frame shape (W, H) (None where a
+loader does not say), the device, whether there is a climatology, whether the rollout is captured, and the mask."""
+
+
+def forecast_sources(with_clim):
+    return ('model', 'persistence') + (('climatology',) if with_clim else ())
+
+
+class Product:
+    """One product of the inference loop for one call; a row of PRODUCTS is its class.  Four entries:
+        __init__(who, call, **options)   check and prepare, on the host and before any launch other than an upload: the checks
+                                         of the method, refused under `who`; `options` are the method's keywords, all given
+        reduce(x)                        make the reduce(y_hat, meshes, x, y, concat) for batches shaped like x
+        collect(result, x)               take one batch's result to the host
+        finish()                         the method's return value from what was collected
+    and, where every batch needs something done before its rollout, begin(x).  reads_y: whether the reduce reads y."""
+    reads_y, begin = True, None
+
+
+class _Frames(Product):
+    """predict: eagerly the reference's path, captured the gathered stack."""
+    reads_y = False
+
+    def __init__(self, who, call):
+        self.graphed, self.T_out, self.preds = call.graphed, call.T_out, []
+        if not call.graphed:
+            if call.shape is None:
+                raise AttributeError(f'{who}: the loader has no dataset.image_shape')
+            self.reference = reference_frames(call.shape, call.mask)
+
+    def reduce(self, x):
+        return frames_product(x, self.T_out) if self.graphed else self.reference
+
+    def collect(self, frames, x):
+        self.preds.extend(frames.cpu().numpy() if self.graphed else frames)     # (the stack comes back with one host copy)
+
+    def finish(self):
+        return np.stack(self.preds, 0)
+
+
+class _Sums(Product):
+    """A product whose reduce leaves (T, B, ...) sums per batch: the loader's (B_total, T, ...) array, one host copy per batch."""
+
+    def __init__(self, who, call, **options):
+        self.sources, self.parts = forecast_sources(call.with_clim), []
+        self.prepare(who, call, **options)
+
+    def reduce(self, x):
+        return self.reducer
+
+    def collect(self, part, x):
+        self.parts.append(np.moveaxis(part.cpu().numpy(), 0, 1))
+
+    def sums(self):
+        return np.concatenate(self.parts, 0)
+
+
+class _Scores(_Sums):
+    maps = None
+
+    def prepare(self, who, call, threshold):
+        self.threshold = threshold
+
+    def reduce(self, x):
+        return sums_product(self.threshold, self.maps)
+
+    def finish(self):
+        from qtmpnn.score import Scores
+        return Scores(self.sums(), self.sources)
+
+
+class _ScoreMaps(_Scores):
+    def prepare(self, who, call, threshold):
+        self.who, self.threshold, self.T_out, self.frame = who, threshold, call.T_out, None
+
+    def begin(self, x):         # the maps buffer exists, zeroed, before the first batch's forward; every batch has its grid
+        if self.maps is None:
+            self.frame = tuple(x.shape[-3:-1])
+            self.maps = torch.zeros(self.T_out, len(self.sources), 8, self.frame[0] * self.frame[1], dtype=torch.float64,
+                                    device=x.device)
+        elif tuple(x.shape[-3:-1]) != self.frame:
+            raise ValueError(f'{self.who}: a batch of {tuple(x.shape[-3:-1])} frames after {self.frame} ones: maps need '
+                             'one grid (use one loader per grid)')
+
+    def finish(self):
+        from qtmpnn.score import ScoreMaps, Scores
+        maps = self.maps
+        if maps is not None:
+            maps = ScoreMaps(maps.cpu().numpy().reshape(*maps.shape[:3], *self.frame), self.sources)
+        return Scores(self.sums(), self.sources, maps=maps)
+
+
+class _Reliability(_Sums):
+    def prepare(self, who, call, threshold, bins):
+        ops.check_bins(who, bins)
+        self.threshold, self.reducer = threshold, reliability_product(threshold, bins)
+
+    def finish(self):
+        from qtmpnn.reliability import Reliability
+        return Reliability(self.sums(), self.sources, self.threshold)                  # (B, T, S, K, 4)
+
+
+class _FSS(_Sums):
+    def prepare(self, who, call, threshold, scales):
+        self.threshold, self.scales = threshold, ops.check_scales(who, scales)
+        self.reducer = fss_product(threshold, self.scales)
+
+    def finish(self):
+        from qtmpnn.fss import FSS
+        return FSS(self.sums(), self.sources, self.threshold, self.scales)             # (B, T, S, K, 5)
+
+
+class _Edges(_Sums):
+    def prepare(self, who, call, threshold):
+        self.threshold, self.reducer = threshold, edge_product(threshold)
+
+    def finish(self):
+        from qtmpnn.edges import EdgeDistance
+        return EdgeDistance(self.sums(), self.sources, self.threshold)                 # (B, T, S, 8)
+
+
+class _Extent(_Sums):
+    def prepare(self, who, call, threshold, regions, areas, region_names):
+        if call.shape is None:
+            raise AttributeError(f'{who}: the loader has no dataset.image_shape')
+        region_dev, area_dev, R, self.names = _extent_maps(who, regions, areas, call.shape, call.device, region_names)
+        self.threshold, self.reducer = threshold, extent_product(threshold, region_dev, area_dev, R)
+
+    def finish(self):
+        from qtmpnn.extent import Extent
+        return Extent(self.sums(), self.sources, self.threshold, self.names)           # (B, T, R, 1 + S, 4)
+
+
+class _Events(Product):
+    def __init__(self, who, call, threshold, kind, persist):
+        if kind not in ops.EVENT_KINDS:
+            raise ValueError(f'{who}: kind must be one of {ops.EVENT_KINDS}, got {kind!r}')
+        if not (isinstance(persist, int) and 1 <= persist <= call.T_out):
+            raise ValueError(f'{who}: persist must be an integer in 1..{call.T_out} (the output steps), got {persist!r}')
+        self.sources = ('observed', 'model') + (('climatology',) if call.with_clim else ())
+        self.options, self.reducer = (kind, persist, threshold), events_product(threshold, kind, persist)
+        self.dates, self.sums = [], []
+
+    def reduce(self, x):
+        return self.reducer
+
+    def collect(self, buf, x):
+        d, s = split_event_buffer(buf.cpu().numpy(), 1 if x.dim() == 4 else x.shape[0], len(self.sources), tuple(x.shape[-3:-1]))
+        self.dates.append(d)
+        self.sums.append(s)
+
+    def finish(self):
+        from qtmpnn.events import EventDates
+        return EventDates(np.concatenate(self.dates, 0), np.concatenate(self.sums, 0), self.sources, *self.options)
+
+
+PRODUCTS = {'predict': _Frames, 'score': _Scores, 'score_maps': _ScoreMaps, 'reliability': _Reliability, 'fss': _FSS,
+            'edge_distance': _Edges, 'extent': _Extent, 'event_dates': _Events}
+DEFAULT_PRODUCTS = ('score', 'reliability', 'fss', 'edge_distance', 'extent', 'event_dates')
+
+
+def product_options(name):
+    """The keywords of product `name` and their defaults: the parameters of the method of that name that follow use_graph."""
+    params = list(inspect.signature(getattr(NextFramePredictorS2S, name)).parameters.values())
+    return {p.name: p.default for p in params[[p.name for p in params].index('use_graph') + 1:]}
+
+
+def make_products(who, products, call):
+    """`products` of a verify call -> {name: Product} in the order given, every one checked and prepared.  products: a sequence
+    of names of PRODUCTS, or a mapping name -> dict of the product's keywords (None: none); a missing keyword takes the default
+    of the product's method.  The refusals of the request itself are ValueErrors under `who` that name the product, and come
+    before any product is looked at; a product's own checks then report under its method's name."""
+    if isinstance(products, collections.abc.Mapping):
+        asked = [(name, {} if options is None else options) for name, options in products.items()]
+    elif isinstance(products, str) or not isinstance(products, collections.abc.Iterable):
+        raise ValueError(f'{who}: products must be a sequence of product names or a mapping from a name to its keywords, got '
+                         f'{products!r}')
+    else:
+        asked = [(name, {}) for name in products]
+    if not asked:
+        raise ValueError(f'{who}: products is empty: name at least one of {tuple(PRODUCTS)}')
+    seen, known = set(), {}
+    for name, options in asked:
+        if not isinstance(name, str) or name not in PRODUCTS:
+            raise ValueError(f'{who}: unknown product {name!r}: the products are {tuple(PRODUCTS)}')
+        if name in seen:
+            raise ValueError(f'{who}: product {name!r} is given twice: one configuration per product (make a second call for a '
+                             'second one)')
+        seen.add(name)
+        known[name] = product_options(name)
+        if not isinstance(options, collections.abc.Mapping):
+            raise ValueError(f'{who}: the keywords of product {name!r} must be a dict, got {options!r}')
+        for key in options:
+            if key not in known[name]:
+                raise ValueError(f'{who}: product {name!r} takes no keyword {key!r}: {name}() takes {tuple(known[name]) or "none"}')
+    return {name: PRODUCTS[name](name, call, **{**known[name], **options}) for name, options in asked}
 
 
 class NextFramePredictor(ABC):
@@ -786,7 +1006,8 @@ class NextFramePredictorS2S(NextFramePredictor):
                                      high_interest_region=high_interest_region, graph_structure=graph_structure)
 
     def _graphed_product(self, reduce, x, y, concat_layers, **fwd):
-        """The capture of one rollout (forward arguments `fwd`) and its product `reduce` on static copies of the batch; y is None
+        """The capture of one rollout (forward arguments `fwd`) and its product `reduce` (one device tensor, or a tuple of them:
+        several products of the one rollout) on static copies of the batch; y is None
         for a product that does not read it, and replay's arguments are then (x, concat), else (x, y, concat)."""
         self.model.static_shapes = True
         sx, sy, sc = (t if t is None else t.clone() for t in (x, y, concat_layers))
@@ -808,16 +1029,18 @@ class NextFramePredictorS2S(NextFramePredictor):
 
     def _graphed_inference(self, body, load):
         """Warm-up, capture and replay of a no-grad inference body (_graphed_product).  body() reads the
-        caller's static inputs and returns a device tensor; load(...) copies a batch into them.  The returned replay(...) loads,
-        replays, advances the host state like an eager rollout and returns the capture's result tensor; replay.warmup is a copy
-        of the eager warm-up's result."""
+        caller's static inputs and returns a device tensor, or a tuple of them (several products of one rollout); load(...)
+        copies a batch into them.  The returned replay(...) loads, replays, advances the host state like an eager rollout and
+        returns the capture's result, tensor or tuple; replay.warmup is a copy of the eager warm-up's result, a tuple cloned
+        element by element."""
         import random
         T_out = self.output_timesteps
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         calls0 = ops._ATTN_CALLS[0]
         with torch.cuda.stream(side):
-            warm = body().clone()
+            warm = body()
+            warm = tuple(t.clone() for t in warm) if isinstance(warm, tuple) else warm.clone()
         torch.cuda.current_stream().wait_stream(side)
         calls1 = ops._ATTN_CALLS[0]
         # the capture records launches without running them: whatever host state it advances is put back, and every replay
@@ -841,6 +1064,9 @@ class NextFramePredictorS2S(NextFramePredictor):
             ops._ATTN_CALLS[0] += calls1 - calls0
             return result
         replay.warmup = warm
+        # the graph reads what the body's closure holds (the device maps of extent_product) at every replay: they live as long as
+        # the replay does, as make_graphed_step's loss weights do
+        replay.body = body
         return replay
 
     @on_device(lambda self, *a, **k: self.device)
@@ -905,6 +1131,28 @@ class NextFramePredictorS2S(NextFramePredictor):
         `events.warmup` is the given batch's.  The scan's first launch initialises its state, so a replay needs no memset."""
         return self._graphed_product(events_product(threshold, kind, persist), x, y, concat_layers, mask=mask,
                                      high_interest_region=high_interest_region, graph_structure=graph_structure)
+
+    @on_device(lambda self, *a, **k: self.device)
+    def make_graphed_verification(self, x, y, concat_layers=None, mask=None, high_interest_region=None, graph_structure=None,
+                                  products=DEFAULT_PRODUCTS):
+        """The makers above in one capture: the rollout and the launches of every product of `products` (verify()'s names and
+        keywords, checked as verify() checks them, before any launch) as ONE hipGraph.  Returns `verification(x, y, concat)` ->
+        the tuple of the products' device tensors in the order given, each what its own maker returns ('predict':
+        make_graphed_rollout's stack; 'event_dates': the buffer of make_graphed_events; 'score_maps': the batch's sums, as
+        make_graphed_scores(maps=...)); `.warmup` is that tuple for the given batch and `.products` the names.  With 'score_maps'
+        the zeroed float64 (T_out, S, 8, P) buffer is allocated here and is `.maps`: the given batch is in it once, and every
+        replay adds its batch once."""
+        call = ProductCall(self.output_timesteps, tuple(x.shape[-3:-1]), x.device, concat_layers is not None, True, mask)
+        made = make_products('make_graphed_verification', products, call)
+        for p in made.values():
+            if p.begin is not None:
+                p.begin(x)
+        reduces = [p.reduce(x) for p in made.values()]
+        replay = self._graphed_product(lambda *rollout: tuple(reduce(*rollout) for reduce in reduces), x, y, concat_layers,
+                                       mask=mask, high_interest_region=high_interest_region, graph_structure=graph_structure)
+        replay.products = tuple(made)
+        replay.maps = made['score_maps'].maps if 'score_maps' in made else None
+        return replay
 
     @on_device(lambda self, *a, **k: self.device)
     def train(self, loader_train, loader_test, climatology=None, n_epochs=200, lr=0.01, lr_decay=0.95, mask=None,
@@ -1009,26 +1257,14 @@ class NextFramePredictorS2S(NextFramePredictor):
         train / eval mode) is captured once per call (make_graphed_rollout; the first batch of that key is predicted eagerly in
         static mode as the warm-up, and its result is the one returned), later batches copy into the captured inputs, replay and
         make one host copy.  The graphs are dropped and `static_shapes` is restored when the call returns."""
-        image_shape = loader.dataset.image_shape
-        preds = []
-
-        def reference_frames(y_hat, meshes, x, y, concat):      # the reference's path, in the caller's (non-static) mode
-            frames = [unflatten(o, ms, image_shape, mask).cpu().numpy() for o, ms in zip(y_hat, meshes)]
-            return np.stack(frames, axis=0)[None] if x.dim() == 4 else np.stack(frames, axis=1)
-
-        if use_graph:           # the stack comes back with one host copy per batch
-            product = lambda x: frames_product(x, self.output_timesteps)
-            consume = lambda stack, x: preds.extend(stack.cpu().numpy())
-        else:
-            product, consume = lambda x: reference_frames, lambda frames, x: preds.extend(frames)
-        self._inference(loader, climatology, product, consume, use_graph, reads_y=False, mask=mask,
-                        high_interest_region=high_interest_region, graph_structure=graph_structure)
-        return np.stack(preds, 0)
+        return self._one('predict', loader, climatology, mask, high_interest_region, graph_structure, use_graph)
 
     def _inference(self, loader, climatology, product, consume, use_graph, reads_y=True, begin=None, **fwd):
-        """The inference loop of predict, score, score_maps, reliability, fss, edge_distance, extent and event_dates: per batch begin(x), if given, then one no-grad
+        """The inference loop of predict, score, score_maps, reliability, fss, edge_distance, extent, event_dates and verify (all
+        through _verify): per batch begin(x), if given, then one no-grad
         rollout (teacher forcing 0, forward arguments `fwd`) reduced by a reduce(y_hat, meshes, x, y, concat), see frames_product,
-        whose result goes to consume(result, x); x is the clipped batch.  product(x) makes the reduce: for every batch of an eager
+        whose result (a tensor, or a tuple of them where several products share the rollout) goes to consume(result, x); x is
+        the clipped batch.  product(x) makes the reduce: for every batch of an eager
         call, for every capture of a graphed one, so it must not do what every batch needs (that is begin's).  use_graph: each
         distinct (x shape, y shape where the product reads y, climatology shape, train / eval mode) is captured once per call on
         first sight (_graphed_product); that batch's result is the eager static-mode warm-up's, later batches of the key are
@@ -1061,6 +1297,54 @@ class NextFramePredictorS2S(NextFramePredictor):
             self.model.static_shapes = static0
         check_tile_errors(always=True)
 
+    def _verify(self, who, loader, climatology, mask, high_interest_region, graph_structure, use_graph, products):
+        """_inference with the products `products` names (make_products: all of them checked and prepared before the first batch)
+        on ONE rollout per batch -> {name: result} in the order given.  Per batch: begin of the products that have one, the
+        rollout, every product's reduce on it in order (a tuple of results; with use_graph all of it is one capture per key),
+        one collect per product."""
+        call = ProductCall(self.output_timesteps, getattr(getattr(loader, 'dataset', None), 'image_shape', None), self.device,
+                           climatology is not None, bool(use_graph), mask)
+        made = make_products(who, products, call)
+        begins = [p.begin for p in made.values() if p.begin is not None]
+
+        def product(x):
+            reduces = [p.reduce(x) for p in made.values()]
+            return lambda *rollout: tuple(reduce(*rollout) for reduce in reduces)
+
+        def consume(results, x):
+            for p, result in zip(made.values(), results):
+                p.collect(result, x)
+
+        self._inference(loader, climatology, product, consume, use_graph, reads_y=any(p.reads_y for p in made.values()),
+                        begin=(lambda x: [begin(x) for begin in begins]) if begins else None, mask=mask,
+                        high_interest_region=high_interest_region, graph_structure=graph_structure)
+        return {name: p.finish() for name, p in made.items()}
+
+    def _one(self, name, loader, climatology, mask, high_interest_region, graph_structure, use_graph, **options):
+        """The method `name`: _verify with that one product."""
+        return self._verify(name, loader, climatology, mask, high_interest_region, graph_structure, use_graph, {name: options})[name]
+
+    @on_device(lambda self, *a, **k: self.device)
+    def verify(self, loader, climatology=None, mask=None, high_interest_region=None, graph_structure=None, use_graph=False,
+               products=DEFAULT_PRODUCTS):
+        """Several verification products from ONE rollout per batch -> qtmpnn.verify.Verification (beyond the reference): what
+        predict, score, score_maps, reliability, fss, edge_distance, extent and event_dates return, each bit for bit what its own
+        method returns with the same arguments, without running the model once per product.
+
+        products: a sequence of those method names (each with its method's defaults), or a mapping name -> dict of that
+        method's own keywords (threshold, bins, scales, regions, areas, region_names, kind, persist); one configuration per
+        product.  Every product is checked as its own method checks it, under the method's name, before the first batch and
+        before any launch; an unknown name, a keyword the method does not take, an empty `products` and a name given twice are
+        ValueErrors.  The result holds the products in the order given: `v['fss']`, `v.fss`, `v.products`, `v.sources`.
+
+        score()'s loop and arguments.  Per batch: the rollout once, then every product's launches on it in order, one host copy
+        per product.  use_graph=True captures the rollout and all products as ONE hipGraph per distinct batch shape
+        (make_graphed_verification).  'predict' is what predict() is in the same mode: eagerly the reference's `unflatten` per
+        step, graphed the gathered stack."""
+        from qtmpnn.verify import Verification
+        results = self._verify('verify', loader, climatology, mask, high_interest_region, graph_structure, use_graph, products)
+        return Verification(results, forecast_sources(climatology is not None))
+
     @on_device(lambda self, *a, **k: self.device)
     def attention_weights(self, x, concat_layers=None, mask=None, high_interest_region=None, graph_structure=None, select=None):
         """The attention coefficients of one no-grad rollout of x (predict's eager forward, teacher forcing 0): the records of
@@ -1087,7 +1371,8 @@ class NextFramePredictorS2S(NextFramePredictor):
         the outputs are probabilities and a caller passes 0.5.  use_graph=True replays rollout + sums as one hipGraph per
         distinct batch shape, as predict(use_graph=True) does (make_graphed_scores).  `.maps` of the result is None: score_maps()
         is this call with the per-pixel maps as well."""
-        return self._score(loader, climatology, mask, high_interest_region, graph_structure, use_graph, threshold, False)
+        return self._one('score', loader, climatology, mask, high_interest_region, graph_structure, use_graph,
+                         threshold=threshold)
 
     @on_device(lambda self, *a, **k: self.device)
     def score_maps(self, loader, climatology=None, mask=None, high_interest_region=None, graph_structure=None, use_graph=False,
@@ -1098,36 +1383,8 @@ class NextFramePredictorS2S(NextFramePredictor):
         for cell areas or a region).  The first batch allocates the zeroed device buffer, every batch adds into it right after
         its sums (ops.rollout_score_maps; inside the capture with use_graph=True) and one host copy follows the last batch.
         Every batch must have the first one's frame shape."""
-        return self._score(loader, climatology, mask, high_interest_region, graph_structure, use_graph, threshold, True)
-
-    def _rollout_sums(self, loader, climatology, product, use_graph, begin=None, **fwd):
-        """_inference with a reduce that leaves (T, B, ...) sums per batch (sums_product, reliability_product, fss_product,
-        edge_product, extent_product) ->(the loader's (B_total, T, ...) array, one host copy per batch; the names of its sources)."""
-        sums = []
-        self._inference(loader, climatology, product, lambda part, x: sums.append(np.moveaxis(part.cpu().numpy(), 0, 1)),
-                        use_graph, begin=begin, **fwd)
-        return np.concatenate(sums, 0), ('model', 'persistence') + (('climatology',) if climatology is not None else ())
-
-    def _score(self, loader, climatology, mask, high_interest_region, graph_structure, use_graph, threshold, with_maps):
-        from qtmpnn.score import ScoreMaps, Scores
-        maps, frame = None, None
-
-        def begin(x):           # the maps buffer exists, zeroed, before the first batch's forward; every batch has its grid
-            nonlocal maps, frame
-            if maps is None:
-                frame = tuple(x.shape[-3:-1])
-                maps = torch.zeros(self.output_timesteps, 2 + (climatology is not None), 8, frame[0] * frame[1],    # per source
-                                   dtype=torch.float64, device=x.device)
-            elif tuple(x.shape[-3:-1]) != frame:
-                raise ValueError(f'score_maps: a batch of {tuple(x.shape[-3:-1])} frames after {frame} ones: maps need '
-                                 'one grid (use one loader per grid)')
-
-        sums, sources = self._rollout_sums(loader, climatology, lambda x: sums_product(threshold, maps), use_graph,
-                                           begin=begin if with_maps else None, mask=mask,
-                                           high_interest_region=high_interest_region, graph_structure=graph_structure)
-        if maps is not None:
-            maps = ScoreMaps(maps.cpu().numpy().reshape(*maps.shape[:3], *frame), sources)
-        return Scores(sums, sources, maps=maps)
+        return self._one('score_maps', loader, climatology, mask, high_interest_region, graph_structure, use_graph,
+                         threshold=threshold)
 
     @on_device(lambda self, *a, **k: self.device)
     def reliability(self, loader, climatology=None, mask=None, high_interest_region=None, graph_structure=None, use_graph=False,
@@ -1141,12 +1398,8 @@ class NextFramePredictorS2S(NextFramePredictor):
         score()'s loop, arguments and sources: every batch leaves four sums per (lead time, clip, source, bin) on the device
         (ops.rollout_reliability: the head's outputs read through the labels, no frame is built) and makes one host copy of
         them.  use_graph=True replays rollout + sums as one hipGraph per distinct batch shape (make_graphed_reliability)."""
-        from qtmpnn.reliability import Reliability
-        ops.check_bins('reliability', bins)
-        reduce = reliability_product(threshold, bins)
-        sums, sources = self._rollout_sums(loader, climatology, lambda x: reduce, use_graph, mask=mask,      # (B, T, S, K, 4)
-                                           high_interest_region=high_interest_region, graph_structure=graph_structure)
-        return Reliability(sums, sources, threshold)
+        return self._one('reliability', loader, climatology, mask, high_interest_region, graph_structure, use_graph,
+                         threshold=threshold, bins=bins)
 
     @on_device(lambda self, *a, **k: self.device)
     def fss(self, loader, climatology=None, mask=None, high_interest_region=None, graph_structure=None, use_graph=False,
@@ -1160,12 +1413,8 @@ class NextFramePredictorS2S(NextFramePredictor):
         score()'s loop, arguments and sources: every batch leaves five integers per (lead time, clip, source, scale) on the
         device (ops.rollout_fss: the head's outputs read through the labels, no frame is built) and makes one host copy of
         them.  use_graph=True replays rollout + sums as one hipGraph per distinct batch shape (make_graphed_fss)."""
-        from qtmpnn.fss import FSS
-        scales = ops.check_scales('fss', scales)
-        reduce = fss_product(threshold, scales)
-        sums, sources = self._rollout_sums(loader, climatology, lambda x: reduce, use_graph, mask=mask,      # (B, T, S, K, 5)
-                                           high_interest_region=high_interest_region, graph_structure=graph_structure)
-        return FSS(sums, sources, threshold, scales)
+        return self._one('fss', loader, climatology, mask, high_interest_region, graph_structure, use_graph,
+                         threshold=threshold, scales=scales)
 
     @on_device(lambda self, *a, **k: self.device)
     def edge_distance(self, loader, climatology=None, mask=None, high_interest_region=None, graph_structure=None, use_graph=False,
@@ -1179,11 +1428,8 @@ class NextFramePredictorS2S(NextFramePredictor):
         score()'s loop, arguments and sources: every batch leaves eight integers per (lead time, clip, source) on the device
         (ops.rollout_edges: the head's outputs read through the labels, no frame is built) and makes one host copy of them.
         use_graph=True replays rollout + sums as one hipGraph per distinct batch shape (make_graphed_edges)."""
-        from qtmpnn.edges import EdgeDistance
-        reduce = edge_product(threshold)
-        sums, sources = self._rollout_sums(loader, climatology, lambda x: reduce, use_graph, mask=mask,      # (B, T, S, 8)
-                                           high_interest_region=high_interest_region, graph_structure=graph_structure)
-        return EdgeDistance(sums, sources, threshold)
+        return self._one('edge_distance', loader, climatology, mask, high_interest_region, graph_structure, use_graph,
+                         threshold=threshold)
 
     @on_device(lambda self, *a, **k: self.device)
     def extent(self, loader, climatology=None, mask=None, high_interest_region=None, graph_structure=None, use_graph=False,
@@ -1200,13 +1446,8 @@ class NextFramePredictorS2S(NextFramePredictor):
         score()'s loop, arguments and sources: every batch leaves (1 + S) * 4 sums per (lead time, clip, region) on the device
         (ops.rollout_extent: the head's outputs read through the labels, no frame is built) and makes one host copy of them.
         use_graph=True replays rollout + sums as one hipGraph per distinct batch shape (make_graphed_extent)."""
-        from qtmpnn.extent import Extent
-        region_dev, area_dev, R, names = _extent_maps('extent', regions, areas, loader.dataset.image_shape, self.device,
-                                                      region_names)
-        reduce = extent_product(threshold, region_dev, area_dev, R)
-        sums, sources = self._rollout_sums(loader, climatology, lambda x: reduce, use_graph, mask=mask,      # (B, T, R, 1 + S, 4)
-                                           high_interest_region=high_interest_region, graph_structure=graph_structure)
-        return Extent(sums, sources, threshold, names)
+        return self._one('extent', loader, climatology, mask, high_interest_region, graph_structure, use_graph,
+                         threshold=threshold, regions=regions, areas=areas, region_names=region_names)
 
     @on_device(lambda self, *a, **k: self.device)
     def event_dates(self, loader, climatology=None, mask=None, high_interest_region=None, graph_structure=None, use_graph=False,
@@ -1222,27 +1463,6 @@ class NextFramePredictorS2S(NextFramePredictor):
         read through every step's labels, no frame is built; ops.rollout_event_dates) and every batch makes one host copy of
         dates and sums.  use_graph=True replays rollout + scan + sums as one hipGraph per distinct batch shape
         (make_graphed_events)."""
-        from qtmpnn.events import EventDates
-        if kind not in ops.EVENT_KINDS:
-            raise ValueError(f'event_dates: kind must be one of {ops.EVENT_KINDS}, got {kind!r}')
-        if not (isinstance(persist, int) and 1 <= persist <= self.output_timesteps):
-            raise ValueError(f'event_dates: persist must be an integer in 1..{self.output_timesteps} (the output steps), '
-                             f'got {persist!r}')
-        sources = ('observed', 'model') + (('climatology',) if climatology is not None else ())
-        dates, sums = [], []
+        return self._one('event_dates', loader, climatology, mask, high_interest_region, graph_structure, use_graph,
+                         threshold=threshold, kind=kind, persist=persist)
 
-        def consume(buf, x):
-            d, s = split_event_buffer(buf.cpu().numpy(), 1 if x.dim() == 4 else x.shape[0], len(sources), tuple(x.shape[-3:-1]))
-            dates.append(d)
-            sums.append(s)
-
-        reduce = events_product(threshold, kind, persist)
-        self._inference(loader, climatology, lambda x: reduce, consume, use_graph, mask=mask,
-                        high_interest_region=high_interest_region, graph_structure=graph_structure)
-        return EventDates(np.concatenate(dates, 0), np.concatenate(sums, 0), sources, kind, persist, threshold)
-
-
-def split_event_buffer(buf, B, S1, frame):
-    """Host copy of ops.rollout_event_dates' buffer -> (dates (B, S1, W, H) int32, sums (B, S1 - 1, 8) int64)."""
-    nsum = 2 * B * (S1 - 1) * 8
-    return buf[nsum:].reshape(B, S1, *frame), buf[:nsum].view(np.int64).reshape(B, S1 - 1, 8)
