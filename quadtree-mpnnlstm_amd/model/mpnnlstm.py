@@ -1358,6 +1358,141 @@ class NextFramePredictorS2S(NextFramePredictor):
         return records
 
     @on_device(lambda self, *a, **k: self.device)
+    def sensitivity(self, x, concat_layers=None, mask=None, high_interest_region=None, graph_structure=None,
+                    target=None, leads=None, method='gradient', baseline=None, steps=16):
+        """Which input days, channels and pixels a forecast is made from -> qtmpnn.sensitivity.Sensitivity (beyond the
+        reference).  x: (T_in, W, H, C) or (B, T_in, W, H, C) on the model's device; concat_layers as in forward_loss.  For
+        every clip and every lead time t of `leads` (strictly increasing output steps; None: all) the forecast is summarised as
+
+            J_t = sum_p w_p y_hat[t, p] / sum_p w_p      over the unmasked pixels, w = `target` (W, H) >= 0 (None: ones)
+
+        -- a region, or cell areas (model.utils.cell_area_weights) -- and `.maps[b, l]`, shaped like the clip's input, is
+
+            method='gradient'           dJ_t / dx
+                   'gradient_x_input'   dJ_t / dx * (x - baseline)
+                   'integrated'         (x - baseline) * mean_k dJ_t / dx at baseline + alpha_k (x - baseline),
+                                        alpha_k = (k + 1/2) / steps, k < steps (1..256): integrated gradients, midpoint rule
+
+        baseline: zeros, one (T_in, W, H, C) array or one shaped like x.  `.J` holds J_t at x, `.J_baseline` ('integrated'
+        only) J_t at the baseline, so `.completeness()` is what the path integral leaves over.
+
+        THE MESHES ARE HELD FIXED: the maps are the derivative of the rollout on the meshes it built for the unperturbed
+        input; the quadtree criterion (which cells split) is a step function of the data and is not differentiated.
+        Gradients do flow through everything that carries values across meshes: the pooling of the frames onto the nodes and the
+        state transfer between the meshes of consecutive decoder steps.  Every path point of 'integrated' is a clip of its own
+        and builds its own meshes, as a batch of different clips does.
+
+        One eager rollout (teacher forcing 0, the caller's train / eval mode) with gradients enabled, then one backward pass
+        per lead (torch.autograd.grad on the sum of J_t over the clips: the graph is block diagonal, so every clip gets its
+        own map); the seed of a pass is the target summed onto the nodes of step t's mesh, on the device.  The path points of
+        'integrated' run as extra clips of batched rollouts, at most 32 clips each.  One host copy ends the call.
+
+        Nothing of the training state changes: for the call's duration no parameter requires a gradient (restored in a
+        `finally`; with it the weight-gradient launches do not run), so every param.grad, the flat gradient vector, the
+        optimiser, `static_shapes` and the mode are what they were; Python's `random` state and the attention-dropout call
+        counter are put back as well.
+
+        Refusals, by argument name and before any launch: ValueError for target (shape, dtype, NaN / infinite, negative, zero
+        sum over the unmasked pixels), leads, method, steps, baseline (also when given with a method that does not use them) and
+        x (shape, dtype); NotImplementedError for remesh_input=True models (their encoder assembles its rows without
+        autograd); RuntimeError in static mode or inside a graph capture.  There is no use_graph option."""
+        from qtmpnn import _lib
+        from qtmpnn.sensitivity import CHUNK, Request, Sensitivity
+        if not torch.is_tensor(x) or not x.is_floating_point() or x.dim() not in (4, 5):
+            raise ValueError('x: a floating-point tensor of shape (T_in, W, H, C) or (B, T_in, W, H, C) is needed, got '
+                             + (f'{x.dtype} {tuple(x.shape)}' if torch.is_tensor(x) else type(x).__name__))
+        req = Request(x.shape, self.output_timesteps, host_mask(mask), target, leads, method, baseline, steps)
+        if self.model.remesh_input:
+            raise NotImplementedError('sensitivity: remesh_input=True models are not covered (their encoder assembles the rows of '
+                                      'every input frame without autograd)')
+        if self.model.static_shapes or (torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()):
+            raise RuntimeError('sensitivity: not in static mode or inside a graph capture (make_graphed_step, make_graphed_rollout, '
+                               'predict(use_graph=True)): the backward passes run eagerly on meshes of their own sizes')
+        _lib.require_cuda(x, 'x')
+        import random
+        single = x.dim() == 4
+        x5 = (x.unsqueeze(0) if single else x).detach().float()
+        B, L = x5.shape[0], len(req.leads)
+        dev = x5.device
+        concat = None
+        if concat_layers is not None:
+            concat = concat_layers.to(dev).float()
+            concat = concat.unsqueeze(0) if concat.dim() == 4 else concat
+        base5 = None
+        if req.baseline is not None:
+            base5 = torch.from_numpy(req.baseline).to(dev)
+            base5 = base5.unsqueeze(0).expand_as(x5) if base5.dim() == 4 else base5
+        w = torch.from_numpy(req.target).to(dev).reshape(-1)                       # (P,), zero under the mask
+        fwd = dict(mask=mask, high_interest_region=high_interest_region, graph_structure=graph_structure)
+
+        def rollout(clips, conc, grads):
+            """One rollout of `clips` (n, T_in, W, H, C) -> (J (n, L) float64, maps (n, L, T_in, W, H, C) or None)."""
+            n = clips.shape[0]
+            leaf = clips.clone().requires_grad_(grads)
+            with torch.enable_grad() if grads else torch.no_grad():
+                y_hat, meshes = self.model(leaf, concat_layers=conc, teacher_forcing_ratio=0, **fwd)
+            J = torch.empty(n, L, dtype=torch.float64, device=dev)
+            maps = torch.empty(n, L, *clips.shape[1:], device=dev) if grads else None
+            for l, t in enumerate(req.leads):
+                out, mesh = y_hat[t], meshes[t]
+                with torch.no_grad():
+                    frame = ops.gather_pixels(out.detach()[:, :1], mesh).view(n, -1)
+                    J[:, l] = (frame.double() * w.double()).sum(dim=1) / req.sum_w
+                    if grads:       # dJ_t / d(node output): the target summed onto the nodes of this step's mesh
+                        seed = ops.pool_image(w.view(1, 1, -1, 1).expand(n, 1, -1, 1), mesh, False)[0] / req.sum_w
+                if grads:
+                    maps[:, l] = torch.autograd.grad((out[:, :1] * seed).sum(), leaf, retain_graph=l + 1 < L)[0]
+            return J, maps
+
+        params = list(self.model.parameters())
+        flat = self.model.__dict__.get('_flat_params')
+        if flat is not None:
+            params.append(flat.param)           # (a packed model: the optimiser's one tensor over the same storage)
+        required = [p.requires_grad for p in params]
+        rstate, calls = random.getstate(), ops._ATTN_CALLS[0]
+        try:
+            for p in params:
+                p.requires_grad_(False)
+            self.model.to(self.device)
+            Jb = None
+            if req.method == 'integrated':
+                start = base5 if base5 is not None else torch.zeros_like(x5)
+                delta = x5 - start
+                alphas = (torch.arange(req.steps, device=dev, dtype=torch.float32) + 0.5) / req.steps
+                # the clips of the path, clip-major: point (b, k) = baseline_b + alpha_k (x_b - baseline_b); then the two ends
+                points = (start.unsqueeze(1) + alphas.view(1, -1, 1, 1, 1, 1) * delta.unsqueeze(1)).reshape(-1, *x5.shape[1:])
+                ends = torch.cat([x5, start])
+                pc = ec = None
+                if concat is not None:
+                    pc = concat.unsqueeze(1).expand(-1, req.steps, *concat.shape[1:]).reshape(-1, *concat.shape[1:])
+                    ec = torch.cat([concat, concat])
+                chunks = lambda clips, conc, grads: [rollout(clips[a:a + CHUNK], None if conc is None else conc[a:a + CHUNK], grads)
+                                                     for a in range(0, clips.shape[0], CHUNK)]
+                Js = torch.cat([j for j, _ in chunks(ends, ec, False)])
+                J, Jb = Js[:B], Js[B:]
+                grads = torch.cat([g for _, g in chunks(points, pc, True)])
+                maps = grads.view(B, req.steps, L, *x5.shape[1:]).mean(dim=1) * delta.unsqueeze(1)
+            else:
+                J, maps = rollout(x5, concat, True)
+                if req.method == 'gradient_x_input':
+                    maps = maps * ((x5 - base5) if base5 is not None else x5).unsqueeze(1)
+            # one host copy: [J | J_baseline] as float64 words in front of the float32 maps
+            nj = J.numel() * (2 if Jb is not None else 1)
+            buf = torch.empty(2 * nj + maps.numel(), dtype=torch.float32, device=dev)
+            buf[:2 * nj].view(torch.float64).copy_(torch.cat([J.reshape(-1)] + ([Jb.reshape(-1)] if Jb is not None else [])))
+            buf[2 * nj:].copy_(maps.reshape(-1))
+            host = buf.cpu().numpy()
+        finally:
+            for p, r in zip(params, required):
+                p.requires_grad_(r)
+            random.setstate(rstate)
+            ops._ATTN_CALLS[0] = calls
+        check_tile_errors()
+        Js = host[:2 * nj].view(np.float64).reshape(-1, B, L)
+        return Sensitivity(host[2 * nj:].reshape(B, L, *x5.shape[1:]).copy(), req.leads, req.method, req.target, Js[0].copy(),
+                           Js[1].copy() if Jb is not None else None)
+
+    @on_device(lambda self, *a, **k: self.device)
     def score(self, loader, climatology=None, mask=None, high_interest_region=None, graph_structure=None, use_graph=False,
               threshold=0.15):
         """Forecast verification over a loader -> qtmpnn.score.Scores (beyond the reference, whose score() is empty; the numbers

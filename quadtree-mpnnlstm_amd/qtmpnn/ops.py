@@ -964,6 +964,8 @@ class _Attention(Function):
         else:
             gproj.zero_()
         none = (None,) * 7
+        if not ctx.needs_input_grad[1]:     # We is data here (input sensitivities): no reduction, and the uses are not counted
+            return (gproj, None) + none
         if acc is not None and not acc.leave(ctx.use_idx):
             return (gproj, None) + none
         psum = proj.new_empty(G * 2 * C)
@@ -1037,11 +1039,12 @@ class _MHAttention(Function):
         else:
             gproj.zero_()
         gWe = gWt = gb = None
-        if acc_e is None or acc_e.leave(ctx.use_e):
+        need_e, need_l = ctx.needs_input_grad[1], any(ctx.needs_input_grad[2:4])      # (False: the weights are data in this pass)
+        if need_e and (acc_e is None or acc_e.leave(ctx.use_e)):
             psum = proj.new_empty(H * 2 * C)
             _lib.call('qt_colsum', ptr(part), nblk, H * 2 * C, ptr(psum))           # part (block, head, 2C)
             gWe = psum.view(H, 2, C).transpose(1, 2).contiguous()
-        if acc_l is None or acc_l.leave(ctx.use_l):
+        if need_l and (acc_l is None or acc_l.leave(ctx.use_l)):
             lsum = proj.new_empty(nl)
             _lib.call('qt_colsum', ptr(part_l), nblk_l, nl, ptr(lsum))
             gWt, gb = lsum[:H * C * C].view(H * C, C), lsum[H * C * C:]
@@ -1243,8 +1246,10 @@ class _MultiConv(Function):
             else:
                 gA.zero_()
             gAs.append(gA)
-        last = acc is None or acc.leave(ctx.use_idx)
         need_w = any(ctx.needs_input_grad[8 + nseg:8 + 2 * nseg])
+        if not (need_w or ctx.needs_input_grad[8 + 2 * nseg]):      # every weight is data here: nothing to reduce, no use counted
+            return (None,) * 8 + tuple(gAs) + (None,) * (nseg + 1)
+        last = acc is None or acc.leave(ctx.use_idx)
         pending = acc.pending if acc is not None else []
         if need_w and N > 0 and len(fused) < nseg:          # (the segments in `fused` have their share in the slabs already)
             pending.append((As, gP, N, mesh.n_dev, mesh.cheb_ones(1), fused))
@@ -1339,14 +1344,17 @@ class _LstmCell(Function):
     @staticmethod
     def backward(ctx, gO, gHn, gCn):
         gates, Cprev, wc, ln = ctx.saved_tensors
-        res = _lstm_backward(gO, gHn, gCn, gates, Cprev, wc, ln, ctx.mesh, ctx.acc, ctx.use_idx)
+        res = _lstm_backward(gO, gHn, gCn, gates, Cprev, wc, ln, ctx.mesh, ctx.acc, ctx.use_idx,
+                             need_p=any(ctx.needs_input_grad[2:5]))
         if ctx.pair:            # both addends receive the same gradient: a stride-0 view, no copy
             res = (res[0].unsqueeze(1).expand(-1, 2, -1),) + tuple(res[1:])
         return (*res, None, None)
 
 
-def _lstm_backward(gO, gHn, gCn, gates, Cprev, wc, ln, mesh, acc, use_idx, dgrad=None, gHn2=None, add0=None):
+def _lstm_backward(gO, gHn, gCn, gates, Cprev, wc, ln, mesh, acc, use_idx, dgrad=None, gHn2=None, add0=None, need_p=True):
     """(gG, gCprev, g_wc, g_b, g_ln) of the cell; the parameter gradients are None until the pass's last backward.
+    need_p False: none of wc, b, ln wants a gradient -- the partial sums are not reduced and the use is not counted (a pass that
+    differentiates with respect to the inputs alone may reach only some uses of a cell, and may run more than once).
     gHn2: a second gradient of H' (added to gHn: by qt_lstm_bwd_dgrad on load, else here); add0: (N, c) added to plane 0 of
     the first part of `dgrad`'s planes (qt_lstm_bwd_dgrad only: the caller checks that this launch serves the use).
     dgrad = (Wrows, K, [part widths], [plane tensors (K, N, c)], out_sm): the data gradient of the gate GEMM, gG @ Wrows^T, is
@@ -1391,7 +1399,7 @@ def _lstm_backward(gO, gHn, gCn, gates, Cprev, wc, ln, mesh, acc, use_idx, dgrad
             part.zero_()
         _lib.call('qt_lstm_bwd', ptr(gO), ld_go, ptr(gHn), ld_gh, ptr(gCn), ld_gc, ptr(gates), ptr(Cprev),
                   ld_c, ptr(wc), ptr(ln), N, ptr(mesh.n_dev), h, ptr(gG), ptr(gCp), ptr(part), 0 if acc is None else 1)
-    if acc is not None and not acc.leave(use_idx):
+    if not need_p or (acc is not None and not acc.leave(use_idx)):
         return gG, gCp, None, None, None
     psum = gates.new_empty(11 * h)
     if N > 0 or acc is not None:
@@ -1486,7 +1494,7 @@ class _GateCell(Function):
             add0 = _c(gXp.float())
             assert add0.shape == (N, Cs[0])
         gG, gCp, gwc, gb, gln = _lstm_backward(gO, gHn, gCn, gates, Cprev, wc, ln, ctx.mesh, ctx.acc_p, ctx.use_p, dgrad,
-                                               gHn2=gHn2, add0=add0)
+                                               gHn2=gHn2, add0=add0, need_p=any(ctx.needs_input_grad[4:7]))
         gZs, gW = _cheb_backward(Zs, TZs, W, gG, ctx.mesh, K, ctx.Ks, ctx.acc_w, ctx.use_w, need, ctx.needs_input_grad[2],
                                  gTs_pre=None if planes is None else (planes, osm), w_fused=w_fused, sm=ctx.sm)
         gZa = gZs[0] if gZs is not None else None
@@ -1564,7 +1572,7 @@ class _Head(Function):
         if N > 0:
             _lib.call('qt_head_bwd', ptr(gZa), ptr(gZb), ptr(O), ld_o, ptr(ln_o), N, ptr(mesh.n_dev), h, ctx.hp, ptr(gO),
                       ptr(gcat), ptr(part), 0 if acc is None else 1)
-        if acc is not None and not acc.leave(ctx.use_idx):
+        if not ctx.needs_input_grad[1] or (acc is not None and not acc.leave(ctx.use_idx)):
             return gO, None, gcat, None, None, None
         psum = O.new_empty(2 * h)
         if N > 0 or acc is not None:
