@@ -8,6 +8,7 @@ import collections
 import collections.abc
 import datetime
 import inspect
+import math
 import os
 import time
 from abc import ABC, abstractmethod
@@ -211,6 +212,70 @@ def masked_bce(outputs, meshes, y, mask=None, weights=None, lead_weights=None, p
     pos_weight = ops.check_pos_weight(pos_weight)
     return _summed_loss(outputs, meshes, y, mesh0.B * lw.sum_lam * lw.sum_w, ops.rollout_wbce_partials, ops.step_wbce_partials, lw,
                         pos_weight)
+
+
+# -- gradient accumulation: one optimiser step from k micro-batches (beyond the reference) -------------------------------------
+def check_accumulate(accumulate):
+    """accumulate as an integer >= 1, or a ValueError that names it."""
+    if isinstance(accumulate, bool) or not isinstance(accumulate, (int, np.integer)) or accumulate < 1:
+        raise ValueError(f'accumulate: an integer >= 1 is needed (the micro-batches of one optimiser step), got {accumulate!r}')
+    return int(accumulate)
+
+
+def micro_weights(clips):
+    """The weights of the micro-batches of one accumulated step, w_i = B_i / sum_j B_j for micro-batches of B_i clips: every
+    rollout loss divides by its own clip count (masked_mse, masked_bce: B x steps x pixels, or B x the weight sums), so these
+    weights make sum_i w_i L_i the loss, and sum_i w_i grad_i the gradient, of the concatenated batch."""
+    clips = [int(b) for b in clips]
+    if not clips or min(clips) < 1:
+        raise ValueError(f'batches: every micro-batch needs at least one clip, got the clip counts {clips}')
+    total = sum(clips)
+    return [b / total for b in clips]
+
+
+def micro_multipliers(clips):
+    """micro_weights as the accumulated step forms them: ([n_i], scale) with n_i = B_i / gcd(B), an integer, and scale =
+    1 / sum_i n_i, so that w_i = n_i * scale.  The sum takes n_i * grad_i and is scaled ONCE at the end; micro-batches of one
+    clip count give n_i = 1 and scale = group_scale(k), what the graphed step computes."""
+    clips = [int(b) for b in clips]
+    micro_weights(clips)                    # (refuses an empty list and a micro-batch without clips)
+    g = math.gcd(*clips)
+    return [b // g for b in clips], 1.0 / sum(b // g for b in clips)
+
+
+def group_scale(j, world=1):
+    """What a graphed accumulated step multiplies the sum of j micro-batch gradients (of one shape, summed over `world` ranks)
+    by: 1 / (j * world).  A short last group of an epoch replays the same graphs with its own j."""
+    if j < 1 or world < 1:
+        raise ValueError(f'batches: a group of {j} micro-batch(es) over {world} rank(s)')
+    return 1.0 / (j * world)
+
+
+def checked_batches(who, batches):
+    """`batches` of an accumulated step as a list of (x, y, concat_layers or None), or a ValueError under `who` that names what
+    is wrong, on the host and before any launch: an empty sequence, an item that is no (x, y) or (x, y, concat_layers), frames
+    of differing shapes, a concat_layers for some items and not for others."""
+    if isinstance(batches, (torch.Tensor, np.ndarray)) or not isinstance(batches, collections.abc.Iterable):
+        raise ValueError(f'{who}: batches must be a sequence of (x, y) or (x, y, concat_layers), got {type(batches).__name__}')
+    items = []
+    for i, item in enumerate(batches):
+        if isinstance(item, (torch.Tensor, np.ndarray)) or not isinstance(item, collections.abc.Sequence) or len(item) not in (2, 3):
+            raise ValueError(f'{who}: batches[{i}] must be (x, y) or (x, y, concat_layers)')
+        items.append((item[0], item[1], item[2] if len(item) == 3 else None))
+    if not items:
+        raise ValueError(f'{who}: batches is empty: an optimiser step needs at least one micro-batch')
+    clip = lambda t: tuple(t.shape[-4:])           # (T, W, H, C): everything but the clip count
+    for i, (x, y, c) in enumerate(items):
+        if x.dim() not in (4, 5) or y.dim() != x.dim():
+            raise ValueError(f'{who}: batches[{i}]: x and y must both be (T, W, H, C) or both (B, T, W, H, C), got '
+                             f'{tuple(x.shape)} and {tuple(y.shape)}')
+        if clip(x) != clip(items[0][0]) or clip(y) != clip(items[0][1]):
+            raise ValueError(f'{who}: batches[{i}] has another frame shape than batches[0]: x {tuple(x.shape)}, y {tuple(y.shape)} '
+                             f'after x {tuple(items[0][0].shape)}, y {tuple(items[0][1].shape)} (only the clip count may differ)')
+        if (c is None) != (items[0][2] is None):
+            raise ValueError(f'{who}: concat_layers is given for some micro-batches and not for others (batches[{i}] '
+                             f'{"has none" if c is None else "has one"}, batches[0] {"none" if items[0][2] is None else "one"})')
+    return items
 
 
 def launch_frame(x):
@@ -831,6 +896,88 @@ class NextFramePredictorS2S(NextFramePredictor):
         check_tile_errors()          # (reads the device only when this step issued tile-resident launches; raises on a failed one)
         return loss.detach()
 
+    def _take_grads(self, acc, n):
+        """After a micro-batch's backward: acc + n * (its gradient), the gradients dropped (set to None) -- one flat vector on
+        the flat path, else a list with one entry per parameter (None: no gradient so far).  acc None: the first micro-batch.
+        The sum lives in memory of its own: what autograd hands out is never written to (two .grad fields may alias one buffer,
+        ops.unalias, and a gradient may be a view of something a later pass reads)."""
+        if self.flat is not None:
+            g = self.flat.grad_vector()
+            if g is None:
+                g = self.flat.gather_grads()
+            acc = g * n if acc is None else acc.add_(g, alpha=n)
+            self.flat.zero_grad()
+            return acc
+        grads = [p.grad for p in self.model.parameters()]
+        if acc is None:
+            acc = [None] * len(grads)
+        both = [(a, g) for a, g in zip(acc, grads) if a is not None and g is not None]
+        if both:
+            torch._foreach_add_([a for a, _ in both], [g for _, g in both], alpha=n)
+        acc = [g * n if a is None and g is not None else a for a, g in zip(acc, grads)]
+        self.optimizer.zero_grad(set_to_none=True)
+        return acc
+
+    def _accumulated_backward(self, items, clips, run_loss):
+        """zero_grad once, then per micro-batch (x, y, concat) of `items` (of `clips`[i] clips), in order: run_loss(x, y, concat)
+        -> loss, backward, sum += n_i * its gradient; at the end sum *= scale, with (n_i, scale) = micro_multipliers(clips), so
+        the weights are w_i = n_i * scale = B_i / sum B.  Micro-batches of one clip count have n_i = 1 and scale = 1 / k: the
+        arithmetic of the graphed step, bit for bit.  Leaves the result where one backward pass leaves a gradient (the flat
+        vector's views on the flat path, .grad per parameter otherwise: what _grads_ready takes) and returns sum_i w_i loss_i,
+        formed the same way, detached.  The order of the sum is the order of the micro-batches: the same inputs give the same
+        bits.  One micro-batch: its backward, untouched."""
+        self.zero_grad()
+        if len(items) == 1:
+            loss = run_loss(*items[0])
+            loss.backward()
+            return loss.detach()
+        mult, scale = micro_multipliers(clips)
+        acc = total = None
+        for item, n in zip(items, mult):
+            loss = run_loss(*item)
+            loss.backward()
+            acc = self._take_grads(acc, n)
+            total = loss.detach() * n if total is None else total.add_(loss.detach(), alpha=n)
+        if self.flat is not None:
+            self.flat.set_grad_vector(acc.mul_(scale))
+        else:
+            torch._foreach_mul_([a for a in acc if a is not None], scale)
+            for p, a in zip(self.model.parameters(), acc):
+                p.grad = a
+        return total.mul_(scale)
+
+    @on_device(lambda self, *a, **k: self.device)
+    def accumulated_step(self, batches, mask=None, high_interest_region=None, graph_structure=None, max_norm=10.0, fused=False,
+                         pos_weight=None, loss_weights=None, lead_weights=None):
+        """Gradient accumulation (beyond the reference): ONE optimiser step from the micro-batches `batches`, a non-empty sequence
+        of (x, y) or (x, y, concat_layers), each shaped as train_step takes them; the frames and T_out agree, the clip counts B_i
+        may differ.  zero_grad once -> per micro-batch, in order: forward, loss, backward, gradient += w_i * its gradient ->
+        [one all-reduce] -> clip_grad_norm_(max_norm) of the ACCUMULATED gradient -> Adam, with w_i = B_i / sum_j B_j
+        (micro_weights): the rollout loss is a mean over clips, so this is train_step on the concatenated batch up to rounding,
+        while only one micro-batch's activations are ever live.  Returns sum_i w_i loss_i, detached.  The weights are applied as
+        integer multiples and ONE scale at the end (micro_multipliers): micro-batches of one shape then give the bits of the
+        graphed step (make_graphed_step(accumulate=k)).  With one micro-batch the call is train_step, bit for bit.  The loss weights are checked and uploaded once, before the first rollout; an empty
+        `batches`, differing frame shapes and a concat_layers for some items only are refused by name before any launch."""
+        loss = self.accumulate_gradients(batches, mask, high_interest_region, graph_structure, fused, pos_weight, loss_weights,
+                                         lead_weights)
+        self._clip_and_step(self._grads_ready(self._world(), self.process_group), max_norm)
+        check_tile_errors()
+        return loss
+
+    @on_device(lambda self, *a, **k: self.device)
+    def accumulate_gradients(self, batches, mask=None, high_interest_region=None, graph_structure=None, fused=False,
+                             pos_weight=None, loss_weights=None, lead_weights=None):
+        """accumulated_step up to the optimiser: the checks, zero_grad, and every micro-batch's forward, loss and backward.  The
+        accumulated gradient is left where one backward pass leaves a gradient, for _grads_ready to take; returns the loss."""
+        items = checked_batches('accumulated_step', batches)
+        if fused and not self.binary:
+            raise ValueError('fused: fused=True selects the fused binary cross-entropy and needs a binary=True predictor')
+        clips = [1 if x.dim() == 4 else x.shape[0] for x, _, _ in items]
+        micro_weights(clips)                # (refuses a micro-batch without clips)
+        lw = self._loss_weights(items[0][0], mask, loss_weights, lead_weights, pos_weight)
+        return self._accumulated_backward(items, clips, lambda x, y, c: self.forward_loss(
+            x, y, c, mask, high_interest_region, graph_structure, fused=fused, loss_weights=lw))
+
     @on_device(lambda self, *a, **k: self.device)
     def truncated_backward(self, x, y, concat_layers, mask, high_interest_region=None, graph_structure=None,
                            truncated_backprop=45, pos_weight=None, loss_weights=None, lead_weights=None):
@@ -869,7 +1016,7 @@ class NextFramePredictorS2S(NextFramePredictor):
 
     @on_device(lambda self, *a, **k: self.device)
     def make_graphed_step(self, x, y, concat_layers=None, mask=None, high_interest_region=None, max_norm=10.0,
-                          warmup=2, graph_structure=None, force_multi=False, pos_weight=None, loss_weights=None,
+                          warmup=2, graph_structure=None, force_multi=False, accumulate=1, pos_weight=None, loss_weights=None,
                           lead_weights=None):
         """Capture one whole training step in hipGraphs and return `step(x, y, concat) -> loss`.
 
@@ -889,17 +1036,14 @@ class NextFramePredictorS2S(NextFramePredictor):
         capture alike: torch's BCELoss path indexes with a host mask and cannot be captured.  Given weights or pos_weight it runs
         the weighted binary cross-entropy (masked_bce) instead; pos_weight goes to the kernels by value, so the captured graph
         keeps the value it was captured with -- it is constant for the life of the step object.
+        accumulate=k > 1: gradient accumulation.  The returned `step(batches) -> loss` takes a sequence of 1..k items (x, y) or
+        (x, y, concat), each of the shape given here, and makes ONE optimiser step from them (_graphed_accumulation); the warm-up
+        steps are eager accumulated steps of the one batch given here.  accumulate=1 is the step described above, untouched.
         """
-        import torch.distributed as dist
-        if force_multi and not (dist.is_available() and dist.is_initialized()):
-            raise RuntimeError('force_multi=True needs an initialised torch.distributed process group')
-        multi = force_multi or (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1)
-        world = dist.get_world_size(self.process_group) if multi else 1
-        self.model.static_shapes = True
-        if not self.optimizer.defaults.get('capturable', False):
-            lr = self.optimizer.param_groups[0]['lr']
-            assert not self.optimizer.state, 'make_graphed_step must be called before the first optimizer step'
-            self.initiate_training(float(lr), self.scheduler.gamma, capturable=True)
+        if check_accumulate(accumulate) > 1:
+            return self._graphed_accumulation([(x, y, concat_layers)], accumulate, mask, high_interest_region, max_norm, warmup,
+                                              graph_structure, force_multi, pos_weight, loss_weights, lead_weights)
+        multi, world = self._capture_setup(force_multi)
         sx, sy = x.clone(), y.clone()
         sc = concat_layers.clone() if concat_layers is not None else None
         lw = self._loss_weights(x, mask, loss_weights, lead_weights, pos_weight)
@@ -989,6 +1133,136 @@ class NextFramePredictorS2S(NextFramePredictor):
             return static_loss
         step.check = lambda: check_tile_errors(always=uses_tiles)
         step.loss_weights = lw          # the graph reads the two device arrays at every replay: they live as long as the step
+        return step
+
+    def _capture_setup(self, force_multi):
+        """What a captured training step needs before anything runs: whether it takes the multi-rank structure and over how many
+        ranks -> (multi, world); static mode; an optimiser whose step counter and learning rate live on the device."""
+        import torch.distributed as dist
+        if force_multi and not (dist.is_available() and dist.is_initialized()):
+            raise RuntimeError('force_multi=True needs an initialised torch.distributed process group')
+        multi = force_multi or (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1)
+        world = dist.get_world_size(self.process_group) if multi else 1
+        self.model.static_shapes = True
+        if not self.optimizer.defaults.get('capturable', False):
+            lr = self.optimizer.param_groups[0]['lr']
+            assert not self.optimizer.state, 'make_graphed_step must be called before the first optimizer step'
+            self.initiate_training(float(lr), self.scheduler.gamma, capturable=True)
+        return multi, world
+
+    def _graphed_accumulation(self, batches, accumulate, mask=None, high_interest_region=None, max_norm=10.0, warmup=2,
+                              graph_structure=None, force_multi=False, pos_weight=None, loss_weights=None, lead_weights=None):
+        """make_graphed_step(accumulate=k > 1): `step(batches) -> loss` for groups of 1..k micro-batches of ONE shape, that of
+        the items of `batches` (1..k of them; the `warmup` steps are eager accumulated steps of exactly these, real training
+        steps).  Two graphs, in single-process runs too:
+
+            micro    forward + loss + backward of the static inputs, then acc += flat gradient, loss_acc += loss
+            update   acc *= scale[0]; clip + Adam on acc; loss = loss_acc * scale[1]; acc = 0, loss_acc = 0
+
+        and a step is: per item copy-in and micro.replay(); under torch.distributed ONE all_reduce(acc); update.replay().
+        `scale` is a device pair that step() sets to (1 / (j * world), 1 / j) for the j items it was given (group_scale), so a
+        short last group of an epoch replays the same two graphs.  The items share a shape, so their weights B_i / sum B are 1 / j.
+        acc is zero between steps: there is no state beside the optimiser's, and a checkpoint is what it was.  Only one
+        micro-batch's activations are ever live.  Stream ordering under torch.distributed as in make_graphed_step: the warm-up and
+        its collectives on the caller's stream, only the captures on the side stream."""
+        k = check_accumulate(accumulate)
+        items = checked_batches('make_graphed_step', batches)
+        shapes = lambda item: tuple(None if t is None else tuple(t.shape) for t in item)
+        if len(items) > k or any(shapes(item) != shapes(items[0]) for item in items):
+            raise ValueError(f'make_graphed_step: batches must be 1..{k} (accumulate) items of one shape, got {len(items)} of shapes '
+                             f'{[shapes(item) for item in items]}')
+        multi, world = self._capture_setup(force_multi)
+        sx, sy, sc = (t if t is None else t.clone() for t in items[0])
+        lw = self._loss_weights(sx, mask, loss_weights, lead_weights, pos_weight)
+        run_loss = lambda x, y, c: self.forward_loss(x, y, c, mask, high_interest_region, graph_structure, fused=self.binary,
+                                                     loss_weights=lw)
+        dev = sx.device
+        n = self.flat.n if self.flat is not None else sum(p.numel() for p in self.model.parameters())
+        acc, loss_acc, scale = torch.zeros(n, device=dev), torch.zeros((), device=dev), torch.ones(2, device=dev)
+
+        def warm():
+            for _ in range(warmup):
+                self.last_warmup_loss = self._accumulated_backward(items, [1] * len(items), run_loss)
+                self._clip_and_step(self._grads_ready(world, self.process_group, force=multi), max_norm)
+
+        side = torch.cuda.Stream()
+        if multi:           # (no collective ever touches a stream that captures: make_graphed_step)
+            warm()
+            torch.cuda.synchronize()
+            side.wait_stream(torch.cuda.current_stream())
+        else:
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                warm()
+            torch.cuda.current_stream().wait_stream(side)
+        micro = torch.cuda.CUDAGraph()
+        self.zero_grad()
+        with torch.cuda.graph(micro, stream=side, capture_error_mode='thread_local'):
+            loss = run_loss(sx, sy, sc)
+            loss.backward()
+            if self.flat is not None:
+                g = self.flat.grad_vector()
+                g = g if g is not None else self.flat.gather_grads()
+            else:
+                params = list(self.model.parameters())
+                g = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1) for p in params])
+            acc.add_(g)
+            loss_acc.add_(loss.detach())
+        # the optimiser reads acc from here on: the gradients become views of it
+        if self.flat is not None:
+            self.flat.set_grad_vector(acc)
+            self.flat.param.grad = acc
+            clip_params = [self.flat.param]
+        else:
+            off = 0
+            for p in params:
+                p.grad = acc[off:off + p.numel()].view_as(p)
+                off += p.numel()
+            clip_params = params
+        update = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(update, stream=side, capture_error_mode='thread_local'):
+            acc.mul_(scale[0])
+            self._clip_and_step(clip_params, max_norm)
+            static_loss = loss_acc * scale[1]
+            acc.zero_()
+            loss_acc.zero_()
+        self._graph = micro
+
+        from qtmpnn import mesh as _mesh
+        uses_tiles = bool(_mesh._TILE_USED)
+        check_tile_errors(always=uses_tiles)
+        replays, scaled_for = [0], [None]
+
+        @on_device(lambda *a, **kw: self.device)
+        def step(batches):
+            group = checked_batches('step', batches)
+            j = len(group)
+            if j > k or any(shapes(item) != shapes((sx, sy, sc)) for item in group):
+                raise ValueError(f'step: batches must be 1..{k} items of the captured shape {shapes((sx, sy, sc))}, got {j} of '
+                                 f'shapes {[shapes(item) for item in group]}')
+            for x, y, c in group:
+                sx.copy_(x)
+                sy.copy_(y)
+                if sc is not None:
+                    sc.copy_(c)
+                micro.replay()
+            if multi:
+                all_reduce_sum(acc, self.process_group)
+            if scaled_for[0] != j:
+                scale[0].fill_(group_scale(j, world))
+                scale[1].fill_(group_scale(j))
+                scaled_for[0] = j
+            update.replay()
+            before, replays[0] = replays[0], replays[0] + j
+            if uses_tiles and before // 64 != replays[0] // 64:
+                check_tile_errors(always=True)
+            return static_loss
+        step.check = lambda: check_tile_errors(always=uses_tiles)
+        step.loss_weights = lw          # the graphs read the two device arrays at every replay: they live as long as the step
+        step.accumulate, step.graphs = k, (micro, update)
+        # the graphs hold bare pointers: every buffer they read or write outside their own pools lives as long as the step (loss_acc
+        # is named nowhere else; freed, the allocator would hand its memory to the next tensor and a replay would add into that)
+        step.buffers = (sx, sy, sc, acc, loss_acc, scale)
         return step
 
     @on_device(lambda self, *a, **k: self.device)
@@ -1156,8 +1430,8 @@ class NextFramePredictorS2S(NextFramePredictor):
 
     @on_device(lambda self, *a, **k: self.device)
     def train(self, loader_train, loader_test, climatology=None, n_epochs=200, lr=0.01, lr_decay=0.95, mask=None,
-              high_interest_region=None, truncated_backprop=45, graph_structure=None, use_graph=False, pos_weight=None,
-              loss_weights=None, lead_weights=None):
+              high_interest_region=None, truncated_backprop=45, graph_structure=None, use_graph=False, accumulate=1,
+              pos_weight=None, loss_weights=None, lead_weights=None):
         """The reference's training loop (mpnnlstm.py:186-387).  use_graph=True (beyond the reference) replays the whole training
         step as a hipGraph: one graph is captured per distinct batch shape on first sight (that batch's own update runs eagerly just
         before the capture) and the learning-rate schedule keeps working because the capturable optimizer holds lr in a device
@@ -1166,10 +1440,22 @@ class NextFramePredictorS2S(NextFramePredictor):
         the whole rollout, without gradient clipping -- mpnnlstm.py:311 is commented out -- and that is what is captured).
         loss_weights (W, H) / lead_weights (T_out,) (beyond the reference): the weighted loss of masked_mse, for the training
         steps and for the test pass alike; checked and uploaded once.  On a binary=True predictor they, and pos_weight (the weight
-        of the positive class), select the weighted binary cross-entropy of masked_bce, for the test pass too."""
+        of the positive class), select the weighted binary cross-entropy of masked_bce, for the test pass too.
+        accumulate=k > 1 (beyond the reference): gradient accumulation.  Consecutive loader items are grouped k at a time and every
+        group is ONE optimiser step (accumulated_step; with use_graph=True one graphed accumulated step per batch shape,
+        _graphed_accumulation, a group of mixed shapes being stepped eagerly); the last group of an epoch may be short and is
+        stepped with what it has.  `running`, `steps` and the Loss/train scalar stay per micro-batch -- every micro-batch of a group
+        is entered with the group's loss, the clip-weighted mean of its micro-batches' -- and the scheduler steps per epoch.  The step
+        has to be ONE rollout as for use_graph (a truncation that covers all output steps: no clipping, as there): the reference's
+        chunk loop zeroes the gradients per chunk, so a real truncation leaves nothing to accumulate and is refused."""
         image_shape = loader_train.dataset.image_shape
+        accumulate = check_accumulate(accumulate)
         truncate_ = truncated_backprop not in (0, None)
         single_chunk = truncate_ and truncated_backprop >= self.output_timesteps
+        if accumulate > 1 and truncate_ and not single_chunk:
+            raise ValueError(f'accumulate: accumulate={accumulate} needs truncated_backprop=0 or >= the output steps, got '
+                             f'truncated_backprop={truncated_backprop} for {self.output_timesteps} steps (the truncated loop zeroes the '
+                             'gradients per chunk: only the last chunk of the last micro-batch would reach the optimiser)')
         if use_graph and truncate_ and not single_chunk:
             raise ValueError('use_graph=True needs truncated_backprop=0 or >= the output steps (the truncated loop re-runs the encoder '
                              'per chunk)')
@@ -1179,17 +1465,19 @@ class NextFramePredictorS2S(NextFramePredictor):
         if mask is not None:
             mshape = tuple(host_mask(mask).shape) if not hasattr(mask, 'shape') else tuple(mask.shape)
             assert mshape == tuple(image_shape), f'Mask and image shapes do not match. Got {mshape} and {image_shape}'
-        truncate = truncate_ and not (use_graph and single_chunk)
+        truncate = truncate_ and not ((use_graph or accumulate > 1) and single_chunk)
         lw = self._loss_weights(None, mask, loss_weights, lead_weights, pos_weight, shape=image_shape)
         st = time.time()
         batch_step = 0
         for epoch in range(n_epochs):
             running, steps = 0.0, 0
             # (the mode is the caller's, as in the reference: train() never calls model.train() / .eval(); ice_exp.py:181, 218 do)
-            for x, y, launch_date in loader_train:
-                x, y = self._clip(x), self._clip(y)
-                concat = self.get_climatology_array(climatology, launch_date) if climatology is not None else None
-                if truncate:
+            for group in self._micro_groups(loader_train, climatology, accumulate):
+                x, y, concat = group[0]
+                if accumulate > 1:
+                    loss = self._group_step(group, accumulate, graphed if use_graph else None, mask, high_interest_region,
+                                            graph_structure, None if single_chunk else 10.0, lw)
+                elif truncate:
                     loss = self.truncated_backward(x, y, concat, mask, high_interest_region, graph_structure,
                                                    truncated_backprop, loss_weights=lw)[-1]
                     # no gradient clipping in this branch (:311 is commented out)
@@ -1209,10 +1497,12 @@ class NextFramePredictorS2S(NextFramePredictor):
                         for part in ('encoder', 'decoder'):
                             gs = [p.grad.detach().norm() for p in getattr(self.model, part).parameters() if p.grad is not None]
                             self.writer.add_scalar(f'Grad/{part}/grad_norms', torch.stack(gs).norm().item(), batch_step)
-                self.writer.add_scalar('Loss/train', loss.item(), batch_step)
-                running += loss.item()
-                steps += 1
-                batch_step += 1
+                value = loss.item()
+                for _ in group:             # (one micro-batch, unless accumulate > 1)
+                    self.writer.add_scalar('Loss/train', value, batch_step)
+                    running += value
+                    steps += 1
+                    batch_step += 1
             running_test, steps_test = 0.0, 0
             for x, y, launch_date in loader_test:
                 x, y = self._clip(x), self._clip(y)
@@ -1237,6 +1527,37 @@ class NextFramePredictorS2S(NextFramePredictor):
         print(f'Finished in {(time.time() - st) / 60} minutes')
         self.writer.flush()
         self.loss = pd.DataFrame({'train_loss': self.train_loss, 'test_loss': self.test_loss})
+
+    def _micro_groups(self, loader, climatology, k):
+        """The loader's items as train() steps them: lists of k consecutive (x, y, concat), clipped and with their climatology
+        (the last list of a pass may be shorter)."""
+        group = []
+        for x, y, launch_date in loader:
+            x, y = self._clip(x), self._clip(y)
+            concat = self.get_climatology_array(climatology, launch_date) if climatology is not None else None
+            group.append((x, y, concat))
+            if len(group) == k:
+                yield group
+                group = []
+        if group:
+            yield group
+
+    def _group_step(self, group, accumulate, graphed, mask, high_interest_region, graph_structure, max_norm, lw):
+        """One optimiser step of train(accumulate > 1) from the micro-batches `group` -> the group's loss.  graphed: the dict of
+        the graphed accumulated steps by batch shape (None: eager).  A group of one shape is captured on first sight of the shape
+        -- the group's own update runs eagerly just before the capture -- and replayed from then on; a group of mixed shapes (a
+        short last batch of the loader among full ones) is stepped eagerly with the loss a captured step runs."""
+        if graphed is None:
+            return self.accumulated_step(group, mask, high_interest_region, graph_structure, max_norm=max_norm, loss_weights=lw)
+        keys = [tuple(None if t is None else tuple(t.shape) for t in item) for item in group]
+        if any(key != keys[0] for key in keys):
+            return self.accumulated_step(group, mask, high_interest_region, graph_structure, max_norm=max_norm, fused=self.binary,
+                                         loss_weights=lw)
+        if keys[0] not in graphed:
+            graphed[keys[0]] = self._graphed_accumulation(group, accumulate, mask, high_interest_region, max_norm, 1,
+                                                          graph_structure, loss_weights=lw)
+            return self.last_warmup_loss
+        return graphed[keys[0]](group)
 
     def _clip(self, t):
         """Loader items are (1, T, W, H, C) like the reference's batch_size=1 loaders, or (B, T, W, H, C)."""

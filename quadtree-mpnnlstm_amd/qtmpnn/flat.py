@@ -80,6 +80,14 @@ class FlatParams:
         self.param.grad = None
         self.last_grad = None
 
+    def set_grad_vector(self, g):
+        """Make `g` (n elements, fp32, the buffer's device) the flat gradient: every parameter's .grad becomes a view of it, so
+        grad_vector() returns it as after a backward pass (gradient accumulation hands its sum over this way)."""
+        assert g.dim() == 1 and g.numel() == self.n and g.dtype == self.buffer.dtype and g.device == self.buffer.device
+        for p, o, n in zip(self.params, self.offs, self.sizes):
+            p.grad = g[o:o + n].view(p.shape)
+        self.last_grad = g
+
 
 def name_table(module):
     """[(name, offset, shape)] of module.named_parameters(): the offsets of FlatParams (same order, same sizes), under the
