@@ -9,7 +9,7 @@ slot; the Mesh already holds the ChebConv normalisation, which PyG recomputes in
 import torch
 import torch.nn as nn
 
-from qtmpnn import ops
+from qtmpnn import ops, recompute
 from qtmpnn.mesh import Mesh
 
 _MULTI_CONV = True     # comparator: tests/test_gpu_ops.py sets it False (one projection + attention launch pair per convolution)
@@ -159,6 +159,7 @@ class TransformerConv(nn.Module):
         return _attention_result(self, out, want, mesh, lambda: ops.attention_weights(proj, pc.We, mesh, cout))
 
 
+@recompute.register_record
 class PackedConv:
     """Packed weights of one attention convolution for one forward pass (+ the gradient accumulators of that pass)."""
     __slots__ = ('W', 'We', 'acc', 'acc_e')
@@ -262,6 +263,7 @@ class MHTransformerConv(nn.Module):
                                  lambda: ops.attention_weights(proj, pc.We, mesh, cout, self.heads, ps=cp, hs=4 * cp))
 
 
+@recompute.register_record
 class PackedMHConv:
     """Packed weights of one MHTransformerConv for one forward pass (+ the gradient accumulators of that pass)."""
     __slots__ = ('W', 'We', 'Wt', 'bl', 'acc', 'acc_e', 'acc_l')
@@ -286,7 +288,7 @@ def _attention_flag(packed, flag):
 def _attention_result(conv, out, want, mesh, weights):
     """The return value of an attention convolution: `out`, or with the flag (out, (edge_index, alpha)).  weights() launches
     qt_attn_weights on the operands the forward just used; it also runs when a recording (Seq2Seq.record_attention) selects `conv`."""
-    rec = _RECORDER[0]
+    rec = _recorder()
     name = rec.name_of(conv) if rec is not None else None
     if not (want or name is not None):
         return out
@@ -333,6 +335,11 @@ class AttentionRecorder:
 
 
 _RECORDER = [None]      # the open AttentionRecorder, or None: then no convolution launches anything for it
+
+
+def _recorder():
+    """The open AttentionRecorder for this call, or None; a recomputed step's replay is no call of its own (it records nothing)."""
+    return None if recompute.replaying() else _RECORDER[0]
 
 
 def _need_mesh(edge_index, *node_tensors):
@@ -584,7 +591,7 @@ class GConvLSTM(nn.Module):
         """The record(P, We) hook of ops.multi_conv for layer l while a recording selects any of its eight convolutions, else None:
         the weights launch reads the layer's projections P (G, 4, N, C) in place -- one launch for all eight stacks, or one per
         selected stack."""
-        rec = _RECORDER[0]
+        rec = _recorder()
         if rec is None:
             return None
         convs = [getattr(self, f'{br}_{g}').convolutions[l] for br in ('conv_x', 'conv_h') for g in self.GATES]
@@ -612,6 +619,7 @@ class GConvLSTM(nn.Module):
         return self.step(X, _need_mesh(edge_index, X, H, C), H, C, self.pack(X.shape[1], None, (H is not None,))[0])
 
 
+@recompute.register_record
 class PackedCell:
     """Packed weights of one GConvLSTM for one forward pass (+ the gradient accumulators of that pass)."""
     __slots__ = ('W', 'K', 'Ks', 'wc', 'b', 'ln', 'acc_w', 'acc_p', 'convs', 'multi')

@@ -6,6 +6,7 @@ Same constructor / train / predict / save / load surface; the train step (mpnnls
 """
 import collections
 import collections.abc
+import contextlib
 import datetime
 import inspect
 import math
@@ -617,6 +618,36 @@ class NextFramePredictorS2S(NextFramePredictor):
                              **model_kwargs).to(device)
         self.training_initiated = False
         self.process_group = None
+
+    # -- activation recomputation (beyond the reference): the mode lives on the Seq2Seq, where the rollout is -------------------
+    @property
+    def recompute(self):
+        return self.model.recompute
+
+    def set_recompute(self, mode):
+        """How the rollouts that build an autograd graph keep their activations: None (default) -- every step's until the
+        backward -- or 'step' -- only what crosses a step boundary; every encoder and decoder step is then re-run, one at a
+        time, while the backward passes it (Seq2Seq.set_recompute has the details).  forward_loss, train_step,
+        accumulated_step / accumulate_gradients, every chunk of truncated_backward, make_graphed_step and train honour it; loss,
+        gradients and parameters are the plain step's bit for bit, for one more forward's launches.  What autograd keeps from
+        the forward shrinks to the boundaries; the peak shrinks less, because the deferred weight gradient still holds every
+        step's Chebyshev planes and gate gradients from that step's backward to the pass's last one (README has the measured
+        figures).  A CAPTURED STEP KEEPS THE MODE IT WAS CAPTURED UNDER: changing the mode afterwards
+        affects new captures only.  Passes without autograd (predict, verify and its products, attention_weights, the test pass
+        of train) do not look at it.  The mode is no training state: checkpoints neither store nor restore it.  Any other value:
+        ValueError, before anything is launched."""
+        self.model.set_recompute(mode)
+
+    @contextlib.contextmanager
+    def recomputing(self, mode):
+        """`with nfp.recomputing('step'):` -- set_recompute(mode) for the block; the previous mode is back afterwards, also after
+        an exception."""
+        previous = self.recompute
+        self.set_recompute(mode)
+        try:
+            yield self
+        finally:
+            self.model.set_recompute(previous)
 
     # -- small helpers of the reference ---------------------------------------------
     def get_n_params(self):
@@ -1711,7 +1742,8 @@ class NextFramePredictorS2S(NextFramePredictor):
         Nothing of the training state changes: for the call's duration no parameter requires a gradient (restored in a
         `finally`; with it the weight-gradient launches do not run), so every param.grad, the flat gradient vector, the
         optimiser, `static_shapes` and the mode are what they were; Python's `random` state and the attention-dropout call
-        counter are put back as well.
+        counter are put back as well.  The recompute mode (set_recompute) is ignored: the lead times' backward passes share one
+        plain graph.
 
         Refusals, by argument name and before any launch: ValueError for target (shape, dtype, NaN / infinite, negative, zero
         sum over the unmasked pixels), leads, method, steps, baseline (also when given with a method that does not use them) and
@@ -1770,8 +1802,9 @@ class NextFramePredictorS2S(NextFramePredictor):
         if flat is not None:
             params.append(flat.param)           # (a packed model: the optimiser's one tensor over the same storage)
         required = [p.requires_grad for p in params]
-        rstate, calls = random.getstate(), ops._ATTN_CALLS[0]
+        rstate, calls, mode = random.getstate(), ops._ATTN_CALLS[0], self.model.recompute
         try:
+            self.model.set_recompute(None)          # (several backward passes over one graph: the plain rollout's)
             for p in params:
                 p.requires_grad_(False)
             self.model.to(self.device)
@@ -1808,6 +1841,7 @@ class NextFramePredictorS2S(NextFramePredictor):
                 p.requires_grad_(r)
             random.setstate(rstate)
             ops._ATTN_CALLS[0] = calls
+            self.model.set_recompute(mode)
         check_tile_errors()
         Js = host[:2 * nj].view(np.float64).reshape(-1, B, L)
         return Sensitivity(host[2 * nj:].reshape(B, L, *x5.shape[1:]).copy(), req.leads, req.method, req.target, Js[0].copy(),

@@ -12,7 +12,7 @@ import torch.nn as nn
 
 from model.graph_functions import Graph, _criterion
 from model.model import CONVOLUTION_KWARGS, ChebConv, GConvLSTM, PackedConv, TransformerConv, _conv_class, _need_mesh
-from qtmpnn import ops
+from qtmpnn import ops, recompute
 from qtmpnn._lib import on_device
 from qtmpnn.flat import flat_params, param_list
 from qtmpnn.mesh import build_mesh, build_pixel_mesh, host_mask
@@ -219,6 +219,18 @@ class Decoder(_NoCachesInPickle, nn.Module):
         state_y is the output once more (same values, same storage, a second autograd alias) for the state update of the
         rollout -- the head's backward launch then sums the two gradients -- or None when there is no such alias (the caller
         uses y itself)."""
+        y, hs, cs, state_y = self.run_rows(X, mesh, concat_layers, H, C, pk, drop)
+        return self.column0(y), hs, cs, self.column0(state_y)
+
+    @staticmethod
+    def column0(rows):
+        """The prediction column of run_rows' output rows (a view: the consumers find the float4 rows as its `_base`)."""
+        return rows if rows is None or rows.shape[1] == 1 else rows[:, :1]
+
+    def run_rows(self, X, mesh, concat_layers, H, C, pk, drop=None):
+        """run() with y and state_y as the head launch wrote them: the (N, 4) float4 rows whose column 0 is the prediction, or
+        (N, 1) where a tensor op made the column (attention heads, binary=True).  What an autograd node of the rollout's own
+        (qtmpnn.recompute) hands out: whole tensors, of which run() takes the column views."""
         assert self.concat_layers_dim == 1
         state_y = None
         hs, cs, inp, Xres = [], [], X, X
@@ -252,16 +264,15 @@ class Decoder(_NoCachesInPickle, nn.Module):
             z, U = ops.cheb_poly(z, pk['fc1'], mesh, self.fc_out1.K, 1, ops.ACT_RELU, acc=pk['acc1'], post=(pk['fc2c'], pk['acc2']))
             # (the output has two consumers -- the loss, and the next step's input through the re-mesh: the second one takes the
             # alias `state_y`, so that the two gradients are summed inside the head's backward launch)
-            Y, Y2 = ops.scalar_cheb3(U, Xres, drop, mesh, alias=True)
-            y = Y[:, :1]
+            y, Y2 = ops.scalar_cheb3(U, Xres, drop, mesh, alias=True)
             if not self.binary:
-                state_y = Y2[:, :1]
+                state_y = Y2
         else:
             z = ops.cheb_poly(z, pk['fc1'], mesh, self.fc_out1.K, 1, ops.ACT_RELU, acc=pk['acc1'])
             # the head GEMM writes float4 rows; column 0 is the prediction (the rest is tanh(0) + X[:, 0], never read as data)
-            y = ops.cheb_poly(z, pk['fc2'], mesh, self.fc_out2.K, 1, ops.ACT_TANH_RES, res=Xres, drop=drop, acc=pk['acc2'])[:, :1]
+            y = ops.cheb_poly(z, pk['fc2'], mesh, self.fc_out2.K, 1, ops.ACT_TANH_RES, res=Xres, drop=drop, acc=pk['acc2'])
         if self.binary:
-            y = torch.sigmoid(y)
+            y = torch.sigmoid(y[:, :1])
         return y, hs, cs, state_y
 
     def forward(self, X, edge_index, edge_weight, concat_layers, H, C, packed=None):
@@ -307,6 +318,29 @@ class Seq2Seq(_NoCachesInPickle, nn.Module):
         self.thresh, self.transform_func, self.graph, self.device = thresh, transform_func, None, device
         self.max_grid_size = 64                      # image_to_graph default, never overridden (graph_functions.py:590)
         self.static_shapes = False                   # True: worst-case capacities + device-side node counts (hipGraph)
+        self._recompute = None                       # None | 'step' (set_recompute): how a rollout with autograd keeps its steps
+
+    # -- activation recomputation ----------------------------------------------------------
+    @property
+    def recompute(self):
+        return self.__dict__.get('_recompute')
+
+    def set_recompute(self, mode):
+        """None (default): a rollout with autograd keeps every step's activations until the backward.  'step': every encoder and
+        decoder step is one autograd node (qtmpnn.recompute.segment) that keeps only what crosses the step's boundary -- its
+        input rows, hidden / cell per layer, the pooled concat column, its slice of the decoder's dropout masks, the packed
+        weights of the pass and its output -- and re-runs the step on the first pass's Mesh when the backward reaches it.  The
+        mesh builds, the state transfer between meshes, teacher forcing and the loss stay outside the nodes and run once.  Loss,
+        gradients and the attention-dropout masks of later steps are the plain rollout's, bit for bit.  Without autograd
+        (predict, verify, attention_weights) the mode does nothing.  remesh_input=True models have no such nodes: with 'step' a
+        rollout with autograd is refused when it starts."""
+        self._recompute = recompute.check_mode(mode)
+
+    def _step(self, run, *args):
+        """run(*args) -- Encoder.run / Decoder.run_rows -- as the mode keeps it."""
+        if self.recompute == 'step':
+            return recompute.segment(run, *args)
+        return run(*args)
 
     # -- attention weights -----------------------------------------------------------------
     @contextlib.contextmanager
@@ -378,6 +412,9 @@ class Seq2Seq(_NoCachesInPickle, nn.Module):
     @on_device(lambda self, *a, **k: self.encoder.norm_h.weight)
     def process_inputs(self, x, mask=None, high_interest_region=None, graph_structure=None):
         """model/seq2seq.py:254-336.  x: (T_in, W, H, C) or (B, T_in, W, H, C)."""
+        if self.remesh_input and self.recompute == 'step' and torch.is_grad_enabled():
+            raise NotImplementedError("set_recompute('step') does not cover remesh_input=True models (their encoder re-meshes between "
+                                      "its steps): set_recompute(None) for this rollout")
         self._single = x.dim() == 4
         self._deferred = None
         if self._single:
@@ -435,8 +472,8 @@ class Seq2Seq(_NoCachesInPickle, nn.Module):
         enc_pack, self._dec_pack = self._packs(c + 3 + fpad)     # (the decoder pack waits for unroll_output)
         hidden = cell = None
         for t in range(self.input_timesteps):
-            hidden, cell = self.encoder.run(feats_in[t], mesh, None if hidden is None else hidden[-1],
-                                            None if cell is None else cell[-1], enc_pack)
+            hidden, cell = self._step(self.encoder.run, feats_in[t], mesh, None if hidden is None else hidden[-1],
+                                      None if cell is None else cell[-1], enc_pack)
         self.graph.hidden, self.graph.cell = hidden, cell            # per-layer lists while the rollout runs
         last = feats[-1]                                                                # x[-1, :, [0,-3,-2,-1]] (:336)
         self.graph.pyg.x = last if (c == 1 and last.is_contiguous()) else torch.cat([last[:, :1], last[:, -3:]], dim=1)
@@ -503,8 +540,9 @@ class Seq2Seq(_NoCachesInPickle, nn.Module):
                 cl = concat_layers[:, t].reshape(mesh.B, 1, mesh.P, 1)
                 concat_t = ops.pool_image(cl, mesh, True)[0]
                 g.concat_layers = concat_t
-            output, hidden, cell, state_y = self.decoder.run(g.pyg.x, mesh, concat_t, g.hidden, g.cell, dec_pack,
-                                                             None if drops is None else drops[si, :mesh.N])
+            output, hidden, cell, state_y = self._step(self.decoder.run_rows, g.pyg.x, mesh, concat_t, g.hidden, g.cell, dec_pack,
+                                                       None if drops is None else drops[si, :mesh.N])
+            output, state_y = self.decoder.column0(output), self.decoder.column0(state_y)
             outputs.append(output)
             if state_y is not None:
                 output = state_y                                                           # (the alias for the state update)

@@ -80,14 +80,21 @@ class GradAcc:
     per-block partial sums into a shared slab buffer (fixed order: each block owns its slab) and only the FIRST
     forward use -- the last one to run in the backward pass, because the recurrent state chains the uses --
     reduces the slabs and hands the gradient to autograd.
+
+    Under qtmpnn.recompute a use is counted (`uses`) by its segment's first pass, which runs without autograd, and never by the
+    replay: while `cursor` is set, enter() hands out the first pass's indices again and leaves `uses` alone.
     """
-    __slots__ = ('uses', 'done', 'part', 'wt', 'pending', 'wslab', 'pslab')
+    __slots__ = ('uses', 'done', 'part', 'wt', 'pending', 'wslab', 'pslab', 'cursor')
 
     def __init__(self):
         self.uses, self.done, self.part, self.wt, self.pending, self.wslab = 0, 0, None, {}, [], None
         self.pslab = {}        # segment -> (blocks, G, cin + 4, co) slabs of the one-pass projection backward (qt_proj_bwd)
+        self.cursor = None     # set while a recomputed segment is replayed (qtmpnn.recompute): the index its next use takes
 
     def enter(self):
+        if self.cursor is not None:     # a replay: the segment's first pass counted this use, the replay takes the same index
+            self.cursor += 1
+            return self.cursor - 1
         self.uses += 1
         return self.uses - 1
 
@@ -1504,6 +1511,9 @@ class _GateCell(Function):
         return gZa, gZb, gW, gCp, gwc, gb, gln, None, None, None, None, None, None, None
 
 
+_SEGMENT_PASS = [0]     # > 0 while qtmpnn.recompute runs a segment's first pass (without autograd)
+
+
 def _forward_only(*ts):
     """True when no backward can follow: autograd is off, or none of the tensors needs a gradient.  lstm_cell then takes the
     forward-only launch (qt_lstm_infer), which skips the store of the (N, 4h) gate activations.  (The gate GEMM with the cell
@@ -1534,6 +1544,8 @@ def gate_cell(X, H, W, Cprev, wc, b, ln, mesh, K, Ks, acc_w=None, acc_p=None, al
 
 def lstm_cell(G, Cprev, wc, b, ln, mesh, acc=None):
     if G.is_cuda and _forward_only(G, Cprev, wc, b, ln):
+        if acc is not None and _SEGMENT_PASS[0]:
+            acc.enter()         # (the first pass of a recomputed segment counts the use its replay takes below; no other pass does)
         return _lstm_cell_infer(G, Cprev, wc, b, ln, mesh)
     return _LstmCell.apply(G, Cprev, wc, b, ln, mesh, acc)
 
