@@ -22,7 +22,7 @@ from torch.optim.lr_scheduler import StepLR
 from model.graph_functions import image_to_graph, unflatten, plot_contours
 from model.seq2seq import Seq2Seq
 from model.utils import add_positional_encoding, get_n_params, int_to_datetime
-from qtmpnn import ops
+from qtmpnn import mesh as _mesh, ops
 from qtmpnn.dist import all_reduce_sum, allreduce_gradients
 from qtmpnn.flat import flat_params, name_table
 from qtmpnn._lib import on_device
@@ -277,6 +277,67 @@ def checked_batches(who, batches):
             raise ValueError(f'{who}: concat_layers is given for some micro-batches and not for others (batches[{i}] '
                              f'{"has none" if c is None else "has one"}, batches[0] {"none" if items[0][2] is None else "one"})')
     return items
+
+
+# -- the capture recipe: what make_graphed_step, _graphed_accumulation and _graphed_inference share -----------------------------
+def batch_shapes(item):
+    """The shapes of a batch (x, y, concat), None for a member that is None: what "the same batch shape" means to every cache of
+    captured graphs and to a captured step that checks what it is given."""
+    return tuple(None if t is None else tuple(t.shape) for t in item)
+
+
+class StaticBatch:
+    """Clones of a batch (x, y, concat), any of which may be None, that captured graphs read their inputs from.  The graphs hold
+    bare pointers: every buffer they read or write outside their own pools -- these clones, the loss weights, an accumulator -- has
+    to live as long as whatever replays them, so a step object keeps them (its closure, step.loss_weights, step.buffers; a buffer
+    named nowhere else is freed, the allocator hands its memory to the next tensor and a replay reads or adds into that)."""
+
+    def __init__(self, x, y, concat):
+        self.tensors = tuple(t if t is None else t.clone() for t in (x, y, concat))
+        self.shapes = batch_shapes(self.tensors)
+
+    def load(self, x, y, concat_layers=None):
+        """Copy a batch of the captured shapes in, x first; what has no clone here is not read."""
+        for static, t in zip(self.tensors, (x, y, concat_layers)):
+            if static is not None:
+                static.copy_(t)
+
+
+def warm_then_sync(side, multi, fn):
+    """Run the eager warm-up fn() and order it against the side stream that captures next -> fn()'s result."""
+    if multi:
+        # The warm-up steps all-reduce, and torch issues a synchronous collective -- and records its completion event -- on the
+        # CURRENT stream.  The process group's watchdog thread polls that event (hipEventQuery) until the work is reaped, and
+        # HIP refuses the query while the event's stream is capturing (hipErrorCapturedEvent: the watchdog dies and takes the
+        # process with it; seen in round 5 as soon as RCCL was executed at all).  So under torch.distributed the warm-up runs
+        # on the caller's stream and only the capture on the side stream: no collective ever touches a stream that captures.
+        result = fn()
+        torch.cuda.synchronize()
+        side.wait_stream(torch.cuda.current_stream())
+    else:
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            result = fn()
+        torch.cuda.current_stream().wait_stream(side)
+    return result
+
+
+class TileWatch:
+    """The captured launches report failures (a tile-resident launch that gave up waiting) only through the device's persistent
+    error word: it is read when this is made, after the capture, and then whenever advance() takes the replay count across a
+    multiple of 64 -- one 4-byte copy, only for graphs that contain such launches at all."""
+
+    def __init__(self):
+        self.uses_tiles, self.replays = bool(_mesh._TILE_USED), 0
+        self.check()
+
+    def check(self):
+        check_tile_errors(always=self.uses_tiles)
+
+    def advance(self, j=1):
+        before, self.replays = self.replays, self.replays + j
+        if self.uses_tiles and before // 64 != self.replays // 64:
+            check_tile_errors(always=True)
 
 
 def launch_frame(x):
@@ -843,14 +904,17 @@ class NextFramePredictorS2S(NextFramePredictor):
         """loss_weights (W, H) / lead_weights (T_out,): the weighted loss of masked_mse (checked before the rollout starts).
         fused=True (binary predictors only): the fused binary cross-entropy of masked_mse.  On a binary=True predictor any of
         loss_weights / lead_weights / pos_weight (the positive-class weight) selects masked_bce, which is always fused."""
-        if fused and not self.binary:
-            raise ValueError('fused: fused=True selects the fused binary cross-entropy and needs a binary=True predictor')
+        self._check_fused(fused)
         lw = self._loss_weights(x, mask, loss_weights, lead_weights, pos_weight)
         y_hat, meshes = self.model(x, y, concat_layers, teacher_forcing_ratio=0, mask=mask,
                                    high_interest_region=high_interest_region, graph_structure=graph_structure)
         if lw is None:
             return masked_mse(y_hat, meshes, y, mask, self.binary, fused=fused)
         return self._weighted_loss(y_hat, meshes, y, mask, lw)
+
+    def _check_fused(self, fused):
+        if fused and not self.binary:
+            raise ValueError('fused: fused=True selects the fused binary cross-entropy and needs a binary=True predictor')
 
     def _loss_weights(self, x, mask, loss_weights, lead_weights, pos_weight=None, shape=None):
         """The checked, uploaded weights of this predictor's loss for batches shaped like x, or of frames of `shape` (None:
@@ -887,14 +951,32 @@ class NextFramePredictorS2S(NextFramePredictor):
             return params
         if not self.flat.intact(self.model):
             raise RuntimeError('the model parameters were moved or replaced after initiate_training(): call it again')
-        g = self.flat.grad_vector()
-        if g is None:                          # gradients that did not come from the model-wide packing gather: by copy
-            g = self.flat.gather_grads()
+        g = self.flat.gradient()               # (gradients that did not come from the model-wide packing gather: by copy)
         if world > 1 or force:
             all_reduce_sum(g, group)
             g.mul_(1.0 / world)
         self.flat.param.grad = g
         return [self.flat.param]
+
+    def _grad_flat(self):
+        """After backward: the gradient as ONE vector in parameters() order -- the packing gather's own output on the flat path
+        (no copy), a concatenation otherwise (zeros for a parameter without a gradient)."""
+        if self.flat is not None:
+            return self.flat.gradient()
+        return torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1) for p in self.model.parameters()])
+
+    def _set_grad_flat(self, g):
+        """Make the vector g (as _grad_flat's) the gradient the optimiser reads: every .grad becomes a view of it, no unpack
+        copies.  Returns the tensors clip_grad_norm_ has to see."""
+        if self.flat is not None:
+            self.flat.set_grad_vector(g)
+            self.flat.param.grad = g
+            return [self.flat.param]
+        params, off = list(self.model.parameters()), 0
+        for p in params:
+            p.grad = g[off:off + p.numel()].view_as(p)
+            off += p.numel()
+        return params
 
     def _clip_and_step(self, clip_params, max_norm):
         """clip_grad_norm_(max_norm) + optimizer.step() (mpnnlstm.py:251, 257); max_norm None: no clipping (:311)."""
@@ -933,9 +1015,7 @@ class NextFramePredictorS2S(NextFramePredictor):
         The sum lives in memory of its own: what autograd hands out is never written to (two .grad fields may alias one buffer,
         ops.unalias, and a gradient may be a view of something a later pass reads)."""
         if self.flat is not None:
-            g = self.flat.grad_vector()
-            if g is None:
-                g = self.flat.gather_grads()
+            g = self._grad_flat()
             acc = g * n if acc is None else acc.add_(g, alpha=n)
             self.flat.zero_grad()
             return acc
@@ -987,8 +1067,9 @@ class NextFramePredictorS2S(NextFramePredictor):
         (micro_weights): the rollout loss is a mean over clips, so this is train_step on the concatenated batch up to rounding,
         while only one micro-batch's activations are ever live.  Returns sum_i w_i loss_i, detached.  The weights are applied as
         integer multiples and ONE scale at the end (micro_multipliers): micro-batches of one shape then give the bits of the
-        graphed step (make_graphed_step(accumulate=k)).  With one micro-batch the call is train_step, bit for bit.  The loss weights are checked and uploaded once, before the first rollout; an empty
-        `batches`, differing frame shapes and a concat_layers for some items only are refused by name before any launch."""
+        graphed step (make_graphed_step(accumulate=k)).  With one micro-batch the call is train_step, bit for bit.  The loss weights
+        are checked and uploaded once, before the first rollout; an empty `batches`, differing frame shapes and a concat_layers for
+        some items only are refused by name before any launch."""
         loss = self.accumulate_gradients(batches, mask, high_interest_region, graph_structure, fused, pos_weight, loss_weights,
                                          lead_weights)
         self._clip_and_step(self._grads_ready(self._world(), self.process_group), max_norm)
@@ -1001,8 +1082,7 @@ class NextFramePredictorS2S(NextFramePredictor):
         """accumulated_step up to the optimiser: the checks, zero_grad, and every micro-batch's forward, loss and backward.  The
         accumulated gradient is left where one backward pass leaves a gradient, for _grads_ready to take; returns the loss."""
         items = checked_batches('accumulated_step', batches)
-        if fused and not self.binary:
-            raise ValueError('fused: fused=True selects the fused binary cross-entropy and needs a binary=True predictor')
+        self._check_fused(fused)
         clips = [1 if x.dim() == 4 else x.shape[0] for x, _, _ in items]
         micro_weights(clips)                # (refuses a micro-batch without clips)
         lw = self._loss_weights(items[0][0], mask, loss_weights, lead_weights, pos_weight)
@@ -1075,95 +1155,51 @@ class NextFramePredictorS2S(NextFramePredictor):
             return self._graphed_accumulation([(x, y, concat_layers)], accumulate, mask, high_interest_region, max_norm, warmup,
                                               graph_structure, force_multi, pos_weight, loss_weights, lead_weights)
         multi, world = self._capture_setup(force_multi)
-        sx, sy = x.clone(), y.clone()
-        sc = concat_layers.clone() if concat_layers is not None else None
+        batch = StaticBatch(x, y, concat_layers)
         lw = self._loss_weights(x, mask, loss_weights, lead_weights, pos_weight)
 
         def fwd_bwd():
             self.zero_grad()
-            loss = self.forward_loss(sx, sy, sc, mask, high_interest_region, graph_structure, fused=self.binary, loss_weights=lw)
+            loss = self.forward_loss(*batch.tensors, mask, high_interest_region, graph_structure, fused=self.binary,
+                                     loss_weights=lw)
             loss.backward()
             return loss.detach()
 
-        def update(clip_params):
-            self._clip_and_step(clip_params, max_norm)
-
-        side = torch.cuda.Stream()
-        if multi:
-            # The warm-up steps all-reduce, and torch issues a synchronous collective -- and records its completion event -- on the
-            # CURRENT stream.  The process group's watchdog thread polls that event (hipEventQuery) until the work is reaped, and
-            # HIP refuses the query while the event's stream is capturing (hipErrorCapturedEvent: the watchdog dies and takes the
-            # process with it; seen in round 5 as soon as RCCL was executed at all).  So under torch.distributed the warm-up runs
-            # on the caller's stream and only the capture on the side stream: no collective ever touches a stream that captures.
+        def warm():
             for _ in range(warmup):
                 self.last_warmup_loss = fwd_bwd()        # (a real training step on this batch)
-                update(self._grads_ready(world, self.process_group, force=multi))
-            torch.cuda.synchronize()
-            side.wait_stream(torch.cuda.current_stream())
-        else:
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for _ in range(warmup):
-                    self.last_warmup_loss = fwd_bwd()        # (a real training step on this batch)
-                    update(self._grads_ready(world, self.process_group, force=multi))
-            torch.cuda.current_stream().wait_stream(side)
-        graph = torch.cuda.CUDAGraph()
+                self._clip_and_step(self._grads_ready(world, self.process_group, force=multi), max_norm)
+
+        side = torch.cuda.Stream()
+        warm_then_sync(side, multi, warm)
+        graph, graph2 = torch.cuda.CUDAGraph(), None
         self.zero_grad()
         # thread_local: other threads (the RCCL watchdog under torch.distributed) may issue HIP calls meanwhile
         with torch.cuda.graph(graph, stream=side, capture_error_mode='thread_local'):
             static_loss = fwd_bwd()
-            if multi:
-                # the graph ends with the gradients in ONE flat buffer: the packing gather's own output on the flat path
-                # (no copy), a concatenation otherwise
-                if self.flat is not None:
-                    flat = self.flat.grad_vector()
-                    flat = flat if flat is not None else self.flat.gather_grads()
-                else:
-                    params = list(self.model.parameters())
-                    flat = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1) for p in params])
+            if multi:                   # the graph ends with the gradients in ONE flat buffer
+                flat = self._grad_flat()
             else:
-                update(self._grads_ready())
+                self._clip_and_step(self._grads_ready(), max_norm)
         self._graph = graph
-        graph2 = None
         if multi:
-            if self.flat is not None:
-                self.flat.param.grad = flat
-                clip_params = [self.flat.param]
-            else:
-                off = 0
-                for p in params:                          # gradients become views of the flat buffer: no unpack copies
-                    p.grad = flat[off:off + p.numel()].view_as(p)
-                    off += p.numel()
-                clip_params = params
+            clip_params = self._set_grad_flat(flat)
             graph2 = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph2, stream=side, capture_error_mode='thread_local'):
                 flat.mul_(1.0 / world)
-                update(clip_params)
-
-        # the captured launches report failures (a tile-resident launch that gave up waiting) only through the device's persistent
-        # error word: it is read here after the capture and then every 64 replays -- one 4-byte copy, only for graphs that
-        # contain such launches at all
-        from qtmpnn import mesh as _mesh
-        uses_tiles = bool(_mesh._TILE_USED)
-        check_tile_errors(always=uses_tiles)
-        replays = [0]
+                self._clip_and_step(clip_params, max_norm)
+        watch = TileWatch()
 
         @on_device(lambda *a, **k: self.device)
         def step(x, y, concat_layers=None):
-            sx.copy_(x)
-            sy.copy_(y)
-            if sc is not None:
-                sc.copy_(concat_layers)
+            batch.load(x, y, concat_layers)
             graph.replay()
             if multi:
                 all_reduce_sum(flat, self.process_group)
                 graph2.replay()
-            replays[0] += 1
-            if uses_tiles and replays[0] % 64 == 0:
-                check_tile_errors(always=True)
+            watch.advance()
             return static_loss
-        step.check = lambda: check_tile_errors(always=uses_tiles)
-        step.loss_weights = lw          # the graph reads the two device arrays at every replay: they live as long as the step
+        step.check, step.loss_weights = watch.check, lw
         return step
 
     def _capture_setup(self, force_multi):
@@ -1194,20 +1230,19 @@ class NextFramePredictorS2S(NextFramePredictor):
         `scale` is a device pair that step() sets to (1 / (j * world), 1 / j) for the j items it was given (group_scale), so a
         short last group of an epoch replays the same two graphs.  The items share a shape, so their weights B_i / sum B are 1 / j.
         acc is zero between steps: there is no state beside the optimiser's, and a checkpoint is what it was.  Only one
-        micro-batch's activations are ever live.  Stream ordering under torch.distributed as in make_graphed_step: the warm-up and
-        its collectives on the caller's stream, only the captures on the side stream."""
+        micro-batch's activations are ever live.  Stream ordering under torch.distributed as in make_graphed_step
+        (warm_then_sync): the warm-up and its collectives on the caller's stream, only the captures on the side stream."""
         k = check_accumulate(accumulate)
         items = checked_batches('make_graphed_step', batches)
-        shapes = lambda item: tuple(None if t is None else tuple(t.shape) for t in item)
-        if len(items) > k or any(shapes(item) != shapes(items[0]) for item in items):
+        if len(items) > k or any(batch_shapes(item) != batch_shapes(items[0]) for item in items):
             raise ValueError(f'make_graphed_step: batches must be 1..{k} (accumulate) items of one shape, got {len(items)} of shapes '
-                             f'{[shapes(item) for item in items]}')
+                             f'{[batch_shapes(item) for item in items]}')
         multi, world = self._capture_setup(force_multi)
-        sx, sy, sc = (t if t is None else t.clone() for t in items[0])
-        lw = self._loss_weights(sx, mask, loss_weights, lead_weights, pos_weight)
+        batch = StaticBatch(*items[0])
+        lw = self._loss_weights(batch.tensors[0], mask, loss_weights, lead_weights, pos_weight)
         run_loss = lambda x, y, c: self.forward_loss(x, y, c, mask, high_interest_region, graph_structure, fused=self.binary,
                                                      loss_weights=lw)
-        dev = sx.device
+        dev = batch.tensors[0].device
         n = self.flat.n if self.flat is not None else sum(p.numel() for p in self.model.parameters())
         acc, loss_acc, scale = torch.zeros(n, device=dev), torch.zeros((), device=dev), torch.ones(2, device=dev)
 
@@ -1217,39 +1252,15 @@ class NextFramePredictorS2S(NextFramePredictor):
                 self._clip_and_step(self._grads_ready(world, self.process_group, force=multi), max_norm)
 
         side = torch.cuda.Stream()
-        if multi:           # (no collective ever touches a stream that captures: make_graphed_step)
-            warm()
-            torch.cuda.synchronize()
-            side.wait_stream(torch.cuda.current_stream())
-        else:
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                warm()
-            torch.cuda.current_stream().wait_stream(side)
+        warm_then_sync(side, multi, warm)
         micro = torch.cuda.CUDAGraph()
         self.zero_grad()
         with torch.cuda.graph(micro, stream=side, capture_error_mode='thread_local'):
-            loss = run_loss(sx, sy, sc)
+            loss = run_loss(*batch.tensors)
             loss.backward()
-            if self.flat is not None:
-                g = self.flat.grad_vector()
-                g = g if g is not None else self.flat.gather_grads()
-            else:
-                params = list(self.model.parameters())
-                g = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1) for p in params])
-            acc.add_(g)
+            acc.add_(self._grad_flat())
             loss_acc.add_(loss.detach())
-        # the optimiser reads acc from here on: the gradients become views of it
-        if self.flat is not None:
-            self.flat.set_grad_vector(acc)
-            self.flat.param.grad = acc
-            clip_params = [self.flat.param]
-        else:
-            off = 0
-            for p in params:
-                p.grad = acc[off:off + p.numel()].view_as(p)
-                off += p.numel()
-            clip_params = params
+        clip_params = self._set_grad_flat(acc)          # the optimiser reads acc from here on
         update = torch.cuda.CUDAGraph()
         with torch.cuda.graph(update, stream=side, capture_error_mode='thread_local'):
             acc.mul_(scale[0])
@@ -1258,24 +1269,17 @@ class NextFramePredictorS2S(NextFramePredictor):
             acc.zero_()
             loss_acc.zero_()
         self._graph = micro
-
-        from qtmpnn import mesh as _mesh
-        uses_tiles = bool(_mesh._TILE_USED)
-        check_tile_errors(always=uses_tiles)
-        replays, scaled_for = [0], [None]
+        watch, scaled_for = TileWatch(), [None]
 
         @on_device(lambda *a, **kw: self.device)
         def step(batches):
             group = checked_batches('step', batches)
             j = len(group)
-            if j > k or any(shapes(item) != shapes((sx, sy, sc)) for item in group):
-                raise ValueError(f'step: batches must be 1..{k} items of the captured shape {shapes((sx, sy, sc))}, got {j} of '
-                                 f'shapes {[shapes(item) for item in group]}')
-            for x, y, c in group:
-                sx.copy_(x)
-                sy.copy_(y)
-                if sc is not None:
-                    sc.copy_(c)
+            if j > k or any(batch_shapes(item) != batch.shapes for item in group):
+                raise ValueError(f'step: batches must be 1..{k} items of the captured shape {batch.shapes}, got {j} of '
+                                 f'shapes {[batch_shapes(item) for item in group]}')
+            for item in group:
+                batch.load(*item)
                 micro.replay()
             if multi:
                 all_reduce_sum(acc, self.process_group)
@@ -1284,16 +1288,10 @@ class NextFramePredictorS2S(NextFramePredictor):
                 scale[1].fill_(group_scale(j))
                 scaled_for[0] = j
             update.replay()
-            before, replays[0] = replays[0], replays[0] + j
-            if uses_tiles and before // 64 != replays[0] // 64:
-                check_tile_errors(always=True)
+            watch.advance(j)
             return static_loss
-        step.check = lambda: check_tile_errors(always=uses_tiles)
-        step.loss_weights = lw          # the graphs read the two device arrays at every replay: they live as long as the step
-        step.accumulate, step.graphs = k, (micro, update)
-        # the graphs hold bare pointers: every buffer they read or write outside their own pools lives as long as the step (loss_acc
-        # is named nowhere else; freed, the allocator would hand its memory to the next tensor and a replay would add into that)
-        step.buffers = (sx, sy, sc, acc, loss_acc, scale)
+        step.check, step.loss_weights, step.accumulate, step.graphs = watch.check, lw, k, (micro, update)
+        step.buffers = (*batch.tensors, acc, loss_acc, scale)       # (loss_acc is named nowhere else: StaticBatch)
         return step
 
     @on_device(lambda self, *a, **k: self.device)
@@ -1315,22 +1313,16 @@ class NextFramePredictorS2S(NextFramePredictor):
         several products of the one rollout) on static copies of the batch; y is None
         for a product that does not read it, and replay's arguments are then (x, concat), else (x, y, concat)."""
         self.model.static_shapes = True
-        sx, sy, sc = (t if t is None else t.clone() for t in (x, y, concat_layers))
+        batch = StaticBatch(x, y, concat_layers)
+        sx, sy, sc = batch.tensors
 
         def body():
             with torch.no_grad():
                 y_hat, meshes = self.model(sx, concat_layers=sc, teacher_forcing_ratio=0, **fwd)
                 return reduce(y_hat, meshes, sx, sy, sc)
-
-        def load(x, y, concat_layers):
-            sx.copy_(x)
-            if sy is not None:
-                sy.copy_(y)
-            if sc is not None:
-                sc.copy_(concat_layers)
         if y is None:
-            return self._graphed_inference(body, lambda x, concat_layers=None: load(x, None, concat_layers))
-        return self._graphed_inference(body, lambda x, y, concat_layers=None: load(x, y, concat_layers))
+            return self._graphed_inference(body, lambda x, concat_layers=None: batch.load(x, None, concat_layers))
+        return self._graphed_inference(body, batch.load)
 
     def _graphed_inference(self, body, load):
         """Warm-up, capture and replay of a no-grad inference body (_graphed_product).  body() reads the
@@ -1340,13 +1332,13 @@ class NextFramePredictorS2S(NextFramePredictor):
         element by element."""
         import random
         T_out = self.output_timesteps
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        calls0 = ops._ATTN_CALLS[0]
-        with torch.cuda.stream(side):
+        def warm_body():
             warm = body()
-            warm = tuple(t.clone() for t in warm) if isinstance(warm, tuple) else warm.clone()
-        torch.cuda.current_stream().wait_stream(side)
+            return tuple(t.clone() for t in warm) if isinstance(warm, tuple) else warm.clone()
+
+        side = torch.cuda.Stream()
+        calls0 = ops._ATTN_CALLS[0]
+        warm = warm_then_sync(side, False, warm_body)
         calls1 = ops._ATTN_CALLS[0]
         # the capture records launches without running them: whatever host state it advances is put back, and every replay
         # advances it as an eager rollout would
@@ -1356,9 +1348,7 @@ class NextFramePredictorS2S(NextFramePredictor):
             result = body()
         random.setstate(rstate)
         ops._ATTN_CALLS[0] = calls1
-        from qtmpnn import mesh as _mesh
-        uses_tiles = bool(_mesh._TILE_USED)
-        check_tile_errors(always=uses_tiles)
+        TileWatch()             # (the check after the capture only: the replays of an inference capture are not counted)
 
         @on_device(lambda *a, **k: self.device)
         def replay(*a, **k):
@@ -1514,14 +1504,9 @@ class NextFramePredictorS2S(NextFramePredictor):
                     # no gradient clipping in this branch (:311 is commented out)
                     self._clip_and_step(self._grads_ready(self._world(), self.process_group), None)
                 elif use_graph:
-                    key = (tuple(x.shape), tuple(y.shape), None if concat is None else tuple(concat.shape))
-                    if key not in graphed:      # first sight of this batch shape: its update runs eagerly, then the capture
-                        graphed[key] = self.make_graphed_step(x, y, concat, mask=mask, high_interest_region=high_interest_region,
-                                                              warmup=1, graph_structure=graph_structure,
-                                                              max_norm=None if single_chunk else 10.0, loss_weights=lw)
-                        loss = self.last_warmup_loss
-                    else:
-                        loss = graphed[key](x, y, concat)
+                    loss = self._first_sight(graphed, group[0], lambda: self.make_graphed_step(
+                        x, y, concat, mask=mask, high_interest_region=high_interest_region, warmup=1, graph_structure=graph_structure,
+                        max_norm=None if single_chunk else 10.0, loss_weights=lw), group[0])
                 else:
                     loss = self.train_step(x, y, concat, mask, high_interest_region, graph_structure, loss_weights=lw)
                     if self.debug:      # gradient norms of the two halves of the model (:259-276; clipped like the reference's)
@@ -1580,15 +1565,21 @@ class NextFramePredictorS2S(NextFramePredictor):
         short last batch of the loader among full ones) is stepped eagerly with the loss a captured step runs."""
         if graphed is None:
             return self.accumulated_step(group, mask, high_interest_region, graph_structure, max_norm=max_norm, loss_weights=lw)
-        keys = [tuple(None if t is None else tuple(t.shape) for t in item) for item in group]
-        if any(key != keys[0] for key in keys):
+        if any(batch_shapes(item) != batch_shapes(group[0]) for item in group):
             return self.accumulated_step(group, mask, high_interest_region, graph_structure, max_norm=max_norm, fused=self.binary,
                                          loss_weights=lw)
-        if keys[0] not in graphed:
-            graphed[keys[0]] = self._graphed_accumulation(group, accumulate, mask, high_interest_region, max_norm, 1,
-                                                          graph_structure, loss_weights=lw)
+        return self._first_sight(graphed, group[0], lambda: self._graphed_accumulation(
+            group, accumulate, mask, high_interest_region, max_norm, 1, graph_structure, loss_weights=lw), (group,))
+
+    def _first_sight(self, graphed, item, capture, args):
+        """train(use_graph=True): the step captured for batches shaped like `item` (batch_shapes), run on *args -> loss.  A shape
+        is captured on first sight by capture(), whose one warm-up step is that batch's own update, run eagerly just before the
+        capture, and whose loss is returned; from then on the shape is replayed."""
+        key = batch_shapes(item)
+        if key not in graphed:
+            graphed[key] = capture()
             return self.last_warmup_loss
-        return graphed[keys[0]](group)
+        return graphed[key](*args)
 
     def _clip(self, t):
         """Loader items are (1, T, W, H, C) like the reference's batch_size=1 loaders, or (B, T, W, H, C)."""
@@ -1632,7 +1623,7 @@ class NextFramePredictorS2S(NextFramePredictor):
                     begin(x)
                 batch = (x, concat) if y is None else (x, y, concat)
                 if use_graph:
-                    key = tuple(None if t is None else tuple(t.shape) for t in batch) + (self.model.training,)
+                    key = batch_shapes(batch) + (self.model.training,)
                     if key not in graphed:
                         graphed[key] = self._graphed_product(product(x), x, y, concat, **fwd)
                         result = graphed[key].warmup

@@ -74,6 +74,11 @@ class FlatParams:
         from one packing gather."""
         return torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1) for p in self.params])
 
+    def gradient(self):
+        """The gradient as one flat vector: grad_vector() itself (no copy) where the gradients are its views, else gather_grads()."""
+        g = self.grad_vector()
+        return g if g is not None else self.gather_grads()
+
     def zero_grad(self):
         for p in self.params:
             p.grad = None

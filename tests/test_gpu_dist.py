@@ -106,7 +106,16 @@ def _rccl_world_of_one(port, out):
         losses = [float(step(x, y, c)) for _ in range(3)]
         torch.cuda.synchronize()
         res[name] = (losses, {k: v.detach().cpu().numpy() for k, v in nfp.model.state_dict().items()})
-    rccl = [m.split()[-1] for m in open('/proc/self/maps') if 'librccl' in m]
+    # the accumulated step the same way: micro graph twice, all_reduce(acc), update graph, against the two graphs alone
+    for name, force in (('forced accumulated', True), ('single accumulated', False)):
+        nfp, dev = _setup()
+        x, y, c = _data(dev, 0, B)
+        group = [(x[:2], y[:2], c[:2]), (x[2:], y[2:], c[2:])]
+        step = nfp.make_graphed_step(*group[0], mask, warmup=1, accumulate=2, force_multi=force)
+        losses = [float(step(group)) for _ in range(3)]
+        torch.cuda.synchronize()
+        res[name] = (losses, {k: v.detach().cpu().numpy() for k, v in nfp.model.state_dict().items()})
+    rccl =[m.split()[-1] for m in open('/proc/self/maps') if 'librccl' in m]
     out.put((res, sorted(set(rccl))))
     dist.barrier()
     dist.destroy_process_group()
@@ -117,7 +126,9 @@ def test_rccl_runs_the_multi_rank_step_structure_in_a_world_of_one():
     forced multi-rank step -- graph1.replay() (forward + loss + backward), dist.all_reduce(flat) on the replay stream,
     graph2.replay() (average + clip + fused Adam) -- must give bit-identical losses and weights to the single-graph step over
     three steps.  It proves that librccl loads, that the collective is ordered correctly between two hipGraph replays on the
-    side stream, and that capture_error_mode='thread_local' survives the process group's watchdog thread."""
+    side stream, and that capture_error_mode='thread_local' survives the process group's watchdog thread.  The same child then
+    holds the accumulated step (accumulate=2, groups of 2 + 2 clips) the same way: micro.replay() per item, dist.all_reduce(acc),
+    update.replay() against the two graphs without the collective."""
     with socket.socket() as s:
         s.bind(('127.0.0.1', 0))
         port = s.getsockname()[1]
@@ -132,10 +143,13 @@ def test_rccl_runs_the_multi_rank_step_structure_in_a_world_of_one():
     p.join(60)
     assert p.exitcode == 0
     assert rccl, 'librccl is not mapped into the process: the collective did not go through RCCL'
-    (la, wa), (lb, wb) = res['forced'], res['single']
-    assert la == lb, (la, lb)
-    for k in wa:
-        assert np.array_equal(wa[k], wb[k]), k
+    # (the accumulated pair: one all_reduce(acc) between the micro and the update graph; over one rank it sums one term and
+    # group_scale(j, 1) == 1 / j, so the forced structure gives the bits of the two graphs alone)
+    for forced, single in (('forced', 'single'), ('forced accumulated', 'single accumulated')):
+        (la, wa), (lb, wb) = res[forced], res[single]
+        assert la == lb and np.isfinite(la).all(), (forced, la, lb)
+        for k in wa:
+            assert np.array_equal(wa[k], wb[k]), (forced, k)
 
 
 def test_bench_two_ranks_prints_one_line_with_probes():
