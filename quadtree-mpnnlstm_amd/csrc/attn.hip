@@ -269,6 +269,10 @@ __global__ __launch_bounds__(QT_ATTN_BS) QT_ATTN_WAVES_T void k_attn_bwd_target(
     F4 dq = {{0, 0, 0, 0}};
     const uint32_t seed = eff_seed(a);
     const int eend = e1 + extra;
+    // A target with ONE pair has alpha = 1 and t = D: its score gradient is an exact zero.  D is taken from the stored output,
+    // (v_j + e + skip_i) - skip_i, which has lost what the forward's rounding took, so t - D would leave g . skip x 2^-24 of noise
+    // in dq_i / dk_j where the exact gradient (and any evaluation that forms D from the same products as t) is 0.
+    const bool one_pair = eend - e0 == 1;
     for (int eb = e0; eb < eend; eb += EPT) {
         int jj[EPT], rv[EPT];
         F4 kk[EPT], vv[EPT];
@@ -303,7 +307,7 @@ __global__ __launch_bounds__(QT_ATTN_BS) QT_ATTN_WAVES_T void k_attn_bwd_target(
             const float alpha = __expf(s - m) * inv;
             const float d = drop_mult(seed, i, j, a.keep);
             const float t = d * group_sum<LPN>(dot4(gi, vj));
-            const float ds = alpha * (t - D) * a.scale;
+            const float ds = one_pair ? 0.0f : alpha * (t - D) * a.scale;
             if (j0 == 0) *reinterpret_cast<float2*>(a.coef + 2 * (uint32_t)rv[u]) = make_float2(ds, alpha * d);
 #pragma unroll
             for (int c = 0; c < 4; ++c) dq.v[c] += ds * kj.v[c];

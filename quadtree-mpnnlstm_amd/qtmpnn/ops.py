@@ -1247,7 +1247,9 @@ class _MultiConv(Function):
             else:
                 gA = A.new_empty(A.shape)
                 go, gso = ptr(gA), 0
-            if N > 0:         # gA_g = gP_g W_g[:cin]^T: the forward weight's own rows are the transposed operand
+            if N > 0 and gin == 1 and co > _PROJ_MAX_K:
+                gA = _proj_dgrad_wide(gP, hoff, N, C, W, cin, co, mesh.n_dev)
+            elif N > 0:       # gA_g = gP_g W_g[:cin]^T: the forward weight's own rows are the transposed operand
                 _lib.call('qt_proj_group', gP.data_ptr() + 4 * hoff * 4 * N * C, C, (co // C) * N * C, co // C, C, None, None, ptr(W),
                           (cin + 4) * co, gin, 1, cin, go, cin, gso, 1, N, ptr(mesh.n_dev))       # (groups last to first: see csrc/attn.hip)
             else:
@@ -1279,6 +1281,25 @@ class _MultiConv(Function):
         _lib.call('qt_colsum', ptr(part), nblk, G * 2 * C, ptr(psum))
         gWe = psum.view(G, 2, C).transpose(1, 2).contiguous()
         return (None,) * 8 + tuple(gAs) + tuple(gWs) + (gWe,)
+
+
+_PROJ_MAX_K = 512      # the longest reduction qt_proj_group takes
+
+
+def _proj_dgrad_wide(gP, hoff, N, C, W, cin, co, n_dev):
+    """The data gradient gP W[:cin]^T of a cell's first-layer segment whose 4 x 4C gradient columns exceed qt_proj_group's longest
+    reduction (hidden 64 and 128: 1024 and 2048 columns): one launch per 512 columns (whole planes) against a dense copy of those
+    weight columns, the partial products added.  -> (N, cin)."""
+    step = _PROJ_MAX_K // C * C
+    out = None
+    for c0 in range(0, co, step):
+        cw = min(step, co - c0)
+        Wc = W[0, :, c0:c0 + cw].contiguous()
+        part = gP.new_empty(N, cin)
+        _lib.call('qt_proj_group', gP.data_ptr() + 4 * (4 * hoff + c0 // C) * N * C, C, 0, cw // C, C, None, None, ptr(Wc), 0, 1, 1, cin,
+                  ptr(part), cin, 0, 1, N, ptr(n_dev))
+        out = part if out is None else out.add_(part)
+    return out
 
 
 def _wgrad_groups(uses, s, seg, C, W):
