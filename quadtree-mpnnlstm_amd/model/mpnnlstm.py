@@ -687,22 +687,25 @@ class NextFramePredictorS2S(NextFramePredictor):
 
     def set_recompute(self, mode):
         """How the rollouts that build an autograd graph keep their activations: None (default) -- every step's until the
-        backward -- or 'step' -- only what crosses a step boundary; every encoder and decoder step is then re-run, one at a
-        time, while the backward passes it (Seq2Seq.set_recompute has the details).  forward_loss, train_step,
+        backward -- 'step' or 'stream' -- only what crosses a step boundary; every encoder and decoder step is then re-run, one at
+        a time, while the backward passes it (Seq2Seq.set_recompute has the details).  forward_loss, train_step,
         accumulated_step / accumulate_gradients, every chunk of truncated_backward, make_graphed_step and train honour it; loss,
         gradients and parameters are the plain step's bit for bit, for one more forward's launches.  What autograd keeps from
         the forward shrinks to the boundaries; the peak shrinks less, because the deferred weight gradient still holds every
         step's Chebyshev planes and gate gradients from that step's backward to the pass's last one (README has the measured
-        figures).  A CAPTURED STEP KEEPS THE MODE IT WAS CAPTURED UNDER: changing the mode afterwards
-        affects new captures only.  Passes without autograd (predict, verify and its products, attention_weights, the test pass
+        figures).  'stream' is 'step' without that hold: every use's weight gradient is reduced inside its own backward and added
+        to a running sum, so the peak no longer grows with those operands; the weight gradients are then the plain step's up to
+        rounding (another order of additions, fixed: two runs give the same bits), everything else stays bit for bit, and the step
+        takes one short launch per step and weight instead of one grouped launch.  A CAPTURED STEP KEEPS THE MODE IT WAS
+        CAPTURED UNDER: changing the mode afterwards affects new captures only.  Passes without autograd (predict, verify and its products, attention_weights, the test pass
         of train) do not look at it.  The mode is no training state: checkpoints neither store nor restore it.  Any other value:
         ValueError, before anything is launched."""
         self.model.set_recompute(mode)
 
     @contextlib.contextmanager
     def recomputing(self, mode):
-        """`with nfp.recomputing('step'):` -- set_recompute(mode) for the block; the previous mode is back afterwards, also after
-        an exception."""
+        """`with nfp.recomputing('step'):` (or 'stream', None) -- set_recompute(mode) for the block; the previous mode is back
+        afterwards, also after an exception."""
         previous = self.recompute
         self.set_recompute(mode)
         try:

@@ -318,7 +318,7 @@ class Seq2Seq(_NoCachesInPickle, nn.Module):
         self.thresh, self.transform_func, self.graph, self.device = thresh, transform_func, None, device
         self.max_grid_size = 64                      # image_to_graph default, never overridden (graph_functions.py:590)
         self.static_shapes = False                   # True: worst-case capacities + device-side node counts (hipGraph)
-        self._recompute = None                       # None | 'step' (set_recompute): how a rollout with autograd keeps its steps
+        self._recompute = None                       # None | 'step' | 'stream' (set_recompute): how a rollout with autograd keeps its steps
 
     # -- activation recomputation ----------------------------------------------------------
     @property
@@ -333,14 +333,24 @@ class Seq2Seq(_NoCachesInPickle, nn.Module):
         mesh builds, the state transfer between meshes, teacher forcing and the loss stay outside the nodes and run once.  Loss,
         gradients and the attention-dropout masks of later steps are the plain rollout's, bit for bit.  Without autograd
         (predict, verify, attention_weights) the mode does nothing.  remesh_input=True models have no such nodes: with 'step' a
-        rollout with autograd is refused when it starts."""
+        rollout with autograd is refused when it starts.  'stream': 'step', and no use of a packed weight keeps its
+        weight-gradient operands (Chebyshev planes and gate gradients, attention inputs and projection gradients) past its own
+        backward: each use is reduced at once by a short launch and added to a running sum, in backward order, instead of all
+        uses by one grouped launch at the end.  Another order of additions: the weight gradients equal the plain rollout's up to
+        rounding; loss, outputs, meshes and dropout masks stay bit for bit, and two runs give the same bits."""
         self._recompute = recompute.check_mode(mode)
 
     def _step(self, run, *args):
         """run(*args) -- Encoder.run / Decoder.run_rows -- as the mode keeps it."""
-        if self.recompute == 'step':
+        if self.recompute in ('step', 'stream'):
             return recompute.segment(run, *args)
         return run(*args)
+
+    def _for_mode(self, pack):
+        """The packed weights of a pass as the mode wants their gradient accumulators."""
+        if self.recompute == 'stream' and pack is not None and torch.is_grad_enabled():
+            recompute.stream_accs(pack)
+        return pack
 
     # -- attention weights -----------------------------------------------------------------
     @contextlib.contextmanager
@@ -412,9 +422,9 @@ class Seq2Seq(_NoCachesInPickle, nn.Module):
     @on_device(lambda self, *a, **k: self.encoder.norm_h.weight)
     def process_inputs(self, x, mask=None, high_interest_region=None, graph_structure=None):
         """model/seq2seq.py:254-336.  x: (T_in, W, H, C) or (B, T_in, W, H, C)."""
-        if self.remesh_input and self.recompute == 'step' and torch.is_grad_enabled():
-            raise NotImplementedError("set_recompute('step') does not cover remesh_input=True models (their encoder re-meshes between "
-                                      "its steps): set_recompute(None) for this rollout")
+        if self.remesh_input and self.recompute is not None and torch.is_grad_enabled():
+            raise NotImplementedError(f"set_recompute({self.recompute!r}) does not cover remesh_input=True models (their encoder "
+                                      "re-meshes between its steps): set_recompute(None) for this rollout")
         self._single = x.dim() == 4
         self._deferred = None
         if self._single:
@@ -469,7 +479,7 @@ class Seq2Seq(_NoCachesInPickle, nn.Module):
             feats = feats_in[:, :, :c + 3]
         self.graph = Graph(None, None)
         self.graph.mapping, self.graph.n_pixels_per_node, self.graph.image_shape = mesh, mesh.npix, (n, m)
-        enc_pack, self._dec_pack = self._packs(c + 3 + fpad)     # (the decoder pack waits for unroll_output)
+        enc_pack, self._dec_pack = self._for_mode(self._packs(c + 3 + fpad))     # (the decoder pack waits for unroll_output)
         hidden = cell = None
         for t in range(self.input_timesteps):
             hidden, cell = self._step(self.encoder.run, feats_in[t], mesh, None if hidden is None else hidden[-1],
@@ -530,7 +540,7 @@ class Seq2Seq(_NoCachesInPickle, nn.Module):
         # the autograd graph alive beyond the pass (a continued unroll packs the decoder on its own)
         dec_pack, self._dec_pack = getattr(self, '_dec_pack', None), None
         if dec_pack is None:
-            dec_pack = self.decoder.pack(4)
+            dec_pack = self._for_mode(self.decoder.pack(4))
         outputs, output_mappings = [], []
         steps = list(unroll_steps)
         drops = self.decoder.dropout_masks(len(steps), mesh.B * mesh.P, g.pyg.x.device)

@@ -83,13 +83,41 @@ class GradAcc:
 
     Under qtmpnn.recompute a use is counted (`uses`) by its segment's first pass, which runs without autograd, and never by the
     replay: while `cursor` is set, enter() hands out the first pass's indices again and leaves `uses` alone.
-    """
-    __slots__ = ('uses', 'done', 'part', 'wt', 'pending', 'wslab', 'pslab', 'cursor')
 
-    def __init__(self):
+    The uses whose partials are no slab sums hand their operands to keep(): kept in `pending` until the pass's last backward, which
+    reduces all of them in one grouped launch (flush) -- or, when the pass streams (`stream`, recompute mode 'stream'), reduced at
+    once, use by use in backward order, into the running sums `total`, and dropped.
+    """
+    __slots__ = ('uses', 'done', 'part', 'wt', 'pending', 'wslab', 'pslab', 'cursor', 'stream', 'total')
+
+    def __init__(self, stream=False):
         self.uses, self.done, self.part, self.wt, self.pending, self.wslab = 0, 0, None, {}, [], None
         self.pslab = {}        # segment -> (blocks, G, cin + 4, co) slabs of the one-pass projection backward (qt_proj_bwd)
         self.cursor = None     # set while a recomputed segment is replayed (qtmpnn.recompute): the index its next use takes
+        self.stream = stream   # True: no use keeps its weight-gradient operands past its own backward (keep)
+        self.total = None      # streaming: the running sums of the uses reduced so far, one per weight of the op (None: no share yet)
+
+    def keep(self, use, reduce):
+        """One use's weight-gradient operands.  reduce(uses) -> [gradient | None per weight of the op], summed over `uses` by the
+        grouped launches.  Deferred: `use` waits in `pending` for flush.  Streaming: reduce([use]) now, added to `total`."""
+        if self.stream:
+            self._add(reduce([use]))
+        else:
+            self.pending.append(use)
+
+    def flush(self, reduce):
+        """[gradient | None per weight] over every use kept in this pass (None: no use was kept); the accumulator keeps nothing."""
+        uses, self.pending = self.pending, []
+        if uses:
+            self._add(reduce(uses))
+        total, self.total = self.total, None
+        return total
+
+    def _add(self, gs):
+        if self.total is None:
+            self.total = list(gs)
+        else:           # (the sums are this accumulator's own buffers: added in place, in the order of the calls)
+            self.total = [g if t is None else (t if g is None else t.add_(g)) for t, g in zip(self.total, gs)]
 
     def enter(self):
         if self.cursor is not None:     # a replay: the segment's first pass counted this use, the replay takes the same index
@@ -508,12 +536,13 @@ def _cheb_backward(Zs, TZs, W, G, mesh, K, Ks, acc, use_idx, need_gZ, need_gW, g
                 _lib.call('qt_colsum', ptr(part), nblk, W.numel(), ptr(gW))
         else:
             # deferred: the weight gradient is off the critical path, so all uses of this pass (<= 16 per launch) are
-            # reduced together by the last backward -- one long launch instead of one short one per rollout step
+            # reduced together by the last backward -- one long launch instead of one short one per rollout step (a streaming
+            # pass takes the short launches: GradAcc.keep)
+            reduce = lambda uses: [_wgrad_group(uses, W, K, Cs, ksp, Co)]
             if not w_fused:
-                acc.pending.append((Zs, TZs, S, G, N, mesh.n_dev, sm))
+                acc.keep((Zs, TZs, S, G, N, mesh.n_dev, sm), reduce)
             if acc.leave(use_idx):
-                gW = _wgrad_group(acc.pending, W, K, Cs, ksp, Co) if acc.pending else None
-                acc.pending = []
+                gW = (acc.flush(reduce) or [None])[0]
                 if acc.wslab is not None:          # + the partials the fused launches added, slab by slab
                     gf = torch.empty_like(W)
                     _lib.call('qt_colsum', ptr(acc.wslab), acc.wslab.shape[0], W.numel(), ptr(gf))
@@ -1259,24 +1288,26 @@ class _MultiConv(Function):
         if not (need_w or ctx.needs_input_grad[8 + 2 * nseg]):      # every weight is data here: nothing to reduce, no use counted
             return (None,) * 8 + tuple(gAs) + (None,) * (nseg + 1)
         last = acc is None or acc.leave(ctx.use_idx)
-        pending = acc.pending if acc is not None else []
+        keeper = acc if acc is not None else GradAcc()
+
+        def reduce(uses):       # per segment: the sum over the uses that did not fuse it (None: every use did)
+            mine = [[u for u in uses if s not in u[5]] for s in range(nseg)]
+            return [_wgrad_groups(m, s, ctx.segs[s], C, Ws[s]) if m else None for s, m in enumerate(mine)]
         if need_w and N > 0 and len(fused) < nseg:          # (the segments in `fused` have their share in the slabs already)
-            pending.append((As, gP, N, mesh.n_dev, mesh.cheb_ones(1), fused))
+            keeper.keep((As, gP, N, mesh.n_dev, mesh.cheb_ones(1), fused), reduce)
         if not last:
             return (None,) * 8 + tuple(gAs) + (None,) * (nseg + 1)
         gWs = [None] * nseg
+        kept = keeper.flush(reduce) or [None] * nseg
         if need_w:
-            for s, (seg, W) in enumerate(zip(ctx.segs, Ws)):
-                uses = [u for u in pending if s not in u[5]]
+            for s, W in enumerate(Ws):
                 if s in pslab:           # every fused use of the pass added its partial sums into the same slabs
                     gWs[s] = torch.empty_like(W)
                     _lib.call('qt_colsum', ptr(pslab[s]), pslab[s].shape[0], W.numel(), ptr(gWs[s]))
-                    if uses:
-                        gWs[s] += _wgrad_groups(uses, s, seg, C, W)
+                    if kept[s] is not None:
+                        gWs[s] += kept[s]
                 else:
-                    gWs[s] = _wgrad_groups(uses, s, seg, C, W)
-        if acc is not None:
-            acc.pending = []
+                    gWs[s] = kept[s] if kept[s] is not None else torch.zeros_like(W)
         psum = P.new_empty(G * 2 * C)
         _lib.call('qt_colsum', ptr(part), nblk, G * 2 * C, ptr(psum))
         gWe = psum.view(G, 2, C).transpose(1, 2).contiguous()

@@ -13,6 +13,10 @@ What a step shares with the other steps of its pass is kept consistent by hand:
   where it found it -- the replayed masks are the first run's, the next pass draws what it would have drawn;
 - a recording of attention weights (Seq2Seq.record_attention) sees the first run only (replaying()).
 Nothing here reads or sets a torch generator, and nothing synchronises: a captured step replays inside its capture.
+
+Mode 'stream' is 'step' with one difference, which is the accumulators' and not this module's: the GradAccs of the pass are marked
+(stream_accs) and then reduce every use's weight-gradient operands inside that use's backward instead of keeping them for one
+grouped launch at the end.  The sum is taken in another order, so the weight gradients are the plain step's up to rounding.
 """
 import copy
 
@@ -22,7 +26,7 @@ from torch.autograd import Function
 from . import ops
 from .mesh import Mesh
 
-MODES = (None, 'step')
+MODES = (None, 'step', 'stream')
 _REPLAYING = [0]
 _RECORDS = []           # the classes of packed-weight records (register_record)
 
@@ -36,10 +40,20 @@ def register_record(cls):
 
 
 def check_mode(mode, who='set_recompute'):
-    """`mode` as it is kept: None or 'step' (ValueError otherwise; True and 1 are no modes)."""
-    if mode is None or (isinstance(mode, str) and mode == 'step'):
+    """`mode` as it is kept: one of MODES (ValueError otherwise; True and 1 are no modes)."""
+    if mode is None or (isinstance(mode, str) and mode in MODES):
         return mode
-    raise ValueError(f"{who}: mode must be None or 'step', got {mode!r}")
+    raise ValueError(f"{who}: mode must be None, 'step' or 'stream', got {mode!r}")
+
+
+def stream_accs(pack):
+    """Every GradAcc in the packed weights `pack` of one pass (dicts / lists / records, as segment takes them) streams from here on:
+    the pass's weight gradients are summed use by use (ops.GradAcc.keep).  Returns `pack`."""
+    accs = []
+    _split(pack, [], accs, {})
+    for a in accs:
+        a.stream = True
+    return pack
 
 
 def replaying():
