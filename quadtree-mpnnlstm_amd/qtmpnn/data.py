@@ -1,0 +1,135 @@
+"""ClipBank: a time series held on the device once, and the training windows formed from it there (beyond the reference, whose
+IceDataset materialises every window on the host: consecutive launch dates share all but one day, so every day is stored
+T_in + T_out times).  The bank's loader yields what the reference's loaders yield -- (x, y, launch_date) per batch -- so train,
+predict, verify and every product take it where they take a DataLoader, unchanged.
+
+No kernel of the library is involved: a batch is one advanced-index gather per field, series[start[:, None] + arange(T)], torch
+indexing on device tensors (capturable; DESIGN.md, "ClipBank").  Everything here is pure torch, so device='cpu' works too."""
+import numpy as np
+import torch
+from torch.utils.data import DataLoader
+
+
+def _whole(v):
+    return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+
+
+def _channels(name, channels, C):
+    if channels is None:
+        return list(range(C))
+    picked = list(channels)
+    if not picked or not all(_whole(c) and 0 <= c < C for c in picked):
+        raise ValueError(f'{name}: channel indices must be a non-empty list of integers in 0..{C - 1}, got {picked}')
+    return [int(c) for c in picked]
+
+
+def window_table(D, input_timesteps, output_timesteps, segments=None):
+    """The first x day of every window, int64 (n,): per segment (s, e) of length L = e - s the windows i, 0 <= i < L - T_in - T_out
+    (the reference's `while i + T_out + T_in < size`: the last window that would fit is left out), numbered segment after
+    segment.  Window i of a segment has x days [s + i, s + i + T_in), y days [s + i + T_in, s + i + T_in + T_out) and the launch
+    date of day s + i + T_in.  ValueErrors by argument name for step counts below 1, segments out of 0..D, unordered or
+    overlapping, and for no window at all."""
+    for name, T in (('input_timesteps', input_timesteps), ('output_timesteps', output_timesteps)):
+        if not _whole(T) or T < 1:
+            raise ValueError(f'{name}: must be an integer >= 1, got {T!r}')
+    segments = [(0, D)] if segments is None else [tuple(seg) for seg in segments]
+    starts, last = [], 0
+    for k, seg in enumerate(segments):
+        if len(seg) != 2 or not all(_whole(v) for v in seg):
+            raise ValueError(f'segments: segments[{k}] must be (start, stop) day numbers, got {seg!r}')
+        s, e = int(seg[0]), int(seg[1])
+        if not 0 <= s < e <= D:
+            raise ValueError(f'segments: segments[{k}] = ({s}, {e}) is not a range of days within 0..{D}')
+        if s < last:
+            raise ValueError(f'segments: segments[{k}] = ({s}, {e}) starts before segments[{k - 1}] stops at day {last} (segments must '
+                             'be ordered and must not overlap)')
+        last = e
+        starts.append(s + np.arange(max(0, e - s - int(input_timesteps) - int(output_timesteps)), dtype=np.int64))
+    table = np.concatenate(starts) if starts else np.zeros(0, np.int64)
+    if not len(table):
+        raise ValueError(f'segments: no segment holds a window: {input_timesteps} in + {output_timesteps} out need a segment of more '
+                         f'than {input_timesteps + output_timesteps} days, got {segments}')
+    return table
+
+
+class ClipBank:
+    """series (D, W, H, C) (numpy or tensor) -> an x series (D, W, H, Cx) and a y series (D, W, H, Cy), float32, contiguous on
+    `device`, each day stored once: converted to float32 and passed through nan_to_num once, split by the channel index lists
+    (default: all channels); with y_binary_thresh the y series is (y > thresh) as float32, the threshold rounded to float32 and
+    compared with the float32 values after nan_to_num.  Normalisation is the caller's (the reference normalises per season,
+    before windowing).  times (D,): the day stamps, int64 ns as the reference's launch_dates.astype(int), kept on the host.
+    segments: (start, stop) day ranges, one per season, which no window crosses (default: one, (0, D)); see window_table for the
+    window rule.  Every argument is checked, by name, before anything is uploaded."""
+
+    def __init__(self, series, times, input_timesteps, output_timesteps, segments=None, x_channels=None, y_channels=None,
+                 y_binary_thresh=None, device=None):
+        series = torch.as_tensor(series)
+        if series.dim() != 4:
+            raise ValueError(f'series: must be (D, W, H, C), got {tuple(series.shape)}')
+        D, W, H, C = series.shape
+        times = np.asarray(times.cpu() if torch.is_tensor(times) else times)
+        if times.shape != (D,):
+            raise ValueError(f'times: must be ({D},), one stamp per day of the series, got {times.shape}')
+        first_day = window_table(D, input_timesteps, output_timesteps, segments)
+        xc, yc = _channels('x_channels', x_channels, C), _channels('y_channels', y_channels, C)
+        self.input_timesteps, self.output_timesteps = int(input_timesteps), int(output_timesteps)
+        self.device = torch.device('cuda' if device is None else device)
+        self.image_shape = (W, H)
+        self.launch_dates = times.astype(np.int64)[first_day + self.input_timesteps]
+        self._first_day = torch.from_numpy(first_day)
+        self._launch = torch.from_numpy(self.launch_dates)
+
+        def stored(channels):           # (one field at a time, selected on the host: the device never holds more than it keeps)
+            return torch.nan_to_num_(series[..., channels].to(torch.float32).to(self.device).contiguous())
+        self.x, self.y = stored(xc), stored(yc)
+        self.device = self.x.device
+        if y_binary_thresh is not None:
+            self.y = (self.y > float(np.float32(y_binary_thresh))).to(torch.float32)
+        self._steps_x = torch.arange(self.input_timesteps, device=self.device)
+        self._steps_y = self.input_timesteps + torch.arange(self.output_timesteps, device=self.device)
+
+    def __len__(self):
+        return len(self._first_day)
+
+    @property
+    def nbytes(self):
+        """The device bytes held: D * W * H * (Cx + Cy) * 4."""
+        return self.x.numel() * 4 + self.y.numel() * 4
+
+    def window(self, idx):
+        """idx: window numbers, a sequence or an int64 tensor (B,) on the host -> (x (B, T_in, W, H, Cx), y (B, T_out, W, H, Cy),
+        launch_dates (B,)): x and y contiguous float32 on the bank's device, one gather each; launch_dates int64 on the host (what
+        get_climatology_array reads).  The one host-to-device transfer is the windows' first days; nothing waits for the device."""
+        idx = torch.as_tensor(idx, dtype=torch.int64, device='cpu').reshape(-1)
+        n = len(self)
+        if len(idx) and not (int(idx.min()) >= 0 and int(idx.max()) < n):
+            raise ValueError(f'idx: window numbers must be in 0..{n - 1}, got {idx.tolist()}')
+        first = self._first_day[idx].to(self.device)[:, None]
+        return self.x[first + self._steps_x], self.y[first + self._steps_y], self._launch[idx]
+
+    def loader(self, batch_size=1, shuffle=False, generator=None, drop_last=False):
+        return ClipLoader(self, batch_size, shuffle, generator, drop_last)
+
+
+class ClipLoader:
+    """Batches of a ClipBank, re-iterable: bank.window(batch) per batch, `.dataset` the bank (train reads
+    loader.dataset.image_shape).  The order of the window numbers IS that of torch.utils.data.DataLoader(dataset_of_len_n,
+    batch_size, shuffle, generator=generator, drop_last=drop_last), because such a loader over range(n) draws them: whatever torch
+    takes from `generator` -- or, with generator=None, from the global CPU generator -- per pass, this loader takes.  A host
+    loader replaced by a bank therefore keeps its sample order, and a run resumed from a checkpoint (which carries the CPU
+    generator's state) its bits."""
+
+    def __init__(self, bank, batch_size=1, shuffle=False, generator=None, drop_last=False):
+        if not _whole(batch_size) or batch_size < 1:
+            raise ValueError(f'batch_size: must be an integer >= 1, got {batch_size!r}')
+        self.dataset = bank
+        self.batch_size = int(batch_size)
+        self._numbers = DataLoader(range(len(bank)), batch_size=self.batch_size, shuffle=bool(shuffle), generator=generator,
+                                   drop_last=bool(drop_last))
+
+    def __len__(self):
+        return len(self._numbers)
+
+    def __iter__(self):
+        for batch in self._numbers:
+            yield self.dataset.window(batch)
