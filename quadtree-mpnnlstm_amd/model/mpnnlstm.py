@@ -20,8 +20,8 @@ import torch
 from torch.optim.lr_scheduler import StepLR
 
 from model.graph_functions import image_to_graph, unflatten, plot_contours
-from model.seq2seq import Seq2Seq
-from model.utils import add_positional_encoding, get_n_params, int_to_datetime
+from model.seq2seq import Seq2Seq, check_concat_clips
+from model.utils import add_positional_encoding, get_n_params, int_to_datetime, output_day_indices
 from qtmpnn import mesh as _mesh, ops
 from qtmpnn.dist import all_reduce_sum, allreduce_gradients
 from qtmpnn.flat import flat_params, name_table
@@ -276,6 +276,7 @@ def checked_batches(who, batches):
         if (c is None) != (items[0][2] is None):
             raise ValueError(f'{who}: concat_layers is given for some micro-batches and not for others (batches[{i}] '
                              f'{"has none" if c is None else "has one"}, batches[0] {"none" if items[0][2] is None else "one"})')
+        check_concat_clips(x, c)
     return items
 
 
@@ -679,6 +680,7 @@ class NextFramePredictorS2S(NextFramePredictor):
                              **model_kwargs).to(device)
         self.training_initiated = False
         self.process_group = None
+        self._output_days = {}          # launch date -> its output days' indices into the daily normals (get_climatology_array)
 
     # -- activation recomputation (beyond the reference): the mode lives on the Seq2Seq, where the rollout is -------------------
     @property
@@ -908,6 +910,7 @@ class NextFramePredictorS2S(NextFramePredictor):
         fused=True (binary predictors only): the fused binary cross-entropy of masked_mse.  On a binary=True predictor any of
         loss_weights / lead_weights / pos_weight (the positive-class weight) selects masked_bce, which is always fused."""
         self._check_fused(fused)
+        check_concat_clips(x, concat_layers)
         lw = self._loss_weights(x, mask, loss_weights, lead_weights, pos_weight)
         y_hat, meshes = self.model(x, y, concat_layers, teacher_forcing_ratio=0, mask=mask,
                                    high_interest_region=high_interest_region, graph_structure=graph_structure)
@@ -1004,6 +1007,7 @@ class NextFramePredictorS2S(NextFramePredictor):
         loss_weights / lead_weights: the weighted loss (masked_mse).  fused=True (binary predictors only): the fused binary
         cross-entropy of masked_mse, the loss a captured step runs.  On a binary=True predictor the weights, and pos_weight, the
         weight of the positive class, select the weighted binary cross-entropy (masked_bce)."""
+        check_concat_clips(x, concat_layers)
         lw = self._loss_weights(x, mask, loss_weights, lead_weights, pos_weight)
         self.zero_grad()
         loss = self.forward_loss(x, y, concat_layers, mask, high_interest_region, graph_structure, fused=fused, loss_weights=lw)
@@ -1107,6 +1111,7 @@ class NextFramePredictorS2S(NextFramePredictor):
         loss_weights / lead_weights: the weighted loss; a chunk takes lead_weights[steps] and divides by that slice's sum (every
         chunk's slice is checked before the first one runs).  pos_weight (binary=True predictors): as in train_step."""
         losses, step = [], 0
+        check_concat_clips(x, concat_layers)
         if y.dim() == 4:
             y = y.unsqueeze(0)
         lw = self._loss_weights(x, mask, loss_weights, lead_weights, pos_weight)
@@ -1157,6 +1162,7 @@ class NextFramePredictorS2S(NextFramePredictor):
         if check_accumulate(accumulate) > 1:
             return self._graphed_accumulation([(x, y, concat_layers)], accumulate, mask, high_interest_region, max_norm, warmup,
                                               graph_structure, force_multi, pos_weight, loss_weights, lead_weights)
+        check_concat_clips(x, concat_layers)
         multi, world = self._capture_setup(force_multi)
         batch = StaticBatch(x, y, concat_layers)
         lw = self._loss_weights(x, mask, loss_weights, lead_weights, pos_weight)
@@ -1315,6 +1321,7 @@ class NextFramePredictorS2S(NextFramePredictor):
         """The capture of one rollout (forward arguments `fwd`) and its product `reduce` (one device tensor, or a tuple of them:
         several products of the one rollout) on static copies of the batch; y is None
         for a product that does not read it, and replay's arguments are then (x, concat), else (x, y, concat)."""
+        check_concat_clips(x, concat_layers)
         self.model.static_shapes = True
         batch = StaticBatch(x, y, concat_layers)
         sx, sy, sc = batch.tensors
@@ -1440,6 +1447,7 @@ class NextFramePredictorS2S(NextFramePredictor):
         make_graphed_scores(maps=...)); `.warmup` is that tuple for the given batch and `.products` the names.  With 'score_maps'
         the zeroed float64 (T_out, S, 8, P) buffer is allocated here and is `.maps`: the given batch is in it once, and every
         replay adds its batch once."""
+        check_concat_clips(x, concat_layers)
         call = ProductCall(self.output_timesteps, tuple(x.shape[-3:-1]), x.device, concat_layers is not None, True, mask)
         made = make_products('make_graphed_verification', products, call)
         for p in made.values():
@@ -1590,9 +1598,21 @@ class NextFramePredictorS2S(NextFramePredictor):
         return t.squeeze(0) if t.shape[0] == 1 else t
 
     def get_climatology_array(self, climatology, launch_date):
-        """Daily normals of the output days, (T_out, W, H, 1) (mpnnlstm.py:389-400)."""
-        doys = [int_to_datetime(launch_date.numpy()[0] + 8.640e13 * t).timetuple().tm_yday - 1
-                for t in range(self.output_timesteps)]
+        """Daily normals of the output days (mpnnlstm.py:389-400).  climatology: (Cy, 366, W, H).  launch_date (1,), as the
+        reference's batch_size=1 loaders give it: (T_out, W, H, Cy), the reference's.  launch_date (B,) with B > 1 (beyond the
+        reference, whose rule reads the first clip's date for a whole batch): (B, T_out, W, H, Cy), entry [c] what the call on
+        launch_date[c:c + 1] returns.  The day indices are model.utils.output_day_indices per clip, kept per distinct launch date
+        (an epoch meets the dates of the one before); they go up as ONE (B, T_out) int64 array and index the normals once."""
+        dates = launch_date.numpy()
+        if dates.ndim != 1 or len(dates) <= 1:
+            return torch.moveaxis(climatology[:, output_day_indices(dates[0], self.output_timesteps)], 0, -1)
+        rows = []
+        for date in dates:
+            key = date.item()
+            if key not in self._output_days:
+                self._output_days[key] = output_day_indices(date, self.output_timesteps)
+            rows.append(self._output_days[key])
+        doys = torch.tensor(rows, dtype=torch.int64).to(climatology.device)
         return torch.moveaxis(climatology[:, doys], 0, -1)
 
     @on_device(lambda self, *a, **k: self.device)
@@ -1622,6 +1642,7 @@ class NextFramePredictorS2S(NextFramePredictor):
             for x, y, launch_date in loader:
                 x, y = self._clip(x), self._clip(y) if reads_y else None
                 concat = self.get_climatology_array(climatology, launch_date) if climatology is not None else None
+                check_concat_clips(x, concat)
                 if begin is not None:
                     begin(x)
                 batch = (x, concat) if y is None else (x, y, concat)
@@ -1698,6 +1719,7 @@ class NextFramePredictorS2S(NextFramePredictor):
         self.model.to(self.device)
         x = x.to(self.device)
         concat = concat_layers.to(self.device) if concat_layers is not None else None
+        check_concat_clips(x, concat)
         with torch.no_grad(), self.model.record_attention(select) as records:
             self.model(x, concat_layers=concat, teacher_forcing_ratio=0, mask=mask, high_interest_region=high_interest_region,
                        graph_structure=graph_structure)
@@ -1749,6 +1771,7 @@ class NextFramePredictorS2S(NextFramePredictor):
             raise ValueError('x: a floating-point tensor of shape (T_in, W, H, C) or (B, T_in, W, H, C) is needed, got '
                              + (f'{x.dtype} {tuple(x.shape)}' if torch.is_tensor(x) else type(x).__name__))
         req = Request(x.shape, self.output_timesteps, host_mask(mask), target, leads, method, baseline, steps)
+        check_concat_clips(x, concat_layers)
         if self.model.remesh_input:
             raise NotImplementedError('sensitivity: remesh_input=True models are not covered (their encoder assembles the rows of '
                                       'every input frame without autograd)')

@@ -283,6 +283,19 @@ class Decoder(_NoCachesInPickle, nn.Module):
         return y, torch.stack(hs), torch.stack(cs)
 
 
+def check_concat_clips(x, concat_layers):
+    """A per-clip concat_layers (B, T_out, W, H, 1) -- a climatology per clip, what get_climatology_array returns for a batch of
+    launch dates -- must hold as many clips as x; a ValueError that names the climatology otherwise, on the host and before any
+    launch.  (T_out, W, H, 1) is one clip's and is left to the rollout, as it was."""
+    if concat_layers is None or not hasattr(concat_layers, 'dim') or concat_layers.dim() != 5:
+        return
+    clips = x.shape[0] if x.dim() == 5 else 1
+    if concat_layers.shape[0] != clips:
+        raise ValueError(f'climatology: concat_layers of shape {tuple(concat_layers.shape)} holds the normals of '
+                         f'{concat_layers.shape[0]} clips, x has {clips} (shape {tuple(x.shape)}): one (T_out, W, H, 1) entry per clip '
+                         'is needed, in the order of the clips')
+
+
 class Seq2Seq(_NoCachesInPickle, nn.Module):
     """model/seq2seq.py:190-527 for the quadtree path (finite `thresh`)."""
 
@@ -594,6 +607,7 @@ class Seq2Seq(_NoCachesInPickle, nn.Module):
     @on_device(lambda self, *a, **k: self.encoder.norm_h.weight)
     def forward(self, x, y=None, concat_layers=None, teacher_forcing_ratio=0.5, mask=None, high_interest_region=None,
                 graph_structure=None, remesh_every=1):
+        check_concat_clips(x, concat_layers)
         self.process_inputs(x, mask=mask, high_interest_region=high_interest_region, graph_structure=graph_structure)
         return self.unroll_output(range(self.output_timesteps), y, concat_layers=concat_layers,
                                   teacher_forcing_ratio=teacher_forcing_ratio, mask=mask,

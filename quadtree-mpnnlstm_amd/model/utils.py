@@ -62,5 +62,17 @@ def int_to_datetime(x):
     return datetime.datetime.fromtimestamp(x / 1e9)
 
 
+def day_of_year_index(stamp):
+    """Nanosecond timestamp (int or float) -> 0-based day of the year, 0..365, in local time: the index of the daily normals
+    (mpnnlstm.py:393).  The one statement of the rule: get_climatology_array and ClipBank.normals both come here."""
+    return int_to_datetime(stamp).timetuple().tm_yday - 1
+
+
+def output_day_indices(launch, output_timesteps):
+    """The day-of-year indices of the output days of a clip launched at `launch` (int64 ns): day t is launch + 8.640e13 * t, a
+    float64 addition as in the reference (mpnnlstm.py:391-394)."""
+    return [day_of_year_index(launch + 8.640e13 * t) for t in range(output_timesteps)]
+
+
 def round_to_day(dt):
     return datetime.datetime(*dt.timetuple()[:3])

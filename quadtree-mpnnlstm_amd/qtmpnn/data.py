@@ -23,6 +23,24 @@ def _channels(name, channels, C):
     return [int(c) for c in picked]
 
 
+def day_ranges(name, ranges, D):
+    """`ranges` as a list of (start, stop) day ranges within 0..D, ordered and without overlap, or a ValueError under `name` (the
+    rule of `segments`, which ClipBank.normals(days=) shares)."""
+    checked, last = [], 0
+    for k, seg in enumerate(tuple(seg) for seg in ranges):
+        if len(seg) != 2 or not all(_whole(v) for v in seg):
+            raise ValueError(f'{name}: {name}[{k}] must be (start, stop) day numbers, got {seg!r}')
+        s, e = int(seg[0]), int(seg[1])
+        if not 0 <= s < e <= D:
+            raise ValueError(f'{name}: {name}[{k}] = ({s}, {e}) is not a range of days within 0..{D}')
+        if s < last:
+            raise ValueError(f'{name}: {name}[{k}] = ({s}, {e}) starts before {name}[{k - 1}] stops at day {last} ({name} must '
+                             'be ordered and must not overlap)')
+        last = e
+        checked.append((s, e))
+    return checked
+
+
 def window_table(D, input_timesteps, output_timesteps, segments=None):
     """The first x day of every window, int64 (n,): per segment (s, e) of length L = e - s the windows i, 0 <= i < L - T_in - T_out
     (the reference's `while i + T_out + T_in < size`: the last window that would fit is left out), numbered segment after
@@ -33,18 +51,8 @@ def window_table(D, input_timesteps, output_timesteps, segments=None):
         if not _whole(T) or T < 1:
             raise ValueError(f'{name}: must be an integer >= 1, got {T!r}')
     segments = [(0, D)] if segments is None else [tuple(seg) for seg in segments]
-    starts, last = [], 0
-    for k, seg in enumerate(segments):
-        if len(seg) != 2 or not all(_whole(v) for v in seg):
-            raise ValueError(f'segments: segments[{k}] must be (start, stop) day numbers, got {seg!r}')
-        s, e = int(seg[0]), int(seg[1])
-        if not 0 <= s < e <= D:
-            raise ValueError(f'segments: segments[{k}] = ({s}, {e}) is not a range of days within 0..{D}')
-        if s < last:
-            raise ValueError(f'segments: segments[{k}] = ({s}, {e}) starts before segments[{k - 1}] stops at day {last} (segments must '
-                             'be ordered and must not overlap)')
-        last = e
-        starts.append(s + np.arange(max(0, e - s - int(input_timesteps) - int(output_timesteps)), dtype=np.int64))
+    starts = [s + np.arange(max(0, e - s - int(input_timesteps) - int(output_timesteps)), dtype=np.int64)
+              for s, e in day_ranges('segments', segments, D)]
     table = np.concatenate(starts) if starts else np.zeros(0, np.int64)
     if not len(table):
         raise ValueError(f'segments: no segment holds a window: {input_timesteps} in + {output_timesteps} out need a segment of more '
@@ -75,7 +83,8 @@ class ClipBank:
         self.input_timesteps, self.output_timesteps = int(input_timesteps), int(output_timesteps)
         self.device = torch.device('cuda' if device is None else device)
         self.image_shape = (W, H)
-        self.launch_dates = times.astype(np.int64)[first_day + self.input_timesteps]
+        self.times = times.astype(np.int64)
+        self.launch_dates = self.times[first_day + self.input_timesteps]
         self._first_day = torch.from_numpy(first_day)
         self._launch = torch.from_numpy(self.launch_dates)
 
@@ -109,6 +118,46 @@ class ClipBank:
 
     def loader(self, batch_size=1, shuffle=False, generator=None, drop_last=False):
         return ClipLoader(self, batch_size, shuffle, generator, drop_last)
+
+    def normals(self, days=None):
+        """The daily normals of the stored y series -> (Cy, 366, W, H) float32 on the bank's device, the layout
+        train(climatology=) and get_climatology_array index: entry [c, d] is the mean of channel c over the selected days whose
+        stamp has the day-of-year index d (model.utils.day_of_year_index of `times`: 0-based, local time, 365 for 31 December of
+        a leap year), and 0 where no selected day has it -- the reference's fillna(0).groupby('time.dayofyear').mean() and
+        nan_to_num.  The series is what the bank stores: float32 after nan_to_num, and after y_binary_thresh if one was given.
+        days: which days enter, a boolean (D,) selection or a list of (start, stop) ranges checked as `segments` are (default:
+        every stored day), so that the test seasons can be left out.
+        The sums are float64, taken in ascending day order within every index, divided in float64 and rounded to float32 once:
+        round r adds the r-th selected day of every index that has one, each a gather and an indexed add on distinct rows.  No
+        atomics, no kernel of the library: two calls give the same bits.  Meant to run once per experiment."""
+        from model.utils import day_of_year_index
+        D, W, H, Cy = self.y.shape
+        if days is None:
+            picked = np.arange(D)
+        elif (torch.is_tensor(days) and days.dtype == torch.bool) or (isinstance(days, np.ndarray) and days.dtype == np.bool_):
+            sel = days.cpu().numpy() if torch.is_tensor(days) else days
+            if sel.shape != (D,):
+                raise ValueError(f'days: a boolean selection must be ({D},), one entry per stored day, got {sel.shape}')
+            picked = np.flatnonzero(sel)
+        elif isinstance(days, (torch.Tensor, np.ndarray)) or not hasattr(days, '__iter__'):
+            raise ValueError(f'days: must be a boolean ({D},) selection or a list of (start, stop) day ranges, got '
+                             f'{getattr(days, "dtype", type(days).__name__)}')
+        else:
+            picked = np.concatenate([np.arange(s, e) for s, e in day_ranges('days', days, D)] + [np.zeros(0, np.int64)])
+        if not len(picked):
+            raise ValueError('days: no day is selected')
+        index = np.array([day_of_year_index(t) for t in self.times[picked]], dtype=np.int64)
+        order = np.argsort(index, kind='stable')                # by index; ascending days within one (picked is ascending)
+        index, picked = index[order], picked[order]
+        groups, first, count = np.unique(index, return_index=True, return_counts=True)
+        sums = torch.zeros(366, W, H, Cy, dtype=torch.float64, device=self.device)
+        for r in range(int(count.max())):
+            has = count > r
+            rows = torch.from_numpy(groups[has]).to(self.device)
+            sums[rows] = sums[rows] + self.y[torch.from_numpy(picked[first[has] + r]).to(self.device)].double()
+        n = torch.ones(366, dtype=torch.float64)
+        n[torch.from_numpy(groups)] = torch.from_numpy(count).double()
+        return (sums / n.to(self.device)[:, None, None, None]).to(torch.float32).permute(3, 0, 1, 2).contiguous()
 
 
 class ClipLoader:
