@@ -2,7 +2,7 @@
 //   k_spmm  -- the CSR message-aggregate  out = alpha * L^ x + beta * p + gamma * q
 //   k_spmm1 -- the same on single strided columns, with an optional output epilogue
 // The dense products that turn the aggregated planes into outputs are in gemm.hip, the gate-cell launches in gatecell.hip.
-#include "qt_common.h"
+#include "qt_gemm.h"      // (act_quad: the epilogue activation, shared with the dense kernels)
 
 namespace {
 
@@ -266,7 +266,7 @@ __global__ __launch_bounds__(64) void k_spmm1(Spmm1Args a) {
     float v = a.alpha * acc;
     if (a.p) v += a.beta * pv;
     if (a.q) v += a.gamma * qv;
-    if (a.act == QT_ACT_TANH_RES) v = tanhf((a.drop ? a.drop[row] : 1.0f) * v) + a.res[row * a.ldr];
+    if (a.act == QT_ACT_TANH_RES) v = act_quad(v, QT_ACT_TANH_RES, a.drop ? a.drop[row] : 1.0f, a.res[row * a.ldr]);
     if (a.pad4)
         *reinterpret_cast<float4*>(a.out + row * a.ldo) = make_float4(v, 0.0f, 0.0f, 0.0f);
     else

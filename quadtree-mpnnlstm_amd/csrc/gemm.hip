@@ -1,4 +1,6 @@
-// The dense products of the library (operands and argument block: qt_gemm.h):
+// The dense products of the library.  qt_gemm.h holds the operands and the argument block, and the one copy of what these kernels
+// share: the epilogue activation (act_quad, relu_bwd_quad), the 4 x 4 FMA block (fma_quad, post_product), the split store
+// (store_split) and the staged epilogue of the three MFMA kernels (stage_and_store).
 //   k_gemm_fwd -- fp32 MFMA (32x32x2) GEMM: Y = [T_0 .. T_{K-1} | S] W of the Chebyshev planes and the data gradients; with CELL,
 //              the gate GEMM that runs the LSTM cell in its epilogue (launched for gatecell.hip by gemm_fwd_cell_launch)
 //   k_gemm_skinny / k_gemm_row16 / k_head_dgrad -- few output columns or a short reduction (the decoder head), on the VALU
@@ -16,9 +18,10 @@ namespace {
 static constexpr int QT_GEMM_OCC = 4;
 static constexpr int QT_GEMM_OCC3 = 3;
 static constexpr int QT_GEMM_OCC4C = 2;
-template <int NT, int KWT, int CELL = 0>     // CELL: 0 = plain epilogue, else the lanes per node (h / 4) of the fused LSTM cell
-__global__ __launch_bounds__(256, (NT == 4 && CELL != 0) ? QT_GEMM_OCC4C : (NT == 3 ? QT_GEMM_OCC3 : QT_GEMM_OCC)) void k_gemm_fwd(GemmArgs g) {   // 4 workgroups per CU: all N/128 blocks of the
-                                                                      // bench shape are resident at once (<= 128 registers)
+// CELL: 0 = plain epilogue, else the lanes per node (h / 4) of the fused LSTM cell.  Workgroups per CU: 4, so that all N/128
+// blocks of the bench shape are resident at once (<= 128 registers); 3 for NT = 3 and 2 for the NT = 4 cell epilogue.
+template <int NT, int KWT, int CELL = 0>
+__global__ __launch_bounds__(256, (NT == 4 && CELL != 0) ? QT_GEMM_OCC4C : (NT == 3 ? QT_GEMM_OCC3 : QT_GEMM_OCC)) void k_gemm_fwd(GemmArgs g) {
     constexpr int BNT = 32 * NT;
     constexpr int PITCH = KWT + 4;      // == 4 (mod 64) floats: the 16 lanes of a ds_read_b128 group hit distinct banks
     // W chunk TRANSPOSED in LDS, Bt[column][k]: a lane's four B operands of one k-quad are one ds_read_b128
@@ -164,45 +167,8 @@ __global__ __launch_bounds__(256, (NT == 4 && CELL != 0) ? QT_GEMM_OCC4C : (NT =
         }
         return;
     }
-    // Epilogue: an MFMA accumulator holds one COLUMN per lane; staging the tile in LDS (the W buffer is free now) lets
-    // every thread write float4 pieces of output ROWS instead (4x fewer, 16-byte wide, row-contiguous stores).
     static_assert(BNT * PITCH >= BM * 64, "LDS staging tile does not fit in the W buffer");
-#pragma unroll
-    for (int h2 = 0; h2 < (NT + 1) / 2; ++h2) {        // two 32-column MFMA tiles per pass (the last pass of an odd NT: one)
-        __syncthreads();
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const int nt = 2 * h2 + u;
-            if (nt < NT)
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    Cs[(wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * half) * 64 + u * 32 + l32] = acc[nt][r];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int u = 0; u < BM * 16 / 256; ++u) {
-            const int e = t + 256 * u;
-            const int row = e >> 4, c4 = (e & 15) * 4;
-            const int64_t i = i0 + row;
-            const int j = j0 + h2 * 64 + c4;
-            if (i >= rows || j >= g.NB || h2 * 64 + c4 >= BNT) continue;
-            float4 v = *reinterpret_cast<const float4*>(&Cs[row * 64 + c4]);
-            if (g.act == QT_ACT_RELU) {
-                const float d = g.drop ? g.drop[i] : 1.0f;       // (x 1.0f is exact: the same bits without a mask)
-                v.x = fmaxf(d * v.x, 0.0f); v.y = fmaxf(d * v.y, 0.0f); v.z = fmaxf(d * v.z, 0.0f); v.w = fmaxf(d * v.w, 0.0f);
-            }
-            if (g.act == QT_ACT_TANH_RES) {
-                const float d = g.drop ? g.drop[i] : 1.0f, rs = g.res[i * g.res_stride];
-                v.x = tanhf(d * v.x) + rs; v.y = tanhf(d * v.y) + rs; v.z = tanhf(d * v.z) + rs; v.w = tanhf(d * v.w) + rs;
-            }
-            const int ct = g.Cb + g.Cbb;
-            const int pl = j / ct, ch = j - pl * ct;              // Cb, Cbb % 4 == 0: a float4 never straddles two parts
-            if (ch < g.Cb)
-                *reinterpret_cast<float4*>(plane_piece(g.out, pl, i, ch, g.Cb, g.M, g.out_sm, g.ldo ? g.ldo : g.Cb)) = v;
-            else
-                *reinterpret_cast<float4*>(plane_piece(g.outb, pl, i, ch - g.Cb, g.Cbb, g.M, g.out_sm, g.Cbb)) = v;
-        }
-    }
+    stage_and_store<NT>(acc, Cs, g, i0, j0, rows);
 }
 
 // ---- skinny shapes: few output columns (the decoder head: 16 or 4) or a short reduction (its data gradients: K = 16 or 4).
@@ -231,16 +197,6 @@ __global__ __launch_bounds__(256) void k_gemm_skinny(GemmArgs g) {
     const bool ok = row < rows;
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
     const float* __restrict__ Wc = g.B + j;
-    auto step = [&](const float4& a, int Q) {
-        const float4 w0 = *reinterpret_cast<const float4*>(Wc + (int64_t)(4 * Q + 0) * g.NB);
-        const float4 w1 = *reinterpret_cast<const float4*>(Wc + (int64_t)(4 * Q + 1) * g.NB);
-        const float4 w2 = *reinterpret_cast<const float4*>(Wc + (int64_t)(4 * Q + 2) * g.NB);
-        const float4 w3 = *reinterpret_cast<const float4*>(Wc + (int64_t)(4 * Q + 3) * g.NB);
-        acc.x = fmaf(a.x, w0.x, acc.x); acc.y = fmaf(a.x, w0.y, acc.y); acc.z = fmaf(a.x, w0.z, acc.z); acc.w = fmaf(a.x, w0.w, acc.w);
-        acc.x = fmaf(a.y, w1.x, acc.x); acc.y = fmaf(a.y, w1.y, acc.y); acc.z = fmaf(a.y, w1.z, acc.z); acc.w = fmaf(a.y, w1.w, acc.w);
-        acc.x = fmaf(a.z, w2.x, acc.x); acc.y = fmaf(a.z, w2.y, acc.y); acc.z = fmaf(a.z, w2.z, acc.z); acc.w = fmaf(a.z, w2.w, acc.w);
-        acc.x = fmaf(a.w, w3.x, acc.x); acc.y = fmaf(a.w, w3.y, acc.y); acc.z = fmaf(a.w, w3.z, acc.z); acc.w = fmaf(a.w, w3.w, acc.w);
-    };
     auto lda = [&](int Q) {
         float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
         if (ok && Q < nquad) r = gload4(qptr[Q] + row * qstr[Q]);
@@ -252,56 +208,31 @@ __global__ __launch_bounds__(256) void k_gemm_skinny(GemmArgs g) {
         for (int u = 0; u < QT_SKINNY_INFLIGHT; ++u) aq[u] = lda(Q + u);
 #pragma unroll
         for (int u = 0; u < QT_SKINNY_INFLIGHT; ++u)
-            if (Q + u < nquad) step(aq[u], Q + u);
+            if (Q + u < nquad) fma_quad(acc, aq[u], Wc + (int64_t)4 * (Q + u) * g.NB, g.NB);
     }
     const bool post = RPB == 64 && g.post_W != nullptr;       // (uniform; the host guarantees NB == 16: all four waves are here)
     if (!ok && !post) return;
     float4 v = acc;
-    if (g.act == QT_ACT_RELU) {
-        const float d = (g.drop && ok) ? g.drop[row] : 1.0f;
-        v.x = fmaxf(d * v.x, 0.0f); v.y = fmaxf(d * v.y, 0.0f); v.z = fmaxf(d * v.z, 0.0f); v.w = fmaxf(d * v.w, 0.0f);
-    }
-    if (g.act == QT_ACT_RELU_BWD && ok) {          // G = v * relu'(Y): k_act_bwd's arithmetic, Y = g.res (M, res_stride)
-        const float4 y = *reinterpret_cast<const float4*>(g.res + row * g.res_stride + j);
-        v.x = y.x > 0.0f ? v.x : 0.0f; v.y = y.y > 0.0f ? v.y : 0.0f; v.z = y.z > 0.0f ? v.z : 0.0f; v.w = y.w > 0.0f ? v.w : 0.0f;
-    }
+    if (g.act == QT_ACT_RELU) v = act_quad(v, QT_ACT_RELU, (g.drop && ok) ? g.drop[row] : 1.0f, 0.0f);
+    if (g.act == QT_ACT_RELU_BWD && ok)            // G = v * relu'(Y): k_act_bwd's arithmetic, Y = g.res (M, res_stride)
+        v = relu_bwd_quad(v, *reinterpret_cast<const float4*>(g.res + row * g.res_stride + j));
     if constexpr (RPB == 64) {
         if (post) {
-            // the second product, by wave 0 from the tile in LDS: the same fused multiply-adds in the same order as a k_gemm_skinny<256>
-            // launch on the stored rows (quads 0 .. 3 of the row, then the bias quad (1, 0, 0, 0))
+            // the second product, by wave 0 from the tile in LDS
             float* h = &hs[(t & 63) * 17 + j];
             h[0] = v.x; h[1] = v.y; h[2] = v.z; h[3] = v.w;
             __syncthreads();
             if (t < 64 && ok) {
-                float4 u = make_float4(0.f, 0.f, 0.f, 0.f);
                 const float* r = &hs[t * 17];
-#pragma unroll
-                for (int Q = 0; Q <= 4; ++Q) {
-                    const float4 a = Q < 4 ? make_float4(r[4 * Q], r[4 * Q + 1], r[4 * Q + 2], r[4 * Q + 3]) : make_float4(1.f, 0.f, 0.f, 0.f);
-                    const float4 w0 = *reinterpret_cast<const float4*>(g.post_W + (4 * Q + 0) * 4);
-                    const float4 w1 = *reinterpret_cast<const float4*>(g.post_W + (4 * Q + 1) * 4);
-                    const float4 w2 = *reinterpret_cast<const float4*>(g.post_W + (4 * Q + 2) * 4);
-                    const float4 w3 = *reinterpret_cast<const float4*>(g.post_W + (4 * Q + 3) * 4);
-                    u.x = fmaf(a.x, w0.x, u.x); u.y = fmaf(a.x, w0.y, u.y); u.z = fmaf(a.x, w0.z, u.z); u.w = fmaf(a.x, w0.w, u.w);
-                    u.x = fmaf(a.y, w1.x, u.x); u.y = fmaf(a.y, w1.y, u.y); u.z = fmaf(a.y, w1.z, u.z); u.w = fmaf(a.y, w1.w, u.w);
-                    u.x = fmaf(a.z, w2.x, u.x); u.y = fmaf(a.z, w2.y, u.y); u.z = fmaf(a.z, w2.z, u.z); u.w = fmaf(a.z, w2.w, u.w);
-                    u.x = fmaf(a.w, w3.x, u.x); u.y = fmaf(a.w, w3.y, u.y); u.z = fmaf(a.w, w3.z, u.z); u.w = fmaf(a.w, w3.w, u.w);
-                }
-                *reinterpret_cast<float4*>(g.post_out + row * 4) = u;
+                const float4 q[4] = {make_float4(r[0], r[1], r[2], r[3]), make_float4(r[4], r[5], r[6], r[7]),
+                                     make_float4(r[8], r[9], r[10], r[11]), make_float4(r[12], r[13], r[14], r[15])};
+                *reinterpret_cast<float4*>(g.post_out + row * 4) = post_product(q, g.post_W);
             }
             if (!ok) return;
         }
     }
-    if (g.act == QT_ACT_TANH_RES) {
-        const float d = g.drop ? g.drop[row] : 1.0f, rs = g.res[row * g.res_stride];
-        v.x = tanhf(d * v.x) + rs; v.y = tanhf(d * v.y) + rs; v.z = tanhf(d * v.z) + rs; v.w = tanhf(d * v.w) + rs;
-    }
-    const int ct = g.Cb + g.Cbb;
-    const int pl = j / ct, ch = j - pl * ct;
-    if (ch < g.Cb)
-        *reinterpret_cast<float4*>(plane_piece(g.out, pl, row, ch, g.Cb, g.M, g.out_sm, g.Cb)) = v;
-    else
-        *reinterpret_cast<float4*>(plane_piece(g.outb, pl, row, ch - g.Cb, g.Cbb, g.M, g.out_sm, g.Cbb)) = v;
+    if (g.act == QT_ACT_TANH_RES) v = act_quad(v, QT_ACT_TANH_RES, g.drop ? g.drop[row] : 1.0f, g.res[row * g.res_stride]);
+    store_split(g, j, row, v, g.Cb);
 }
 
 // ---- one lane = one node row, ALL 16 output columns: the decoder head's products (fc_out1: 20 -> 16 channels over K = 3 planes,
@@ -353,34 +284,13 @@ __global__ __launch_bounds__(64) void k_gemm_row16(GemmArgs g) {
     if (g.act == QT_ACT_RELU) {
         const float d = g.drop ? g.drop[row] : 1.0f;
 #pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            acc[c].x = fmaxf(d * acc[c].x, 0.0f); acc[c].y = fmaxf(d * acc[c].y, 0.0f); acc[c].z = fmaxf(d * acc[c].z, 0.0f); acc[c].w = fmaxf(d * acc[c].w, 0.0f);
-        }
+        for (int c = 0; c < 4; ++c) acc[c] = act_quad(acc[c], QT_ACT_RELU, d, 0.0f);
     }
     if (g.act == QT_ACT_RELU_BWD) {
 #pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const float4 y = *reinterpret_cast<const float4*>(g.res + row * g.res_stride + 4 * c);
-            acc[c].x = y.x > 0.0f ? acc[c].x : 0.0f; acc[c].y = y.y > 0.0f ? acc[c].y : 0.0f;
-            acc[c].z = y.z > 0.0f ? acc[c].z : 0.0f; acc[c].w = y.w > 0.0f ? acc[c].w : 0.0f;
-        }
+        for (int c = 0; c < 4; ++c) acc[c] = relu_bwd_quad(acc[c], *reinterpret_cast<const float4*>(g.res + row * g.res_stride + 4 * c));
     }
-    if (g.post_W) {
-        float4 u = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int Q = 0; Q <= 4; ++Q) {
-            const float4 a = Q < 4 ? acc[Q] : make_float4(1.f, 0.f, 0.f, 0.f);
-            const float4 w0 = *reinterpret_cast<const float4*>(g.post_W + (4 * Q + 0) * 4);
-            const float4 w1 = *reinterpret_cast<const float4*>(g.post_W + (4 * Q + 1) * 4);
-            const float4 w2 = *reinterpret_cast<const float4*>(g.post_W + (4 * Q + 2) * 4);
-            const float4 w3 = *reinterpret_cast<const float4*>(g.post_W + (4 * Q + 3) * 4);
-            u.x = fmaf(a.x, w0.x, u.x); u.y = fmaf(a.x, w0.y, u.y); u.z = fmaf(a.x, w0.z, u.z); u.w = fmaf(a.x, w0.w, u.w);
-            u.x = fmaf(a.y, w1.x, u.x); u.y = fmaf(a.y, w1.y, u.y); u.z = fmaf(a.y, w1.z, u.z); u.w = fmaf(a.y, w1.w, u.w);
-            u.x = fmaf(a.z, w2.x, u.x); u.y = fmaf(a.z, w2.y, u.y); u.z = fmaf(a.z, w2.z, u.z); u.w = fmaf(a.z, w2.w, u.w);
-            u.x = fmaf(a.w, w3.x, u.x); u.y = fmaf(a.w, w3.y, u.y); u.z = fmaf(a.w, w3.z, u.z); u.w = fmaf(a.w, w3.w, u.w);
-        }
-        *reinterpret_cast<float4*>(g.post_out + row * 4) = u;
-    }
+    if (g.post_W) *reinterpret_cast<float4*>(g.post_out + row * 4) = post_product(acc, g.post_W);
 #pragma unroll
     for (int c = 0; c < 4; ++c) *reinterpret_cast<float4*>(g.out + row * 16 + 4 * c) = acc[c];
 }
@@ -418,7 +328,7 @@ __global__ __launch_bounds__(64) void k_head_dgrad(HeadDgradArgs g) {
             const float4 w = *reinterpret_cast<const float4*>(g.Wb2 + k * 16 + 4 * c);
             a.x = fmaf(guv[k], w.x, a.x); a.y = fmaf(guv[k], w.y, a.y); a.z = fmaf(guv[k], w.z, a.z); a.w = fmaf(guv[k], w.w, a.w);
         }
-        a.x = y[c].x > 0.0f ? a.x : 0.0f; a.y = y[c].y > 0.0f ? a.y : 0.0f; a.z = y[c].z > 0.0f ? a.z : 0.0f; a.w = y[c].w > 0.0f ? a.w : 0.0f;
+        a = relu_bwd_quad(a, y[c]);
         G[4 * c] = a.x; G[4 * c + 1] = a.y; G[4 * c + 2] = a.z; G[4 * c + 3] = a.w;
         if (ok) *reinterpret_cast<float4*>(g.G + row * 16 + 4 * c) = a;
     }
@@ -555,42 +465,7 @@ __global__ __launch_bounds__(256) void k_gemm_fwd3(GemmArgs g) {
             }
         }
     }
-    float* Cs = reinterpret_cast<float*>(Bt);    // 128 rows x 64 columns per pass
-#pragma unroll
-    for (int h2 = 0; h2 < NT / 2; ++h2) {
-        __syncthreads();
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const int nt = 2 * h2 + u;
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-                Cs[(wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * half) * 64 + u * 32 + l32] = acc[nt][r];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int u = 0; u < BM * 16 / 256; ++u) {
-            const int e = t + 256 * u;
-            const int row = e >> 4, c4 = (e & 15) * 4;
-            const int64_t i = i0 + row;
-            const int j = j0 + h2 * 64 + c4;
-            if (i >= rows || j >= g.NB) continue;
-            float4 v = *reinterpret_cast<const float4*>(&Cs[row * 64 + c4]);
-            if (g.act == QT_ACT_RELU) {
-                const float d = g.drop ? g.drop[i] : 1.0f;       // (x 1.0f is exact: the same bits without a mask)
-                v.x = fmaxf(d * v.x, 0.0f); v.y = fmaxf(d * v.y, 0.0f); v.z = fmaxf(d * v.z, 0.0f); v.w = fmaxf(d * v.w, 0.0f);
-            }
-            if (g.act == QT_ACT_TANH_RES) {
-                const float d = g.drop ? g.drop[i] : 1.0f, rs = g.res[i * g.res_stride];
-                v.x = tanhf(d * v.x) + rs; v.y = tanhf(d * v.y) + rs; v.z = tanhf(d * v.z) + rs; v.w = tanhf(d * v.w) + rs;
-            }
-            const int ct = g.Cb + g.Cbb;
-            const int pl = j / ct, ch = j - pl * ct;
-            if (ch < g.Cb)
-                *reinterpret_cast<float4*>(plane_piece(g.out, pl, i, ch, g.Cb, g.M, g.out_sm, g.Cb)) = v;
-            else
-                *reinterpret_cast<float4*>(plane_piece(g.outb, pl, i, ch - g.Cb, g.Cbb, g.M, g.out_sm, g.Cbb)) = v;
-        }
-    }
+    stage_and_store<NT>(acc, reinterpret_cast<float*>(Bt), g, i0, j0, rows);
 }
 
 // Data-gradient GEMM as a split-bf16 product (gradients only): out planes = A (N x K fp32 rows) @ B, with B^T given as two bf16
@@ -666,34 +541,7 @@ __global__ __launch_bounds__(256, 4) void k_gemm_sb(GemmArgs g, const __bf16* __
             }
         }
     }
-    float* Cs = reinterpret_cast<float*>(lds);    // 128 rows x 64 columns per pass
-#pragma unroll
-    for (int h2 = 0; h2 < NT / 2; ++h2) {
-        __syncthreads();
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const int nt = 2 * h2 + u;
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-                Cs[(wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * half) * 64 + u * 32 + l32] = acc[nt][r];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int u = 0; u < BM * 16 / 256; ++u) {
-            const int e = t + 256 * u;
-            const int row = e >> 4, c4 = (e & 15) * 4;
-            const int64_t i = i0 + row;
-            const int j = j0 + h2 * 64 + c4;
-            if (i >= rows || j >= g.NB) continue;
-            const float4 v = *reinterpret_cast<const float4*>(&Cs[row * 64 + c4]);
-            const int ct = g.Cb + g.Cbb;
-            const int pl = j / ct, ch = j - pl * ct;
-            if (ch < g.Cb)
-                *reinterpret_cast<float4*>(plane_piece(g.out, pl, i, ch, g.Cb, g.M, g.out_sm, g.Cb)) = v;
-            else
-                *reinterpret_cast<float4*>(plane_piece(g.outb, pl, i, ch - g.Cb, g.Cbb, g.M, g.out_sm, g.Cbb)) = v;
-        }
-    }
+    stage_and_store<NT>(acc, reinterpret_cast<float*>(lds), g, i0, j0, rows);      // (g.act == QT_ACT_NONE: no activation)
 }
 
 constexpr int WR = 32;

@@ -1,5 +1,7 @@
 // What the dense products (gemm.hip) and the gate-cell launches (gatecell.hip) both need: the node-feature operand and the
-// argument block of the GEMM kernels, the tile constants, and the device helpers that address planes and rows.
+// argument block of the GEMM kernels, the tile constants, the device helpers that address planes and rows, and the pieces the
+// dense kernels share: act_quad / relu_bwd_quad, fma_quad / post_product, store_split and stage_and_store (cheb.hip's
+// k_spmm1 takes act_quad from here too).
 #pragma once
 #include "qt_common.h"
 
@@ -44,7 +46,7 @@ struct GemmArgs {
     int64_t row0_step;  // wgrad: rows per block
     const int32_t* n_dev;  // valid node rows on the device (NULL: A.N)
     int accumulate;        // wgrad: add into part instead of overwriting (sums several uses of one weight)
-    // gate GEMM with the LSTM cell as its epilogue (k_gemm_fwd<2, 128, true>): the (N, 4h) pre-activations never leave LDS
+    // gate GEMM with the LSTM cell as its epilogue (k_gemm_fwd<NT, KWT, CELL = h / 4>): the (N, 4h) pre-activations never leave LDS
     const float* Cprev;
     const float* wc;
     const float* bias;
@@ -84,6 +86,94 @@ __device__ __forceinline__ float4 gload4(const float* p) {
 __device__ __forceinline__ float* plane_piece(float* base, int pl, int64_t i, int ch, int C, int64_t M, int sm, int ld) {
     if (sm && pl > 0) return base + (((int64_t)pl * (C >> 2) + (ch >> 2)) * M + i) * 4;
     return base + (int64_t)pl * M * C + i * ld + ch;
+}
+
+// ---- the arithmetic and the stores that several dense kernels share.  One copy each: the kernels' bit-identity claims
+// ("the same fused multiply-adds in the same order as ...") rest on these staying the same everywhere.
+
+// Epilogue activation: QT_ACT_RELU = max(d v, 0), QT_ACT_TANH_RES = tanh(d v) + rs, d = the row's dropout factor (a row
+// without a mask passes 1.0f: x 1.0f is exact, the same bits), rs = the row's residual.  Any other act: v unchanged.
+__device__ __forceinline__ float act_quad(float v, int act, float d, float rs) {
+    if (act == QT_ACT_RELU) return fmaxf(d * v, 0.0f);
+    if (act == QT_ACT_TANH_RES) return tanhf(d * v) + rs;
+    return v;
+}
+__device__ __forceinline__ float4 act_quad(float4 v, int act, float d, float rs) {
+    if (act == QT_ACT_RELU) v = make_float4(fmaxf(d * v.x, 0.0f), fmaxf(d * v.y, 0.0f), fmaxf(d * v.z, 0.0f), fmaxf(d * v.w, 0.0f));
+    if (act == QT_ACT_TANH_RES) v = make_float4(tanhf(d * v.x) + rs, tanhf(d * v.y) + rs, tanhf(d * v.z) + rs, tanhf(d * v.w) + rs);
+    return v;
+}
+// QT_ACT_RELU_BWD: v * relu'(y), y = the forward output
+__device__ __forceinline__ float4 relu_bwd_quad(float4 v, float4 y) {
+    return make_float4(y.x > 0.0f ? v.x : 0.0f, y.y > 0.0f ? v.y : 0.0f, y.z > 0.0f ? v.z : 0.0f, y.w > 0.0f ? v.w : 0.0f);
+}
+
+// acc (4 output columns) += a (4 consecutive k) x the 4 x 4 block of W whose rows start at W, ldw apart: sixteen fused multiply-adds, k ascending
+__device__ __forceinline__ void fma_quad(float4& acc, const float4& a, const float* __restrict__ W, int64_t ldw) {
+    const float4 w0 = *reinterpret_cast<const float4*>(W);
+    const float4 w1 = *reinterpret_cast<const float4*>(W + ldw);
+    const float4 w2 = *reinterpret_cast<const float4*>(W + 2 * ldw);
+    const float4 w3 = *reinterpret_cast<const float4*>(W + 3 * ldw);
+    acc.x = fmaf(a.x, w0.x, acc.x); acc.y = fmaf(a.x, w0.y, acc.y); acc.z = fmaf(a.x, w0.z, acc.z); acc.w = fmaf(a.x, w0.w, acc.w);
+    acc.x = fmaf(a.y, w1.x, acc.x); acc.y = fmaf(a.y, w1.y, acc.y); acc.z = fmaf(a.y, w1.z, acc.z); acc.w = fmaf(a.y, w1.w, acc.w);
+    acc.x = fmaf(a.z, w2.x, acc.x); acc.y = fmaf(a.z, w2.y, acc.y); acc.z = fmaf(a.z, w2.z, acc.z); acc.w = fmaf(a.z, w2.w, acc.w);
+    acc.x = fmaf(a.w, w3.x, acc.x); acc.y = fmaf(a.w, w3.y, acc.y); acc.z = fmaf(a.w, w3.z, acc.z); acc.w = fmaf(a.w, w3.w, acc.w);
+}
+// The decoder head's second product, (4 columns) = [q[0] .. q[3] | 1 0 0 0] @ post_W (20, 4): the fused multiply-adds, in the
+// order, of a k_gemm_skinny<256> launch on the stored 16-column row (quads 0 .. 3, then the bias quad)
+__device__ __forceinline__ float4 post_product(const float4 (&q)[4], const float* __restrict__ post_W) {
+    float4 u = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int Q = 0; Q <= 4; ++Q) fma_quad(u, Q < 4 ? q[Q] : make_float4(1.f, 0.f, 0.f, 0.f), post_W + 16 * Q, 4);
+    return u;
+}
+
+// float4 v = columns j .. j + 3 of output row i: to its plane and part (out | outb; Cb, Cbb % 4 == 0: a float4 never straddles
+// two parts).  ld: the row stride of part a (g.Cb, or g.ldo for a column block of a wider matrix)
+__device__ __forceinline__ void store_split(const GemmArgs& g, int j, int64_t i, float4 v, int ld) {
+    const int ct = g.Cb + g.Cbb;
+    const int pl = j / ct, ch = j - pl * ct;
+    if (ch < g.Cb)
+        *reinterpret_cast<float4*>(plane_piece(g.out, pl, i, ch, g.Cb, g.M, g.out_sm, ld)) = v;
+    else
+        *reinterpret_cast<float4*>(plane_piece(g.outb, pl, i, ch - g.Cb, g.Cbb, g.M, g.out_sm, g.Cbb)) = v;
+}
+
+// The staged epilogue of the MFMA kernels (256 threads, wave w owns rows [32 w, 32 w + 32) of the 128 x 32 NT tile at (i0, j0)).
+// An MFMA accumulator holds one COLUMN per lane; staging the tile in LDS (Cs: BM x 64 floats, the W buffer, free by now) lets
+// every thread write float4 pieces of output ROWS instead (4x fewer, 16-byte wide, row-contiguous stores).  Two 32-column MFMA
+// tiles per pass (the last pass of an odd NT: one).  Every thread of the workgroup must call it: both barriers of a pass are
+// outside any divergent code.
+template <int NT>
+__device__ __forceinline__ void stage_and_store(f32x16 (&acc)[NT], float* Cs, const GemmArgs& g, int64_t i0, int j0, int64_t rows) {
+    const int t = threadIdx.x, wave = t >> 6, l32 = t & 31, half = (t >> 5) & 1;
+    const int ld = g.ldo ? g.ldo : g.Cb;
+#pragma unroll
+    for (int h2 = 0; h2 < (NT + 1) / 2; ++h2) {
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int nt = 2 * h2 + u;
+            if (nt < NT)
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    Cs[(wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * half) * 64 + u * 32 + l32] = acc[nt][r];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < BM * 16 / 256; ++u) {
+            const int e = t + 256 * u;
+            const int row = e >> 4, c4 = (e & 15) * 4;
+            const int64_t i = i0 + row;
+            const int j = j0 + h2 * 64 + c4;
+            if (i >= rows || j >= g.NB || h2 * 64 + c4 >= 32 * NT) continue;
+            float4 v = *reinterpret_cast<const float4*>(&Cs[row * 64 + c4]);
+            // (a call per activation: g.drop and g.res are read only under the test that needs them -- res may be null otherwise)
+            if (g.act == QT_ACT_RELU) v = act_quad(v, QT_ACT_RELU, g.drop ? g.drop[i] : 1.0f, 0.0f);
+            if (g.act == QT_ACT_TANH_RES) v = act_quad(v, QT_ACT_TANH_RES, g.drop ? g.drop[i] : 1.0f, g.res[i * g.res_stride]);
+            store_split(g, j, i, v, ld);
+        }
+    }
 }
 
 // Quad table: quad Q of a node row lives at qptr[Q] + row * qstr[Q] (plane Q*4/Ca of the operand, or S).
