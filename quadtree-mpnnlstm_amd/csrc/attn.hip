@@ -7,39 +7,20 @@
 //
 // q | k | v | skip are the four column blocks of ONE projection GEMM (proj, row stride ld).  Incoming edges of i are
 // row i of the mesh CSR (the quadtree adjacency is symmetric) plus the self pair (i, i) that get_adj emits for
-// multi-pixel cells (attrs (0, 0)); edge attributes are recomputed from the node centroids instead of being stored.
-// One node per group of C/4 lanes (float4 each), online softmax, dot products reduced with xor shuffles.
-// Backward in gather form, no atomics: pass A per target (dq_i + the messages' coefficients), pass B per source (dk_j, dv_j, dWe partials).
-#include "qt_common.h"
-#include <math.h>
+// multi-pixel cells (attrs (0, 0)); edge attributes come from the node centroids, once per mesh (qt_attn_edge_attrs).
+// One node per group of C/4 lanes (float4 each), online softmax, dot products reduced with xor shuffles: the lane-group
+// primitives, the dropout rule, the trip over a node's pairs and the forward's node body are qt_attn.h's, shared with mhattn.hip
+// and attnw.hip.  Here: the operand views of a G-head launch, the forward kernel around node_forward, and the backward in gather
+// form, no atomics: pass A per target (dq_i + the messages' coefficients), pass B per source (dk_j, dv_j, dWe partials).
+#include "qt_attn.h"
 
 namespace {
-
-struct F4 {
-    float v[4];
-};
-__device__ __forceinline__ F4 ld4(const float* p) {
-    const float4 f = *reinterpret_cast<const float4*>(p);
-    return F4{{f.x, f.y, f.z, f.w}};
-}
-__device__ __forceinline__ void st4(float* p, const F4& a) {
-    *reinterpret_cast<float4*>(p) = make_float4(a.v[0], a.v[1], a.v[2], a.v[3]);
-}
-template <int LPN>
-__device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-    for (int d = 1; d < LPN; d <<= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-__device__ __forceinline__ float dot4(const F4& a, const F4& b) {
-    return (a.v[0] * b.v[0] + a.v[1] * b.v[1]) + (a.v[2] * b.v[2] + a.v[3] * b.v[3]);
-}
+using namespace qtattn;
 
 struct AttnArgs {
     const int32_t* rowptr;
     const int32_t* col;
-    const float* xy;        // (N, 2): centroid x, y in edge-attribute units
-    const float* eattr;     // (E, 2) [angle, dist] of the message col[e] -> row(e), or NULL: recomputed from xy per lane
+    const float* eattr;     // (E, 2) [angle, dist] of the message col[e] -> row(e) (qt_attn_edge_attrs)
     const float* selfloop;  // (N) > 0 where the node carries a self pair, or NULL
     const float* proj;      // (N, ld): q | k | v | skip, C columns each
     const float* We;        // (C, 2)
@@ -53,10 +34,9 @@ struct AttnArgs {
     int ld_g;               // backward: row stride of g (a column block of a wider gradient is read in place)
     int accumulate;         // backward: add the We partials into `part` (several uses of one convolution share the slab)
     uint32_t seed;
-    const uint32_t* seed_dev;   // optional step counter on the device, mixed into the seed: a captured launch (fixed `seed`
-                                // argument) then still draws a new dropout mask at every replay
+    const uint32_t* seed_dev;   // optional step counter on the device, mixed into the seed (head_seed)
     // G convolutions on the same mesh in one launch (blockIdx.y = head): head g reads the column block [g 4C, (g+1) 4C) of the
-    // proj rows (ld >= G 4C), We[g], writes the column block g C of the out rows (ld_o) and its own stats / Dn / coef / part
+    // proj rows (ld >= G 4C), We[g], writes the column block g C of the out rows (ld_o) and its own stats / coef / part
     // slabs.  gmod: head g reads the column block (g % gmod) C of the incoming gradient (a sum of head groups downstream).
     int ld_o, gmod;
     // strides in floats: ps between the q / k / v / skip blocks of a proj (and gproj) row, hs between heads of proj, hs_o of out,
@@ -65,37 +45,22 @@ struct AttnArgs {
     int64_t ps, hs, hs_o, hs_g;
 };
 
-// per-head views of the operands (head = blockIdx.y; a single convolution is head 0 of 1)
+// Per-head views of the operands (a single convolution is head 0 of 1); returns the head of this workgroup.
+// Last in, first out over the heads: an 8-head operand is 510 MB, the memory-side cache 256 MB, so a launch should start with
+// the heads its predecessor touched last.  The grouped projection writes heads 0..7 -> the forward pass walks 7..0; in the
+// backward the target pass walks 7..0, the source pass 0..7 (it re-reads the q planes the target pass just read), and the data
+// gradient after it takes its groups 7..0 (qt_proj_group, reverse).  cfg4t: 47.1 ms per step with every launch ascending,
+// 46.6 with the three passes descending, 46.2 with this order.
 static constexpr int QT_ATTN_DESC = 3;      // bit 0 / 1 / 2: the forward / target / source pass walks the heads from the last to the first
 template <int PASS>
 __device__ __forceinline__ int head_setup(AttnArgs& a) {
-    if (!((QT_ATTN_DESC >> PASS) & 1)) {
-        const int hd0 = blockIdx.y;
-        if (hd0) {
-            a.proj += hd0 * a.hs;
-            a.We += (int64_t)hd0 * 2 * a.C;
-            if (a.coef) a.coef += (int64_t)hd0 * 2 * ((int64_t)a.E + a.Ncap);
-            a.seed += (uint32_t)hd0 * 0x632BE5ABu;
-        }
-        return hd0;
-    }
-    // Last in, first out over the heads: an 8-head operand is 510 MB, the memory-side cache 256 MB, so a launch should start with
-    // the heads its predecessor touched last.  The grouped projection writes heads 0..7 -> the forward pass walks 7..0; in the
-    // backward the target pass walks 7..0, the source pass 0..7 (it re-reads the q planes the target pass just read), and the data
-    // gradient after it takes its groups 7..0 (qt_proj_group, reverse).  cfg4t: 47.1 ms per step with every launch ascending,
-    // 46.6 with the three passes descending, 46.2 with this order.
-    const int hd = (int)gridDim.y - 1 - (int)blockIdx.y;
+    const int hd = (QT_ATTN_DESC >> PASS) & 1 ? (int)gridDim.y - 1 - (int)blockIdx.y : (int)blockIdx.y;
     if (hd) {
         a.proj += hd * a.hs;
         a.We += (int64_t)hd * 2 * a.C;
         if (a.coef) a.coef += (int64_t)hd * 2 * ((int64_t)a.E + a.Ncap);
-        a.seed += (uint32_t)hd * 0x632BE5ABu;        // every head draws its own attention-dropout mask
     }
     return hd;
-}
-
-__device__ __forceinline__ uint32_t eff_seed(const AttnArgs& a) {
-    return a.seed_dev ? a.seed ^ (*a.seed_dev * 0x9E3779B9u) : a.seed;
 }
 
 // [angle, dist] of the message j -> i from (dx, dy) = xy_j - xy_i (graph_functions.py:358-370): atan2(dx, dy) mod 2pi / 2pi
@@ -106,56 +71,11 @@ __device__ __forceinline__ void edge_attr_xy(float dx, float dy, float* ang, flo
     *dst = sqrtf(dy * dy + dx * dx);
 }
 
-// inverted-dropout multiplier of the attention coefficient of edge (j -> i): the same in forward and both backward passes
-__device__ __forceinline__ float drop_mult(uint32_t seed, int i, int j, float keep) {
-    if (keep >= 1.0f) return 1.0f;
-    uint32_t h = seed ^ ((uint32_t)i * 0x9E3779B1u) ^ ((uint32_t)j * 0x85EBCA77u);
-    h ^= h >> 16; h *= 0x7FEB352Du; h ^= h >> 15; h *= 0x846CA68Bu; h ^= h >> 16;
-    return ((h >> 8) * (1.0f / 16777216.0f)) < keep ? 1.0f / keep : 0.0f;
-}
-
-// Workgroups are dealt round-robin to the 8 XCDs, each with a private L2: XCD x gets the contiguous node range
-// [x * chunk, (x + 1) * chunk) (chunk from the VALID rows), so a node's neighbours -- close in the mesh's node order -- sit in
-// the L2 that gathers them (the same mapping as k_spmm).  Returns the node-group index of this workgroup or -1.
-__device__ __forceinline__ int xcd_block(int rows, int nodes_per_block) {
-    const int nblk = (rows + nodes_per_block - 1) / nodes_per_block;
-    const int chunk = (nblk + 7) >> 3;
-    const int bid = blockIdx.x;
-    if ((bid >> 3) >= chunk) return -1;
-    return (bid & 7) * chunk + (bid >> 3);
-}
-
-#ifndef QT_ATTN_EPT
-#define QT_ATTN_EPT 2     // edges per trip (their gathers are issued together).  8 heads at the cfg4 shapes, forward / target /
-                          // source pass: 1: 178 / 258 / 194 us, 2: 158 / 266 / 181, 4: 202 / 313 / 231 -- fewer registers, more waves
-#endif
-constexpr int EPT = QT_ATTN_EPT;
-// register budgets: waves per SIMD the forward / target / source kernels are compiled for (0 = the compiler's choice)
-#define QT_ATTN_OCC_F 0
-#define QT_ATTN_OCC_T 0
-#define QT_ATTN_OCC_S 0
-#define QT_WAVES_ATTR_(n) __attribute__((amdgpu_waves_per_eu(n, n)))
-#define QT_WAVES_ATTR(n) QT_WAVES_ATTR_(n)
-#if QT_ATTN_OCC_F
-#define QT_ATTN_WAVES_F QT_WAVES_ATTR(QT_ATTN_OCC_F)
-#else
-#define QT_ATTN_WAVES_F
-#endif
-#if QT_ATTN_OCC_T
-#define QT_ATTN_WAVES_T QT_WAVES_ATTR(QT_ATTN_OCC_T)
-#else
-#define QT_ATTN_WAVES_T
-#endif
-#if QT_ATTN_OCC_S
-#define QT_ATTN_WAVES_S QT_WAVES_ATTR(QT_ATTN_OCC_S)
-#else
-#define QT_ATTN_WAVES_S
-#endif
 static constexpr int QT_ATTN_BS = 64;      // one wave per workgroup (forward 32.4 -> 31.0 us at the cfg4 shapes; 128: 31.3)
 // Addresses: the block bases (head, q / k / v / skip block) are uniform, so a row is reached as base + a 32-bit element offset
 // (one VGPR per address instead of a 64-bit pair; the host checks that a head's rows span < 2^31 floats).
 template <int LPN>
-__global__ __launch_bounds__(QT_ATTN_BS) QT_ATTN_WAVES_F void k_attn_fwd(AttnArgs a, float* __restrict__ out, float* __restrict__ stats) {
+__global__ __launch_bounds__(QT_ATTN_BS) void k_attn_fwd(AttnArgs a, float* __restrict__ out, float* __restrict__ stats) {
     const int hd = head_setup<0>(a);
     out += hd * a.hs_o;
     stats += (int64_t)hd * 2 * a.Ncap;
@@ -164,68 +84,11 @@ __global__ __launch_bounds__(QT_ATTN_BS) QT_ATTN_WAVES_F void k_attn_fwd(AttnArg
     if (blk < 0) return;
     const int i = blk * (QT_ATTN_BS / LPN) + (int)threadIdx.x / LPN;
     if (i >= rows) return;
-    const uint32_t j0 = ((uint32_t)threadIdx.x % LPN) * 4, ld = a.ld;
-    const float* __restrict__ kb = a.proj + a.ps;
-    const float* __restrict__ vb = a.proj + 2 * a.ps;
-    const F4 q = ld4(a.proj + ((uint32_t)i * ld + j0));
-    const F4 w0 = {{a.We[2 * j0], a.We[2 * j0 + 2], a.We[2 * j0 + 4], a.We[2 * j0 + 6]}};
-    const F4 w1 = {{a.We[2 * j0 + 1], a.We[2 * j0 + 3], a.We[2 * j0 + 5], a.We[2 * j0 + 7]}};
-    float m = -INFINITY, l = 0.0f;
-    F4 acc = {{0, 0, 0, 0}};
-    const int e0 = a.rowptr[i], e1 = a.rowptr[i + 1];
-    const int extra = (a.selfloop && a.selfloop[i] > 0.0f) ? 1 : 0;
-    const uint32_t seed = eff_seed(a);
-    const int eend = e1 + extra;
-    for (int eb = e0; eb < eend; eb += EPT) {
-        // the gathers of EPT edges are issued together; the online-softmax updates then run in edge order
-        int jj[EPT];
-        F4 kk[EPT], vv[EPT];
-        float2 ea[EPT];
-#pragma unroll
-        for (int u = 0; u < EPT; ++u) {
-            const int e = eb + u;
-            jj[u] = e < e1 ? a.col[e] : (e < eend ? i : -1);
-        }
-#pragma unroll
-        for (int u = 0; u < EPT; ++u)
-            if (jj[u] >= 0) {
-                const uint32_t off = (uint32_t)jj[u] * ld + j0;
-                kk[u] = ld4(kb + off);
-                vv[u] = ld4(vb + off);
-                ea[u] = eb + u < e1 ? *reinterpret_cast<const float2*>(a.eattr + 2 * (uint32_t)(eb + u)) : make_float2(0.0f, 0.0f);
-            }
-#pragma unroll
-        for (int u = 0; u < EPT; ++u) {
-            if (jj[u] < 0) break;                  // (uniform over the node's lane group)
-            const int j = jj[u];
-            const float ang = ea[u].x, dst = ea[u].y;       // stored per edge: no atan2 / sqrt in the loop
-            F4 kj = kk[u], vj = vv[u];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const float ee = w0.v[c] * ang + w1.v[c] * dst;
-                kj.v[c] += ee;
-                vj.v[c] += ee;
-            }
-            const float s = group_sum<LPN>(dot4(q, kj)) * a.scale;
-            const float mn = fmaxf(m, s);
-            const float r = __expf(m - mn), p = __expf(s - mn);       // m = -inf on the first edge: r = 0
-            const float pd = p * drop_mult(seed, i, j, a.keep);
-            l = l * r + p;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) acc.v[c] = acc.v[c] * r + pd * vj.v[c];
-            m = mn;
-        }
-    }
-    const F4 sk = ld4(a.proj + 3 * a.ps + ((uint32_t)i * ld + j0));
-    const float inv = l > 0.0f ? 1.0f / l : 0.0f;
-    F4 o;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) o.v[c] = acc.v[c] * inv + sk.v[c];
-    st4(out + ((uint32_t)i * (uint32_t)a.ld_o + j0), o);
-    if (j0 == 0) {
-        stats[2 * i] = m;
-        stats[2 * i + 1] = l;
-    }
+    const uint32_t j0 = ((uint32_t)threadIdx.x % LPN) * 4;
+    const NodeOut r = node_forward<LPN>(a.rowptr, a.col, a.eattr, a.selfloop, a.proj, a.proj + a.ps, a.proj + 2 * a.ps, a.proj + 3 * a.ps,
+                                        a.ld, a.We, i, j0, a.scale, a.keep, head_seed(a.seed, a.seed_dev, hd));
+    st4(out + ((uint32_t)i * (uint32_t)a.ld_o + j0), r.o);
+    put_stats(stats, i, j0, r);
 }
 
 // pass A: per target i -- dq_i = scale * sum_e alpha_e (t_e - D_i)(k_j + e), t_e = d_e g_i.(v_j + e), D_i = sum_e alpha_e t_e.
@@ -235,7 +98,7 @@ __global__ __launch_bounds__(QT_ATTN_BS) QT_ATTN_WAVES_F void k_attn_fwd(AttnArg
 // transposed entry (row j, column i), which pass B then reads in row order -- no gather of coefficients, softmax statistics or D_i
 // over there, only the q_i / g_i rows.
 template <int LPN>
-__global__ __launch_bounds__(QT_ATTN_BS) QT_ATTN_WAVES_T void k_attn_bwd_target(AttnArgs a, const float* __restrict__ g, const float* __restrict__ stats,
+__global__ __launch_bounds__(QT_ATTN_BS) void k_attn_bwd_target(AttnArgs a, const float* __restrict__ g, const float* __restrict__ stats,
                                                          const float* __restrict__ outf, float* __restrict__ gproj) {
     const int hd = head_setup<1>(a);
     g += (hd % a.gmod) * a.hs_g;
@@ -260,43 +123,31 @@ __global__ __launch_bounds__(QT_ATTN_BS) QT_ATTN_WAVES_T void k_attn_bwd_target(
         for (int c = 0; c < 4; ++c) att.v[c] = of.v[c] - sk.v[c];
         D = group_sum<LPN>(dot4(gi, att));
     }
-    const F4 w0 = {{a.We[2 * j0], a.We[2 * j0 + 2], a.We[2 * j0 + 4], a.We[2 * j0 + 6]}};
-    const F4 w1 = {{a.We[2 * j0 + 1], a.We[2 * j0 + 3], a.We[2 * j0 + 5], a.We[2 * j0 + 7]}};
+    F4 w0, w1;
+    we_columns(a.We, j0, &w0, &w1);
     const float m = stats[2 * i], l = stats[2 * i + 1];
     const float inv = l > 0.0f ? 1.0f / l : 0.0f;
     const int e0 = a.rowptr[i], e1 = a.rowptr[i + 1];
     const int extra = (a.selfloop && a.selfloop[i] > 0.0f) ? 1 : 0;
     F4 dq = {{0, 0, 0, 0}};
-    const uint32_t seed = eff_seed(a);
+    const uint32_t seed = head_seed(a.seed, a.seed_dev, hd);
     const int eend = e1 + extra;
     // A target with ONE pair has alpha = 1 and t = D: its score gradient is an exact zero.  D is taken from the stored output,
     // (v_j + e + skip_i) - skip_i, which has lost what the forward's rounding took, so t - D would leave g . skip x 2^-24 of noise
     // in dq_i / dk_j where the exact gradient (and any evaluation that forms D from the same products as t) is 0.
     const bool one_pair = eend - e0 == 1;
     for (int eb = e0; eb < eend; eb += EPT) {
-        int jj[EPT], rv[EPT];
-        F4 kk[EPT], vv[EPT];
-        float2 ea[EPT];
+        int rv[EPT];                    // where pair u's coefficients go: the transposed entry's slot, E + i for the self pair
+#pragma unroll
+        for (int u = 0; u < EPT; ++u) rv[u] = eb + u < e1 ? a.rev[eb + u] : a.E + i;
+        Trip tr;
+        tr.gather(a.col, a.eattr, kb, vb, ld, j0, i, eb, e1, eend);
 #pragma unroll
         for (int u = 0; u < EPT; ++u) {
-            const int e = eb + u;
-            jj[u] = e < e1 ? a.col[e] : (e < eend ? i : -1);
-            rv[u] = e < e1 ? a.rev[e] : a.E + i;
-        }
-#pragma unroll
-        for (int u = 0; u < EPT; ++u)
-            if (jj[u] >= 0) {
-                const uint32_t off = (uint32_t)jj[u] * ld + j0;
-                kk[u] = ld4(kb + off);
-                vv[u] = ld4(vb + off);
-                ea[u] = eb + u < e1 ? *reinterpret_cast<const float2*>(a.eattr + 2 * (uint32_t)(eb + u)) : make_float2(0.0f, 0.0f);
-            }
-#pragma unroll
-        for (int u = 0; u < EPT; ++u) {
-            if (jj[u] < 0) break;
-            const int j = jj[u];
-            const float ang = ea[u].x, dst = ea[u].y;
-            F4 kj = kk[u], vj = vv[u];
+            if (tr.jj[u] < 0) break;
+            const int j = tr.jj[u];
+            const float ang = tr.ea[u].x, dst = tr.ea[u].y;
+            F4 kj = tr.kk[u], vj = tr.vv[u];
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 const float ee = w0.v[c] * ang + w1.v[c] * dst;
@@ -321,7 +172,7 @@ __global__ __launch_bounds__(QT_ATTN_BS) QT_ATTN_WAVES_T void k_attn_bwd_target(
 // the coefficients of j -> i were left at this row's own slots by pass A:
 //   dk_j = sum_i ds q_i,  dv_j = sum_i ad g_i,  dWe = sum_edges (dk + dv terms) [angle, dist]
 template <int LPN>
-__global__ __launch_bounds__(256) QT_ATTN_WAVES_S void k_attn_bwd_source(AttnArgs a, const float* __restrict__ g, float* __restrict__ gproj,
+__global__ __launch_bounds__(256) void k_attn_bwd_source(AttnArgs a, const float* __restrict__ g, float* __restrict__ gproj,
                                                          float* __restrict__ part) {
     __shared__ float sm[4 * LPN * 2 * 4];
     const int hd = head_setup<2>(a);
@@ -440,32 +291,19 @@ __global__ void k_attn_edge_attrs(const int32_t* __restrict__ rowptr, const int3
     }
 }
 
-inline bool c_ok(int C) { return C == 4 || C == 8 || C == 16 || C == 32 || C == 64 || C == 128; }
+constexpr int LPN_MAX = 32;       // C = 4 .. 128
+
+void fill_args(AttnArgs* a, const int32_t* rowptr, const int32_t* col, const float* eattr, const float* selfloop, const float* proj,
+               int ld, const float* We, int C, int c_real, int N, const int32_t* n_dev, float keep, uint32_t seed,
+               const uint32_t* seed_dev) {
+    a->rowptr = rowptr; a->col = col; a->eattr = eattr; a->selfloop = selfloop; a->proj = proj; a->We = We;
+    a->ld = ld; a->C = C; a->Ncap = N; a->n_dev = n_dev; a->scale = 1.0f / sqrtf((float)c_real); a->keep = keep; a->seed = seed; a->seed_dev = seed_dev;
+}
 
 }  // namespace
 
-#define QT_ATTN_DISPATCH_BS(C, KERNEL, grid, BS, stream, ...)                                                               \
-    switch ((C) / 4) {                                                                                               \
-        case 1: hipLaunchKernelGGL(KERNEL<1>, dim3(grid), dim3(BS), 0, (hipStream_t)stream, __VA_ARGS__); break;    \
-        case 2: hipLaunchKernelGGL(KERNEL<2>, dim3(grid), dim3(BS), 0, (hipStream_t)stream, __VA_ARGS__); break;    \
-        case 4: hipLaunchKernelGGL(KERNEL<4>, dim3(grid), dim3(BS), 0, (hipStream_t)stream, __VA_ARGS__); break;    \
-        case 8: hipLaunchKernelGGL(KERNEL<8>, dim3(grid), dim3(BS), 0, (hipStream_t)stream, __VA_ARGS__); break;    \
-        case 16: hipLaunchKernelGGL(KERNEL<16>, dim3(grid), dim3(BS), 0, (hipStream_t)stream, __VA_ARGS__); break;  \
-        default: hipLaunchKernelGGL(KERNEL<32>, dim3(grid), dim3(BS), 0, (hipStream_t)stream, __VA_ARGS__); break;  \
-    }
-
-#define QT_ATTN_DISPATCH(C, KERNEL, grid, stream, ...) QT_ATTN_DISPATCH_BS(C, KERNEL, grid, 256, stream, __VA_ARGS__)
-
-static int fill_args(AttnArgs* a, const int32_t* rowptr, const int32_t* col, const float* xy, const float* eattr, const float* selfloop,
-                     const float* proj, int ld, const float* We, int C, int c_real, int N, const int32_t* n_dev,
-                     float keep, uint32_t seed, const uint32_t* seed_dev) {
-    a->rowptr = rowptr; a->col = col; a->xy = xy; a->eattr = eattr; a->selfloop = selfloop; a->proj = proj; a->We = We;
-    a->ld = ld; a->C = C; a->Ncap = N; a->n_dev = n_dev; a->scale = 1.0f / sqrtf((float)c_real); a->keep = keep; a->seed = seed; a->seed_dev = seed_dev;
-    return 0;
-}
-
 extern "C" int qt_attn_blocks(int N, int C) {
-    if (N <= 0 || !c_ok(C)) return 0;
+    if (N <= 0 || !c_ok(C, LPN_MAX)) return 0;
     const int need = qt_cdiv((int64_t)N * (C / 4), 256);
 static constexpr int QT_ATTN_BLOCKS = 4096;
     return need < QT_ATTN_BLOCKS ? need : QT_ATTN_BLOCKS;     // (512 left two waves per SIMD for a gather-latency-bound sweep)
@@ -490,16 +328,16 @@ extern "C" int qt_attn_fwd(const int32_t* rowptr, const int32_t* col, const floa
     if (hs == 0) hs = 4 * C;
     if (hs_o == 0) hs_o = C;
     if (ld_o == 0) ld_o = G * C;
-    QT_ARG(c_ok(C) && ld >= C && ld % 4 == 0 && c_real >= 1 && c_real <= C, "bad channel count / row stride");
+    QT_ARG(c_ok(C, LPN_MAX) && ld >= C && ld % 4 == 0 && c_real >= 1 && c_real <= C, "bad channel count / row stride");
     QT_ARG(G <= 64 && ld_o >= C && ld_o % 4 == 0 && ps % 4 == 0 && hs % 4 == 0 && hs_o % 4 == 0, "bad head count / strides");
     QT_ARG((int64_t)N * ld < (1ll << 31) && (int64_t)N * ld_o < (1ll << 31), "a head's rows must span fewer than 2^31 floats");
     if (N <= 0) return QT_OK;
     AttnArgs a;
-    fill_args(&a, rowptr, col, xy, eattr, selfloop, proj, ld, We, C, c_real, N, n_dev, keep, seed, seed_dev);
+    fill_args(&a, rowptr, col, eattr, selfloop, proj, ld, We, C, c_real, N, n_dev, keep, seed, seed_dev);
     a.ld_g = C; a.accumulate = 0; a.rev = nullptr; a.coef = nullptr; a.E = 0; a.ld_o = ld_o; a.gmod = G;
     a.ps = ps; a.hs = hs; a.hs_o = hs_o; a.hs_g = C;
     const int grid = (qt_cdiv((int64_t)N * (C / 4), QT_ATTN_BS) + 7) & ~7;      // whole rounds over the 8 XCDs (xcd_block)
-    QT_ATTN_DISPATCH_BS(C, k_attn_fwd, dim3(grid, G), QT_ATTN_BS, stream, a, out, stats);
+    QT_ATTN_LAUNCH(C, LPN_MAX, k_attn_fwd, dim3(grid, G), QT_ATTN_BS, stream, a, out, stats);
     QT_LAUNCHED();
     return QT_OK;
 }
@@ -517,7 +355,7 @@ extern "C" int qt_attn_bwd(const int32_t* rowptr, const int32_t* col, const floa
     if (hs_g == 0) hs_g = C;
     if (hs_o == 0) hs_o = C;
     if (ld_o == 0) ld_o = G * C;
-    QT_ARG(c_ok(C) && ld >= C && ld % 4 == 0 && c_real >= 1 && c_real <= C, "bad channel count / row stride");
+    QT_ARG(c_ok(C, LPN_MAX) && ld >= C && ld % 4 == 0 && c_real >= 1 && c_real <= C, "bad channel count / row stride");
     if (ld_g == 0) ld_g = gmod * C;
     QT_ARG(G <= 64 && gmod <= G && ld_g >= C && ld_g % 4 == 0 && ((uintptr_t)g & 15) == 0 && ps % 4 == 0 && hs % 4 == 0 && hs_g % 4 == 0 &&
            ld_o >= C && ld_o % 4 == 0 && hs_o % 4 == 0 && ((uintptr_t)out & 15) == 0 && ((uintptr_t)coef & 7) == 0 && E >= 0,
@@ -526,13 +364,13 @@ extern "C" int qt_attn_bwd(const int32_t* rowptr, const int32_t* col, const floa
            "a head's rows must span fewer than 2^31 floats");
     if (N <= 0) return QT_OK;
     AttnArgs a;
-    fill_args(&a, rowptr, col, xy, eattr, selfloop, proj, ld, We, C, c_real, N, n_dev, keep, seed, seed_dev);
+    fill_args(&a, rowptr, col, eattr, selfloop, proj, ld, We, C, c_real, N, n_dev, keep, seed, seed_dev);
     a.ld_g = ld_g; a.accumulate = accumulate; a.rev = rev; a.coef = coef; a.E = E; a.ld_o = ld_o; a.gmod = gmod;
     a.ps = ps; a.hs = hs; a.hs_o = hs_o; a.hs_g = hs_g;
     const int grid = (qt_cdiv((int64_t)N * (C / 4), QT_ATTN_BS) + 7) & ~7;
-    QT_ATTN_DISPATCH_BS(C, k_attn_bwd_target, dim3(grid, G), QT_ATTN_BS, stream, a, g, stats, out, gproj);
+    QT_ATTN_LAUNCH(C, LPN_MAX, k_attn_bwd_target, dim3(grid, G), QT_ATTN_BS, stream, a, g, stats, out, gproj);
     const int gridB = qt_attn_blocks(N, C);
-    QT_ATTN_DISPATCH(C, k_attn_bwd_source, dim3(gridB, G), stream, a, g, gproj, part);
+    QT_ATTN_LAUNCH(C, LPN_MAX, k_attn_bwd_source, dim3(gridB, G), 256, stream, a, g, gproj, part);
     QT_LAUNCHED();
     return QT_OK;
 }

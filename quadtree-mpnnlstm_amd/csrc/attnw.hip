@@ -10,39 +10,13 @@
 // Outputs: alpha_e (G, E): the coefficient of the message col[e] -> row(e), stored at rev[e] (the transposed entry), so that
 // alpha_e follows the CSR order of the pairs (src = row, dst = col); alpha_s (G, Ncap): the coefficient of node i's self pair,
 // 0 where the node has none.  Rows beyond n_dev are not touched.  No atomics, no random numbers.
-#include "qt_common.h"
-#include <math.h>
+#include "qt_attn.h"
 
 namespace {
-
-struct F4 {
-    float v[4];
-};
-__device__ __forceinline__ F4 ld4(const float* p) {
-    const float4 f = *reinterpret_cast<const float4*>(p);
-    return F4{{f.x, f.y, f.z, f.w}};
-}
-template <int LPN>
-__device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-    for (int d = 1; d < LPN; d <<= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-__device__ __forceinline__ float dot4(const F4& a, const F4& b) {
-    return (a.v[0] * b.v[0] + a.v[1] * b.v[1]) + (a.v[2] * b.v[2] + a.v[3] * b.v[3]);
-}
-
-// contiguous node ranges per XCD (attn.hip: xcd_block)
-__device__ __forceinline__ int xcd_block(int rows, int nodes_per_block) {
-    const int nblk = (rows + nodes_per_block - 1) / nodes_per_block;
-    const int chunk = (nblk + 7) >> 3;
-    const int bid = blockIdx.x;
-    if ((bid >> 3) >= chunk) return -1;
-    return (bid & 7) * chunk + (bid >> 3);
-}
+using namespace qtattn;
 
 constexpr int AW_BS = 64;       // one wave per workgroup, as k_attn_fwd
-constexpr int EPT = 2;          // edges per trip (their gathers are issued together), as attn.hip
+constexpr int LPN_MAX = 8;      // C = 4 .. 32
 
 struct WArgs {
     const int32_t* rowptr;
@@ -61,6 +35,7 @@ struct WArgs {
 };
 
 // The scores of EPT consecutive edges eb .. eb + EPT - 1 of node i (the self pair after the stored edges); jj[u] < 0 past the end.
+// Its own trip, not qt_attn.h's Trip: through that one the compiler fuses another product of w0 angle + w1 dist (other bits).
 template <int LPN>
 __device__ __forceinline__ void scores(const WArgs& a, const float* __restrict__ kb, const F4& q, const F4& w0, const F4& w1, int i,
                                        uint32_t j0, int eb, int e1, int eend, int* jj, float* s) {
@@ -102,8 +77,8 @@ __global__ __launch_bounds__(AW_BS) void k_attn_weights(WArgs a) {
     if (i >= rows) return;
     const uint32_t j0 = ((uint32_t)threadIdx.x % LPN) * 4;
     const F4 q = ld4(qb + ((uint32_t)i * (uint32_t)a.ld + j0));
-    const F4 w0 = {{We[2 * j0], We[2 * j0 + 2], We[2 * j0 + 4], We[2 * j0 + 6]}};
-    const F4 w1 = {{We[2 * j0 + 1], We[2 * j0 + 3], We[2 * j0 + 5], We[2 * j0 + 7]}};
+    F4 w0, w1;
+    we_columns(We, j0, &w0, &w1);
     const int e0 = a.rowptr[i], e1 = a.rowptr[i + 1];
     const int extra = (a.selfloop && a.selfloop[i] > 0.0f) ? 1 : 0;
     const int eend = e1 + extra;
@@ -142,15 +117,13 @@ __global__ __launch_bounds__(AW_BS) void k_attn_weights(WArgs a) {
     if (j0 == 0 && !extra) alpha_s[i] = 0.0f;
 }
 
-inline bool c_ok(int C) { return C == 4 || C == 8 || C == 16 || C == 32; }
-
 }  // namespace
 
 extern "C" int qt_attn_weights(const int32_t* rowptr, const int32_t* col, const float* eattr, const float* selfloop, const float* proj,
                                int ld, int64_t ps, int64_t hs, const float* We, int C, int c_real, int G, int N, const int32_t* n_dev,
                                const int32_t* rev, int E, float* alpha_e, float* alpha_s, void* stream) {
     QT_ARG(rowptr && col && eattr && proj && We && rev && alpha_e && alpha_s, "null pointer");
-    QT_ARG(c_ok(C) && c_real >= 1 && c_real <= C, "bad channel count (the kernels are built for C = 4, 8, 16, 32)");
+    QT_ARG(c_ok(C, LPN_MAX) && c_real >= 1 && c_real <= C, "bad channel count (the kernels are built for C = 4, 8, 16, 32)");
     QT_ARG(G >= 1 && G <= 64, "bad group count (1 .. 64)");
     if (ps == 0) ps = C;
     if (hs == 0) hs = 4 * C;
@@ -163,13 +136,7 @@ extern "C" int qt_attn_weights(const int32_t* rowptr, const int32_t* col, const 
     a.alpha_e = alpha_e; a.alpha_s = alpha_s; a.ps = ps; a.hs = hs; a.ld = ld; a.C = C; a.Ncap = N; a.E = E;
     a.scale = 1.0f / sqrtf((float)c_real);
     const int grid = (qt_cdiv((int64_t)N * (C / 4), AW_BS) + 7) & ~7;      // whole rounds over the 8 XCDs (xcd_block)
-    const dim3 g(grid, G);
-    switch (C / 4) {
-        case 1: hipLaunchKernelGGL(k_attn_weights<1>, g, dim3(AW_BS), 0, (hipStream_t)stream, a); break;
-        case 2: hipLaunchKernelGGL(k_attn_weights<2>, g, dim3(AW_BS), 0, (hipStream_t)stream, a); break;
-        case 4: hipLaunchKernelGGL(k_attn_weights<4>, g, dim3(AW_BS), 0, (hipStream_t)stream, a); break;
-        default: hipLaunchKernelGGL(k_attn_weights<8>, g, dim3(AW_BS), 0, (hipStream_t)stream, a); break;
-    }
+    QT_ATTN_LAUNCH(C, LPN_MAX, k_attn_weights, dim3(grid, G), AW_BS, stream, a);
     QT_LAUNCHED();
     return QT_OK;
 }

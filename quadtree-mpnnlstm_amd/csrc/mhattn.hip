@@ -12,56 +12,16 @@
 // rows of the four groups are summed with two xor shuffles.
 // Backward: k_mh_merge_bwd gives gcat = g Wlin (per row) and per-block partials of dWlin / dblin (summed by qt_colsum: fixed
 // order, no atomics); the attention gradient is then qt_attn_bwd with G = H on gcat, with the cat plane as its `out`.
-#include "qt_common.h"
-#include <math.h>
+// The per-head body is qt_attn.h's node_forward, the one k_attn_fwd runs, with head_seed per head: the fused launch draws exactly
+// the mask of qt_attn_fwd with G = H for the same seed / seed_dev (tests/test_gpu_mh.py compares the two with dropout on).
+#include "qt_attn.h"
 
 namespace {
-
-struct F4 {
-    float v[4];
-};
-__device__ __forceinline__ F4 ld4(const float* p) {
-    const float4 f = *reinterpret_cast<const float4*>(p);
-    return F4{{f.x, f.y, f.z, f.w}};
-}
-__device__ __forceinline__ void st4(float* p, const F4& a) {
-    *reinterpret_cast<float4*>(p) = make_float4(a.v[0], a.v[1], a.v[2], a.v[3]);
-}
-template <int LPN>
-__device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-    for (int d = 1; d < LPN; d <<= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-__device__ __forceinline__ float dot4(const F4& a, const F4& b) {
-    return (a.v[0] * b.v[0] + a.v[1] * b.v[1]) + (a.v[2] * b.v[2] + a.v[3] * b.v[3]);
-}
-
-// The dropout draw of attn.hip (drop_mult, head seeds of head_setup, eff_seed), kept identical: the fused launch draws exactly the
-// mask of qt_attn_fwd with G = H for the same seed / seed_dev (tests/test_gpu_mh.py compares the two with dropout on).
-__device__ __forceinline__ float drop_mult(uint32_t seed, int i, int j, float keep) {
-    if (keep >= 1.0f) return 1.0f;
-    uint32_t h = seed ^ ((uint32_t)i * 0x9E3779B1u) ^ ((uint32_t)j * 0x85EBCA77u);
-    h ^= h >> 16; h *= 0x7FEB352Du; h ^= h >> 15; h *= 0x846CA68Bu; h ^= h >> 16;
-    return ((h >> 8) * (1.0f / 16777216.0f)) < keep ? 1.0f / keep : 0.0f;
-}
-__device__ __forceinline__ uint32_t head_seed(uint32_t seed, const uint32_t* seed_dev, int hd) {
-    const uint32_t s = seed + (uint32_t)hd * 0x632BE5ABu;
-    return seed_dev ? s ^ (*seed_dev * 0x9E3779B9u) : s;
-}
-
-// contiguous node ranges per XCD (attn.hip: xcd_block)
-__device__ __forceinline__ int xcd_block(int rows, int nodes_per_block) {
-    const int nblk = (rows + nodes_per_block - 1) / nodes_per_block;
-    const int chunk = (nblk + 7) >> 3;
-    const int bid = blockIdx.x;
-    if ((bid >> 3) >= chunk) return -1;
-    return (bid & 7) * chunk + (bid >> 3);
-}
+using namespace qtattn;
 
 constexpr int MH_BS = 256;
 constexpr int MH_MAX_HEADS = 4;
-constexpr int EPT = 2;      // edges per trip, as in attn.hip
+constexpr int LPN_MAX = 8;      // C = 4 .. 32: four head groups of a node fit a wave, Wlin^T fits LDS
 
 struct MhArgs {
     const int32_t* rowptr;
@@ -99,68 +59,12 @@ __global__ __launch_bounds__(MH_BS) void k_mh_fwd(MhArgs a) {
     const bool live = hd < H;
     F4 o = {{0, 0, 0, 0}};
     if (live) {
-        const float* __restrict__ qb = a.proj + hd * 4 * C;
-        const float* __restrict__ kb = qb + C;
-        const float* __restrict__ vb = qb + 2 * C;
-        const float* We = a.We + hd * 2 * C;
-        const F4 q = ld4(qb + ((uint32_t)i * ld + j0));
-        const F4 w0 = {{We[2 * j0], We[2 * j0 + 2], We[2 * j0 + 4], We[2 * j0 + 6]}};
-        const F4 w1 = {{We[2 * j0 + 1], We[2 * j0 + 3], We[2 * j0 + 5], We[2 * j0 + 7]}};
-        float m = -INFINITY, lsum = 0.0f;
-        F4 acc = {{0, 0, 0, 0}};
-        const int e0 = a.rowptr[i], e1 = a.rowptr[i + 1];
-        const int extra = (a.selfloop && a.selfloop[i] > 0.0f) ? 1 : 0;
-        const uint32_t seed = head_seed(a.seed, a.seed_dev, hd);
-        const int eend = e1 + extra;
-        for (int eb = e0; eb < eend; eb += EPT) {
-            int jj[EPT];
-            F4 kk[EPT], vv[EPT];
-            float2 ea[EPT];
-#pragma unroll
-            for (int u = 0; u < EPT; ++u) {
-                const int e = eb + u;
-                jj[u] = e < e1 ? a.col[e] : (e < eend ? i : -1);
-            }
-#pragma unroll
-            for (int u = 0; u < EPT; ++u)
-                if (jj[u] >= 0) {
-                    const uint32_t off = (uint32_t)jj[u] * ld + j0;
-                    kk[u] = ld4(kb + off);
-                    vv[u] = ld4(vb + off);
-                    ea[u] = eb + u < e1 ? *reinterpret_cast<const float2*>(a.eattr + 2 * (uint32_t)(eb + u)) : make_float2(0.0f, 0.0f);
-                }
-#pragma unroll
-            for (int u = 0; u < EPT; ++u) {
-                if (jj[u] < 0) break;
-                const int j = jj[u];
-                const float ang = ea[u].x, dst = ea[u].y;
-                F4 kj = kk[u], vj = vv[u];
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    const float ee = w0.v[c] * ang + w1.v[c] * dst;
-                    kj.v[c] += ee;
-                    vj.v[c] += ee;
-                }
-                const float s = group_sum<LPN>(dot4(q, kj)) * a.scale;
-                const float mn = fmaxf(m, s);
-                const float r = __expf(m - mn), p = __expf(s - mn);
-                const float pd = p * drop_mult(seed, i, j, a.keep);
-                lsum = lsum * r + p;
-#pragma unroll
-                for (int c = 0; c < 4; ++c) acc.v[c] = acc.v[c] * r + pd * vj.v[c];
-                m = mn;
-            }
-        }
-        const F4 sk = ld4(qb + 3 * C + ((uint32_t)i * ld + j0));
-        const float inv = lsum > 0.0f ? 1.0f / lsum : 0.0f;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) o.v[c] = acc.v[c] * inv + sk.v[c];
+        const float* __restrict__ qb = a.proj + hd * 4 * C;      // k_attn_fwd's node at ld = 4CH, ps = C, hs = 4C
+        const NodeOut r = node_forward<LPN>(a.rowptr, a.col, a.eattr, a.selfloop, qb, qb + C, qb + 2 * C, qb + 3 * C, ld,
+                                            a.We + hd * 2 * C, i, j0, a.scale, a.keep, head_seed(a.seed, a.seed_dev, hd));
+        o = r.o;
         if (a.cat) st4(a.cat + ((uint32_t)i * (uint32_t)HC + hd * C + j0), o);
-        if (j0 == 0) {
-            float* st = a.stats + (int64_t)hd * 2 * a.Ncap;
-            st[2 * i] = m;
-            st[2 * i + 1] = lsum;
-        }
+        put_stats(a.stats + (int64_t)hd * 2 * a.Ncap, i, j0, r);
     }
     // head merge: this group's partial of y_i[j0 .. j0 + 3] = sum_c cat_i[hd C + c] Wt[hd C + c][j0 .. j0 + 3]
     F4 p = {{0, 0, 0, 0}};
@@ -194,11 +98,11 @@ __global__ __launch_bounds__(MH_BS) void k_mh_fwd(MhArgs a) {
 // Backward of the merge, NB rows per trip: gcat_i = Wlin^T-transposed g_i (gcat[k] = sum_o Wt[k][o] g_i[o]) for every row, and
 // this block's partial sums of dWt[k][o] = sum_i cat_i[k] g_i[o] and dblin[o] = sum_i g_i[o] (part row blockIdx.x).
 constexpr int MB_NB = 32;
-template <int C>
+template <int LPN>
 __global__ __launch_bounds__(MH_BS) void k_mh_merge_bwd(const float* __restrict__ g, int ld_g, const float* __restrict__ Wt,
                                                        const float* __restrict__ cat, int heads, int Ncap, const int32_t* __restrict__ n_dev,
                                                        float* __restrict__ gcat, float* __restrict__ part, int accumulate) {
-    constexpr int CP = C + 1, R = (MH_MAX_HEADS * C * C + C + MH_BS - 1) / MH_BS;
+    constexpr int C = 4 * LPN, CP = C + 1, R = (MH_MAX_HEADS * C * C + C + MH_BS - 1) / MH_BS;
     __shared__ float sW[MH_MAX_HEADS * C * CP];             // rows padded by one: consecutive rows fall in different banks
     __shared__ float sg[MB_NB * C];
     __shared__ float sc[MB_NB * MH_MAX_HEADS * C];
@@ -253,12 +157,10 @@ __global__ __launch_bounds__(MH_BS) void k_mh_merge_bwd(const float* __restrict_
     }
 }
 
-inline bool mh_c_ok(int C) { return C == 4 || C == 8 || C == 16 || C == 32; }
-
 }  // namespace
 
 extern "C" int qt_mhattn_blocks(int N, int C, int heads) {
-    if (N <= 0 || !mh_c_ok(C) || heads < 1 || heads > MH_MAX_HEADS) return 0;
+    if (N <= 0 || !c_ok(C, LPN_MAX) || heads < 1 || heads > MH_MAX_HEADS) return 0;
     const int need = qt_cdiv(N, MB_NB);
     return need < 256 ? need : 256;
 }
@@ -268,7 +170,7 @@ extern "C" int qt_mhattn_fwd(const int32_t* rowptr, const int32_t* col, const fl
                              const int32_t* n_dev, float keep, uint32_t seed, const uint32_t* seed_dev, float* y, float* stats,
                              float* cat, void* stream) {
     QT_ARG(rowptr && col && eattr && proj && We && Wt && blin && y && stats, "null pointer");
-    QT_ARG(mh_c_ok(C) && c_real >= 1 && c_real <= C, "bad channel count (C = 4, 8, 16 or 32, 1 <= c_real <= C)");
+    QT_ARG(c_ok(C, LPN_MAX) && c_real >= 1 && c_real <= C, "bad channel count (C = 4, 8, 16 or 32, 1 <= c_real <= C)");
     QT_ARG(heads >= 1 && heads <= MH_MAX_HEADS, "bad head count (1 .. 4)");
     QT_ARG(N >= 0 && (int64_t)N * 4 * C * heads < (1ll << 31), "the proj rows must span fewer than 2^31 floats");
     QT_ARG((((uintptr_t)proj | (uintptr_t)Wt | (uintptr_t)blin | (uintptr_t)y | (uintptr_t)cat) & 15) == 0, "operands must be 16-byte aligned");
@@ -279,12 +181,7 @@ extern "C" int qt_mhattn_fwd(const int32_t* rowptr, const int32_t* col, const fl
     a.seed_dev = seed_dev; a.y = y; a.stats = stats; a.cat = cat;
     const int npb = MH_BS / C;                                                  // 4 head groups of C / 4 lanes per node
     const int grid = (qt_cdiv(N, npb) + 7) & ~7;                                // whole rounds over the 8 XCDs (xcd_block)
-    switch (C) {
-        case 4: hipLaunchKernelGGL(k_mh_fwd<1>, dim3(grid), dim3(MH_BS), 0, (hipStream_t)stream, a); break;
-        case 8: hipLaunchKernelGGL(k_mh_fwd<2>, dim3(grid), dim3(MH_BS), 0, (hipStream_t)stream, a); break;
-        case 16: hipLaunchKernelGGL(k_mh_fwd<4>, dim3(grid), dim3(MH_BS), 0, (hipStream_t)stream, a); break;
-        default: hipLaunchKernelGGL(k_mh_fwd<8>, dim3(grid), dim3(MH_BS), 0, (hipStream_t)stream, a); break;
-    }
+    QT_ATTN_LAUNCH(C, LPN_MAX, k_mh_fwd, grid, MH_BS, stream, a);
     QT_LAUNCHED();
     return QT_OK;
 }
@@ -292,16 +189,11 @@ extern "C" int qt_mhattn_fwd(const int32_t* rowptr, const int32_t* col, const fl
 extern "C" int qt_mhattn_bwd_merge(const float* g, int ld_g, const float* Wt, const float* cat, int C, int heads, int N,
                                    const int32_t* n_dev, float* gcat, float* part, int accumulate, void* stream) {
     QT_ARG(g && Wt && cat && gcat && part, "null pointer");
-    QT_ARG(mh_c_ok(C) && heads >= 1 && heads <= MH_MAX_HEADS, "bad channel / head count");
+    QT_ARG(c_ok(C, LPN_MAX) && heads >= 1 && heads <= MH_MAX_HEADS, "bad channel / head count");
     QT_ARG(ld_g >= C && N >= 0 && (int64_t)N * heads * C < (1ll << 31) && (int64_t)N * ld_g < (1ll << 31), "bad row stride / size");
     if (N == 0) return QT_OK;
     const int grid = qt_mhattn_blocks(N, C, heads);
-    switch (C) {
-        case 4: hipLaunchKernelGGL(k_mh_merge_bwd<4>, dim3(grid), dim3(MH_BS), 0, (hipStream_t)stream, g, ld_g, Wt, cat, heads, N, n_dev, gcat, part, accumulate); break;
-        case 8: hipLaunchKernelGGL(k_mh_merge_bwd<8>, dim3(grid), dim3(MH_BS), 0, (hipStream_t)stream, g, ld_g, Wt, cat, heads, N, n_dev, gcat, part, accumulate); break;
-        case 16: hipLaunchKernelGGL(k_mh_merge_bwd<16>, dim3(grid), dim3(MH_BS), 0, (hipStream_t)stream, g, ld_g, Wt, cat, heads, N, n_dev, gcat, part, accumulate); break;
-        default: hipLaunchKernelGGL(k_mh_merge_bwd<32>, dim3(grid), dim3(MH_BS), 0, (hipStream_t)stream, g, ld_g, Wt, cat, heads, N, n_dev, gcat, part, accumulate); break;
-    }
+    QT_ATTN_LAUNCH(C, LPN_MAX, k_mh_merge_bwd, grid, MH_BS, stream, g, ld_g, Wt, cat, heads, N, n_dev, gcat, part, accumulate);
     QT_LAUNCHED();
     return QT_OK;
 }

@@ -29,11 +29,11 @@ print('heads', G, 'layout', 'planes (G, 4, N, C)' if planes else 'rows (N, G 4C)
 proj = torch.randn(G * N * 4 * C, device=dev)
 We = torch.randn(G, C, 2, device=dev)
 out = torch.empty(G * N * C, device=dev); stats = torch.empty(G, N, 2, device=dev)
-g = torch.randn(G * N * C, device=dev); gproj = torch.empty_like(proj); Dn = torch.empty(G, N, device=dev)
+g = torch.randn(G * N * C, device=dev); gproj = torch.empty_like(proj)
 coef = torch.empty(G, rev.numel() + N, 2, device=dev)
 nblk = _lib.value('qt_attn_blocks', N, C); part = torch.zeros(nblk, G * 2 * C, device=dev)
 ld, ps, hs, ld_o, hs_o = (C, N * C, 4 * N * C, C, N * C) if planes else (G * 4 * C, C, 4 * C, G * C, C)
-common = (ptr(mesh.rowptr), ptr(mesh.col), ptr(xy), ptr(eattr) if os.environ.get('QT_NO_EATTR') != '1' else None, ptr(selfpair), ptr(proj), ld, ptr(We), C, C, N, ptr(mesh.n_dev))
+common = (ptr(mesh.rowptr), ptr(mesh.col), ptr(xy), ptr(eattr), ptr(selfpair), ptr(proj), ld, ptr(We), C, C, N, ptr(mesh.n_dev))
 
 
 def timeit(fn, reps=20):
