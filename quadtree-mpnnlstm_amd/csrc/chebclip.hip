@@ -102,10 +102,6 @@ template <int W> __device__ __forceinline__ fvec<W> vzero() {
     return z;
 }
 
-// Workgroup barrier between two hops: only LDS is shared between the threads, so the barrier waits for this wave's LDS
-// operations (lgkmcnt) and NOT for its global stores / prefetches (vmcnt), which __syncthreads() would also drain.
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 // LDS rows are addressed by row * 16 (< 65536: two offsets per register); a slice row is 4 W bytes
 template <int W> __device__ __forceinline__ fvec<W> lds_row(const char* plane, unsigned off16) {
     return vload<W>(plane + off16 * (unsigned)W / 4u);
@@ -376,7 +372,7 @@ __global__ __launch_bounds__(CL_T) void k_cheb_clip(ClipArgs g) {
 #pragma unroll                 // its registers would sit beside the ELL vectors' and spill)
         for (int u = 0; u < CL_RPT; ++u) nxt[u] = ldg<W>(pt.planes + grad_off(K - 2, rowc[u]));
     }
-    lds_barrier();
+    qt_lds_barrier();
     // One hop with the gathered plane at byte offset CO of Pl (compile-time: the hop loops below are unrolled by two, so the plane
     // offsets are instruction immediates).  Per row: its four gathers AND its own old value (OWN: the plane being overwritten) are
     // requested together -- one LDS round trip (the first version took two per row: 3.6 us per hop with 0.7 us of gather work
@@ -513,7 +509,7 @@ __global__ __launch_bounds__(CL_T) void k_cheb_clip(ClipArgs g) {
                 if (t < nh) vstore<W>(HB + t * (4 * W), hv);
             }
         }
-        lds_barrier();
+        qt_lds_barrier();
     };
     using Co0 = std::integral_constant<unsigned, 0u>;
     using Co1 = std::integral_constant<unsigned, PLANE>;

@@ -21,10 +21,11 @@
 //     level 6 (a whole tile) is formed by the tile's quadrant-0 workgroup, which walks all four quadrants.
 // No per-node cell record, no direct-index side array, no pixel loops of data-dependent length, no atomics.  Summation order:
 // (top-left + top-right) + (bottom-left + bottom-right) at every level.
-#include "qt_common.h"
+#include "qt_transfer.h"
 #include <type_traits>
 
 namespace {
+using namespace qttransfer;
 
 constexpr int RC_T = 1024;          // threads of a workgroup: 256 2 x 2 pixel blocks of a quadrant x 4 float4 chunks
 constexpr int RC_ROWS = 4096;       // source rows of a clip that fit (qt_remesh_clip_rows: a 64 x 64 frame's pixels)
@@ -32,10 +33,8 @@ constexpr int RC_WIN = 1024;        // source rows staged at a time (64 bytes ea
 constexpr int RC_GROUPS = 256;      // column groups of one launch
 
 struct RcArgs {
-    const float* part[8];           // source state as up to 8 matrices side by side (row strides part_ld, float4 prefix part_end)
-    int part_ld[8], part_end[8];
-    float* opart[8];                // the result likewise, dense rows (widths opart_w, float4 prefix opart_end)
-    int opart_w[8], opart_end[8];
+    PartTable<const float> sparts;  // the source state and
+    PartTable<float> oparts;        // the result, each as up to 8 matrices side by side
     const int32_t* src_labels;      // (B, n, m) source mesh
     const float* src_npix;
     const int32_t* labels;          // (B, n, m) destination mesh
@@ -53,8 +52,6 @@ struct RcArgs {
     unsigned grp[RC_GROUPS];        // column group g = float4 chunks [grp & 0xffff, + (grp >> 16)), 1 .. 4 of them
 };
 
-__device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-__device__ __forceinline__ float4 mul4(float4 a, float s) { return make_float4(a.x * s, a.y * s, a.z * s, a.w * s); }
 __device__ __forceinline__ unsigned compact_bits(unsigned v) {       // even bits of v -> low half
     v &= 0x55555555u;
     v = (v | (v >> 1)) & 0x33333333u;
@@ -62,12 +59,11 @@ __device__ __forceinline__ unsigned compact_bits(unsigned v) {       // even bit
     v = (v | (v >> 4)) & 0x00FF00FFu;
     return v;
 }
-// Workgroup barrier that waits for this wave's LDS traffic only (not for its global loads / stores)
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-// Pairwise sums over four lanes, in the pyramid's order: the lanes hold child 0 .. child 3 of an entry (Morton order, child =
-// row bit | col bit << 1) 1 << sh lanes apart -> every one of them gets (c0 + c2) + (c1 + c3) (a + b = b + a bit for bit, so the
-// four lanes hold the same bits).  sh = log2 of the distance between the children: 2 and 4 for levels 2 and 3.
+// quad_add over four lanes: the lanes hold child 0 .. child 3 of an entry (Morton order, child = row bit | col bit << 1)
+// 1 << sh lanes apart -> every one of them gets (c0 + c2) + (c1 + c3) (a + b = b + a bit for bit, so the four lanes hold the
+// same bits; in two shuffles, where quad_add itself would take three).  sh = log2 of the distance between the children: 2 and
+// 4 for levels 2 and 3.
 __device__ __forceinline__ float quad_sum(float v, int sh) {
     const float a = v + __shfl_xor(v, 2 << sh, 64);
     return a + __shfl_xor(a, 1 << sh, 64);
@@ -100,21 +96,19 @@ __global__ __launch_bounds__(RC_T, 8) void k_remesh_clip(RcArgs a) {
     const bool ride = a.ride && g == 0;           // (workgroup-uniform) this workgroup also transfers column 0 of chunk 0
     const int R0 = (tile / a.tiles_c) * 64, C0 = (tile % a.tiles_c) * 64;
     const int P = a.n * a.m;
-    int sp = 0, op = 0;
-    while (ch0 >= a.part_end[sp]) ++sp;
-    while (ch0 >= a.opart_end[op]) ++op;
-    const int lds = a.part_ld[sp];
+    // row 0 of the group's first chunk = the group's base in its source / output part, with that part's row stride (a group
+    // lies inside one part); rows and the lane's chunk are added where they are used
+    int lds, ldd;
     // (uniform base + a small per-lane offset: the spare lanes of a narrow group read its last chunk again)
-    const float* src = a.part[sp] + (ch0 - (sp ? a.part_end[sp - 1] : 0)) * 4;
+    const float* src = part_chunk(a.sparts, 0, ch0, &lds);
     const int ksrc = 4 * min(k, nch - 1);
-    const int ldd = a.opart_w[op];
-    float* dst = a.opart[op] + (ch0 - (op ? a.opart_end[op - 1] : 0)) * 4;          // (uniform; + 4 k per lane)
-    const float* src0 = a.part[0];
-    const int lds0 = a.part_ld[0];
+    float* dst = part_chunk(a.oparts, 0, ch0, &ldd);         // (uniform; + 4 k per lane)
+    const float* src0 = a.sparts.p[0];
+    const int lds0 = a.sparts.ld[0];
     const bool first_only = a.src_first_only && ch == 0;       // (the scalar chunk on its own: a transfer of that chunk alone)
     const bool dec = a.posfeat != nullptr;          // chunk 0 of the result = [value | position, size] of the node
-    float* dst0 = a.opart[0];
-    const int ldd0 = a.opart_w[0];
+    float* dst0 = a.oparts.p[0];
+    const int ldd0 = a.oparts.ld[0];
     auto put = [&](int node, float4 v) {
         if (dec && ch == 0) {
             const float* pf = a.posfeat + 3 * (int64_t)node;
@@ -180,7 +174,7 @@ __global__ __launch_bounds__(RC_T, 8) void k_remesh_clip(RcArgs a) {
             smin[wq] = lo;
             smax[wq] = hi;
         }
-        lds_barrier();                              // (also: the previous quadrant's gathers and S3 reads are done)
+        qt_lds_barrier();                              // (also: the previous quadrant's gathers and S3 reads are done)
         lo = smin[t & 15];
         hi = smax[t & 15];
 #pragma unroll
@@ -224,7 +218,7 @@ __global__ __launch_bounds__(RC_T, 8) void k_remesh_clip(RcArgs a) {
             float x0[4], sc[4];
             stage(wb0, min(hi - wb0 + 1, RC_WIN), 0, 4, x, x0, sc);
         }
-        lds_barrier();
+        qt_lds_barrier();
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const unsigned lr = (unsigned)(sl[q] - wb0);
@@ -239,14 +233,14 @@ __global__ __launch_bounds__(RC_T, 8) void k_remesh_clip(RcArgs a) {
 #pragma nounroll
         for (int wb = wb0 + RC_WIN; any && wb <= hi; wb += RC_WIN) {
             const int nr = min(hi - wb + 1, RC_WIN);
-            lds_barrier();                          // the previous window's gathers are done
+            qt_lds_barrier();                          // the previous window's gathers are done
 #pragma nounroll
             for (int u = 0; u < 4; ++u) {
                 float4 x[1];
                 float x0[1], sc[1];
                 stage(wb, nr, u, u + 1, x, x0, sc);
             }
-            lds_barrier();
+            qt_lds_barrier();
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const unsigned lr = (unsigned)(sl[q] - wb);
@@ -267,26 +261,26 @@ __global__ __launch_bounds__(RC_T, 8) void k_remesh_clip(RcArgs a) {
         }
         // ---- sum pyramid, (top-left + top-right) + (bottom-left + bottom-right) at every level: level 1 in registers, levels 2
         // and 3 between lanes 4 / 8 and 16 / 32 apart, the waves' level-3 sums through LDS
-        const float4 s1 = add4(add4(v[0], v[1]), add4(v[2], v[3]));
+        const float4 s1 = quad_add(v[0], v[1], v[2], v[3]);
         const float4 s2 = quad_sum4(s1, 2), s3 = quad_sum4(s2, 4);
         float r1 = 0.0f, r2 = 0.0f, r3 = 0.0f;
         if (ride) {
-            r1 = (v0[0] + v0[1]) + (v0[2] + v0[3]);
+            r1 = quad_add(v0[0], v0[1], v0[2], v0[3]);
             r2 = quad_sum(r1, 2); r3 = quad_sum(r2, 4);
         }
         if ((t & 63) < 4) {
             S3[4 * wq + k] = s3;
             if (k == 0) S30[wq] = r3;
         }
-        lds_barrier();
+        qt_lds_barrier();
         // levels 4 and 5: the first wave of every level-4 entry sums its four waves' entries (wave 0: lanes 4 e + k take entry e,
         // so that its lanes 0 .. 15 hold the quadrant's four level-4 sums and two more shuffles give level 5)
         float4 s4 = s3, s5 = s3;
         float r4 = r3, r5 = r3;
         if ((w & 3) == 0) {                         // (wave-uniform)
             const int e = w == 0 ? (j & 3) : w >> 2;
-            s4 = add4(add4(S3[16 * e + k], S3[16 * e + 8 + k]), add4(S3[16 * e + 4 + k], S3[16 * e + 12 + k]));
-            if (ride) r4 = (S30[4 * e] + S30[4 * e + 2]) + (S30[4 * e + 1] + S30[4 * e + 3]);
+            s4 = quad_add(S3[16 * e + k], S3[16 * e + 8 + k], S3[16 * e + 4 + k], S3[16 * e + 12 + k]);
+            if (ride) r4 = quad_add(S30[4 * e], S30[4 * e + 2], S30[4 * e + 1], S30[4 * e + 3]);
             if (w == 0) {
                 s5 = quad_sum4(s4, 2);
                 if (ride) r5 = quad_sum(r4, 2);
@@ -326,9 +320,9 @@ __global__ __launch_bounds__(RC_T, 8) void k_remesh_clip(RcArgs a) {
 #pragma nounroll
     for (int qq = 0; qq < 4; ++qq) quadrant(qq, std::true_type());
     if (t < 4 && node6 >= 0) {
-        const float4 s = add4(add4(S5[k], S5[8 + k]), add4(S5[4 + k], S5[12 + k]));
+        const float4 s = quad_add(S5[k], S5[8 + k], S5[4 + k], S5[12 + k]);
         if (mine) put(node6, mul4(s, oscale6));
-        if (ride && k == 0) put0(node6, ((S50[0] + S50[2]) + (S50[1] + S50[3])) * oscale6);
+        if (ride && k == 0) put0(node6, quad_add(S50[0], S50[2], S50[1], S50[3]) * oscale6);
     }
 }
 
@@ -380,22 +374,22 @@ __global__ __launch_bounds__(RC_T) void k_pool_clip(PcArgs a) {
         if (lab[q] < 0) v[q] = 0.0f;
         else if (lv[q] == 0) out[(int64_t)lab[q] * a.out_stride] = v[q];
     }
-    const float s1 = (v[0] + v[1]) + (v[2] + v[3]);
+    const float s1 = quad_add(v[0], v[1], v[2], v[3]);
     const int L = lab[0] >= 0 ? lv[0] : 0;
     float oscale = 1.0f;
     if (L >= 1 && a.mean) oscale = 1.0f / a.npix[lab[0]];
     L1[t] = s1;
-    lds_barrier();
-    if (t < 256) L2[t] = (L1[4 * t] + L1[4 * t + 2]) + (L1[4 * t + 1] + L1[4 * t + 3]);
-    lds_barrier();
-    if (t < 64) L3[t] = (L2[4 * t] + L2[4 * t + 2]) + (L2[4 * t + 1] + L2[4 * t + 3]);
-    lds_barrier();
-    if (t < 16) L4[t] = (L3[4 * t] + L3[4 * t + 2]) + (L3[4 * t + 1] + L3[4 * t + 3]);
-    lds_barrier();
-    if (t < 4) L5[t] = (L4[4 * t] + L4[4 * t + 2]) + (L4[4 * t + 1] + L4[4 * t + 3]);
-    lds_barrier();
-    if (t < 1) L6[0] = (L5[0] + L5[2]) + (L5[1] + L5[3]);
-    lds_barrier();
+    qt_lds_barrier();
+    if (t < 256) L2[t] = quad_add(L1[4 * t], L1[4 * t + 2], L1[4 * t + 1], L1[4 * t + 3]);
+    qt_lds_barrier();
+    if (t < 64) L3[t] = quad_add(L2[4 * t], L2[4 * t + 2], L2[4 * t + 1], L2[4 * t + 3]);
+    qt_lds_barrier();
+    if (t < 16) L4[t] = quad_add(L3[4 * t], L3[4 * t + 2], L3[4 * t + 1], L3[4 * t + 3]);
+    qt_lds_barrier();
+    if (t < 4) L5[t] = quad_add(L4[4 * t], L4[4 * t + 2], L4[4 * t + 1], L4[4 * t + 3]);
+    qt_lds_barrier();
+    if (t < 1) L6[0] = quad_add(L5[0], L5[2], L5[1], L5[3]);
+    qt_lds_barrier();
     if (L >= 1 && ((2 * br) & ((1 << L) - 1)) == 0 && ((2 * bc) & ((1 << L) - 1)) == 0) {
         float sum;
         switch (L) {
@@ -426,26 +420,12 @@ extern "C" int qt_remesh_clip(const float* const* src_parts, const int* widths, 
     QT_ARG(!mean || npix, "mean pooling needs npix");
     QT_ARG(!src_inv || src_npix, "src_inv needs src_npix");
     RcArgs a = {};
-    int c4 = 0;
-    for (int i = 0; i < nparts; ++i) {
-        QT_ARG(src_parts[i] && widths[i] > 0 && widths[i] % 4 == 0 && lds[i] % 4 == 0 && lds[i] >= widths[i] &&
-               ((uintptr_t)src_parts[i] & 15) == 0, "source parts must be 16-byte aligned with widths / strides that are multiples of 4");
-        a.part[i] = src_parts[i];
-        a.part_ld[i] = lds[i];
-        c4 += widths[i] / 4;
-        a.part_end[i] = c4;
-    }
-    for (int i = nparts; i < 8; ++i) { a.part[i] = nullptr; a.part_ld[i] = 0; a.part_end[i] = 1 << 30; }
-    int o4 = 0;
-    for (int i = 0; i < nout; ++i) {
-        QT_ARG(out_parts[i] && out_widths[i] > 0 && out_widths[i] % 4 == 0 && ((uintptr_t)out_parts[i] & 15) == 0,
-               "output parts must be 16-byte aligned with widths that are multiples of 4");
-        a.opart[i] = out_parts[i];
-        a.opart_w[i] = out_widths[i];
-        o4 += out_widths[i] / 4;
-        a.opart_end[i] = o4;
-    }
-    for (int i = nout; i < 8; ++i) { a.opart[i] = nullptr; a.opart_w[i] = 0; a.opart_end[i] = 1 << 30; }
+    const int c4 = fill_parts(__func__, "source parts must be 16-byte aligned with widths / strides that are multiples of 4", src_parts,
+                              widths, lds, nparts, a.sparts);
+    if (c4 < 0) return QT_E_ARG;
+    const int o4 = fill_parts(__func__, "output parts must be 16-byte aligned with widths that are multiples of 4", out_parts, out_widths,
+                              nullptr, nout, a.oparts);
+    if (o4 < 0) return QT_E_ARG;
     QT_ARG(o4 == c4, "the output parts must add up to the source width");
     QT_ARG(c4 < (1 << 16), "state too wide");
     a.src_labels = src_labels;
@@ -466,9 +446,9 @@ extern "C" int qt_remesh_clip(const float* const* src_parts, const int* widths, 
     // column groups: runs of up to four chunks inside one source part and one output part (the rider's chunk 0 has none)
     int sp = 0, op = 0;
     for (int c = a.ride; c < c4;) {
-        while (c >= a.part_end[sp]) ++sp;
-        while (c >= a.opart_end[op]) ++op;
-        const int e = std::min(std::min(a.part_end[sp], a.opart_end[op]), c + 4);
+        while (c >= a.sparts.end[sp]) ++sp;
+        while (c >= a.oparts.end[op]) ++op;
+        const int e = std::min(std::min(a.sparts.end[sp], a.oparts.end[op]), c + 4);
         QT_ARG(a.ngroups < RC_GROUPS, "too many column groups for one launch");
         a.grp[a.ngroups++] = (unsigned)c | (unsigned)(e - c) << 16;
         c = e;

@@ -9,17 +9,18 @@
 // pyramid.  A quadtree leaf of level L is exactly one level-L pyramid entry, so every
 // node value is written once, in a fixed order, with no atomics.
 #include <cfloat>
-#include "qt_common.h"
+#include "qt_transfer.h"
 
 namespace {
+using namespace qttransfer;
 
 struct PoolArgs {
     const float* img;
     int S;
     int64_t img_clip_stride;   // floats between clips of img (S*P*C when dense)
-    const float* src_val;      // source node values: one (N_src, C) matrix, or
-    const float* part[8];      // up to 8 matrices side by side (row strides part_ld, widths as float4 prefix part_end)
-    int part_ld[8], part_end[8], nparts;
+    const float* src_val;      // source node values: one (N_src, C) matrix (nparts == 0), or
+    PartTable<const float> sparts;      // the nparts matrices of sparts side by side
+    int nparts;
     const int32_t* src_labels;
     const float* src_npix;
     int src_inv;
@@ -31,8 +32,8 @@ struct PoolArgs {
     int B, n, m, N;
     float* out;
     int out_stride, out_coff;
-    float* opart[8];         // mesh -> mesh: the result as up to 8 dense matrices side by side (widths as float4 prefix
-    int opart_w[8], opart_end[8], noparts;   // opart_end), so that every consumer reads dense rows; 0: one matrix `out`
+    PartTable<float> oparts;   // mesh -> mesh: the result as noparts dense matrices side by side (noparts == 0: one matrix `out`).  (The
+    int noparts;               // two tables stand apart: side by side they moved the arguments, and k_pool / k_pool_nodes lost 1 %)
     int tiles_r, tiles_c;
     const int32_t* cell;     // (N, 4) r, c, size, clip: given -> nodes up to 4x4 pixels go through k_pool_nodes
     const int32_t* n_dev;
@@ -42,50 +43,19 @@ struct PoolArgs {
                              // transposed index), -1 = multi-pixel node (general path); NULL: general path for all
 };
 
-template <int VEC>
-struct Vec {
-    float v[VEC];
-};
-
 // address of channel chunk `ch` (VEC floats) of source node `sl`
-template <int VEC>
-__device__ __forceinline__ const float* src_chunk(const PoolArgs& a, int64_t sl, int ch) {
+template <int VEC> __device__ __forceinline__ const float* src_chunk(const PoolArgs& a, int64_t sl, int ch) {
     if (VEC != 4 || a.nparts == 0) return a.src_val + sl * a.C + ch * VEC;
-    int s = 0;
-    while (ch >= a.part_end[s]) ++s;
-    return a.part[s] + sl * a.part_ld[s] + (ch - (s ? a.part_end[s - 1] : 0)) * 4;
+    return part_chunk(a.sparts, sl, ch);
 }
 
 // address of channel chunk `ch` of output node `node` (step s)
-template <int VEC>
-__device__ __forceinline__ float* dst_chunk(const PoolArgs& a, int s, int64_t node, int ch) {
+template <int VEC> __device__ __forceinline__ float* dst_chunk(const PoolArgs& a, int s, int64_t node, int ch) {
     if (VEC != 4 || a.noparts == 0) return a.out + ((int64_t)s * a.N + node) * a.out_stride + a.out_coff + ch * VEC;
-    int o = 0;
-    while (ch >= a.opart_end[o]) ++o;
-    return a.opart[o] + node * a.opart_w[o] + (ch - (o ? a.opart_end[o - 1] : 0)) * 4;
+    return part_chunk(a.oparts, node, ch);
 }
 
-template <int VEC>
-__device__ __forceinline__ Vec<VEC> vload(const float* p) {
-    Vec<VEC> r;
-    if constexpr (VEC == 4) {
-        const float4 f = *reinterpret_cast<const float4*>(p);
-        r.v[0] = f.x; r.v[1] = f.y; r.v[2] = f.z; r.v[3] = f.w;
-    } else {
-        r.v[0] = *p;
-    }
-    return r;
-}
-
-template <int VEC>
-__device__ __forceinline__ void vstore(float* p, const Vec<VEC>& r, float scale) {
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) p[k] = r.v[k] * scale;
-}
-
-// (experiment switches: the node kernel takes nodes up to QT_NODE_MAX_Z pixels wide, the tile kernel those from level QT_TILE_MIN_LV)
-static constexpr int QT_TILE_MIN_LV = 3;
-static constexpr int QT_NODE_MAX_Z = 4;
+// The node kernel takes nodes up to 4 x 4 pixels (levels 0 .. 2), the tile kernel in big-only mode those from level 3.
 // WY (compile time; the weighted losses, k_pool_targets<true>): the image is one channel y and the two "channels" summed are the pixel
 // weight and its product with y, (w_p, w_p y_p), formed in registers at the load: VEC = 2, rows [sum w | sum w y] of `out`.
 template <int VEC, bool WY = false>
@@ -107,11 +77,10 @@ __device__ __forceinline__ void tile_body(const PoolArgs& a, int bx, int by, int
     // big-only mode: a node of 8x8 pixels or more covers whole 4x4 blocks, so the block's first pixel tells whether any
     // of its 16 pixels is this kernel's business
     bool mine = true;
-    if (a.big_only && QT_TILE_MIN_LV >= 3) {
+    if (a.big_only) {
         const int r = R0 + 4 * br, c = C0 + 4 * bc;
         mine = r < a.n && c < a.m && lvl_img[(int64_t)r * a.m + c] >= 3;
     }
-    bool any_mine_t = false;
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -127,20 +96,15 @@ __device__ __forceinline__ void tile_body(const PoolArgs& a, int bx, int by, int
                 const unsigned lv = lvl_img[p];
                 lv_pack[i] |= lv << (8 * j);
                 big |= (lv >= 3);
-                any_mine_t |= (lv >= QT_TILE_MIN_LV);
-                if (a.src_labels && (!a.big_only || lv >= QT_TILE_MIN_LV)) {
+                if (a.src_labels && (!a.big_only || lv >= 3)) {
                     slab[q] = a.src_labels[b * P + p];
                     if (a.src_inv && slab[q] >= 0) sscale[q] = 1.0f / a.src_npix[slab[q]];
                 }
-                if (a.big_only && lv < QT_TILE_MIN_LV) lab[q] = -1;       // not this kernel's pixel: no load, no store
+                if (a.big_only && lv < 3) lab[q] = -1;       // not this kernel's pixel: no load, no store
             }
         }
     const bool any_big = __syncthreads_or(big ? 1 : 0) != 0;
-    if (QT_TILE_MIN_LV >= 3) {
-        if (a.big_only && !any_big) return;
-    } else if (a.big_only && __syncthreads_or(any_mine_t ? 1 : 0) == 0) {
-        return;
-    }
+    if (a.big_only && !any_big) return;
 
     const int nch = a.C / VEC;
     const int total = (a.src_labels ? 1 : a.S) * nch;
@@ -188,12 +152,9 @@ __device__ __forceinline__ void tile_body(const PoolArgs& a, int bx, int by, int
 #pragma unroll
             for (int j2 = 0; j2 < 2; ++j2) {
                 const int q0 = (2 * i2) * 4 + 2 * j2;
-                Vec<VEC> s1;
+                const Vec<VEC> s1 = quad_add<VEC>(val[q0], val[q0 + 1], val[q0 + 4], val[q0 + 5]);
 #pragma unroll
-                for (int k = 0; k < VEC; ++k) {
-                    s1.v[k] = (val[q0].v[k] + val[q0 + 1].v[k]) + (val[q0 + 4].v[k] + val[q0 + 5].v[k]);
-                    s2.v[k] += s1.v[k];
-                }
+                for (int k = 0; k < VEC; ++k) s2.v[k] += s1.v[k];
                 const unsigned lv = (lv_pack[2 * i2] >> (8 * (2 * j2))) & 0xff;
                 if (lab[q0] >= 0 && lv == 1)
                     vstore<VEC>(dst_chunk<VEC>(a, s, lab[q0], ch), s1, a.mean ? 1.0f / a.npix[lab[q0]] : 1.0f);
@@ -215,7 +176,7 @@ __device__ __forceinline__ void tile_body(const PoolArgs& a, int bx, int by, int
 #pragma unroll
                     for (int k = 0; k < VEC; ++k) {
                         const float* sp = pyr + (src_off + (2 * i) * src_dim + 2 * j) * VEC + k;
-                        acc.v[k] = (sp[0] + sp[VEC]) + (sp[src_dim * VEC] + sp[(src_dim + 1) * VEC]);
+                        acc.v[k] = quad_add(sp[0], sp[VEC], sp[src_dim * VEC], sp[(src_dim + 1) * VEC]);
                         pyr[(dst_off + t) * VEC + k] = acc.v[k];
                     }
                     const int r = R0 + (i << L), c = C0 + (j << L);
@@ -235,9 +196,8 @@ __device__ __forceinline__ void tile_body(const PoolArgs& a, int bx, int by, int
     }
 }
 
-static constexpr int QT_POOL_OCC = 1;
 template <int VEC>
-__global__ __launch_bounds__(256, QT_POOL_OCC) void k_pool(PoolArgs a) {
+__global__ __launch_bounds__(256, 1) void k_pool(PoolArgs a) {
     __shared__ float pyr[(256 + 64 + 16 + 4 + 1) * VEC];
     tile_body<VEC>(a, blockIdx.x, blockIdx.y, gridDim.y, pyr);
 }
@@ -274,15 +234,11 @@ __global__ __launch_bounds__(256) void k_pool_targets(PoolArgs a, LossSeg sg, in
         tile_body<1>(a, blockIdx.x, 0, 1, pyr);
 }
 
-// Node-centric transfer for nodes of 1x1 .. 4x4 pixels: thread = (node, float4 chunk of its row), chunk fastest, so the
-// source-row gathers and the output stores move whole rows and consecutive threads write consecutive memory.  (The tile
-// kernel above touches 16 bytes of every row per workgroup and has only B * tiles workgroups of pixel-serial work:
-// 39 us for 68 channels at 64x64x32, against a ~16 us stream.)  Masked pixels inside a cell carry another label.
+// Node-centric transfer for nodes of 1x1 .. 4x4 pixels: thread = (node, group of CPT consecutive VEC-float chunks of its row),
+// group fastest, so the source-row gathers and the output stores move whole rows and consecutive threads write consecutive
+// memory.  One chunk per thread is the fastest (measurements: HISTORY section AJ).  Masked pixels inside a cell carry another label.
 static constexpr int QT_NODES_BS = 256;
 static constexpr int QT_POOL_CPT = 1;      // row chunks per thread
-// thread = (node, group of CPT consecutive VEC-float chunks of its row), group fastest.  One chunk per thread is the fastest:
-// at the bench shape (68 channels, forward / backward transfer) 23.2 / 36.8 us with 1, 28.1 / 44.2 with 2, 37.1 / 66.6 with 4 --
-// the waves that hold a 2x2 / 4x4 node set the launch time, and more chunks per thread lengthen exactly those.
 static constexpr int QT_POOL_CPT_A = 2;    // row chunks per thread of the direct-copy role
 // Direct-copy role of k_pool_nodes: destination nodes whose single source row is known (a.direct[i] >= 0: a single-pixel node of a
 // mesh -> mesh transfer) are a gathered row copy -- index -> CPTA chunks of the row in flight -> stores, no cell record, no pixel
@@ -367,7 +323,7 @@ __global__ __launch_bounds__(QT_NODES_BS) void k_pool_nodes(PoolArgs a, int grid
         }
     }
     const int4 cl = reinterpret_cast<const int4*>(a.cell)[i];
-    if (cl.z > QT_NODE_MAX_Z) return;
+    if (cl.z > 4) return;                           // (8x8 pixels and more: the tile kernel's)
     const int64_t P = (int64_t)a.n * a.m, base = (int64_t)cl.w * P;
     if (cl.z == 1 && a.src_labels) {
         // a single-pixel node (almost all of them on noisy frames) owns its pixel: straight-line code, no pixel loop, no
@@ -757,20 +713,14 @@ static int pool_launch(PoolArgs& a, bool v4, const int32_t* cell, const int32_t*
         const int grid_b = qt_cdiv((int64_t)a.N * (a.src_labels ? 1 : a.S) * ((nch + cpt - 1) / cpt), QT_NODES_BS);
         const int cpta = v4 ? QT_POOL_CPT_A : 1;
         const int grid_a = (a.direct && a.src_labels) ? qt_cdiv((int64_t)a.N * ((nch + cpta - 1) / cpta), QT_NODES_BS) : 0;
-        if (v4)
-            hipLaunchKernelGGL(k_pool_nodes<4>, dim3(grid_b + grid_a), dim3(QT_NODES_BS), 0, stream, a, grid_b);
-        else
-            hipLaunchKernelGGL(k_pool_nodes<1>, dim3(grid_b + grid_a), dim3(QT_NODES_BS), 0, stream, a, grid_b);
+        QT_TRANSFER_LAUNCH(v4, k_pool_nodes, grid_b + grid_a, QT_NODES_BS, stream, a, grid_b);
         QT_LAUNCHED();
     }
     const int blocks = a.B * a.tiles_r * a.tiles_c;
     int gy = total;
     if (blocks * gy > 2048) gy = max(1, 2048 / blocks);
     if (gy > total) gy = total;
-    if (v4)
-        hipLaunchKernelGGL(k_pool<4>, dim3(blocks, gy), dim3(256), 0, stream, a);
-    else
-        hipLaunchKernelGGL(k_pool<1>, dim3(blocks, gy), dim3(256), 0, stream, a);
+    QT_TRANSFER_LAUNCH(v4, k_pool, dim3(blocks, gy), 256, stream, a);
     QT_LAUNCHED();
     return QT_OK;
 }
@@ -782,10 +732,7 @@ extern "C" int qt_gather(const float* val, int C, const int32_t* labels, const f
     const bool v4 = (C % 4 == 0) && (((uintptr_t)val | (uintptr_t)img) % 16 == 0);
     const int nch = v4 ? C / 4 : C;
     const int grid = qt_cdiv(npixels_total * nch, 256);
-    if (v4)
-        hipLaunchKernelGGL(k_gather<4>, dim3(grid), dim3(256), 0, (hipStream_t)stream, val, C, labels, inv_npix, npixels_total, img);
-    else
-        hipLaunchKernelGGL(k_gather<1>, dim3(grid), dim3(256), 0, (hipStream_t)stream, val, C, labels, inv_npix, npixels_total, img);
+    QT_TRANSFER_LAUNCH(v4, k_gather, grid, 256, stream, val, C, labels, inv_npix, npixels_total, img);
     QT_LAUNCHED();
     return QT_OK;
 }
@@ -835,30 +782,16 @@ extern "C" int qt_remesh(const float* const* src_parts, const int* widths, const
     QT_ARG(!mean || npix, "mean pooling needs npix");
     QT_ARG(!src_inv || src_npix, "src_inv needs src_npix");
     PoolArgs a = {};
-    int c4 = 0;
-    for (int i = 0; i < nparts; ++i) {
-        QT_ARG(src_parts[i] && widths[i] > 0 && widths[i] % 4 == 0 && lds[i] % 4 == 0 && lds[i] >= widths[i] &&
-               ((uintptr_t)src_parts[i] & 15) == 0, "source parts must be 16-byte aligned with widths / strides that are multiples of 4");
-        a.part[i] = src_parts[i];
-        a.part_ld[i] = lds[i];
-        c4 += widths[i] / 4;
-        a.part_end[i] = c4;
-    }
-    for (int i = nparts; i < 8; ++i) { a.part[i] = nullptr; a.part_ld[i] = 0; a.part_end[i] = c4; }
+    const int c4 = fill_parts(__func__, "source parts must be 16-byte aligned with widths / strides that are multiples of 4", src_parts,
+                              widths, lds, nparts, a.sparts);
+    if (c4 < 0) return QT_E_ARG;
     a.nparts = nparts;
     if (N <= 0) return QT_OK;
     a.img = nullptr; a.S = 1; a.img_clip_stride = 0; a.src_val = src_parts[0]; a.src_labels = src_labels; a.src_npix = src_npix;
     a.src_inv = src_inv; a.C = 4 * c4; a.labels = labels; a.level = level; a.npix = npix; a.mean = mean;
-    int o4 = 0;
-    for (int i = 0; i < nout; ++i) {
-        QT_ARG(out_parts[i] && out_widths[i] > 0 && out_widths[i] % 4 == 0 && ((uintptr_t)out_parts[i] & 15) == 0,
-               "output parts must be 16-byte aligned with widths that are multiples of 4");
-        a.opart[i] = out_parts[i];
-        a.opart_w[i] = out_widths[i];
-        o4 += out_widths[i] / 4;
-        a.opart_end[i] = o4;
-    }
-    for (int i = nout; i < 8; ++i) { a.opart[i] = nullptr; a.opart_w[i] = 0; a.opart_end[i] = o4; }
+    const int o4 = fill_parts(__func__, "output parts must be 16-byte aligned with widths that are multiples of 4", out_parts, out_widths,
+                              nullptr, nout, a.oparts);
+    if (o4 < 0) return QT_E_ARG;
     QT_ARG(o4 == c4, "the output parts must add up to the source width");
     a.noparts = nout > 1 ? nout : 0;
     a.B = B; a.n = n; a.m = m; a.N = N; a.out = out_parts[0]; a.out_stride = 4 * c4; a.out_coff = 0;
