@@ -215,6 +215,13 @@ def masked_bce(outputs, meshes, y, mask=None, weights=None, lead_weights=None, p
                         pos_weight)
 
 
+def weighted_loss(y_hat, meshes, y, mask, lw, binary):
+    """The weighted loss of a head, lw its LossWeights: masked_bce on a binary=True one, else masked_mse."""
+    if binary:
+        return masked_bce(y_hat, meshes, y, mask, weights=lw, pos_weight=lw.pos_weight)
+    return masked_mse(y_hat, meshes, y, mask, weights=lw)
+
+
 # -- gradient accumulation: one optimiser step from k micro-batches (beyond the reference) -------------------------------------
 def check_accumulate(accumulate):
     """accumulate as an integer >= 1, or a ValueError that names it."""
@@ -381,6 +388,18 @@ def sums_product(threshold, maps=None):
     return reduce
 
 
+def loss_product(mask, lw, binary, fused):
+    """Loss: the rollout's training loss against y as a 0-d float32 device tensor -- what forward_loss computes after its
+    forward, by the same rule: masked_mse(binary, fused) without weights (lw None), else the weighted loss of the head
+    (weighted_loss).  The reduce of train()'s test pass; no row of PRODUCTS.  fused=True (binary heads) is the loss a capture can
+    hold."""
+    def reduce(y_hat, meshes, x, y, concat):
+        if lw is None:
+            return masked_mse(y_hat, meshes, y, mask, binary, fused=fused)
+        return weighted_loss(y_hat, meshes, y, mask, lw, binary)
+    return reduce
+
+
 def reliability_product(threshold, bins):
     """Bin sums: the (T_out, B, S, K, 4) float64 probability verification sums of model, persistence and (with concat)
     climatology, K = bins (ops.rollout_reliability)."""
@@ -456,7 +475,9 @@ class Product:
         reduce(x)                        make the reduce(y_hat, meshes, x, y, concat) for batches shaped like x
         collect(result, x)               take one batch's result to the host
         finish()                         the method's return value from what was collected
-    and, where every batch needs something done before its rollout, begin(x).  reads_y: whether the reduce reads y."""
+    and, where every batch needs something done before its rollout, begin(x).  reads_y: whether the reduce reads y.
+    reset() forgets what was collected and keeps what was prepared: the same object then serves another pass over a loader,
+    the captures made from its reduce included (train()'s test pass, once per epoch)."""
     reads_y, begin = True, None
 
 
@@ -480,6 +501,9 @@ class _Frames(Product):
     def finish(self):
         return np.stack(self.preds, 0)
 
+    def reset(self):
+        self.preds = []
+
 
 class _Sums(Product):
     """A product whose reduce leaves (T, B, ...) sums per batch: the loader's (B_total, T, ...) array, one host copy per batch."""
@@ -496,6 +520,9 @@ class _Sums(Product):
 
     def sums(self):
         return np.concatenate(self.parts, 0)
+
+    def reset(self):
+        self.parts = []
 
 
 class _Scores(_Sums):
@@ -531,6 +558,11 @@ class _ScoreMaps(_Scores):
         if maps is not None:
             maps = ScoreMaps(maps.cpu().numpy().reshape(*maps.shape[:3], *self.frame), self.sources)
         return Scores(self.sums(), self.sources, maps=maps)
+
+    def reset(self):            # (the buffer is zeroed where it is: a capture made for this product adds into it by pointer)
+        self.parts = []
+        if self.maps is not None:
+            self.maps.zero_()
 
 
 class _Reliability(_Sums):
@@ -595,6 +627,9 @@ class _Events(Product):
     def finish(self):
         from qtmpnn.events import EventDates
         return EventDates(np.concatenate(self.dates, 0), np.concatenate(self.sums, 0), self.sources, *self.options)
+
+    def reset(self):
+        self.dates, self.sums = [], []
 
 
 PRODUCTS = {'predict': _Frames, 'score': _Scores, 'score_maps': _ScoreMaps, 'reliability': _Reliability, 'fss': _FSS,
@@ -681,6 +716,9 @@ class NextFramePredictorS2S(NextFramePredictor):
         self.training_initiated = False
         self.process_group = None
         self._output_days = {}          # launch date -> its output days' indices into the daily normals (get_climatology_array)
+        # what train()'s validation keywords leave (patience, restore_best, keep_best, monitor): see train()
+        self.best_epoch = self.best_value = self.stopped_epoch = None
+        self.monitor_history = []
 
     # -- activation recomputation (beyond the reference): the mode lives on the Seq2Seq, where the rollout is -------------------
     @property
@@ -857,6 +895,7 @@ class NextFramePredictorS2S(NextFramePredictor):
         sched['base_lrs'], sched['_last_lr'] = [group['initial_lr']], [group['lr']]     # (the scheduler's own aliases)
         self.scheduler.load_state_dict(sched)
         self.train_loss, self.test_loss = list(ckpt['train_loss']), list(ckpt['test_loss'])
+        self.monitor_history = []           # (no checkpoint field: a Monitor's patience count starts anew after a load)
         rng, dev = ckpt['rng'], next(self.model.parameters()).device
         torch.set_rng_state(rng['torch'])
         if dev.type == 'cuda' and rng['cuda'] is not None:
@@ -901,6 +940,7 @@ class NextFramePredictorS2S(NextFramePredictor):
         self.scheduler = StepLR(self.optimizer, step_size=3, gamma=lr_decay)
         self.writer = SummaryWriter('runs/' + self.experiment_name + '_' + datetime.datetime.now().strftime('%Y%m%d_%H_%M_%S'))
         self.test_loss, self.train_loss = [], []
+        self.monitor_history = []
         self.training_initiated = True
 
     # -- the measured unit -----------------------------------------------------------
@@ -935,10 +975,8 @@ class NextFramePredictorS2S(NextFramePredictor):
         return lw if lw is None else lw.to(self.device if self.device is not None else ('cpu' if x is None else x.device))
 
     def _weighted_loss(self, y_hat, meshes, y, mask, lw):
-        """The weighted loss of this predictor's head: masked_bce on a binary=True one, else masked_mse."""
-        if self.binary:
-            return masked_bce(y_hat, meshes, y, mask, weights=lw, pos_weight=lw.pos_weight)
-        return masked_mse(y_hat, meshes, y, mask, weights=lw)
+        """The weighted loss of this predictor's head (weighted_loss)."""
+        return weighted_loss(y_hat, meshes, y, mask, lw, self.binary)
 
     def zero_grad(self):
         """Drop all gradients (set to None, like optimizer.zero_grad(set_to_none=True) on the reference's per-tensor optimizer)."""
@@ -1463,7 +1501,8 @@ class NextFramePredictorS2S(NextFramePredictor):
     @on_device(lambda self, *a, **k: self.device)
     def train(self, loader_train, loader_test, climatology=None, n_epochs=200, lr=0.01, lr_decay=0.95, mask=None,
               high_interest_region=None, truncated_backprop=45, graph_structure=None, use_graph=False, accumulate=1,
-              pos_weight=None, loss_weights=None, lead_weights=None):
+              pos_weight=None, test_graph=False, patience=None, min_delta=0.0, restore_best=False, keep_best=None,
+              monitor='loss', loss_weights=None, lead_weights=None):
         """The reference's training loop (mpnnlstm.py:186-387).  use_graph=True (beyond the reference) replays the whole training
         step as a hipGraph: one graph is captured per distinct batch shape on first sight (that batch's own update runs eagerly just
         before the capture) and the learning-rate schedule keeps working because the capturable optimizer holds lr in a device
@@ -1479,9 +1518,51 @@ class NextFramePredictorS2S(NextFramePredictor):
         stepped with what it has.  `running`, `steps` and the Loss/train scalar stay per micro-batch -- every micro-batch of a group
         is entered with the group's loss, the clip-weighted mean of its micro-batches' -- and the scheduler steps per epoch.  The step
         has to be ONE rollout as for use_graph (a truncation that covers all output steps: no clipping, as there): the reference's
-        chunk loop zeroes the gradients per chunk, so a real truncation leaves nothing to accumulate and is refused."""
+        chunk loop zeroes the gradients per chunk, so a real truncation leaves nothing to accumulate and is refused.
+
+        Validation (beyond the reference; with none of the following given the call is what it was, bit for bit).  The test pass
+        is the inference loop of predict / verify (_inference) with the loss as its product (loss_product): every batch's loss is
+        added as a float64 on the device, in loader order, and the epoch's sum is read ONCE.
+        test_graph=True replays the test pass as hipGraphs: one capture per distinct (batch shape, train / eval mode), the first
+        batch of a shape being the eager static-mode warm-up, replays from then on and in every later epoch; the captures live
+        until train() returns and `static_shapes` is restored after every pass.  A binary=True predictor then runs the fused
+        binary cross-entropy, as make_graphed_step does.  It does not need use_graph=True, and use_graph=True does not imply it:
+        the default test pass stays eager under use_graph as well.
+        patience=k: stop after the first epoch that has seen k epochs without improvement (qtmpnn.validation.best_and_wait:
+        an epoch improves when its value is below the best so far by more than min_delta; ties and NaN do not).  The rule reads
+        the predictor's WHOLE history, self.test_loss, which checkpoints carry: load_checkpoint + train(patience=k) stops where
+        the run that was never interrupted stops.  self.stopped_epoch is the index into that history of the epoch after which
+        the run stopped, None if it did not stop early.
+        restore_best=True: every improving epoch copies the model's parameters (its state_dict) into device buffers allocated
+        before the first batch -- one torch._foreach_copy_, no host traffic -- and after the last epoch they are copied back, in
+        place: a make_graphed_step captured earlier keeps working.  THE OPTIMISER'S MOMENTS AND STEP COUNT ARE LEFT AS THEY ARE,
+        those of the last epoch.  Only epochs of this call can be restored: if none of them improves on the history the
+        predictor came with, the weights stay the last epoch's.
+        keep_best=path: every improving epoch calls save_checkpoint(path), after scheduler.step() and after the histories were
+        appended, so the file resumes like any checkpoint (its test_loss ends with the best epoch); the format is untouched.
+        self.best_epoch / self.best_value (best_and_wait's, indices into the history) are set whenever one of patience,
+        restore_best, keep_best or a Monitor is given; every call starts with them, and stopped_epoch, at None, so a call
+        without these keywords leaves None and not an earlier call's values.
+        monitor='loss', or a qtmpnn.validation.Monitor(products, value, mode): the test pass then makes the monitor's
+        verification products (verify()'s names and keywords, checked under the name `train` before the first training batch)
+        beside the loss, on the SAME rollout -- one model forward per test batch, with test_graph=True one capture per shape --
+        and value(Verification) of every epoch goes to self.monitor_history and the 'Monitor/test' scalar.  patience,
+        restore_best and keep_best then read monitor_history in the monitor's mode; self.test_loss stays the loss, and the NaN and
+        divergence refusals stay with it.  monitor_history BELONGS TO ONE CALL AND IS NOT CHECKPOINTED: every call with a Monitor
+        starts it empty (the next call may monitor another quantity, in another mode), load_checkpoint and initiate_training
+        empty it, so a second call and a resumed run start their patience count anew.  A value that is not one finite float is refused
+        under `monitor` after the test pass that produced it.
+        Each of these keywords is refused by name (TypeError for a wrong type, ValueError for a wrong value) before anything is
+        launched and before the optimiser is made."""
+        from qtmpnn import validation
         image_shape = loader_train.dataset.image_shape
         accumulate = check_accumulate(accumulate)
+        test_graph = validation.check_flag('test_graph', test_graph)
+        patience, min_delta = validation.check_patience(patience), validation.check_min_delta(min_delta)
+        restore_best, keep_best = validation.check_flag('restore_best', restore_best), validation.check_keep_best(keep_best)
+        monitor = validation.check_monitor(monitor)
+        on_loss = isinstance(monitor, str)
+        selecting = patience is not None or restore_best or keep_best is not None or not on_loss
         truncate_ = truncated_backprop not in (0, None)
         single_chunk = truncate_ and truncated_backprop >= self.output_timesteps
         if accumulate > 1 and truncate_ and not single_chunk:
@@ -1491,6 +1572,11 @@ class NextFramePredictorS2S(NextFramePredictor):
         if use_graph and truncate_ and not single_chunk:
             raise ValueError('use_graph=True needs truncated_backprop=0 or >= the output steps (the truncated loop re-runs the encoder '
                              'per chunk)')
+        made = {}
+        if not on_loss:
+            made = make_products('train', monitor.products, ProductCall(
+                self.output_timesteps, getattr(getattr(loader_test, 'dataset', None), 'image_shape', None), self.device,
+                climatology is not None, test_graph, mask))
         if not self.training_initiated:
             self.initiate_training(lr, lr_decay, capturable=use_graph)
         graphed = {}
@@ -1499,6 +1585,20 @@ class NextFramePredictorS2S(NextFramePredictor):
             assert mshape == tuple(image_shape), f'Mask and image shapes do not match. Got {mshape} and {image_shape}'
         truncate = truncate_ and not ((use_graph or accumulate > 1) and single_chunk)
         lw = self._loss_weights(None, mask, loss_weights, lead_weights, pos_weight, shape=image_shape)
+        # the test pass: the loss of every batch (a capture holds the fused BCE, as a captured step does) and the monitor's products
+        test_reduce = loss_product(mask, lw, self.binary, fused=test_graph and self.binary)
+        test_graphs = {} if test_graph else None            # (the captures of the test pass, kept across the epochs)
+        history = lambda: self.test_loss if on_loss else self.monitor_history       # (what the stopping rule reads)
+        mode = 'min' if on_loss else monitor.mode
+        state = lambda: list(self.model.state_dict().values())          # (the parameters where they live: views, no copies)
+        # what an earlier call left does not speak for this one; a Monitor's history is its call's (another call may monitor another
+        # quantity, in another mode), while test_loss goes on across calls
+        self.best_epoch = self.best_value = self.stopped_epoch = None
+        if not on_loss:
+            self.monitor_history = []
+        best_state = saved = None
+        if restore_best:
+            best_state = [torch.empty_like(t) for t in state()]
         st = time.time()
         batch_step = 0
         for epoch in range(n_epochs):
@@ -1530,30 +1630,77 @@ class NextFramePredictorS2S(NextFramePredictor):
                     running += value
                     steps += 1
                     batch_step += 1
-            running_test, steps_test = 0.0, 0
-            for x, y, launch_date in loader_test:
-                x, y = self._clip(x), self._clip(y)
-                concat = self.get_climatology_array(climatology, launch_date) if climatology is not None else None
-                with torch.no_grad():
-                    running_test += self.forward_loss(x, y, concat, mask, high_interest_region, graph_structure,
-                                                      loss_weights=lw).item()
-                steps_test += 1
-            check_tile_errors(always=True)      # once per epoch: the graph-replayed steps and the test loop report only here
+            # once per epoch: the graph-replayed steps and the test pass report their tile errors only at the end of the pass
+            running_test, steps_test = self._test_pass(loader_test, climatology, test_reduce, made, test_graph, test_graphs,
+                                                       mask=mask, high_interest_region=high_interest_region,
+                                                       graph_structure=graph_structure)
             running, running_test = running / (steps + 1), running_test / (steps_test + 1)   # (+1 as the reference, :360-361)
             if np.isnan(running_test):
                 raise ValueError('NaN loss :(')
             if running_test > 4:
                 raise ValueError('Diverged :(')
             self.writer.add_scalar('Loss/test', running_test, epoch)
+            if not on_loss:
+                from qtmpnn.verify import Verification
+                results = Verification({name: p.finish() for name, p in made.items()}, forecast_sources(climatology is not None))
+                monitored = validation.monitored_value(monitor.value(results), epoch)
+                self.writer.add_scalar('Monitor/test', monitored, epoch)
             self.scheduler.step()
             self.train_loss.append(running)
             self.test_loss.append(running_test)
+            if not on_loss:
+                self.monitor_history.append(monitored)
+            if selecting:
+                self.best_epoch, self.best_value, waited = validation.best_and_wait(history(), min_delta, mode)
+                if self.best_epoch == len(history()) - 1:       # this epoch improved
+                    if restore_best:
+                        torch._foreach_copy_(best_state, state())
+                        saved = self.best_epoch
+                    if keep_best is not None:
+                        self.save_checkpoint(keep_best)
             print(f'{self.experiment_name} | Epoch {epoch} train {self.loss_func_name}: {running:.4f}, '
                   f'test {self.loss_func_name}: {running_test:.4f}, lr: {self.scheduler.get_last_lr()[0]:.4f}, '
                   f'time_per_epoch: {(time.time() - st) / (epoch + 1):.1f}')
+            if patience is not None and waited >= patience:
+                self.stopped_epoch = len(history()) - 1
+                print(f'{self.experiment_name} | Stopped after epoch {epoch}: {waited} epochs without improvement on '
+                      f'{self.best_value!r} (epoch {self.best_epoch} of the history)')
+                break
+        if saved is not None:
+            torch._foreach_copy_(state(), best_state)
+            print(f'{self.experiment_name} | Restored the parameters of epoch {saved} of the history')
         print(f'Finished in {(time.time() - st) / 60} minutes')
         self.writer.flush()
         self.loss = pd.DataFrame({'train_loss': self.train_loss, 'test_loss': self.test_loss})
+
+    def _test_pass(self, loader, climatology, loss_reduce, made, use_graph, graphed, **fwd):
+        """The test pass of one epoch of train(): _inference over `loader` with the loss (loss_reduce, a loss_product) and the
+        products `made` ({name: Product}, possibly empty; reset here, collected as _verify collects them) reduced from ONE rollout
+        per batch -> (the sum of the batches' losses, the number of batches).  Every batch's float32 loss is added, as a float64
+        and in loader order, to one device scalar that is read once after the last batch: the float64 sum of the floats, what a
+        Python sum of the .item()s is, to the bit.  graphed: the caller's dict of captures (use_graph), see _inference."""
+        products = list(made.values())
+        for p in products:
+            p.reset()
+        begins = [p.begin for p in products if p.begin is not None]
+        total, batches = [None], [0]
+
+        def product(x):
+            if not products:
+                return loss_reduce
+            reduces = [p.reduce(x) for p in products]
+            return lambda *rollout: (loss_reduce(*rollout), *(reduce(*rollout) for reduce in reduces))
+
+        def consume(result, x):
+            loss, results = (result[0], result[1:]) if products else (result, ())
+            total[0] = loss.double() if total[0] is None else total[0].add_(loss.double())      # (0.0 + v is v)
+            batches[0] += 1
+            for p, r in zip(products, results):
+                p.collect(r, x)
+
+        self._inference(loader, climatology, product, consume, use_graph, graphed=graphed,
+                        begin=(lambda x: [begin(x) for begin in begins]) if begins else None, **fwd)
+        return (0.0 if total[0] is None else total[0].item()), batches[0]
 
     def _micro_groups(self, loader, climatology, k):
         """The loader's items as train() steps them: lists of k consecutive (x, y, concat), clipped and with their climatology
@@ -1625,9 +1772,9 @@ class NextFramePredictorS2S(NextFramePredictor):
         make one host copy.  The graphs are dropped and `static_shapes` is restored when the call returns."""
         return self._one('predict', loader, climatology, mask, high_interest_region, graph_structure, use_graph)
 
-    def _inference(self, loader, climatology, product, consume, use_graph, reads_y=True, begin=None, **fwd):
+    def _inference(self, loader, climatology, product, consume, use_graph, reads_y=True, begin=None, graphed=None, **fwd):
         """The inference loop of predict, score, score_maps, reliability, fss, edge_distance, extent, event_dates and verify (all
-        through _verify): per batch begin(x), if given, then one no-grad
+        through _verify) and of train()'s test pass (_test_pass): per batch begin(x), if given, then one no-grad
         rollout (teacher forcing 0, forward arguments `fwd`) reduced by a reduce(y_hat, meshes, x, y, concat), see frames_product,
         whose result (a tensor, or a tuple of them where several products share the rollout) goes to consume(result, x); x is
         the clipped batch.  product(x) makes the reduce: for every batch of an eager
@@ -1635,9 +1782,13 @@ class NextFramePredictorS2S(NextFramePredictor):
         distinct (x shape, y shape where the product reads y, climatology shape, train / eval mode) is captured once per call on
         first sight (_graphed_product); that batch's result is the eager static-mode warm-up's, later batches of the key are
         replays.  The graphs are dropped and `static_shapes` is restored when the call ends, also by an exception of begin or
-        consume; the tile error word is read once after the last batch."""
+        consume; the tile error word is read once after the last batch.  graphed: a dict the CALLER owns, for the captures to
+        outlive the call (train()'s test pass: captured in the first epoch, replayed in every later one); it is filled here and
+        left as it is, and whoever owns it passes the same product, forward arguments and mode with it every time.
+        `static_shapes` is restored all the same."""
         self.model.to(self.device)
-        graphed, static0 = {}, self.model.static_shapes
+        own = graphed is None
+        graphed, static0 = {} if own else graphed, self.model.static_shapes
         try:
             for x, y, launch_date in loader:
                 x, y = self._clip(x), self._clip(y) if reads_y else None
@@ -1660,7 +1811,8 @@ class NextFramePredictorS2S(NextFramePredictor):
                         result = reduce(y_hat, meshes, x, y, concat)
                 consume(result, x)
         finally:
-            graphed.clear()
+            if own:
+                graphed.clear()
             self.model.static_shapes = static0
         check_tile_errors(always=True)
 
