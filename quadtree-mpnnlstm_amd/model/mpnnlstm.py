@@ -21,8 +21,10 @@ from torch.optim.lr_scheduler import StepLR
 
 from model.graph_functions import image_to_graph, unflatten, plot_contours
 from model.seq2seq import Seq2Seq, check_concat_clips
-from model.utils import add_positional_encoding, get_n_params, int_to_datetime, output_day_indices
+from model.utils import add_positional_encoding, get_n_params, int_to_datetime, launch_day_index, output_day_indices
 from qtmpnn import mesh as _mesh, ops
+from qtmpnn.baselines import (check_references, default_references, forecast_sources, launch_frame, needs_launch_climatology,
+                              reference_fields, reference_launches, spec_name)
 from qtmpnn.dist import all_reduce_sum, allreduce_gradients
 from qtmpnn.flat import flat_params, name_table
 from qtmpnn._lib import on_device
@@ -295,18 +297,20 @@ def batch_shapes(item):
 
 
 class StaticBatch:
-    """Clones of a batch (x, y, concat), any of which may be None, that captured graphs read their inputs from.  The graphs hold
+    """Clones of a batch (x, y, concat, c0), any of which may be None, that captured graphs read their inputs from.  The graphs hold
     bare pointers: every buffer they read or write outside their own pools -- these clones, the loss weights, an accumulator -- has
     to live as long as whatever replays them, so a step object keeps them (its closure, step.loss_weights, step.buffers; a buffer
     named nowhere else is freed, the allocator hands its memory to the next tensor and a replay reads or adds into that)."""
 
-    def __init__(self, x, y, concat):
-        self.tensors = tuple(t if t is None else t.clone() for t in (x, y, concat))
+    def __init__(self, x, y, concat, c0=None):
+        """c0: the climatology of the launch-state day (get_launch_climatology), which travels with the batch as concat does
+        where an anomaly-persistence reference is asked for; None otherwise, and then no member."""
+        self.tensors = tuple(t if t is None else t.clone() for t in (x, y, concat) + (() if c0 is None else (c0,)))
         self.shapes = batch_shapes(self.tensors)
 
-    def load(self, x, y, concat_layers=None):
+    def load(self, x, y, concat_layers=None, c0=None):
         """Copy a batch of the captured shapes in, x first; what has no clone here is not read."""
-        for static, t in zip(self.tensors, (x, y, concat_layers)):
+        for static, t in zip(self.tensors, (x, y, concat_layers, c0)):
             if static is not None:
                 static.copy_(t)
 
@@ -348,19 +352,20 @@ class TileWatch:
             check_tile_errors(always=True)
 
 
-def launch_frame(x):
-    """Channel 0 of the last input frame, (W, H) or (B, W, H): the persistence forecast of every lead time, and the state at launch
-    that the event dates count from."""
-    return x[..., -1, :, :, 0]
+# The products of one inference rollout.  Each is reduce(y_hat, meshes, x, y, concat, named=None) -> one device tensor, written
+# once: the eager branch of the inference loop and the captured body (NextFramePredictorS2S._graphed_product) call the same
+# function.  None writes what another reads, so any of them may follow one rollout in any order (PRODUCTS, below the trainer).
+# named: the product's reference forecasts for the batch, the ordered [(name, tensor)] that ops.with_references takes, made
+# from the batch's fields (baselines.reference_fields: built once per batch for all products); None: the default ones.
+def default_named(x, concat, persistence=True):
+    """The default references of a batch as [(name, tensor)]: persistence (not for the event dates) and, with concat, climatology."""
+    return ([('persistence', launch_frame(x))] if persistence else []) + ([('climatology', concat)] if concat is not None else [])
 
 
-# The products of one inference rollout.  Each is reduce(y_hat, meshes, x, y, concat) -> one device tensor, written once: the
-# eager branch of the inference loop and the captured body (NextFramePredictorS2S._graphed_product) call the same function.
-# None writes what another reads, so any of them may follow one rollout in any order (PRODUCTS, below the trainer).
 def reference_frames(image_shape, mask):
     """Frames by the reference's path (`unflatten` per step, in the caller's mode, one host copy per step): what an eager predict
     returns.  The only reduce whose result is a host array, (B, T_out, W, H, 1); it cannot be captured."""
-    def reduce(y_hat, meshes, x, y, concat):
+    def reduce(y_hat, meshes, x, y, concat, named=None):
         frames = [unflatten(o, ms, image_shape, mask).cpu().numpy() for o, ms in zip(y_hat, meshes)]
         return np.stack(frames, axis=0)[None] if x.dim() == 4 else np.stack(frames, axis=1)
     return reduce
@@ -370,7 +375,7 @@ def frames_product(x, T_out):
     """Frames: every step gathered by one launch into its slot of a (B, T_out, W, H, 1) stack for batches shaped like x."""
     out = torch.empty(1 if x.dim() == 4 else x.shape[0], T_out, x.shape[-3], x.shape[-2], 1, device=x.device)
 
-    def reduce(y_hat, meshes, x, y, concat):
+    def reduce(y_hat, meshes, x, y, concat, named=None):
         for t, (o, ms) in enumerate(zip(y_hat, meshes)):
             ops.gather_frame_into(o, ms, out, t)
         return out
@@ -378,14 +383,29 @@ def frames_product(x, T_out):
 
 
 def sums_product(threshold, maps=None):
-    """Sums: the (T_out, B, S, 8) float64 verification sums of model, persistence and (with concat) climatology; with `maps`, a
-    float64 (T_out, S, 8, P) device buffer, the batch's per-pixel sums are added into it as well."""
-    def reduce(y_hat, meshes, x, y, concat):
-        part = ops.rollout_scores(y_hat, meshes, y, threshold, persistence=launch_frame(x), climatology=concat)
-        if maps is not None:
-            ops.rollout_score_maps(y_hat, meshes, y, maps, threshold, persistence=launch_frame(x), climatology=concat)
+    """Sums: the (T_out, B, S, 8) float64 verification sums of the model and the references `named` (None: persistence and, with
+    concat, climatology); with `maps`, a float64 (T_out, S, 8, P) device buffer, the batch's per-pixel sums are added into it as
+    well -- for more than two references a list of buffers, one per launch (maps_shapes): every launch adds into a block of
+    its own, so that the model's sums are not added twice."""
+    def reduce(y_hat, meshes, x, y, concat, named=None):
+        named = default_named(x, concat) if named is None else named
+        part = ops.with_references(lambda **slots: ops.rollout_scores(y_hat, meshes, y, threshold, **slots), named, 2)
+        if maps is not None:           # (each launch adds into its block in place: nothing to collect, joined_maps reads them once)
+            blocks = maps if isinstance(maps, (list, tuple)) else [maps]
+            for block, (i, j) in zip(blocks, reference_launches(len(named)), strict=True):
+                ops.rollout_score_maps(y_hat, meshes, y, block, threshold, **ops.reference_slots(named[i:j]))
         return part
     return reduce
+
+
+def maps_blocks(T_out, k, P, device):
+    """The zeroed maps buffers of k references: one float64 (T_out, 1 + n_i, 8, P) block per launch, n_i its references."""
+    return [torch.zeros(T_out, 1 + j - i, 8, P, dtype=torch.float64, device=device) for i, j in reference_launches(k)]
+
+
+def joined_maps(blocks):
+    """(T_out, S, 8, P) of maps_blocks' buffers: the model's and the first launch's rows, then every other launch's own."""
+    return blocks[0] if len(blocks) == 1 else torch.cat([blocks[0]] + [b[:, 1:] for b in blocks[1:]], dim=1)
 
 
 def loss_product(mask, lw, binary, fused):
@@ -393,7 +413,7 @@ def loss_product(mask, lw, binary, fused):
     forward, by the same rule: masked_mse(binary, fused) without weights (lw None), else the weighted loss of the head
     (weighted_loss).  The reduce of train()'s test pass; no row of PRODUCTS.  fused=True (binary heads) is the loss a capture can
     hold."""
-    def reduce(y_hat, meshes, x, y, concat):
+    def reduce(y_hat, meshes, x, y, concat, named=None):
         if lw is None:
             return masked_mse(y_hat, meshes, y, mask, binary, fused=fused)
         return weighted_loss(y_hat, meshes, y, mask, lw, binary)
@@ -401,35 +421,38 @@ def loss_product(mask, lw, binary, fused):
 
 
 def reliability_product(threshold, bins):
-    """Bin sums: the (T_out, B, S, K, 4) float64 probability verification sums of model, persistence and (with concat)
-    climatology, K = bins (ops.rollout_reliability)."""
-    def reduce(y_hat, meshes, x, y, concat):
-        return ops.rollout_reliability(y_hat, meshes, y, threshold, bins, persistence=launch_frame(x), climatology=concat)
+    """Bin sums: the (T_out, B, S, K, 4) float64 probability verification sums of the model and the references (sums_product),
+    K = bins (ops.rollout_reliability)."""
+    def reduce(y_hat, meshes, x, y, concat, named=None):
+        return ops.with_references(lambda **slots: ops.rollout_reliability(y_hat, meshes, y, threshold, bins, **slots),
+                                   default_named(x, concat) if named is None else named, 2)
     return reduce
 
 
 def fss_product(threshold, scales):
-    """Neighbourhood sums: the (T_out, B, S, K, 5) int64 Fractions Skill Score sums of model, persistence and (with concat)
-    climatology, K = len(scales) (ops.rollout_fss)."""
-    def reduce(y_hat, meshes, x, y, concat):
-        return ops.rollout_fss(y_hat, meshes, y, threshold, scales, persistence=launch_frame(x), climatology=concat)
+    """Neighbourhood sums: the (T_out, B, S, K, 5) int64 Fractions Skill Score sums of the model and the references
+    (sums_product), K = len(scales) (ops.rollout_fss)."""
+    def reduce(y_hat, meshes, x, y, concat, named=None):
+        return ops.with_references(lambda **slots: ops.rollout_fss(y_hat, meshes, y, threshold, scales, **slots),
+                                   default_named(x, concat) if named is None else named, 2)
     return reduce
 
 
 def edge_product(threshold):
-    """Ice-edge distance sums: the (T_out, B, S, 8) int64 sums of model, persistence and (with concat) climatology
+    """Ice-edge distance sums: the (T_out, B, S, 8) int64 sums of the model and the references (sums_product)
     (ops.rollout_edges)."""
-    def reduce(y_hat, meshes, x, y, concat):
-        return ops.rollout_edges(y_hat, meshes, y, threshold, persistence=launch_frame(x), climatology=concat)
+    def reduce(y_hat, meshes, x, y, concat, named=None):
+        return ops.with_references(lambda **slots: ops.rollout_edges(y_hat, meshes, y, threshold, **slots),
+                                   default_named(x, concat) if named is None else named, 2)
     return reduce
 
 
 def extent_product(threshold, region_dev, area_dev, R):
-    """Regional extent sums: the (T_out, B, R, 1 + S, 4) float64 sums of the truth (row 0) and of model, persistence and (with
-    concat) climatology (ops.rollout_extent); region_dev / area_dev: the device maps of ops.rollout_extent, or None."""
-    def reduce(y_hat, meshes, x, y, concat):
-        return ops.rollout_extent(y_hat, meshes, y, threshold, region_dev, area_dev, R, persistence=launch_frame(x),
-                                  climatology=concat)
+    """Regional extent sums: the (T_out, B, R, 1 + S, 4) float64 sums of the truth (row 0) and of the model and the references
+    (sums_product) (ops.rollout_extent); region_dev / area_dev: the device maps of ops.rollout_extent, or None."""
+    def reduce(y_hat, meshes, x, y, concat, named=None):
+        return ops.with_references(lambda **slots: ops.rollout_extent(y_hat, meshes, y, threshold, region_dev, area_dev, R, **slots),
+                                   default_named(x, concat) if named is None else named, 3, lead=2)
     return reduce
 
 
@@ -445,9 +468,11 @@ def _extent_maps(who, regions, areas, shape, device, region_names=None):
 
 
 def events_product(threshold, kind, persist):
-    """Event buffer: int32, the int64 sums (B, S1 - 1, 8) followed by the dates (B, S1, P) (split_event_buffer)."""
-    def reduce(y_hat, meshes, x, y, concat):
-        return ops._event_buffer(y_hat, meshes, y, launch_frame(x), threshold, kind, persist, concat)[0]
+    """Event buffer: int32, the int64 sums (B, S1 - 1, 8) followed by the dates (B, S1, P) (split_event_buffer) of observed,
+    model and the references `named` (None: climatology, with concat; there is no persistence by default)."""
+    def reduce(y_hat, meshes, x, y, concat, named=None):
+        return ops.event_buffer(y_hat, meshes, y, launch_frame(x), threshold, kind, persist,
+                                default_named(x, concat, persistence=False) if named is None else named)
     return reduce
 
 
@@ -459,13 +484,11 @@ def split_event_buffer(buf, B, S1, frame):
 
 # The product table: what each method of the inference loop is, stated once.  NextFramePredictorS2S.verify and the product's own
 # method (predict, score, ...) both read it.
-ProductCall = collections.namedtuple('ProductCall', 'T_out shape device with_clim graphed mask')
+ProductCall = collections.namedtuple('ProductCall', 'T_out shape device with_clim graphed mask references', defaults=(None,))
 ProductCall.__doc__ = """What a product is told about the call it is part of: the output steps, the frame shape (W, H) (None where a
-loader does not say), the device, whether there is a climatology, whether the rollout is captured, and the mask."""
-
-
-def forecast_sources(with_clim):
-    return ('model', 'persistence') + (('climatology',) if with_clim else ())
+loader does not say), the device, whether there is a climatology, whether the rollout is captured, the mask, and the call's
+`references` (None: the default): as given where make_products gets it, checked (baselines.check_references) and, where
+verify(products={name: dict(references=...)}) gives the product its own, replaced by those where a product gets it."""
 
 
 class Product:
@@ -479,6 +502,11 @@ class Product:
     reset() forgets what was collected and keeps what was prepared: the same object then serves another pass over a loader,
     the captures made from its reduce included (train()'s test pass, once per epoch)."""
     reads_y, begin = True, None
+    refs = None         # the reference specs of this product in the call, as make_products checked them; None: the default ones
+
+    def named(self, fields):
+        """This product's references for a batch, [(name, tensor)] from the batch's fields; None: the default ones."""
+        return None if self.refs is None else [(spec_name(s), fields[s]) for s in self.refs]
 
 
 class _Frames(Product):
@@ -509,7 +537,8 @@ class _Sums(Product):
     """A product whose reduce leaves (T, B, ...) sums per batch: the loader's (B_total, T, ...) array, one host copy per batch."""
 
     def __init__(self, who, call, **options):
-        self.sources, self.parts = forecast_sources(call.with_clim), []
+        self.refs = call.references
+        self.sources, self.parts = forecast_sources(call.with_clim, self.refs), []
         self.prepare(who, call, **options)
 
     def reduce(self, x):
@@ -546,8 +575,8 @@ class _ScoreMaps(_Scores):
     def begin(self, x):         # the maps buffer exists, zeroed, before the first batch's forward; every batch has its grid
         if self.maps is None:
             self.frame = tuple(x.shape[-3:-1])
-            self.maps = torch.zeros(self.T_out, len(self.sources), 8, self.frame[0] * self.frame[1], dtype=torch.float64,
-                                    device=x.device)
+            blocks = maps_blocks(self.T_out, len(self.sources) - 1, self.frame[0] * self.frame[1], x.device)
+            self.maps = blocks[0] if len(blocks) == 1 else blocks       # (more than two references: one block per launch)
         elif tuple(x.shape[-3:-1]) != self.frame:
             raise ValueError(f'{self.who}: a batch of {tuple(x.shape[-3:-1])} frames after {self.frame} ones: maps need '
                              'one grid (use one loader per grid)')
@@ -556,13 +585,14 @@ class _ScoreMaps(_Scores):
         from qtmpnn.score import ScoreMaps, Scores
         maps = self.maps
         if maps is not None:
+            maps = joined_maps(maps if isinstance(maps, list) else [maps])
             maps = ScoreMaps(maps.cpu().numpy().reshape(*maps.shape[:3], *self.frame), self.sources)
         return Scores(self.sums(), self.sources, maps=maps)
 
     def reset(self):            # (the buffer is zeroed where it is: a capture made for this product adds into it by pointer)
         self.parts = []
-        if self.maps is not None:
-            self.maps.zero_()
+        for block in (self.maps if isinstance(self.maps, list) else [] if self.maps is None else [self.maps]):
+            block.zero_()
 
 
 class _Reliability(_Sums):
@@ -612,7 +642,8 @@ class _Events(Product):
             raise ValueError(f'{who}: kind must be one of {ops.EVENT_KINDS}, got {kind!r}')
         if not (isinstance(persist, int) and 1 <= persist <= call.T_out):
             raise ValueError(f'{who}: persist must be an integer in 1..{call.T_out} (the output steps), got {persist!r}')
-        self.sources = ('observed', 'model') + (('climatology',) if call.with_clim else ())
+        refs = self.refs = call.references             # (no persistence by default here)
+        self.sources = ('observed',) + forecast_sources(call.with_clim, default_references(call.with_clim)[1:] if refs is None else refs)
         self.options, self.reducer = (kind, persist, threshold), events_product(threshold, kind, persist)
         self.dates, self.sums = [], []
 
@@ -669,9 +700,58 @@ def make_products(who, products, call):
         if not isinstance(options, collections.abc.Mapping):
             raise ValueError(f'{who}: the keywords of product {name!r} must be a dict, got {options!r}')
         for key in options:
-            if key not in known[name]:
+            if key not in known[name] and (key != 'references' or name == 'predict'):
                 raise ValueError(f'{who}: product {name!r} takes no keyword {key!r}: {name}() takes {tuple(known[name]) or "none"}')
-    return {name: PRODUCTS[name](name, call, **{**known[name], **options}) for name, options in asked}
+    # the call's references are checked once and shared, so that every product reads the same fields; a product's own go first
+    check = lambda who, refs: None if refs is None else check_references(who, refs, call.with_clim, call.T_out, call.shape)
+    shared = check(who, call.references)
+    made = {}
+    for name, options in asked:
+        options = dict(options)
+        own = check(name, options.pop('references', None))
+        made[name] = PRODUCTS[name](name, call._replace(references=shared if own is None else own), **{**known[name], **options})
+    return made
+
+
+def product_specs(products):
+    """The distinct reference specs of some products, in order of first use: what one batch's fields are built for."""
+    specs = []
+    for p in products:
+        specs += [s for s in (p.refs or ()) if not any(s is t or (isinstance(s, str) and s == t) for t in specs)]
+    return tuple(specs)
+
+
+def with_fields(products, reduces):
+    """One reduce for several products of a rollout: every product's reduce on it, each with its own references from the
+    batch's fields -> the tuple of their results."""
+    pairs = list(zip(products, reduces))
+    return lambda y_hat, meshes, x, y, concat, fields=None: tuple(
+        reduce(y_hat, meshes, x, y, concat, p.named(fields)) for p, reduce in pairs)
+
+
+def takes_references(method):
+    """Gives a verification method of the predictor the keyword `references=None` (qtmpnn.baselines: a sequence of
+    'persistence', 'climatology', 'anomaly_persistence' or AnomalyPersistence objects; None: persistence and, with a
+    climatology, climatology, the call as it was) and a maker of a captured product (make_graphed_*), and only a maker, besides,
+    `launch_climatology=None`: the given batch's climatology of the launch-state day (get_launch_climatology), which an anomaly reference reads and which
+    then follows concat in the replay's arguments.  The parameter lists of these methods are read by the product table
+    (product_options: what follows use_graph is a product's keywords) and stay as they are; what every one of them takes
+    alike is taken here, in one place, and held in self._asked while the call runs -- _verify and the makers read it there.
+    The specs are checked with the products (make_products), before the first batch and before any launch."""
+    import functools
+    maker = method.__name__.startswith('make_graphed_')
+
+    @functools.wraps(method)
+    def wrapper(self, *args, references=None, **keywords):
+        launch_climatology = keywords.pop('launch_climatology', None) if maker else None       # (refused as unknown elsewhere)
+        # every call sets its own, None included: a call made while another runs (a Monitor's value function, a callback)
+        # does not inherit the outer call's references
+        previous, self._asked = self._asked, (references, launch_climatology)
+        try:
+            return method(self, *args, **keywords)
+        finally:
+            self._asked = previous
+    return wrapper
 
 
 class NextFramePredictor(ABC):
@@ -716,6 +796,8 @@ class NextFramePredictorS2S(NextFramePredictor):
         self.training_initiated = False
         self.process_group = None
         self._output_days = {}          # launch date -> its output days' indices into the daily normals (get_climatology_array)
+        self._launch_days = {}          # launch date -> its launch-state day's index (get_launch_climatology)
+        self._asked = (None, None)      # the `references` / `launch_climatology` of the call that runs (takes_references)
         # what train()'s validation keywords leave (patience, restore_best, keep_best, monitor): see train()
         self.best_epoch = self.best_value = self.stopped_epoch = None
         self.monitor_history = []
@@ -1355,22 +1437,43 @@ class NextFramePredictorS2S(NextFramePredictor):
         return self._graphed_product(frames_product(x, self.output_timesteps), x, None, concat_layers, mask=mask,
                                      high_interest_region=high_interest_region, graph_structure=graph_structure)
 
-    def _graphed_product(self, reduce, x, y, concat_layers, **fwd):
+    def _graphed_product(self, reduce, x, y, concat_layers, c0=None, specs=(), **fwd):
         """The capture of one rollout (forward arguments `fwd`) and its product `reduce` (one device tensor, or a tuple of them:
         several products of the one rollout) on static copies of the batch; y is None
-        for a product that does not read it, and replay's arguments are then (x, concat), else (x, y, concat)."""
+        for a product that does not read it, and replay's arguments are then (x, concat), else (x, y, concat).
+        specs: the reference specs whose fields the body builds from the static batch (baselines.reference_fields: the torch
+        ops are captured with the rollout, so a replay recomputes them) and hands to reduce as its sixth argument; c0: the
+        climatology of the launch-state day, for the anomaly references among them -- it then follows concat in replay's
+        arguments."""
         check_concat_clips(x, concat_layers)
         self.model.static_shapes = True
-        batch = StaticBatch(x, y, concat_layers)
-        sx, sy, sc = batch.tensors
+        batch = StaticBatch(x, y, concat_layers, c0)
+        sx, sy, sc, sc0 = batch.tensors + (None,) * (c0 is None)
 
         def body():
             with torch.no_grad():
                 y_hat, meshes = self.model(sx, concat_layers=sc, teacher_forcing_ratio=0, **fwd)
-                return reduce(y_hat, meshes, sx, sy, sc)
+                if not specs:
+                    return reduce(y_hat, meshes, sx, sy, sc)
+                return reduce(y_hat, meshes, sx, sy, sc, reference_fields(sx, sc, sc0, specs))
         if y is None:
-            return self._graphed_inference(body, lambda x, concat_layers=None: batch.load(x, None, concat_layers))
+            return self._graphed_inference(body, lambda x, concat_layers=None, c0=None: batch.load(x, None, concat_layers, c0))
         return self._graphed_inference(body, batch.load)
+
+    def _graphed_one(self, who, reduce, x, y, concat_layers, **fwd):
+        """_graphed_product of one product's reduce with the references the maker `who` was asked for (takes_references):
+        checked here, before any launch; none asked for is the capture as it was.  With more than two references
+        make_graphed_scores(maps=) takes a list of buffers, one per launch (maps_blocks)."""
+        references, c0 = self._asked
+        if references is None:
+            return self._graphed_product(reduce, x, y, concat_layers, **fwd)
+        specs = check_references(who, references, concat_layers is not None, self.output_timesteps, tuple(x.shape[-3:-1]))
+        if needs_launch_climatology(specs) and c0 is None:
+            raise ValueError(f'{who}: references: an anomaly reference needs launch_climatology=, the climatology of the '
+                             'launch-state day of the given batch (get_launch_climatology)')
+        named = lambda fields: [(spec_name(s), fields[s]) for s in specs]
+        return self._graphed_product(lambda y_hat, meshes, x, y, concat, fields: reduce(y_hat, meshes, x, y, concat, named(fields)),
+                                     x, y, concat_layers, c0=c0 if needs_launch_climatology(specs) else None, specs=specs, **fwd)
 
     def _graphed_inference(self, body, load):
         """Warm-up, capture and replay of a no-grad inference body (_graphed_product).  body() reads the
@@ -1413,6 +1516,7 @@ class NextFramePredictorS2S(NextFramePredictor):
         return replay
 
     @on_device(lambda self, *a, **k: self.device)
+    @takes_references
     def make_graphed_scores(self, x, y, concat_layers=None, mask=None, high_interest_region=None, graph_structure=None,
                             threshold=0.15, maps=None):
         """make_graphed_rollout with the verification sums in place of the frames: the capture holds the rollout and
@@ -1420,40 +1524,46 @@ class NextFramePredictorS2S(NextFramePredictor):
         frame gather.  Returns `scores(x, y, concat) -> (T_out, B, S, 8)` float64 device tensor; `scores.warmup` is the given
         batch's.  maps: a float64 (T_out, S, 8, P) device buffer that the body also adds the batch's per-pixel sums into
         (ops.rollout_score_maps).  The warm-up runs the body once and the capture records it without running, so the given
-        batch is added exactly once, and every replay adds its batch once."""
-        return self._graphed_product(sums_product(threshold, maps), x, y, concat_layers, mask=mask,
-                                     high_interest_region=high_interest_region, graph_structure=graph_structure)
+        batch is added exactly once, and every replay adds its batch once.  With more than two `references` maps is a LIST of
+        buffers, one (T_out, 1 + n_i, 8, P) block per launch as maps_blocks makes them; joined_maps(blocks) is the
+        (T_out, S, 8, P) array of all sources."""
+        return self._graphed_one('make_graphed_scores', sums_product(threshold, maps), x, y, concat_layers, mask=mask,
+                                 high_interest_region=high_interest_region, graph_structure=graph_structure)
 
     @on_device(lambda self, *a, **k: self.device)
+    @takes_references
     def make_graphed_reliability(self, x, y, concat_layers=None, mask=None, high_interest_region=None, graph_structure=None,
                                  threshold=0.15, bins=10):
         """make_graphed_scores with the per-bin probability sums in place of the verification sums: the capture holds the
         rollout and ops.rollout_reliability (sources as make_graphed_scores), no frame gather.  Returns
         `reliability(x, y, concat) -> (T_out, B, S, bins, 4)` float64 device tensor; `reliability.warmup` is the given batch's."""
         ops.check_bins('make_graphed_reliability', bins)
-        return self._graphed_product(reliability_product(threshold, bins), x, y, concat_layers, mask=mask,
-                                     high_interest_region=high_interest_region, graph_structure=graph_structure)
+        return self._graphed_one('make_graphed_reliability', reliability_product(threshold, bins), x, y, concat_layers, mask=mask,
+                                 high_interest_region=high_interest_region, graph_structure=graph_structure)
 
     @on_device(lambda self, *a, **k: self.device)
+    @takes_references
     def make_graphed_fss(self, x, y, concat_layers=None, mask=None, high_interest_region=None, graph_structure=None,
                          threshold=0.15, scales=(1, 3, 5, 9, 17, 33)):
         """make_graphed_scores with the per-scale neighbourhood sums in place of the verification sums: the capture holds the
         rollout and ops.rollout_fss (sources as make_graphed_scores), no frame gather.  Returns
         `fss(x, y, concat) -> (T_out, B, S, len(scales), 5)` int64 device tensor; `fss.warmup` is the given batch's."""
         scales = ops.check_scales('make_graphed_fss', scales)
-        return self._graphed_product(fss_product(threshold, scales), x, y, concat_layers, mask=mask,
-                                     high_interest_region=high_interest_region, graph_structure=graph_structure)
+        return self._graphed_one('make_graphed_fss', fss_product(threshold, scales), x, y, concat_layers, mask=mask,
+                                 high_interest_region=high_interest_region, graph_structure=graph_structure)
 
     @on_device(lambda self, *a, **k: self.device)
+    @takes_references
     def make_graphed_edges(self, x, y, concat_layers=None, mask=None, high_interest_region=None, graph_structure=None,
                            threshold=0.15):
         """make_graphed_scores with the ice-edge distance sums in place of the verification sums: the capture holds the rollout
         and ops.rollout_edges (sources as make_graphed_scores), no frame gather.  Returns `edges(x, y, concat) -> (T_out, B, S,
         8)` int64 device tensor; `edges.warmup` is the given batch's."""
-        return self._graphed_product(edge_product(threshold), x, y, concat_layers, mask=mask,
-                                     high_interest_region=high_interest_region, graph_structure=graph_structure)
+        return self._graphed_one('make_graphed_edges', edge_product(threshold), x, y, concat_layers, mask=mask,
+                                 high_interest_region=high_interest_region, graph_structure=graph_structure)
 
     @on_device(lambda self, *a, **k: self.device)
+    @takes_references
     def make_graphed_extent(self, x, y, concat_layers=None, mask=None, high_interest_region=None, graph_structure=None,
                             threshold=0.15, regions=None, areas=None):
         """make_graphed_scores with the regional extent sums in place of the verification sums: the capture holds the rollout
@@ -1461,10 +1571,11 @@ class NextFramePredictorS2S(NextFramePredictor):
         extent(), checked (ops.check_regions) and uploaded here, once.  Returns `extent(x, y, concat) -> (T_out, B, R, 1 + S, 4)`
         float64 device tensor; `extent.warmup` is the given batch's."""
         region_dev, area_dev, R, _ = _extent_maps('make_graphed_extent', regions, areas, x.shape[-3:-1], x.device)
-        return self._graphed_product(extent_product(threshold, region_dev, area_dev, R), x, y, concat_layers, mask=mask,
-                                     high_interest_region=high_interest_region, graph_structure=graph_structure)
+        return self._graphed_one('make_graphed_extent', extent_product(threshold, region_dev, area_dev, R), x, y, concat_layers,
+                                 mask=mask, high_interest_region=high_interest_region, graph_structure=graph_structure)
 
     @on_device(lambda self, *a, **k: self.device)
+    @takes_references
     def make_graphed_events(self, x, y, concat_layers=None, mask=None, high_interest_region=None, graph_structure=None,
                             threshold=0.15, kind='breakup', persist=5):
         """make_graphed_scores with the event dates in place of the verification sums: the capture holds the rollout, the
@@ -1472,10 +1583,11 @@ class NextFramePredictorS2S(NextFramePredictor):
         last input frame, climatology = concat_layers when given), no frame gather.  Returns `events(x, y, concat)` -> one
         int32 device buffer, the int64 sums (B, S1 - 1, 8) followed by the dates (B, S1, P) (split_event_buffer);
         `events.warmup` is the given batch's.  The scan's first launch initialises its state, so a replay needs no memset."""
-        return self._graphed_product(events_product(threshold, kind, persist), x, y, concat_layers, mask=mask,
-                                     high_interest_region=high_interest_region, graph_structure=graph_structure)
+        return self._graphed_one('make_graphed_events', events_product(threshold, kind, persist), x, y, concat_layers, mask=mask,
+                                 high_interest_region=high_interest_region, graph_structure=graph_structure)
 
     @on_device(lambda self, *a, **k: self.device)
+    @takes_references
     def make_graphed_verification(self, x, y, concat_layers=None, mask=None, high_interest_region=None, graph_structure=None,
                                   products=DEFAULT_PRODUCTS):
         """The makers above in one capture: the rollout and the launches of every product of `products` (verify()'s names and
@@ -1484,15 +1596,21 @@ class NextFramePredictorS2S(NextFramePredictor):
         make_graphed_rollout's stack; 'event_dates': the buffer of make_graphed_events; 'score_maps': the batch's sums, as
         make_graphed_scores(maps=...)); `.warmup` is that tuple for the given batch and `.products` the names.  With 'score_maps'
         the zeroed float64 (T_out, S, 8, P) buffer is allocated here and is `.maps`: the given batch is in it once, and every
-        replay adds its batch once."""
+        replay adds its batch once.  With more than two references on 'score_maps', `.maps` is the LIST of per-launch blocks
+        (maps_blocks) and joined_maps(replay.maps) the (T_out, S, 8, P) array."""
         check_concat_clips(x, concat_layers)
-        call = ProductCall(self.output_timesteps, tuple(x.shape[-3:-1]), x.device, concat_layers is not None, True, mask)
+        references, c0 = self._asked
+        call = ProductCall(self.output_timesteps, tuple(x.shape[-3:-1]), x.device, concat_layers is not None, True, mask, references)
         made = make_products('make_graphed_verification', products, call)
+        specs = product_specs(made.values())
+        if needs_launch_climatology(specs) and c0 is None:
+            raise ValueError('make_graphed_verification: references: an anomaly reference needs launch_climatology=, the '
+                             'climatology of the launch-state day of the given batch (get_launch_climatology)')
         for p in made.values():
             if p.begin is not None:
                 p.begin(x)
-        reduces = [p.reduce(x) for p in made.values()]
-        replay = self._graphed_product(lambda *rollout: tuple(reduce(*rollout) for reduce in reduces), x, y, concat_layers,
+        replay = self._graphed_product(with_fields(made.values(), [p.reduce(x) for p in made.values()]), x, y, concat_layers,
+                                       c0=c0 if needs_launch_climatology(specs) else None, specs=specs,
                                        mask=mask, high_interest_region=high_interest_region, graph_structure=graph_structure)
         replay.products = tuple(made)
         replay.maps = made['score_maps'].maps if 'score_maps' in made else None
@@ -1688,8 +1806,8 @@ class NextFramePredictorS2S(NextFramePredictor):
         def product(x):
             if not products:
                 return loss_reduce
-            reduces = [p.reduce(x) for p in products]
-            return lambda *rollout: (loss_reduce(*rollout), *(reduce(*rollout) for reduce in reduces))
+            results = with_fields(products, [p.reduce(x) for p in products])
+            return lambda *rollout: (loss_reduce(*rollout[:5]), *results(*rollout))
 
         def consume(result, x):
             loss, results = (result[0], result[1:]) if products else (result, ())
@@ -1698,7 +1816,7 @@ class NextFramePredictorS2S(NextFramePredictor):
             for p, r in zip(products, results):
                 p.collect(r, x)
 
-        self._inference(loader, climatology, product, consume, use_graph, graphed=graphed,
+        self._inference(loader, climatology, product, consume, use_graph, graphed=graphed, specs=product_specs(products),
                         begin=(lambda x: [begin(x) for begin in begins]) if begins else None, **fwd)
         return (0.0 if total[0] is None else total[0].item()), batches[0]
 
@@ -1762,6 +1880,24 @@ class NextFramePredictorS2S(NextFramePredictor):
         doys = torch.tensor(rows, dtype=torch.int64).to(climatology.device)
         return torch.moveaxis(climatology[:, doys], 0, -1)
 
+    def get_launch_climatology(self, climatology, launch_date):
+        """Daily normals of the launch-state day, the day before the first output day (model.utils.launch_day_index): what
+        get_climatology_array is for the output days, by the same rules.  launch_date (1,): (W, H, Cy); launch_date (B,) with
+        B > 1: (B, W, H, Cy), entry [c] what the call on launch_date[c:c + 1] returns, ONE (B,) int64 index array and one
+        gather.  The index is kept per distinct launch date beside get_climatology_array's (self._launch_days), on first use
+        here: a call that asks for no anomaly reference converts no date more than it did."""
+        dates = launch_date.numpy()
+        if dates.ndim != 1 or len(dates) <= 1:
+            return torch.moveaxis(climatology[:, launch_day_index(dates[0])], 0, -1)
+        rows = []
+        for date in dates:
+            key = date.item()
+            if key not in self._launch_days:
+                self._launch_days[key] = launch_day_index(date)
+            rows.append(self._launch_days[key])
+        doys = torch.tensor(rows, dtype=torch.int64).to(climatology.device)
+        return torch.moveaxis(climatology[:, doys], 0, -1)
+
     @on_device(lambda self, *a, **k: self.device)
     def predict(self, loader, climatology=None, mask=None, high_interest_region=None, graph_structure=None, use_graph=False):
         """Inference over a loader -> (n_clips, T_out, W, H, 1) array (mpnnlstm.py:402-440).
@@ -1772,7 +1908,8 @@ class NextFramePredictorS2S(NextFramePredictor):
         make one host copy.  The graphs are dropped and `static_shapes` is restored when the call returns."""
         return self._one('predict', loader, climatology, mask, high_interest_region, graph_structure, use_graph)
 
-    def _inference(self, loader, climatology, product, consume, use_graph, reads_y=True, begin=None, graphed=None, **fwd):
+    def _inference(self, loader, climatology, product, consume, use_graph, reads_y=True, begin=None, graphed=None, specs=(),
+                   **fwd):
         """The inference loop of predict, score, score_maps, reliability, fss, edge_distance, extent, event_dates and verify (all
         through _verify) and of train()'s test pass (_test_pass): per batch begin(x), if given, then one no-grad
         rollout (teacher forcing 0, forward arguments `fwd`) reduced by a reduce(y_hat, meshes, x, y, concat), see frames_product,
@@ -1785,8 +1922,13 @@ class NextFramePredictorS2S(NextFramePredictor):
         consume; the tile error word is read once after the last batch.  graphed: a dict the CALLER owns, for the captures to
         outlive the call (train()'s test pass: captured in the first epoch, replayed in every later one); it is filled here and
         left as it is, and whoever owns it passes the same product, forward arguments and mode with it every time.
-        `static_shapes` is restored all the same."""
+        `static_shapes` is restored all the same.
+        specs: the reference specs of the products (product_specs).  Their fields are built once per batch, on the device, from
+        x, concat and -- for the anomaly references -- the climatology of the launch-state day, which then travels with the
+        batch as concat does (get_launch_climatology; part of the captures' key); the reduce gets them as its sixth argument.
+        Without specs (every product on its default references) nothing of this happens."""
         self.model.to(self.device)
+        with_c0 = needs_launch_climatology(specs)
         own = graphed is None
         graphed, static0 = {} if own else graphed, self.model.static_shapes
         try:
@@ -1797,10 +1939,15 @@ class NextFramePredictorS2S(NextFramePredictor):
                 if begin is not None:
                     begin(x)
                 batch = (x, concat) if y is None else (x, y, concat)
+                if with_c0:
+                    c0 = self.get_launch_climatology(climatology, launch_date)
+                    batch, fwd_c0 = batch + (c0,), dict(c0=c0, specs=specs)
+                else:
+                    c0, fwd_c0 = None, dict(specs=specs) if specs else {}
                 if use_graph:
                     key = batch_shapes(batch) + (self.model.training,)
                     if key not in graphed:
-                        graphed[key] = self._graphed_product(product(x), x, y, concat, **fwd)
+                        graphed[key] = self._graphed_product(product(x), x, y, concat, **fwd_c0, **fwd)
                         result = graphed[key].warmup
                     else:
                         result = graphed[key](*batch)
@@ -1808,7 +1955,10 @@ class NextFramePredictorS2S(NextFramePredictor):
                     reduce = product(x)
                     with torch.no_grad():
                         y_hat, meshes = self.model(x, concat_layers=concat, teacher_forcing_ratio=0, **fwd)
-                        result = reduce(y_hat, meshes, x, y, concat)
+                        if specs:
+                            result = reduce(y_hat, meshes, x, y, concat, reference_fields(x, concat, c0, specs))
+                        else:
+                            result = reduce(y_hat, meshes, x, y, concat)
                 consume(result, x)
         finally:
             if own:
@@ -1818,32 +1968,34 @@ class NextFramePredictorS2S(NextFramePredictor):
 
     def _verify(self, who, loader, climatology, mask, high_interest_region, graph_structure, use_graph, products):
         """_inference with the products `products` names (make_products: all of them checked and prepared before the first batch)
-        on ONE rollout per batch -> {name: result} in the order given.  Per batch: begin of the products that have one, the
+        on ONE rollout per batch -> ({name: result} in the order given, the call's sources).  Per batch: begin of the products that have one, the
         rollout, every product's reduce on it in order (a tuple of results; with use_graph all of it is one capture per key),
         one collect per product."""
         call = ProductCall(self.output_timesteps, getattr(getattr(loader, 'dataset', None), 'image_shape', None), self.device,
-                           climatology is not None, bool(use_graph), mask)
+                           climatology is not None, bool(use_graph), mask, self._asked[0])
         made = make_products(who, products, call)
         begins = [p.begin for p in made.values() if p.begin is not None]
 
         def product(x):
-            reduces = [p.reduce(x) for p in made.values()]
-            return lambda *rollout: tuple(reduce(*rollout) for reduce in reduces)
+            return with_fields(made.values(), [p.reduce(x) for p in made.values()])
 
         def consume(results, x):
             for p, result in zip(made.values(), results):
                 p.collect(result, x)
 
         self._inference(loader, climatology, product, consume, use_graph, reads_y=any(p.reads_y for p in made.values()),
-                        begin=(lambda x: [begin(x) for begin in begins]) if begins else None, mask=mask,
-                        high_interest_region=high_interest_region, graph_structure=graph_structure)
-        return {name: p.finish() for name, p in made.items()}
+                        begin=(lambda x: [begin(x) for begin in begins]) if begins else None, specs=product_specs(made.values()),
+                        mask=mask, high_interest_region=high_interest_region, graph_structure=graph_structure)
+        # (the call's own sources: the names of its references, which make_products has checked by now)
+        sources = forecast_sources(call.with_clim, None if call.references is None else tuple(call.references))
+        return {name: p.finish() for name, p in made.items()}, sources
 
     def _one(self, name, loader, climatology, mask, high_interest_region, graph_structure, use_graph, **options):
         """The method `name`: _verify with that one product."""
-        return self._verify(name, loader, climatology, mask, high_interest_region, graph_structure, use_graph, {name: options})[name]
+        return self._verify(name, loader, climatology, mask, high_interest_region, graph_structure, use_graph, {name: options})[0][name]
 
     @on_device(lambda self, *a, **k: self.device)
+    @takes_references
     def verify(self, loader, climatology=None, mask=None, high_interest_region=None, graph_structure=None, use_graph=False,
                products=DEFAULT_PRODUCTS):
         """Several verification products from ONE rollout per batch -> qtmpnn.verify.Verification (beyond the reference): what
@@ -1861,8 +2013,8 @@ class NextFramePredictorS2S(NextFramePredictor):
         (make_graphed_verification).  'predict' is what predict() is in the same mode: eagerly the reference's `unflatten` per
         step, graphed the gathered stack."""
         from qtmpnn.verify import Verification
-        results = self._verify('verify', loader, climatology, mask, high_interest_region, graph_structure, use_graph, products)
-        return Verification(results, forecast_sources(climatology is not None))
+        return Verification(*self._verify('verify', loader, climatology, mask, high_interest_region, graph_structure, use_graph,
+                                          products))
 
     @on_device(lambda self, *a, **k: self.device)
     def attention_weights(self, x, concat_layers=None, mask=None, high_interest_region=None, graph_structure=None, select=None):
@@ -2017,6 +2169,7 @@ class NextFramePredictorS2S(NextFramePredictor):
                            Js[1].copy() if Jb is not None else None)
 
     @on_device(lambda self, *a, **k: self.device)
+    @takes_references
     def score(self, loader, climatology=None, mask=None, high_interest_region=None, graph_structure=None, use_graph=False,
               threshold=0.15):
         """Forecast verification over a loader -> qtmpnn.score.Scores (beyond the reference, whose score() is empty; the numbers
@@ -2029,11 +2182,16 @@ class NextFramePredictorS2S(NextFramePredictor):
         'climatology' (the daily normals the decoder gets).  `threshold` separates ice from no ice (strict >); with binary=True
         the outputs are probabilities and a caller passes 0.5.  use_graph=True replays rollout + sums as one hipGraph per
         distinct batch shape, as predict(use_graph=True) does (make_graphed_scores).  `.maps` of the result is None: score_maps()
-        is this call with the per-pixel maps as well."""
+        is this call with the per-pixel maps as well.
+        references= (a keyword of this and every other product method, of verify and of the makers: takes_references) names the
+        reference forecasts in place of that default pair: a sequence of 'persistence', 'climatology', 'anomaly_persistence' or
+        qtmpnn.baselines.AnomalyPersistence objects; the sources are then ('model',) + their names in the order given, and more
+        than two cost one more launch of the same kernels per pair."""
         return self._one('score', loader, climatology, mask, high_interest_region, graph_structure, use_graph,
                          threshold=threshold)
 
     @on_device(lambda self, *a, **k: self.device)
+    @takes_references
     def score_maps(self, loader, climatology=None, mask=None, high_interest_region=None, graph_structure=None, use_graph=False,
                    threshold=0.15):
         """score() with per-pixel maps from the same pass: the returned Scores has the same `.sums`, bit for bit, and `.maps`, a
@@ -2046,6 +2204,7 @@ class NextFramePredictorS2S(NextFramePredictor):
                          threshold=threshold)
 
     @on_device(lambda self, *a, **k: self.device)
+    @takes_references
     def reliability(self, loader, climatology=None, mask=None, high_interest_region=None, graph_structure=None, use_graph=False,
                     threshold=0.15, bins=10):
         """Probability verification over a loader -> qtmpnn.reliability.Reliability (beyond the reference): every source's value
@@ -2061,6 +2220,7 @@ class NextFramePredictorS2S(NextFramePredictor):
                          threshold=threshold, bins=bins)
 
     @on_device(lambda self, *a, **k: self.device)
+    @takes_references
     def fss(self, loader, climatology=None, mask=None, high_interest_region=None, graph_structure=None, use_graph=False,
             threshold=0.15, scales=(1, 3, 5, 9, 17, 33)):
         """Neighbourhood verification over a loader -> qtmpnn.fss.FSS (beyond the reference): the Fractions Skill Score
@@ -2076,6 +2236,7 @@ class NextFramePredictorS2S(NextFramePredictor):
                          threshold=threshold, scales=scales)
 
     @on_device(lambda self, *a, **k: self.device)
+    @takes_references
     def edge_distance(self, loader, climatology=None, mask=None, high_interest_region=None, graph_structure=None, use_graph=False,
                       threshold=0.15):
         """Ice-edge verification over a loader -> qtmpnn.edges.EdgeDistance (beyond the reference): how far, in pixels, the
@@ -2091,6 +2252,7 @@ class NextFramePredictorS2S(NextFramePredictor):
                          threshold=threshold)
 
     @on_device(lambda self, *a, **k: self.device)
+    @takes_references
     def extent(self, loader, climatology=None, mask=None, high_interest_region=None, graph_structure=None, use_graph=False,
                threshold=0.15, regions=None, areas=None, region_names=None):
         """Sea-ice extent, sea-ice area and the integrated ice-edge error over a loader -> qtmpnn.extent.Extent (beyond the
@@ -2109,6 +2271,7 @@ class NextFramePredictorS2S(NextFramePredictor):
                          threshold=threshold, regions=regions, areas=areas, region_names=region_names)
 
     @on_device(lambda self, *a, **k: self.device)
+    @takes_references
     def event_dates(self, loader, climatology=None, mask=None, high_interest_region=None, graph_structure=None, use_graph=False,
                     threshold=0.15, kind='breakup', persist=5):
         """Break-up / freeze-up dates over a loader -> qtmpnn.events.EventDates (beyond the reference): per clip, source and

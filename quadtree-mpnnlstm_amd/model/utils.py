@@ -74,5 +74,13 @@ def output_day_indices(launch, output_timesteps):
     return [day_of_year_index(launch + 8.640e13 * t) for t in range(output_timesteps)]
 
 
+def launch_day_index(launch):
+    """The day-of-year index of the launch-state day of a clip launched at `launch` (int64 ns): the calendar day before the first
+    output day, launch - 8.640e13 in the float64 arithmetic of output_day_indices, by the same rule (31 December of a leap year
+    is 365; a 1 January launch reads the previous year's 31 December).  It is the day of the last input frame, whose anomaly
+    the anomaly-persistence reference carries (qtmpnn.baselines)."""
+    return day_of_year_index(launch - 8.640e13)
+
+
 def round_to_day(dt):
     return datetime.datetime(*dt.timetuple()[:3])

@@ -79,6 +79,7 @@ class ClipBank:
         if times.shape != (D,):
             raise ValueError(f'times: must be ({D},), one stamp per day of the series, got {times.shape}')
         first_day = window_table(D, input_timesteps, output_timesteps, segments)
+        self.segments = day_ranges('segments', [(0, D)] if segments is None else [tuple(seg) for seg in segments], D)
         xc, yc = _channels('x_channels', x_channels, C), _channels('y_channels', y_channels, C)
         self.input_timesteps, self.output_timesteps = int(input_timesteps), int(output_timesteps)
         self.device = torch.device('cuda' if device is None else device)
@@ -132,6 +133,24 @@ class ClipBank:
         atomics, no kernel of the library: two calls give the same bits.  Meant to run once per experiment."""
         from model.utils import day_of_year_index
         D, W, H, Cy = self.y.shape
+        picked = self._picked(days)
+        index = np.array([day_of_year_index(t) for t in self.times[picked]], dtype=np.int64)
+        order = np.argsort(index, kind='stable')                # by index; ascending days within one (picked is ascending)
+        index, picked = index[order], picked[order]
+        groups, first, count = np.unique(index, return_index=True, return_counts=True)
+        sums = torch.zeros(366, W, H, Cy, dtype=torch.float64, device=self.device)
+        for r in range(int(count.max())):
+            has = count > r
+            rows = torch.from_numpy(groups[has]).to(self.device)
+            sums[rows] = sums[rows] + self.y[torch.from_numpy(picked[first[has] + r]).to(self.device)].double()
+        n = torch.ones(366, dtype=torch.float64)
+        n[torch.from_numpy(groups)] = torch.from_numpy(count).double()
+        return (sums / n.to(self.device)[:, None, None, None]).to(torch.float32).permute(3, 0, 1, 2).contiguous()
+
+    def _picked(self, days):
+        """The stored days that `days` selects, ascending: a boolean (D,) selection, a list of (start, stop) ranges checked as
+        `segments` are, or None for every day; a ValueError that names `days` otherwise (normals, anomaly_autocorrelation)."""
+        D = self.y.shape[0]
         if days is None:
             picked = np.arange(D)
         elif (torch.is_tensor(days) and days.dtype == torch.bool) or (isinstance(days, np.ndarray) and days.dtype == np.bool_):
@@ -146,18 +165,56 @@ class ClipBank:
             picked = np.concatenate([np.arange(s, e) for s, e in day_ranges('days', days, D)] + [np.zeros(0, np.int64)])
         if not len(picked):
             raise ValueError('days: no day is selected')
-        index = np.array([day_of_year_index(t) for t in self.times[picked]], dtype=np.int64)
-        order = np.argsort(index, kind='stable')                # by index; ascending days within one (picked is ascending)
-        index, picked = index[order], picked[order]
-        groups, first, count = np.unique(index, return_index=True, return_counts=True)
-        sums = torch.zeros(366, W, H, Cy, dtype=torch.float64, device=self.device)
-        for r in range(int(count.max())):
-            has = count > r
-            rows = torch.from_numpy(groups[has]).to(self.device)
-            sums[rows] = sums[rows] + self.y[torch.from_numpy(picked[first[has] + r]).to(self.device)].double()
-        n = torch.ones(366, dtype=torch.float64)
-        n[torch.from_numpy(groups)] = torch.from_numpy(count).double()
-        return (sums / n.to(self.device)[:, None, None, None]).to(torch.float32).permute(3, 0, 1, 2).contiguous()
+        return picked
+
+    def anomaly_autocorrelation(self, max_lag, days=None, normals=None):
+        """The lag autocorrelation of the stored y series' anomalies per pixel -> (Cy, max_lag, W, H) float32 on the bank's
+        device; entry [c, k] is that of lag k + 1:
+
+            a[d]    = y[d] - normals[c, day_of_year_index(d)]
+            r[c, k] = sum a[d] a[d + lag] / sqrt(sum a[d]^2 * sum a[d + lag]^2),   lag = k + 1
+
+        over the day pairs (d, d + lag) that lie in one segment of the bank and are both selected by `days` (normals()'s
+        selection, checked the same way); 0 where the denominator is 0.  normals: (Cy, 366, W, H), default self.normals(days).
+        r[0, :T_out] is what qtmpnn.baselines.AnomalyPersistence(damping=) takes.  max_lag: an integer >= 1 and less than the
+        number of selected days of the shortest segment that has any.
+        The sums are float64 and take the pairs in ascending order of d, every lag at once: one rounded product and one add
+        per day, element-wise torch ops (a pair that does not count adds an exact 0), rounded to float32 once.  No atomics, no
+        kernel of the library: two calls give the same bits.  Meant to run once per experiment."""
+        from model.utils import day_of_year_index
+        D, W, H, Cy = self.y.shape
+        picked = self._picked(days)
+        selected = np.zeros(D, bool)
+        selected[picked] = True
+        shortest = min(int(selected[s:e].sum()) for s, e in self.segments if selected[s:e].any())
+        if not _whole(max_lag) or not 1 <= max_lag < shortest:
+            raise ValueError(f'max_lag: must be an integer >= 1 and less than the {shortest} selected days of the shortest segment, '
+                             f'got {max_lag!r}')
+        L = int(max_lag)
+        if normals is None:
+            normals = self.normals(days)
+        normals = torch.as_tensor(normals).to(self.device, torch.float32)
+        if tuple(normals.shape) != (Cy, 366, W, H):
+            raise ValueError(f'normals: shape {tuple(normals.shape)}, expected {(Cy, 366, W, H)}')
+        index = torch.tensor([day_of_year_index(t) for t in self.times], dtype=torch.int64, device=self.device)
+        a = torch.zeros(D + L, W, H, Cy, dtype=torch.float64, device=self.device)          # (zero days past the end: never counted)
+        a[:D] = self.y.double() - normals.permute(1, 2, 3, 0)[index].double()
+        segment = np.full(D + L, -1)
+        for k, (s, e) in enumerate(self.segments):
+            segment[s:e] = k
+        counts = np.zeros((D, L))
+        for k in range(L):
+            counts[:D - k - 1, k] = selected[:D - k - 1] & selected[k + 1:] & (segment[:D - k - 1] == segment[k + 1:D])
+        counts = torch.from_numpy(counts).to(self.device)[:, :, None, None, None]
+        sxy, sxx, syy = (torch.zeros(L, W, H, Cy, dtype=torch.float64, device=self.device) for _ in range(3))
+        for d in np.flatnonzero(selected):
+            here, there, v = a[d], a[d + 1:d + 1 + L], counts[d]
+            sxy += torch.mul(here, there) * v
+            sxx += torch.mul(here, here) * v
+            syy += torch.mul(there, there) * v
+        den = torch.sqrt(sxx * syy)
+        r = torch.where(den > 0, sxy / den, torch.zeros_like(den))
+        return r.to(torch.float32).permute(3, 0, 1, 2).contiguous()
 
 
 class ClipLoader:

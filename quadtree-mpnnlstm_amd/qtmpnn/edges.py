@@ -31,7 +31,7 @@ def _distances(s, defined):
 
 
 class EdgeDistance:
-    """sums (n_clips, T_out, S, 8) int64 in SLOTS order.  sources: S names ('model', 'persistence', 'climatology'); threshold:
+    """sums (n_clips, T_out, S, 8) int64 in SLOTS order.  sources: S names ('model', then the references'); threshold:
     the one that defined ice.  All distances are in pixels."""
 
     def __init__(self, sums, sources, threshold):

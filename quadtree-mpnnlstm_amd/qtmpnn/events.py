@@ -30,7 +30,8 @@ def derive(sums):
 
 class EventDates:
     """dates (n_clips, S1, W, H) int32 in the codes above; sums (n_clips, S1 - 1, 8) int64 in SLOTS order, one row per
-    forecast source; sources: S1 names, 'observed' first, then 'model' and, when given, 'climatology'."""
+    forecast source; sources: S1 names, 'observed' first, then 'model' and the references' names (by default 'climatology', when
+    given)."""
 
     def __init__(self, dates, sums, sources, kind, persist, threshold):
         self.dates = np.asarray(dates)

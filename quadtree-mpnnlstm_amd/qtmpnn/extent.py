@@ -24,7 +24,7 @@ def _ratio(a, b):
 
 class Extent:
     """sums (n_clips, T_out, R, 1 + S, 4) float64: row 0 in TRUTH_SLOTS order, row 1 + s of source s in SOURCE_SLOTS order, in
-    the unit of the areas the call was given (pixels without them).  sources: S names ('model', 'persistence', 'climatology');
+    the unit of the areas the call was given (pixels without them).  sources: S names ('model', then the references');
     where a method takes a source, 'observed' is one too (the truth: its errors are zero).  threshold: the one that separates ice
     from no ice; region_names: R names (default 'region0' ...)."""
 

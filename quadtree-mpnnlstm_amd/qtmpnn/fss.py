@@ -25,8 +25,8 @@ def _fss(s):
 
 class FSS:
     """sums (n_clips, T_out, S, K, 5) int64 in SLOTS order: per scale the counted pixels n, the observed events
-    (y > threshold) among them, and the three sums of squares of the window counts.  sources: S names ('model', 'persistence',
-    'climatology'); threshold: the one that defined ice; scales: the K odd window sizes, increasing."""
+    (y > threshold) among them, and the three sums of squares of the window counts.  sources: S names ('model', then the
+    references'); threshold: the one that defined ice; scales: the K odd window sizes, increasing."""
 
     def __init__(self, sums, sources, threshold, scales):
         sums = np.asarray(sums)

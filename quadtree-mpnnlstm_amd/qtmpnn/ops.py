@@ -2166,9 +2166,37 @@ def step_wbce_partials(out, y, mesh, w, lam_t, pos_weight=1.0):
     return (lam_t * (terms * (keep.float() * w.view(1, mesh.P))).sum()).view(1)
 
 
+def named_fields(persistence, climatology):
+    """The two dense slots of a verification launch as [(name, tensor)], those that are given: a slot holds a tensor, named after
+    the slot, or a (name, tensor) pair -- any reference forecast under its own name (with_references)."""
+    return [t if isinstance(t, tuple) else (name, t) for name, t in (('persistence', persistence), ('climatology', climatology))
+            if t is not None]
+
+
+def reference_slots(pair):
+    """Up to two named references [(name, tensor)] as the keywords of one verification launch: the first goes into the
+    `persistence` slot and the second into `climatology`, each as a (name, tensor) pair, whatever the references are."""
+    return dict(zip(('persistence', 'climatology'), pair))
+
+
+def with_references(rollout, references, axis, lead=1):
+    """A verification product of k references from the launches that take two: rollout(persistence=, climatology=) -> the
+    product's sums with `lead` rows (the model; the truth and the model) and one row per given slot along `axis`;
+    references: the ordered [(name, tensor)].  Launch i carries the references 2 i and 2 i + 1 (baselines.reference_launches),
+    ceil(k / 2) launches; the leading rows are taken from launch 0 and dropped from the others.  Up to two references are the
+    one launch, its result returned as it is."""
+    from .baselines import reference_launches
+    parts = []
+    for i, j in reference_launches(len(references)):
+        part = rollout(**reference_slots(references[i:j]))
+        parts.append(part if not parts else part.narrow(axis, lead, j - i))
+    return parts[0] if len(parts) == 1 else torch.cat(parts, dim=axis)
+
+
 def _score_args(who, outputs, meshes, y, persistence, climatology):
     """The checked operands rollout_scores and rollout_score_maps share: (outs, y, bases, S, B, T, P), bases = two
-    (field or None, clip stride, step stride).  Refusals carry `who`."""
+    (field or None, clip stride, step stride); each slot a tensor or a (name, tensor) pair (named_fields).  Refusals carry
+    `who` and the field's name."""
     if not outputs or len(outputs) != len(meshes):
         raise ValueError(f'{who}: {len(outputs)} output steps for {len(meshes)} meshes')
     outs = [o.detach() for o in outputs]        # (a column view of the head's 4-wide rows is read through its row stride)
@@ -2185,8 +2213,7 @@ def _score_args(who, outputs, meshes, y, persistence, climatology):
         t = t.detach().to(outs[0].device, torch.float32).contiguous()
         return (t, T * P, P) if t.numel() == B * T * P else (t, P, 0)      # (field, clip stride, step stride)
     y = dense(y, 'y', (B * T * P,))[0]
-    bases = [dense(t, name, (B * P, B * T * P)) for t, name in ((persistence, 'persistence'), (climatology, 'climatology'))
-             if t is not None]
+    bases = [dense(t, name, (B * P, B * T * P)) for name, t in named_fields(persistence, climatology)]
     S = 1 + len(bases)
     bases += [(None, 0, 0)] * (2 - len(bases))
     return outs, y, bases, S, B, T, P
@@ -2214,8 +2241,11 @@ def rollout_scores(outputs, meshes, y, threshold=0.15, persistence=None, climato
     """Verification sums of a rollout, float64 (T, B, S, 8) on the device (qt_score_rollout; the slot table is in
     include/qtmpnn.h): per output step, clip and source [n, sum d, sum |d|, sum d^2, hits, over, under, correct negatives] over
     the counted pixels, d = forecast - y, the classes at `threshold` (strict >).  Sources: the model (outputs[t] (N_t, 1) or
-    (N_t, W): column 0 is read in place through the step's labels), then the dense baselines that are given: `persistence`
-    (B*P values, one frame for every lead time, or B*T*P) and `climatology` (likewise).  y: B*T*P values laid out (B, T, P).
+    (N_t, W): column 0 is read in place through the step's labels), then the dense fields that are given, in slot order:
+    `persistence` and `climatology`, each B*P values (one frame for every lead time) or B*T*P (a frame per step).  The two
+    slots are alike: each takes a tensor, named after the slot, or a (name, tensor) pair of any reference forecast
+    (named_fields; with_references fills them in order, so a lone 'climatology' travels in the first).  y: B*T*P values laid
+    out (B, T, P).
     Pixels without a node, and those under meshes[0].loss_mask, are not counted.  No autograd, no host read: capturable.
     per_tile=True returns the launch's own fp32 partials (T, B, ceil(P/1024), S, 8) instead of their float64 sum over the tiles."""
     outs, y, bases, S, B, T, P = _score_args('rollout_scores', outputs, meshes, y, persistence, climatology)
@@ -2436,10 +2466,23 @@ def rollout_event_dates(outputs, meshes, y, launch, threshold=0.15, kind='breaku
     from which a pixel is no ice ('breakup') or ice ('freezeup') for `persist` consecutive steps, ice = value > threshold
     (strict, fp32); pixels already in that state in `launch` (B*P values: channel 0 of the last input frame) have none.
     Sources: observed (y, B*T*P values laid out (B, T, P)), model (outputs[t] read in place through the step's labels, as
-    rollout_scores) and `climatology` when given (a dense field as rollout_scores'); sums compare each forecast source with
+    rollout_scores) and `climatology` when given (a dense field as rollout_scores', or a (name, tensor) pair of any
+    reference forecast; event_buffer runs one scan per reference); sums compare each forecast source with
     the observed dates.  Pixels without a node at any step, and those under meshes[0].loss_mask, are -2 and not counted.
     No autograd, no host read: capturable, and a replay gives the same bits."""
     return _event_buffer(outputs, meshes, y, launch, threshold, kind, persist, climatology)[1:]
+
+
+def event_buffer(outputs, meshes, y, launch, threshold, kind, persist, references):
+    """_event_buffer's buffer for k references, the ordered [(name, tensor)]: the sums (B, 1 + k, 8) followed by the dates
+    (B, 2 + k, P).  The scan takes one dense field, so every reference beyond the first costs one more scan and its sums;
+    observed and model are taken from the first.  Up to one reference is the one scan, its buffer returned as it is."""
+    if len(references) <= 1:
+        return _event_buffer(outputs, meshes, y, launch, threshold, kind, persist, references[0] if references else None)[0]
+    runs = [_event_buffer(outputs, meshes, y, launch, threshold, kind, persist, ref)[1:] for ref in references]
+    dates = torch.cat([runs[0][0]] + [d[:, 2:] for d, _ in runs[1:]], dim=1)
+    sums = torch.cat([runs[0][1]] + [s[:, 1:] for _, s in runs[1:]], dim=1)
+    return torch.cat([sums.reshape(-1).view(torch.int32), dates.reshape(-1)])
 
 
 def step_sse_partials(out, y, mesh):

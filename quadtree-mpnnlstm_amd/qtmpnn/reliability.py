@@ -20,7 +20,7 @@ def _ratio(a, b):
 class Reliability:
     """sums (n_clips, T_out, S, K, 4) float64 in SLOTS order: per bin the counted pixels n, the observed events
     (y > threshold), the sum of the forecast values f and the sum of (f - o)^2 with o the event as 0 / 1.  sources: S names
-    ('model', 'persistence', 'climatology'); threshold: the one that defined the event."""
+    ('model', then the references'); threshold: the one that defined the event."""
 
     def __init__(self, sums, sources, threshold):
         self.sums = np.asarray(sums, dtype=np.float64)

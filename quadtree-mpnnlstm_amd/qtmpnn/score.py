@@ -21,7 +21,7 @@ def derive(sums):
 
 
 class Scores:
-    """sums (n_clips, T_out, S, 8) float64 in SLOTS order, sources: S names ('model', 'persistence', 'climatology').
+    """sums (n_clips, T_out, S, 8) float64 in SLOTS order, sources: S names ('model', then the references').
     Every metric of METRICS is a method metric(source='model') -> (n_clips, T_out); by_lead pools the clips.  maps: the
     ScoreMaps of the same pass, or None."""
 

@@ -7,8 +7,9 @@ array of predict)."""
 
 class Verification:
     """`v['fss']` and `v.fss` are the result objects, each what the method of that name returns; `v.products` the names in the
-    order they were asked for and computed; `v.sources` the forecast sources every product compares, ('model', 'persistence') and,
-    with a climatology, 'climatology' (event_dates lists 'observed' first and has no persistence: see its `.sources`).
+    order they were asked for and computed; `v.sources` the forecast sources of the call: 'model', then the names of its
+    `references` in the order asked for -- by default 'persistence' and, with a climatology, 'climatology' (event_dates lists
+    'observed' first and has no persistence by default, and a product given references of its own has those: see its `.sources`).
     `name in v`, `len(v)` and iteration run over the names."""
 
     def __init__(self, results, sources):
