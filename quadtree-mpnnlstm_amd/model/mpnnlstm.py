@@ -30,7 +30,7 @@ from qtmpnn.flat import flat_params, name_table
 from qtmpnn._lib import on_device
 from qtmpnn.mesh import check_tile_errors, host_mask
 
-CHECKPOINT_FORMAT = 1       # of save_checkpoint(); load_checkpoint() refuses a newer one
+CHECKPOINT_FORMAT = 2       # the newest save_checkpoint() writes (1 without averaged weights, 2 with); load_checkpoint() refuses a newer one
 
 try:                                        # pragma: no cover - optional dependency
     from torch.utils.tensorboard import SummaryWriter
@@ -754,6 +754,31 @@ def takes_references(method):
     return wrapper
 
 
+def takes_ema(method):
+    """Gives train() the keywords `ema=None` and `ema_eval=True` (NextFramePredictorS2S.set_ema, averaged_weights).  train()'s
+    parameter list is read by signature tests and stays as it is (takes_references); the two are taken and checked here, on
+    the host and before anything else runs, and held in self._ema_asked = (decay or None, ema_eval) while the call runs.
+    Refusals name the keyword: `ema` as set_ema refuses it; `ema_eval` a TypeError unless True or False, and a ValueError
+    when it is given at all while no average is or becomes active (there is nothing to evaluate)."""
+    import functools
+    from qtmpnn import validation
+    from qtmpnn.ema import check_decay
+
+    @functools.wraps(method)
+    def wrapper(self, *args, **keywords):
+        given = 'ema_eval' in keywords
+        ema, ema_eval = keywords.pop('ema', None), validation.check_flag('ema_eval', keywords.pop('ema_eval', True))
+        decay = None if ema is None else check_decay(ema)
+        if given and decay is None and self.ema is None:
+            raise ValueError(f'ema_eval: ema_eval={ema_eval} without averaged weights: pass ema=decay (or call set_ema) first')
+        previous, self._ema_asked = self._ema_asked, (decay, ema_eval)
+        try:
+            return method(self, *args, **keywords)
+        finally:
+            self._ema_asked = previous
+    return wrapper
+
+
 class NextFramePredictor(ABC):
     """The abstract trainer facade of the reference (model/mpnnlstm.py:34-79; moving_mnist_example.ipynb cell 2 imports it):
     it holds the decomposition settings and names the three methods a predictor offers.  `thresh` is kept as given here;
@@ -801,6 +826,92 @@ class NextFramePredictorS2S(NextFramePredictor):
         # what train()'s validation keywords leave (patience, restore_best, keep_best, monitor): see train()
         self.best_epoch = self.best_value = self.stopped_epoch = None
         self.monitor_history = []
+        # the averaged weights (set_ema; None: off), the stash averaged_weights() keeps the live ones in, whether a block of it
+        # is open, and train()'s (ema, ema_eval) while it runs (takes_ema)
+        self.ema = self._ema_stash = None
+        self._ema_inside, self._ema_asked = False, (None, True)
+
+    # -- averaged weights (beyond the reference): qtmpnn.ema.WeightEMA, updated after every optimiser step ----------------------
+    def set_ema(self, decay):
+        """Keep an exponential moving average of the weights: after EVERY optimiser step s <- decay * s + (1 - decay) * p
+        (qtmpnn.ema.WeightEMA has the op sequence; _clip_and_step is the one place every step goes through: train_step,
+        accumulated_step -- one update per optimiser step, none per micro-batch --, every chunk of the truncated loop, the
+        captured steps, both recompute modes; under torch.distributed the update follows the all-reduce, so every rank keeps
+        the same shadow without a collective).  decay: a float in [0, 1); None (the default state) switches the average off
+        and drops its state, and every path is then what it was, bit for bit.  The same decay again keeps the state, another one
+        starts anew; initiate_training() drops it with the optimiser.  Training itself never reads the average:
+        averaged_weights(), apply_ema() and train(ema=, ema_eval=) do, and save_checkpoint() stores it.
+        A CAPTURED STEP KEEPS THE SETTING IT WAS CAPTURED UNDER, as it keeps its recompute mode -- the update is part of the
+        graph that holds clip + Adam -- and refuses to run (RuntimeError, `ema`) once the predictor's setting is another one.
+        Refusals, before any launch: TypeError for what is no number (True included), ValueError for a decay outside [0, 1)
+        or a NaN, and for a predictor without initiate_training() / train()."""
+        from qtmpnn.ema import WeightEMA, check_decay
+        if decay is not None:
+            decay = check_decay(decay)
+            if not self.training_initiated:
+                raise ValueError('ema: the average follows the optimiser: call initiate_training() first (or pass train(ema=decay))')
+        if self._ema_inside:
+            raise RuntimeError('ema: set_ema() inside averaged_weights(): leave the block first')
+        if decay is None:
+            self.ema = self._ema_stash = None
+        elif self.ema is None or self.ema.decay != decay:
+            self.ema = WeightEMA(self.flat.param if self.flat is not None else list(self.model.parameters()), decay)
+
+    def _live_weights(self):
+        """The parameters as the average sees them, detached: the flat tensor, or the list."""
+        if self.flat is not None:
+            if not self.flat.intact(self.model):
+                raise RuntimeError('the model parameters were moved or replaced after initiate_training(): call it again')
+            return self.flat.param.detach()
+        return [p.detach() for p in self.model.parameters()]
+
+    @contextlib.contextmanager
+    def averaged_weights(self):
+        """`with nfp.averaged_weights():` -- the model runs on the averaged weights inside the block.  On entry the live
+        parameters are copied to a stash (allocated on first use, kept) and WeightEMA.averaged() is written into the parameters
+        IN PLACE: the flat buffer keeps its views and its zero pad tail, and every capture that reads the parameters by pointer
+        (predict(use_graph=True), verify, train()'s test_graph captures, a make_graphed_rollout made before) works unchanged
+        inside.  On exit, also after an exception, the live parameters are copied back: bit for bit what they were.  Refused by
+        name (`ema`): no average (set_ema), no optimiser step averaged yet, a nested block; and inside the block every
+        optimiser step, set_ema and apply_ema."""
+        if self.ema is None:
+            raise ValueError('ema: averaged_weights() needs averaged weights: call set_ema(decay) (or train(ema=decay)) first')
+        if self._ema_inside:
+            raise RuntimeError('ema: averaged_weights() is not re-entrant: the block is already open')
+        self.ema.divisor()              # (refuses an average of no step before anything is copied)
+        live = self._live_weights()         # (detached: the copies below are no autograd operations)
+        if self._ema_stash is None:
+            self._ema_stash = torch.empty_like(live) if torch.is_tensor(live) else [torch.empty_like(p) for p in live]
+        copy = (lambda dst, src: dst.copy_(src)) if torch.is_tensor(live) else torch._foreach_copy_
+        copy(self._ema_stash, live)
+        self._ema_inside = True
+        try:
+            self.ema.averaged(live)
+            yield self
+        finally:
+            copy(live, self._ema_stash)
+            self._ema_inside = False
+
+    def apply_ema(self):
+        """Copy the averaged weights into the parameters for good (in place), for save() and export: the live weights are gone
+        then, the average and the optimiser are left as they are.  save() / load() themselves are what they were."""
+        if self.ema is None:
+            raise ValueError('ema: apply_ema() needs averaged weights: call set_ema(decay) (or train(ema=decay)) first')
+        if self._ema_inside:
+            raise RuntimeError('ema: apply_ema() inside averaged_weights(): leave the block first')
+        self.ema.averaged(self._live_weights())
+
+    def _ema_guard(self, captured=False, ema=None):
+        """Before an optimiser step: refused inside averaged_weights() (the step would move the averaged weights and the exit
+        would throw it away); captured: the step is a replay of a capture that was made while the average was `ema` (None:
+        off) -- refused unless that still is the predictor's."""
+        if self._ema_inside:
+            raise RuntimeError('ema: an optimiser step inside averaged_weights(): the parameters are the averaged ones there')
+        if captured and ema is not self.ema:
+            say = lambda e: 'ema=None' if e is None else f'ema={e.decay!r}'
+            raise RuntimeError(f'ema: this step was captured under {say(ema)} and the predictor is now at {say(self.ema)}'
+                               + (' (set anew)' if ema is not None and self.ema is not None and ema.decay == self.ema.decay else '')
+                               + ': a captured step keeps the setting it was captured under; capture a new one')
 
     # -- activation recomputation (beyond the reference): the mode lives on the Seq2Seq, where the rollout is -------------------
     @property
@@ -859,7 +970,7 @@ class NextFramePredictorS2S(NextFramePredictor):
         """Write the whole training state to the file `path` (torch.save of a dict of host tensors and plain Python values: it
         loads with torch.load(path, weights_only=True)), so that load_checkpoint + train(n_epochs=k) continues this run bit for bit:
 
-            format        1
+            format        1; 2 when averaged weights are kept (set_ema), and only then
             description   convolution_type, hidden_size, n_layers, n_conv_layers, input_features, input_timesteps,
                           output_timesteps, binary, parameters [[name, shape], ...] in module order
             state_dict    model.state_dict(), the keys and values save() writes
@@ -869,6 +980,8 @@ class NextFramePredictorS2S(NextFramePredictor):
             train_loss, test_loss, capturable
             rng           torch (torch.get_rng_state()), cuda (torch.cuda.get_rng_state(device), None on the CPU), attention
                           (ops.dropout_state: the call counter and device step counter the attention kernels' seeds are made of)
+            ema           format 2 only: shadow {name: tensor in the parameter's shape}, decay, updates (WeightEMA.state: one
+                          layout for the flat shadow and the per-parameter one, so either loads the other's file)
 
         The file is written under a temporary name beside `path` and moved there by os.replace: an interrupted save leaves
         whatever was under `path` as it was.  Under torch.distributed the ranks hold the same state: one rank saves."""
@@ -878,7 +991,9 @@ class NextFramePredictorS2S(NextFramePredictor):
         group = self.optimizer.param_groups[0]
         dev = next(self.model.parameters()).device
         host = lambda v: float(v) if torch.is_tensor(v) else [host(e) for e in v] if isinstance(v, (list, tuple)) else v
-        ckpt = {'format': CHECKPOINT_FORMAT, 'description': self._description(),
+        if self._ema_inside:
+            raise RuntimeError('ema: save_checkpoint() inside averaged_weights(): the parameters are the averaged ones there')
+        ckpt = {'format': 1 if self.ema is None else 2, 'description': self._description(),
                 'state_dict': {k: v.detach().cpu().clone() for k, v in self.model.state_dict().items()},
                 'optimizer': adam_state(self.optimizer, self.model),
                 'scheduler': {k: host(v) for k, v in self.scheduler.state_dict().items()},
@@ -886,6 +1001,8 @@ class NextFramePredictorS2S(NextFramePredictor):
                 'capturable': bool(group.get('capturable', False)),
                 'rng': {'torch': torch.get_rng_state(), 'cuda': torch.cuda.get_rng_state(dev) if dev.type == 'cuda' else None,
                         'attention': ops.dropout_state(dev)}}
+        if self.ema is not None:
+            ckpt['ema'] = self.ema.state(self.model)
         path = os.fspath(path)
         tmp = f'{path}.tmp{os.getpid()}'
         try:
@@ -899,6 +1016,7 @@ class NextFramePredictorS2S(NextFramePredictor):
     def _checked_checkpoint(self, path):
         """The checkpoint under `path`, host tensors, or a ValueError that names the field that does not fit this predictor.
         Reads the file and this predictor, changes neither."""
+        from qtmpnn.ema import check_state
         from qtmpnn.optim import check_adam_state
         ckpt = torch.load(path, map_location='cpu', weights_only=True)
         if not isinstance(ckpt, dict) or 'format' not in ckpt:
@@ -908,6 +1026,10 @@ class NextFramePredictorS2S(NextFramePredictor):
         for k in ('description', 'state_dict', 'optimizer', 'scheduler', 'train_loss', 'test_loss', 'capturable', 'rng'):
             if k not in ckpt:
                 raise ValueError(f'{k}: missing in the file')
+        if ckpt['format'] >= 2 and 'ema' not in ckpt:
+            raise ValueError(f"format: the file has format {ckpt['format']} and no 'ema': format 2 is format 1 with averaged weights")
+        if ckpt['format'] < 2 and 'ema' in ckpt:
+            raise ValueError(f"ema: averaged weights in a file of format {ckpt['format']}: they belong to format 2")
         here, there = self._description(), ckpt['description']
         for k, v in here.items():
             if k != 'parameters' and there.get(k) != v:
@@ -929,6 +1051,8 @@ class NextFramePredictorS2S(NextFramePredictor):
                 raise ValueError(f'state_dict[{k!r}]: shape {tuple(sd[k].shape) if torch.is_tensor(sd[k]) else None} in the file, '
                                  f'{tuple(v.shape)} here')
         check_adam_state(ckpt['optimizer'], name_table(self.model))
+        if 'ema' in ckpt:
+            check_state(ckpt['ema'], name_table(self.model))
         sched = ckpt['scheduler']
         for k in ('last_epoch', '_last_lr', 'step_size', 'gamma', 'base_lrs'):
             if not isinstance(sched, dict) or k not in sched:
@@ -956,13 +1080,17 @@ class NextFramePredictorS2S(NextFramePredictor):
         and its zero pad tail), Adam moments, step counters, a device learning rate and the attention-dropout counter by copy_ /
         fill_ into the storage that is there.  A make_graphed_step object captured before the load holds pointers into
         exactly these buffers: it keeps working and its next replay continues from the loaded state.  The weight packing reads
-        the parameters in every forward pass, so nothing else has to be told.
+        the parameters in every forward pass, so nothing else has to be told.  Averaged weights (set_ema) follow the file: with an
+        average of the file's decay active the shadow is loaded in place and the count taken; otherwise the average is made with the
+        file's decay; a file without one switches it off.
 
         A file that does not fit is refused with a ValueError that names the field -- no checkpoint, a newer format, another
         description (`convolution_type='ChebConv' in the file, 'GCNConv' here`), parameter names, shapes, non-finite moments,
-        negative exp_avg_sq, step < 0 -- after reading the file on the host and before anything here changes.  Every rank of a
+        negative exp_avg_sq, step < 0, averaged weights that do not fit -- after reading the file on the host and before anything here changes.  Every rank of a
         torch.distributed run loads the same file; there is no collective."""
         from qtmpnn.optim import load_adam_state, set_lr
+        if self._ema_inside:
+            raise RuntimeError('ema: load_checkpoint() inside averaged_weights(): leave the block first')
         ckpt = self._checked_checkpoint(path)
         opt, sched = ckpt['optimizer'], dict(ckpt['scheduler'])
         want = bool(ckpt['capturable']) if capturable is None else bool(capturable)
@@ -972,6 +1100,9 @@ class NextFramePredictorS2S(NextFramePredictor):
         if self.flat is not None and not self.flat.intact(self.model):
             raise RuntimeError('the model parameters were moved or replaced after initiate_training(): call it again')
         load_adam_state(self.optimizer, self.model, opt)
+        self.set_ema(ckpt['ema']['decay'] if 'ema' in ckpt else None)       # (an average of that decay stays where it is)
+        if self.ema is not None:
+            self.ema.load_state(ckpt['ema'])
         group = self.optimizer.param_groups[0]
         set_lr(group, 'initial_lr', sched['base_lrs'][0])
         sched['base_lrs'], sched['_last_lr'] = [group['initial_lr']], [group['lr']]     # (the scheduler's own aliases)
@@ -1023,6 +1154,7 @@ class NextFramePredictorS2S(NextFramePredictor):
         self.writer = SummaryWriter('runs/' + self.experiment_name + '_' + datetime.datetime.now().strftime('%Y%m%d_%H_%M_%S'))
         self.test_loss, self.train_loss = [], []
         self.monitor_history = []
+        self.ema = self._ema_stash = None       # (the average follows the optimiser: set_ema() starts a new one)
         self.training_initiated = True
 
     # -- the measured unit -----------------------------------------------------------
@@ -1105,13 +1237,17 @@ class NextFramePredictorS2S(NextFramePredictor):
         return params
 
     def _clip_and_step(self, clip_params, max_norm):
-        """clip_grad_norm_(max_norm) + optimizer.step() (mpnnlstm.py:251, 257); max_norm None: no clipping (:311)."""
+        """clip_grad_norm_(max_norm) + optimizer.step() (mpnnlstm.py:251, 257); max_norm None: no clipping (:311).  The one
+        place every optimiser step goes through: with averaged weights (set_ema) their update follows the step."""
+        self._ema_guard()
         if self.flat is not None:
             self.optimizer.step(max_norm=max_norm)
-            return
-        if max_norm is not None:
-            torch.nn.utils.clip_grad_norm_(clip_params, max_norm=max_norm)
-        self.optimizer.step()
+        else:
+            if max_norm is not None:
+                torch.nn.utils.clip_grad_norm_(clip_params, max_norm=max_norm)
+            self.optimizer.step()
+        if self.ema is not None:
+            self.ema.update()
 
     def _world(self):
         d = torch.distributed
@@ -1302,6 +1438,7 @@ class NextFramePredictorS2S(NextFramePredictor):
         side = torch.cuda.Stream()
         warm_then_sync(side, multi, warm)
         graph, graph2 = torch.cuda.CUDAGraph(), None
+        ema, averaged = self.ema, self.ema.updates if self.ema is not None else 0
         self.zero_grad()
         # thread_local: other threads (the RCCL watchdog under torch.distributed) may issue HIP calls meanwhile
         with torch.cuda.graph(graph, stream=side, capture_error_mode='thread_local'):
@@ -1317,18 +1454,23 @@ class NextFramePredictorS2S(NextFramePredictor):
             with torch.cuda.graph(graph2, stream=side, capture_error_mode='thread_local'):
                 flat.mul_(1.0 / world)
                 self._clip_and_step(clip_params, max_norm)
+        if ema is not None:
+            ema.updates = averaged      # (the capture recorded the update's launches without running them; a replay counts)
         watch = TileWatch()
 
         @on_device(lambda *a, **k: self.device)
         def step(x, y, concat_layers=None):
+            self._ema_guard(True, ema)
             batch.load(x, y, concat_layers)
             graph.replay()
             if multi:
                 all_reduce_sum(flat, self.process_group)
                 graph2.replay()
+            if ema is not None:
+                ema.advance()
             watch.advance()
             return static_loss
-        step.check, step.loss_weights = watch.check, lw
+        step.check, step.loss_weights, step.ema = watch.check, lw, ema
         return step
 
     def _capture_setup(self, force_multi):
@@ -1343,7 +1485,9 @@ class NextFramePredictorS2S(NextFramePredictor):
         if not self.optimizer.defaults.get('capturable', False):
             lr = self.optimizer.param_groups[0]['lr']
             assert not self.optimizer.state, 'make_graphed_step must be called before the first optimizer step'
+            decay = None if self.ema is None else self.ema.decay
             self.initiate_training(float(lr), self.scheduler.gamma, capturable=True)
+            self.set_ema(decay)         # (no step was taken: the average starts with the new optimiser, as it stood)
         return multi, world
 
     def _graphed_accumulation(self, batches, accumulate, mask=None, high_interest_region=None, max_norm=10.0, warmup=2,
@@ -1390,6 +1534,7 @@ class NextFramePredictorS2S(NextFramePredictor):
             acc.add_(self._grad_flat())
             loss_acc.add_(loss.detach())
         clip_params = self._set_grad_flat(acc)          # the optimiser reads acc from here on
+        ema, averaged = self.ema, self.ema.updates if self.ema is not None else 0
         update = torch.cuda.CUDAGraph()
         with torch.cuda.graph(update, stream=side, capture_error_mode='thread_local'):
             acc.mul_(scale[0])
@@ -1397,11 +1542,14 @@ class NextFramePredictorS2S(NextFramePredictor):
             static_loss = loss_acc * scale[1]
             acc.zero_()
             loss_acc.zero_()
+        if ema is not None:
+            ema.updates = averaged      # (as in make_graphed_step: one update per call of step, counted there)
         self._graph = micro
         watch, scaled_for = TileWatch(), [None]
 
         @on_device(lambda *a, **kw: self.device)
         def step(batches):
+            self._ema_guard(True, ema)
             group = checked_batches('step', batches)
             j = len(group)
             if j > k or any(batch_shapes(item) != batch.shapes for item in group):
@@ -1417,9 +1565,11 @@ class NextFramePredictorS2S(NextFramePredictor):
                 scale[1].fill_(group_scale(j))
                 scaled_for[0] = j
             update.replay()
+            if ema is not None:
+                ema.advance()
             watch.advance(j)
             return static_loss
-        step.check, step.loss_weights, step.accumulate, step.graphs = watch.check, lw, k, (micro, update)
+        step.check, step.loss_weights, step.accumulate, step.graphs, step.ema = watch.check, lw, k, (micro, update), ema
         step.buffers = (*batch.tensors, acc, loss_acc, scale)       # (loss_acc is named nowhere else: StaticBatch)
         return step
 
@@ -1617,6 +1767,7 @@ class NextFramePredictorS2S(NextFramePredictor):
         return replay
 
     @on_device(lambda self, *a, **k: self.device)
+    @takes_ema
     def train(self, loader_train, loader_test, climatology=None, n_epochs=200, lr=0.01, lr_decay=0.95, mask=None,
               high_interest_region=None, truncated_backprop=45, graph_structure=None, use_graph=False, accumulate=1,
               pos_weight=None, test_graph=False, patience=None, min_delta=0.0, restore_best=False, keep_best=None,
@@ -1671,7 +1822,15 @@ class NextFramePredictorS2S(NextFramePredictor):
         empty it, so a second call and a resumed run start their patience count anew.  A value that is not one finite float is refused
         under `monitor` after the test pass that produced it.
         Each of these keywords is refused by name (TypeError for a wrong type, ValueError for a wrong value) before anything is
-        launched and before the optimiser is made."""
+        launched and before the optimiser is made.
+        ema=decay, ema_eval=True (keywords of this method through takes_ema; beyond the reference): ema=decay is set_ema(decay)
+        once the optimiser exists and before the first capture; None leaves the predictor's setting as it is.  With averaged
+        weights and ema_eval=True the test pass of every epoch runs inside averaged_weights() -- the loss, a Monitor's products,
+        eager or test_graph=True -- so test_loss, monitor_history, patience, best_epoch / best_value and the scalars are those
+        of the AVERAGED weights; restore_best snapshots the weights the test pass saw and writes them into the parameters after
+        the last epoch; keep_best writes an ordinary checkpoint, live weights and average (format 2).  ema_eval=False only
+        maintains the average.  Training itself never reads it: train_loss and the parameters after every epoch are those of the
+        run without `ema`, bit for bit.  ema_eval given without averaged weights is refused under its name."""
         from qtmpnn import validation
         image_shape = loader_train.dataset.image_shape
         accumulate = check_accumulate(accumulate)
@@ -1697,6 +1856,9 @@ class NextFramePredictorS2S(NextFramePredictor):
                 climatology is not None, test_graph, mask))
         if not self.training_initiated:
             self.initiate_training(lr, lr_decay, capturable=use_graph)
+        if self._ema_asked[0] is not None:
+            self.set_ema(self._ema_asked[0])
+        averaging = self.averaged_weights if self.ema is not None and self._ema_asked[1] else contextlib.nullcontext
         graphed = {}
         if mask is not None:
             mshape = tuple(host_mask(mask).shape) if not hasattr(mask, 'shape') else tuple(mask.shape)
@@ -1749,9 +1911,10 @@ class NextFramePredictorS2S(NextFramePredictor):
                     steps += 1
                     batch_step += 1
             # once per epoch: the graph-replayed steps and the test pass report their tile errors only at the end of the pass
-            running_test, steps_test = self._test_pass(loader_test, climatology, test_reduce, made, test_graph, test_graphs,
-                                                       mask=mask, high_interest_region=high_interest_region,
-                                                       graph_structure=graph_structure)
+            with averaging():
+                running_test, steps_test = self._test_pass(loader_test, climatology, test_reduce, made, test_graph, test_graphs,
+                                                           mask=mask, high_interest_region=high_interest_region,
+                                                           graph_structure=graph_structure)
             running, running_test = running / (steps + 1), running_test / (steps_test + 1)   # (+1 as the reference, :360-361)
             if np.isnan(running_test):
                 raise ValueError('NaN loss :(')
@@ -1772,7 +1935,8 @@ class NextFramePredictorS2S(NextFramePredictor):
                 self.best_epoch, self.best_value, waited = validation.best_and_wait(history(), min_delta, mode)
                 if self.best_epoch == len(history()) - 1:       # this epoch improved
                     if restore_best:
-                        torch._foreach_copy_(best_state, state())
+                        with averaging():           # (the weights the test pass saw)
+                            torch._foreach_copy_(best_state, state())
                         saved = self.best_epoch
                     if keep_best is not None:
                         self.save_checkpoint(keep_best)
