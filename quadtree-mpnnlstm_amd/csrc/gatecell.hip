@@ -3,6 +3,10 @@
 //   k_dgrad_cell     -- backward: the cell backward feeding the data gradient gG W^T from LDS
 //   k_cell_bwd_fused -- backward, opt-in: cell backward, data gradient and weight gradient in one persistent launch
 // qt_dense_lstm's other shapes (hidden 32, long reductions) take k_gemm_fwd's fused epilogue in gemm.hip.
+// What these kernels share with lstm.hip and gemm.hip stands once: in qt_cell.h the cell arithmetic, cell_params / cell_bwd_params,
+// the backward's operand read (cell_bwd_load), ld_gates / st_gates and block_param_reduce; in qt_gemm.h the quad table
+// (build_quad_table), the MFMA step of a k-quad (mfma_quad), the accumulator row map (acc_row) and store_split.  Where a kernel
+// still spells one of these out, the comment at the site says what the helper changed in its generated code (HISTORY.md, AL).
 #include "qt_cell.h"
 #include "qt_gemm.h"
 
@@ -125,12 +129,7 @@ __global__ __launch_bounds__(512, 2) void k_gate_cell_p(GemmArgs g, int pitch) {
             for (int nt = 0; nt < NT; ++nt)
                 bq[nt] = *reinterpret_cast<const float4*>(&Bt[(nt * 32 + l32) * pitch + 8 * j + 4 * half]);
 #pragma unroll
-            for (int nt = 0; nt < NT; ++nt) {
-                acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, bq[nt].x, acc[nt], 0, 0, 0);
-                acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, bq[nt].y, acc[nt], 0, 0, 0);
-                acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, bq[nt].z, acc[nt], 0, 0, 0);
-                acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, bq[nt].w, acc[nt], 0, 0, 0);
-            }
+            for (int nt = 0; nt < NT; ++nt) mfma_quad(acc[nt], a, bq[nt]);
         };
         if constexpr (R > 0) {
 #pragma unroll
@@ -155,26 +154,22 @@ __global__ __launch_bounds__(512, 2) void k_gate_cell_p(GemmArgs g, int pitch) {
 #pragma unroll
         for (int u = 0; u < NT; ++u)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) Cs[((r & 3) + 8 * (r >> 2) + 4 * half) * CP + u * 32 + l32] = acc[u][r];
+            for (int r = 0; r < 16; ++r) Cs[acc_row(r, half) * CP + u * 32 + l32] = acc[u][r];
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
         for (int ps = 0; ps < NPASS; ++ps) {
             const int row = ps * NPW + nl;
             const int64_t node = (int64_t)unit * 32 + row;
-            const float* cs = Cs + row * CP + j0;
-            const F4 gi = ld4(cs), gf = ld4(cs + h), gc = ld4(cs + 2 * h), go = ld4(cs + 3 * h);
+            F4 gi, gf, gc, go;
+            ld_gates(Cs + row * CP + j0, h, &gi, &gf, &gc, &go);
             const F4 cp = {{cpre[ps].x, cpre[ps].y, cpre[ps].z, cpre[ps].w}};
             const CellOut r = cell_forward<LPN>(gi, gf, gc, go, cp, cpar);
-            if (node < rows) {
+            if (node < rows) {          // (store_cell's text: through the helper the hidden-16 instances order their address arithmetic differently)
                 if (g.O) st4(g.O + node * h + j0, r.Og);
                 st4(g.Hn + node * h + j0, r.hn);
                 st4(g.Cn + node * h + j0, r.cn);
-                float* gs = g.gates + node * 4 * h + j0;
-                st4(gs, r.I);
-                st4(gs + h, r.F);
-                st4(gs + 2 * h, r.T);
-                st4(gs + 3 * h, r.Og);
+                st_gates(g.gates + node * 4 * h + j0, h, r.I, r.F, r.T, r.Og);
             }
         }
         if (!has_next) break;
@@ -206,17 +201,15 @@ struct DgradCellArgs {
                             // operand: that gradient rides into the Clenshaw recurrence as part of A_0)
 };
 
-// BG: the right operand (the weight rows, <= 32 KB, L1 / L2 resident) is read straight from global memory by the lanes that
-// need it instead of being staged in LDS: the workgroup's LDS drops from 64 KB to 38 KB, so THREE workgroups fit a CU instead
-// of two -- more workgroups whose load / arithmetic / MFMA / store phases overlap.
-static constexpr int QT_DGRAD_BG = 1;
+// The right operand (the weight rows, <= 32 KB, L1 / L2 resident) is read straight from global memory by the lanes that need
+// it and is not staged in LDS: the workgroup's LDS is 38 KB where the staged form took 64 KB, so more than two workgroups fit
+// a CU -- more workgroups whose load / arithmetic / MFMA / store phases overlap (the staged form's numbers: HISTORY.md, AL).
 static constexpr int QT_DGRAD_OCC = 4;      // 128 VGPRs (8-10 spilled): FOUR workgroups per CU = all 940 tiles of the bench shape resident at once
                           // (3: 138-155 VGPRs, 768 resident + a second round; 8.41 -> 8.34 ms per frozen step)
-template <int NT, int LPN, bool BG = (QT_DGRAD_BG != 0)>
-__global__ __launch_bounds__(256, BG ? QT_DGRAD_OCC : 2) void k_dgrad_cell(DgradCellArgs g) {
+template <int NT, int LPN>
+__global__ __launch_bounds__(256, QT_DGRAD_OCC) void k_dgrad_cell(DgradCellArgs g) {
     using namespace qtcell;
-    constexpr int BNT = 32 * NT, K = 16 * LPN, PITCH = K + 4, RP = 256 / LPN;
-    __shared__ __attribute__((aligned(16))) float Bt[BG ? 4 : BNT * PITCH];
+    constexpr int K = 16 * LPN, PITCH = K + 4, RP = 256 / LPN;
     __shared__ __attribute__((aligned(16))) float As[128 * (PITCH > 68 ? PITCH : 68)];       // (>= 128 x 68: the epilogue's staging tile)
     __shared__ float sm[4 * LPN * 11 * 4];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -225,24 +218,10 @@ __global__ __launch_bounds__(256, BG ? QT_DGRAD_OCC : 2) void k_dgrad_cell(Dgrad
     const int64_t rows = qt_rows(g.n_dev, g.M);
     constexpr int h = 4 * LPN;     // (== g.h: the host picks the instance by it)
     if (i0 >= rows) return;        // past the valid rows: nothing to add to the partials (the slab rows start at zero)
-    // W chunk (all of it: K = 4h fits one pass) -> LDS; independent of the cell phase below
-    if constexpr (!BG) {
-        for (int e = t; e < BNT * (K / 4); e += 256) {
-            const int c = e / (K / 4), kq = e - c * (K / 4);
-            float4 w = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (c < g.NB) w = *reinterpret_cast<const float4*>(g.BT + (int64_t)c * K + 4 * kq);
-            *reinterpret_cast<float4*>(&Bt[c * PITCH + 4 * kq]) = w;
-        }
-    }
     // cell backward of this workgroup's rows (rows past the valid count contribute zeros)
     {
         const int j0 = (t % LPN) * 4;
-        const F4 wci = ld4(g.wc + j0), wcf = ld4(g.wc + h + j0), wco = ld4(g.wc + 2 * h + j0);
-        F4 gam_h = {{1, 1, 1, 1}}, gam_c = {{1, 1, 1, 1}};
-        if (g.ln) {
-            gam_h = ld4(g.ln + j0);
-            gam_c = ld4(g.ln + 2 * h + j0);
-        }
+        const CellBwdParams P = cell_bwd_params(g.wc, g.ln, h, j0);
         float acc[11][4];
 #pragma unroll
         for (int a = 0; a < 11; ++a)
@@ -253,34 +232,18 @@ __global__ __launch_bounds__(256, BG ? QT_DGRAD_OCC : 2) void k_dgrad_cell(Dgrad
             const int r = r0 + t / LPN;
             const int64_t node = i0 + r;
             const bool ok = node < rows;
-            const F4 z = {{0, 0, 0, 0}};
-            F4 I = z, F = z, T = z, Og = z, cp = z, gyh = z, gyc = z, go_in = z;
+            const CellBwdIn x = cell_bwd_load(ok, node, h, j0, g.gates, g.Cprev, g.ld_c, g.gHn, g.ld_gh, g.gCn, g.ld_gc, g.gO,
+                                              g.ld_go, g.gHn2, g.ld_gh2);
+            const CellBwdOut o = cell_backward<LPN>(x, P, acc);
+            st_gates(As + r * PITCH + j0, h, o.ggi, o.ggf, o.ggc, o.ggo);
             if (ok) {
-                const float* gs = g.gates + node * 4 * h + j0;
-                I = ld4(gs); F = ld4(gs + h); T = ld4(gs + 2 * h); Og = ld4(gs + 3 * h);
-                if (g.Cprev) cp = ld4(g.Cprev + node * g.ld_c + j0);
-                if (g.gHn) gyh = ld4(g.gHn + node * g.ld_gh + j0);
-                if (g.gCn) gyc = ld4(g.gCn + node * g.ld_gc + j0);
-                if (g.gO) go_in = ld4(g.gO + node * g.ld_go + j0);
-                if (g.gHn2) {
-                    const F4 h2 = ld4(g.gHn2 + node * g.ld_gh2 + j0);
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) gyh.v[k] += h2.v[k];
-                }
-            }
-            const CellBwdOut o = cell_backward<LPN>(I, F, T, Og, cp, gyh, gyc, go_in, wci, wcf, wco, gam_h, gam_c,
-                                                    g.ln != nullptr, acc);
-            float* as = As + r * PITCH + j0;
-            st4(as, o.ggi); st4(as + h, o.ggf); st4(as + 2 * h, o.ggc); st4(as + 3 * h, o.ggo);
-            if (ok) {
-                float* gg = g.gG + node * 4 * h + j0;
-                st4(gg, o.ggi); st4(gg + h, o.ggf); st4(gg + 2 * h, o.ggc); st4(gg + 3 * h, o.ggo);
+                st_gates(g.gG + node * 4 * h + j0, h, o.ggi, o.ggf, o.ggc, o.ggo);
                 if (g.gCprev) st4(g.gCprev + node * h + j0, o.gcp);
             }
         }
         block_param_reduce<LPN, 11>(acc, h, sm, g.part + (int64_t)blockIdx.x * 11 * h, g.accumulate);
     }
-    qt_lds_barrier();                                 // Bt, As complete
+    qt_lds_barrier();                                 // As complete
     f32x16 acc2[NT];
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt)
@@ -326,22 +289,13 @@ __global__ __launch_bounds__(256, BG ? QT_DGRAD_OCC : 2) void k_dgrad_cell(Dgrad
         float4 bq[NT];
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
-            if constexpr (BG) {
-                // (columns past NB: a clamped load.  An accumulator column depends on its own column of the operand only and
-                // the epilogue stores no column past NB, so the value needs no zeroing: 4 NT selects per k-group saved)
-                const int c = nt * 32 + l32;
-                bq[nt] = gload4(g.BT + (int64_t)(c < g.NB ? c : 0) * K + 8 * j + 4 * half);
-            } else {
-                bq[nt] = *reinterpret_cast<const float4*>(&Bt[(nt * 32 + l32) * PITCH + 8 * j + 4 * half]);
-            }
+            // (columns past NB: a clamped load.  An accumulator column depends on its own column of the operand only and
+            // the epilogue stores no column past NB, so the value needs no zeroing: 4 NT selects per k-group saved)
+            const int c = nt * 32 + l32;
+            bq[nt] = gload4(g.BT + (int64_t)(c < g.NB ? c : 0) * K + 8 * j + 4 * half);
         }
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            acc2[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, bq[nt].x, acc2[nt], 0, 0, 0);
-            acc2[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, bq[nt].y, acc2[nt], 0, 0, 0);
-            acc2[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, bq[nt].z, acc2[nt], 0, 0, 0);
-            acc2[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, bq[nt].w, acc2[nt], 0, 0, 0);
-        }
+        for (int nt = 0; nt < NT; ++nt) mfma_quad(acc2[nt], a, bq[nt]);
     }
     }
     // epilogue as in k_gemm_fwd: the tile goes through LDS (As is free now) so that rows leave as float4 pieces.  The staging
@@ -359,7 +313,7 @@ __global__ __launch_bounds__(256, BG ? QT_DGRAD_OCC : 2) void k_dgrad_cell(Dgrad
             if (nt < NT) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r)
-                    Cs[(wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * half) * CP + u * 32 + l32] = acc2[nt][r];
+                    Cs[(wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * half) * CP + u * 32 + l32] = acc2[nt][r];   // (acc_row's text: the helper's sum associates differently and two vector instructions change place)
             }
         }
         qt_lds_barrier();
@@ -372,18 +326,8 @@ __global__ __launch_bounds__(256, BG ? QT_DGRAD_OCC : 2) void k_dgrad_cell(Dgrad
             const int64_t i = i0 + row;
             const int j = h2 * 64 + c4;
             if (i >= rows || j >= g.NB) continue;
-            float4 v = *reinterpret_cast<const float4*>(&Cs[row * CP + c4]);
-            const int ct = g.Cb + g.Cbb;
-            const int pl = j / ct, ch = j - pl * ct;
-            if (ch < g.Cb) {
-                if (pl == 0 && g.add0) {
-                    const float4 e = *reinterpret_cast<const float4*>(g.add0 + i * g.Cb + ch);
-                    v.x += e.x; v.y += e.y; v.z += e.z; v.w += e.w;
-                }
-                *reinterpret_cast<float4*>(plane_piece(g.out, pl, i, ch, g.Cb, g.M, g.out_sm, g.Cb)) = v;
-            } else {
-                *reinterpret_cast<float4*>(plane_piece(g.outb, pl, i, ch - g.Cb, g.Cbb, g.M, g.out_sm, g.Cbb)) = v;
-            }
+            const float4 v = *reinterpret_cast<const float4*>(&Cs[row * CP + c4]);
+            store_split(g.out, g.outb, g.Cb, g.Cbb, g.M, g.out_sm, j, i, v, g.Cb, g.add0);
         }
     }
 }
@@ -409,6 +353,10 @@ struct CellBwdFusedArgs {
     float* slab;              // (gridDim.x, Kt, 4h): this launch ADDS its partial weight gradients (zeroed by the caller)
 };
 
+// The opt-in kernel keeps its own copies of the column sum (block_param_reduce of qt_cell.h with the wave count as a parameter,
+// the butterfly through __shfl_xor, a full barrier) and of the quad table (build_quad_table of qt_gemm.h).  Its 64-row instances
+// sit at 254 - 256 VGPRs: with either shared piece, or with the shared operand read and stores, they spill 36 - 44 bytes more,
+// and the launch took 63.1 us against 60.2 at the bench shape (HISTORY.md, AL).  Same bits either way.
 template <int LPN, int NW, int NACC>
 __device__ __forceinline__ void block_param_reduce_n(float (&acc)[NACC][4], int h, float* sm, float* part_row, int accumulate) {
     using namespace qtcell;
@@ -442,7 +390,8 @@ __device__ __forceinline__ void block_param_reduce_n(float (&acc)[NACC][4], int 
 // TR = rows per tile (threads = 4 TR): 64 -> two 256-thread workgroups per CU whose phases (loads + cell arithmetic / MFMA /
 // stores) drift apart and overlap; 128 -> one 512-thread workgroup per CU (every phase of the CU in lockstep: 71 us per launch
 // at the bench shape against 68 us for the separate launches it replaces).
-template <int NT, int LPN, int TR>
+constexpr int fused_tile_rows(int nt) { return nt <= 3 ? 64 : 128; }      // nt: 32-column tiles of the data gradient
+template <int NT, int LPN, int TR = fused_tile_rows(NT)>
 __global__ __launch_bounds__(4 * TR, 2) void k_cell_bwd_fused(CellBwdFusedArgs f) {
     using namespace qtcell;
     const DgradCellArgs& g = f.d;
@@ -468,7 +417,7 @@ __global__ __launch_bounds__(4 * TR, 2) void k_cell_bwd_fused(CellBwdFusedArgs f
         return;
     }
     const int nquad = f.Kt >> 2;
-    for (int Q = t; Q < nquad; Q += NTHR) {              // (build_quad_table strides by 256 threads)
+    for (int Q = t; Q < nquad; Q += NTHR) {              // (build_quad_table's text: see the note above the kernel)
         const PlaneSrc& A = f.A;
         const int ct = A.Ca + A.Cab;
         const int k = 4 * Q, kc = A.Ka * ct;
@@ -561,8 +510,7 @@ __global__ __launch_bounds__(4 * TR, 2) void k_cell_bwd_fused(CellBwdFusedArgs f
                     gam_h = ld4(g.ln + j0);
                     gam_c = ld4(g.ln + 2 * h + j0);
                 }
-                const CellBwdOut o = cell_backward<LPN>(I, F, T, Og, cp, gyh, gyc, go_in, wci, wcf, wco, gam_h, gam_c,
-                                                        g.ln != nullptr, pacc);
+                const CellBwdOut o = cell_backward<LPN>(CellBwdIn{I, F, T, Og, cp, gyh, gyc, go_in}, CellBwdParams{wci, wcf, wco, gam_h, gam_c, g.ln != nullptr}, pacc);
                 float* as = Gt + crow * GP + j0;
                 st4(as, o.ggi); st4(as + h, o.ggf); st4(as + 2 * h, o.ggc); st4(as + 3 * h, o.ggo);
                 if (ok && g.gCprev) st4(g.gCprev + node * h + j0, o.gcp);
@@ -659,6 +607,23 @@ __global__ __launch_bounds__(4 * TR, 2) void k_cell_bwd_fused(CellBwdFusedArgs f
 
 }  // namespace
 
+// Launches KERNEL<NT, h / 4> (hidden 8 / 16: the entries' check comes first) for nt 32-column tiles, NT = nt clamped to the
+// instances that exist: NT_LO .. NT_HI8 at hidden 8, NT_LO .. 4 at hidden 16.
+#define QT_GATE_BWD_NT_(n, LO, HI) ((n) < (LO) ? (LO) : (n) > (HI) ? (HI) : (n))
+#define QT_GATE_BWD_LAUNCH_(KERNEL, n, LO, HI, LPN, grid, block, stream, arg) \
+    hipLaunchKernelGGL((KERNEL<QT_GATE_BWD_NT_(n, LO, HI), LPN>), dim3(grid), dim3(block), 0, (hipStream_t)stream, arg)
+#define QT_GATE_BWD_LAUNCH(KERNEL, h, nt, NT_LO, NT_HI8, grid, block, stream, arg)                          \
+    switch (((h) == 16 ? 4 : 0) + ((nt) < 1 ? 1 : (nt) > 4 ? 4 : (nt))) {                                   \
+        case 1: QT_GATE_BWD_LAUNCH_(KERNEL, 1, NT_LO, NT_HI8, 2, grid, block, stream, arg); break;          \
+        case 2: QT_GATE_BWD_LAUNCH_(KERNEL, 2, NT_LO, NT_HI8, 2, grid, block, stream, arg); break;          \
+        case 3: QT_GATE_BWD_LAUNCH_(KERNEL, 3, NT_LO, NT_HI8, 2, grid, block, stream, arg); break;          \
+        case 4: QT_GATE_BWD_LAUNCH_(KERNEL, 4, NT_LO, NT_HI8, 2, grid, block, stream, arg); break;          \
+        case 5: QT_GATE_BWD_LAUNCH_(KERNEL, 1, NT_LO, 4, 4, grid, block, stream, arg); break;               \
+        case 6: QT_GATE_BWD_LAUNCH_(KERNEL, 2, NT_LO, 4, 4, grid, block, stream, arg); break;               \
+        case 7: QT_GATE_BWD_LAUNCH_(KERNEL, 3, NT_LO, 4, 4, grid, block, stream, arg); break;               \
+        default: QT_GATE_BWD_LAUNCH_(KERNEL, 4, NT_LO, 4, 4, grid, block, stream, arg); break;              \
+    }
+
 // What qt_lstm_bwd_dgrad and qt_lstm_bwd_fused check and fill alike: the cell operands with their row strides, the output
 // planes and the alignment of both.  Returns the reason for a refusal (the entry reports it under its own name) or nullptr;
 // g arrives value-initialised and each entry adds its own fields.
@@ -701,17 +666,8 @@ extern "C" int qt_lstm_bwd_dgrad(const float* gO, int ld_go, const float* gHn, i
     g.BThi = (const __bf16*)Whi; g.BTlo = (const __bf16*)Wlo;
     g.out_sm = out_sm != 0;
     g.gHn2 = gHn2; g.ld_gh2 = ld_gh2; g.add0 = add0;
-    const dim3 grid(qt_cdiv(N, BM));
-    // 32-column MFMA tiles: as many as the output planes need (K' C = 80 or 96 columns take three, not four)
-    if (h == 16) {
-        if (NB <= 64) hipLaunchKernelGGL((k_dgrad_cell<2, 4>), grid, dim3(256), 0, (hipStream_t)stream, g);
-        else if (NB <= 96) hipLaunchKernelGGL((k_dgrad_cell<3, 4>), grid, dim3(256), 0, (hipStream_t)stream, g);
-        else hipLaunchKernelGGL((k_dgrad_cell<4, 4>), grid, dim3(256), 0, (hipStream_t)stream, g);
-    } else {
-        if (NB <= 64) hipLaunchKernelGGL((k_dgrad_cell<2, 2>), grid, dim3(256), 0, (hipStream_t)stream, g);
-        else if (NB <= 96) hipLaunchKernelGGL((k_dgrad_cell<3, 2>), grid, dim3(256), 0, (hipStream_t)stream, g);
-        else hipLaunchKernelGGL((k_dgrad_cell<4, 2>), grid, dim3(256), 0, (hipStream_t)stream, g);
-    }
+    // 32-column MFMA tiles: as many as the output planes need (K' C = 80 or 96 columns take three, not four), two at the least
+    QT_GATE_BWD_LAUNCH(k_dgrad_cell, h, qt_cdiv(NB, 32), 2, 4, qt_cdiv(N, BM), 256, stream, g);
     QT_LAUNCHED();
     return QT_OK;
 }
@@ -744,22 +700,12 @@ extern "C" int qt_lstm_bwd_fused(const float* gO, int ld_go, const float* gHn, i
     QT_ARG(f.Kt <= 128, "the weight must have at most 128 rows (one accumulator tile column per wave)");
     const int NTc = qt_cdiv(NB, 32);
     // 64-row tiles, two 256-thread workgroups per CU (their LDS fits twice up to three column tiles); else 128-row tiles
-    const bool small = NTc <= 3;
+    const bool small = fused_tile_rows(NTc) == 64;
     const int grid = small ? min(2 * qt_num_cus(), qt_cdiv(N, 64)) : min(qt_num_cus(), qt_cdiv(N, 128));
     QT_ARG(nslab >= grid, "slab too small: one (Kt, 4h) slab per workgroup, qt_lstm_fused_blocks() of them");
     if (N <= 0) return QT_OK;
     f.slab = slab;
-#define QT_FUSED(NT_, LPN_) hipLaunchKernelGGL((k_cell_bwd_fused<NT_, LPN_, 64>), dim3(grid), dim3(256), 0, (hipStream_t)stream, f)
-    if (h == 16) {
-        if (NTc <= 1) QT_FUSED(1, 4);
-        else if (NTc == 2) QT_FUSED(2, 4);
-        else if (NTc == 3) QT_FUSED(3, 4);
-        else hipLaunchKernelGGL((k_cell_bwd_fused<4, 4, 128>), dim3(grid), dim3(512), 0, (hipStream_t)stream, f);
-    } else {
-        if (NTc <= 1) QT_FUSED(1, 2);
-        else QT_FUSED(2, 2);
-    }
-#undef QT_FUSED
+    QT_GATE_BWD_LAUNCH(k_cell_bwd_fused, h, NTc, 1, 2, grid, 4 * fused_tile_rows(NTc), stream, f);      // (hidden 8: NB <= 64, two tiles)
     QT_LAUNCHED();
     return QT_OK;
 }

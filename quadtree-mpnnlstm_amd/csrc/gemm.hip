@@ -114,7 +114,7 @@ __global__ __launch_bounds__(256, (NT == 4 && CELL != 0) ? QT_GEMM_OCC4C : (NT =
             for (int nt = 0; nt < NT; ++nt)
                 bq[nt] = *reinterpret_cast<const float4*>(&Bt[(nt * 32 + l32) * PITCH + 8 * j + 4 * half]);
 #pragma unroll
-            for (int nt = 0; nt < NT; ++nt) {
+            for (int nt = 0; nt < NT; ++nt) {      // (mfma_quad's text: through the helper four register moves of the ring shift change place)
                 acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, bq[nt].x, acc[nt], 0, 0, 0);
                 acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, bq[nt].y, acc[nt], 0, 0, 0);
                 acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, bq[nt].z, acc[nt], 0, 0, 0);
@@ -129,6 +129,7 @@ __global__ __launch_bounds__(256, (NT == 4 && CELL != 0) ? QT_GEMM_OCC4C : (NT =
         // time with a row pitch of 5 h floats: the rows a 16-lane ds_read_b128 phase touches then start h banks apart.
         // Same arithmetic, in the same order, as qt_dense followed by qt_lstm_fwd.
         using namespace qtcell;
+        __builtin_assume(g.gates != nullptr);    // (qt_dense_lstm refuses a launch without them: store_cell's test folds away)
         constexpr int lpn = CELL;                // 2, 4 or 8 lanes per node
         constexpr int h = 4 * lpn;
         constexpr int CP = 5 * h;
@@ -143,27 +144,18 @@ __global__ __launch_bounds__(256, (NT == 4 && CELL != 0) ? QT_GEMM_OCC4C : (NT =
 #pragma unroll
                     for (int r = 0; r < 16; ++r)
                         if (u * 32 < 4 * h)      // (h = 8: the second 32-column tile is padding)
-                            Cs[(wave * 32 - r0 + (r & 3) + 8 * (r >> 2) + 4 * half) * CP + u * 32 + l32] = acc[u][r];
+                            Cs[(wave * 32 - r0 + acc_row(r, half)) * CP + u * 32 + l32] = acc[u][r];
             }
             __syncthreads();
             const int row = t / lpn, j0 = (t - row * lpn) * 4;
             const int64_t node = i0 + r0 + row;
             const bool ok = node < rows;
-            const float* cs = Cs + row * CP + j0;
-            const F4 gi = ld4(cs), gf = ld4(cs + h), gc = ld4(cs + 2 * h), go = ld4(cs + 3 * h);
+            F4 gi, gf, gc, go;
+            ld_gates(Cs + row * CP + j0, h, &gi, &gf, &gc, &go);
             const float4 c4 = cpre[r0 / RP];
             const F4 cp = {{c4.x, c4.y, c4.z, c4.w}};
             const CellOut r = cell_forward<lpn>(gi, gf, gc, go, cp, g.wc, g.bias, g.ln, h, j0);
-            if (ok) {
-                if (g.O) st4(g.O + node * h + j0, r.Og);
-                st4(g.Hn + node * h + j0, r.hn);
-                st4(g.Cn + node * h + j0, r.cn);
-                float* gs = g.gates + node * 4 * h + j0;
-                st4(gs, r.I);
-                st4(gs + h, r.F);
-                st4(gs + 2 * h, r.T);
-                st4(gs + 3 * h, r.Og);
-            }
+            if (ok) store_cell(g.O, g.Hn, g.Cn, g.gates, node, h, j0, r);
         }
         return;
     }

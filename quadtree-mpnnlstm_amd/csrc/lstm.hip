@@ -6,6 +6,9 @@
 // statistics are xor-shuffle reductions inside that lane group.  Parameter gradients are
 // accumulated per thread, reduced over the wave with shuffles and over the workgroup
 // through LDS in a fixed order, and leave as one partial row per workgroup.
+// qt_cell.h holds what these kernels share with gemm.hip's CELL epilogue and gatecell.hip: the cell arithmetic, its parameters
+// (cell_params, cell_bwd_params), the backward's operand read (cell_bwd_load), ld_gates / st_gates, store_cell and
+// block_param_reduce.
 #include "qt_cell.h"
 
 namespace {
@@ -22,11 +25,11 @@ __global__ __launch_bounds__(256) void k_lstm_fwd(const float* __restrict__ G, c
     const int64_t node = gid / LPN;
     if (node >= qt_rows(n_dev, Ncap)) return;
     const int j0 = (int)(gid % LPN) * 4;
-    const float* g = G + node * ld_g + j0;
-    F4 gi = ld4(g), gf = ld4(g + h), gc = ld4(g + 2 * h), go = ld4(g + 3 * h);
+    F4 gi, gf, gc, go;
+    ld_gates(G + node * ld_g + j0, h, &gi, &gf, &gc, &go);
     if (G2) {                   // conv_x(X) + conv_h(H) of the four gates (model/model.py:394-424), summed here
-        const float* g2 = G2 + node * ld_g + j0;
-        const F4 hi = ld4(g2), hf = ld4(g2 + h), hc = ld4(g2 + 2 * h), ho = ld4(g2 + 3 * h);
+        F4 hi, hf, hc, ho;
+        ld_gates(G2 + node * ld_g + j0, h, &hi, &hf, &hc, &ho);
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             gi.v[c] += hi.v[c];
@@ -37,18 +40,8 @@ __global__ __launch_bounds__(256) void k_lstm_fwd(const float* __restrict__ G, c
     }
     F4 cp = {{0, 0, 0, 0}};
     if (Cprev) cp = ld4(Cprev + node * ld_c + j0);
-    const CellOut r = cell_forward<LPN>(gi, gf, gc, go, cp, wc, b, ln, h, j0);
-    const F4 &I = r.I, &F = r.F, &T = r.T, &Og = r.Og, &hn = r.hn, &cn = r.cn;
-    st4(O + node * h + j0, Og);
-    st4(Hn + node * h + j0, hn);
-    st4(Cn + node * h + j0, cn);
-    if (gates) {                // (NULL: a forward-only launch, qt_lstm_infer -- nothing will read the gates back)
-        float* gs = gates + node * 4 * h + j0;
-        st4(gs, I);
-        st4(gs + h, F);
-        st4(gs + 2 * h, T);
-        st4(gs + 3 * h, Og);
-    }
+    // (gates NULL: a forward-only launch, qt_lstm_infer -- nothing will read the gates back)
+    store_cell(O, Hn, Cn, gates, node, h, j0, cell_forward<LPN>(gi, gf, gc, go, cp, wc, b, ln, h, j0));
 }
 
 template <int LPN>
@@ -62,12 +55,7 @@ __global__ __launch_bounds__(256) void k_lstm_bwd(const float* __restrict__ gO, 
     __shared__ float sm[4 * LPN * 11 * 4];
     const int N = qt_rows(n_dev, Ncap);
     const int j0 = (threadIdx.x % LPN) * 4;
-    const F4 wci = ld4(wc + j0), wcf = ld4(wc + h + j0), wco = ld4(wc + 2 * h + j0);
-    F4 gam_h = {{1, 1, 1, 1}}, gam_c = {{1, 1, 1, 1}};
-    if (ln) {
-        gam_h = ld4(ln + j0);
-        gam_c = ld4(ln + 2 * h + j0);
-    }
+    const CellBwdParams P = cell_bwd_params(wc, ln, h, j0);
     float acc[11][4];
 #pragma unroll
     for (int a = 0; a < 11; ++a)
@@ -76,23 +64,10 @@ __global__ __launch_bounds__(256) void k_lstm_bwd(const float* __restrict__ gO, 
 
     const int64_t stride = (int64_t)gridDim.x * (256 / LPN);
     for (int64_t node = (int64_t)blockIdx.x * (256 / LPN) + threadIdx.x / LPN; node < N; node += stride) {
-        const float* gs = gates + node * 4 * h + j0;
-        const F4 I = ld4(gs), F = ld4(gs + h), T = ld4(gs + 2 * h), Og = ld4(gs + 3 * h);
-        F4 cp = {{0, 0, 0, 0}};
-        if (Cprev) cp = ld4(Cprev + node * ld_c + j0);
-        F4 gyh = {{0, 0, 0, 0}}, gyc = {{0, 0, 0, 0}};      // an output nobody used has no gradient
-        if (gHn) gyh = ld4(gHn + node * ld_gh + j0);
-        if (gCn) gyc = ld4(gCn + node * ld_gc + j0);
-        F4 go_in = {{0, 0, 0, 0}};
-        if (gO) go_in = ld4(gO + node * ld_go + j0);
-        const CellBwdOut r = cell_backward<LPN>(I, F, T, Og, cp, gyh, gyc, go_in, wci, wcf, wco, gam_h, gam_c, ln != nullptr, acc);
-        const F4 &ggi = r.ggi, &ggf = r.ggf, &ggc = r.ggc, &ggo = r.ggo, &gcp = r.gcp;
-        float* gg = gG + node * 4 * h + j0;
-        st4(gg, ggi);
-        st4(gg + h, ggf);
-        st4(gg + 2 * h, ggc);
-        st4(gg + 3 * h, ggo);
-        if (gCprev) st4(gCprev + node * h + j0, gcp);
+        const CellBwdIn x = cell_bwd_load(true, node, h, j0, gates, Cprev, ld_c, gHn, ld_gh, gCn, ld_gc, gO, ld_go);
+        const CellBwdOut r = cell_backward<LPN>(x, P, acc);
+        st_gates(gG + node * 4 * h + j0, h, r.ggi, r.ggf, r.ggc, r.ggo);
+        if (gCprev) st4(gCprev + node * h + j0, r.gcp);
     }
     block_param_reduce<LPN, 11>(acc, h, sm, part + (int64_t)blockIdx.x * 11 * h, accumulate);
 }
@@ -227,40 +202,43 @@ inline bool h_ok(int h) { return h == 8 || h == 16 || h == 32 || h == 64 || h ==
         default: hipLaunchKernelGGL(KERNEL<32>, dim3(grid), dim3(256), 0, (hipStream_t)stream, __VA_ARGS__); break; \
     }
 
+// qt_lstm_fwd and qt_lstm_infer: the same checks and the same launch; the forward-only entry has no gates to store (NULL).
+// `fn`: the entry's name, for the error text.
+static int lstm_fwd(const char* fn, bool want_gates, const float* G, const float* G2, int ld_g, const float* Cprev, int ld_c,
+                    const float* wc, const float* b, const float* ln, int N, const int32_t* n_dev, int h, float* O, float* Hn,
+                    float* Cn, float* gates, void* stream) {
+    auto refuse = [fn](const char* msg) { qt_set_error("%s: %s", fn, msg); return (int)QT_E_ARG; };
+    if (!(G && wc && b && O && Hn && Cn && (gates || !want_gates))) return refuse("null pointer");
+    if (ld_g == 0) ld_g = 4 * h;
+    if (!(ld_g >= 4 * h && ld_g % 4 == 0 && (((uintptr_t)G | (uintptr_t)G2) & 15) == 0)) return refuse("bad gate row stride / alignment");
+    if (!h_ok(h)) return refuse("hidden size must be 8, 16, 32, 64 or 128");
+    if (N <= 0) return QT_OK;
+    const int grid = qt_cdiv((int64_t)N * lanes_per_node(h), 256);
+    if (!(!Cprev || (ld_c >= h && ld_c % 4 == 0))) return refuse("bad Cprev row stride");
+    QT_DISPATCH_LPN(h, k_lstm_fwd, grid, stream, G, G2, ld_g, Cprev, wc, b, ln, N, n_dev, h, ld_c, O, Hn, Cn, gates);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        qt_set_error("%s: %s", fn, hipGetErrorString(e));
+        return QT_E_LAUNCH;
+    }
+    return QT_OK;
+}
+
 extern "C" int qt_lstm_fwd(const float* G, const float* G2, int ld_g, const float* Cprev, int ld_c, const float* wc, const float* b,
                            const float* ln, int N, const int32_t* n_dev, int h, float* O, float* Hn, float* Cn, float* gates,
                            void* stream) {
-    QT_ARG(G && wc && b && O && Hn && Cn && gates, "null pointer");
-    if (ld_g == 0) ld_g = 4 * h;
-    QT_ARG(ld_g >= 4 * h && ld_g % 4 == 0 && (((uintptr_t)G | (uintptr_t)G2) & 15) == 0, "bad gate row stride / alignment");
-    QT_ARG(h_ok(h), "hidden size must be 8, 16, 32, 64 or 128");
-    if (N <= 0) return QT_OK;
-    const int grid = qt_cdiv((int64_t)N * lanes_per_node(h), 256);
-    QT_ARG(!Cprev || (ld_c >= h && ld_c % 4 == 0), "bad Cprev row stride");
-    QT_DISPATCH_LPN(h, k_lstm_fwd, grid, stream, G, G2, ld_g, Cprev, wc, b, ln, N, n_dev, h, ld_c, O, Hn, Cn, gates);
-    QT_LAUNCHED();
-    return QT_OK;
+    return lstm_fwd(__func__, true, G, G2, ld_g, Cprev, ld_c, wc, b, ln, N, n_dev, h, O, Hn, Cn, gates, stream);
 }
 
 extern "C" int qt_lstm_infer(const float* G, const float* G2, int ld_g, const float* Cprev, int ld_c, const float* wc, const float* b,
                              const float* ln, int N, const int32_t* n_dev, int h, float* O, float* Hn, float* Cn, void* stream) {
-    QT_ARG(G && wc && b && O && Hn && Cn, "null pointer");
-    if (ld_g == 0) ld_g = 4 * h;
-    QT_ARG(ld_g >= 4 * h && ld_g % 4 == 0 && (((uintptr_t)G | (uintptr_t)G2) & 15) == 0, "bad gate row stride / alignment");
-    QT_ARG(h_ok(h), "hidden size must be 8, 16, 32, 64 or 128");
-    if (N <= 0) return QT_OK;
-    const int grid = qt_cdiv((int64_t)N * lanes_per_node(h), 256);
-    QT_ARG(!Cprev || (ld_c >= h && ld_c % 4 == 0), "bad Cprev row stride");
-    float* no_gates = nullptr;
-    QT_DISPATCH_LPN(h, k_lstm_fwd, grid, stream, G, G2, ld_g, Cprev, wc, b, ln, N, n_dev, h, ld_c, O, Hn, Cn, no_gates);
-    QT_LAUNCHED();
-    return QT_OK;
+    return lstm_fwd(__func__, false, G, G2, ld_g, Cprev, ld_c, wc, b, ln, N, n_dev, h, O, Hn, Cn, nullptr, stream);
 }
 
+static constexpr int QT_LSTM_BLOCKS = 512;      // workgroups of the grid-stride backward launches (one partial row each)
 extern "C" int qt_lstm_bwd_blocks(int N, int h) {
     if (N <= 0 || !h_ok(h)) return 0;
     const int need = qt_cdiv((int64_t)N * lanes_per_node(h), 256);
-static constexpr int QT_LSTM_BLOCKS = 512;
     return need < QT_LSTM_BLOCKS ? need : QT_LSTM_BLOCKS;
 }
 

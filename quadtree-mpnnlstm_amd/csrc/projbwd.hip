@@ -21,16 +21,10 @@
 // next tile's operands are requested before the current tile's MFMA chain.  Each workgroup
 // owns one slab of the partial weight gradient (fixed summation order: deterministic); the uses of a pass add into the same slabs and
 // the pass's last backward reduces them with qt_colsum.
-#include "qt_common.h"
+// The MFMA step of a k-quad (mfma_quad), the accumulator row map (acc_row) and the global load (gload4) are qt_gemm.h's.
+#include "qt_gemm.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float pb_v4f __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float4 pb_gload4(const float* p) {
-    const pb_v4f v = *(const __attribute__((address_space(1))) pb_v4f*)p;
-    return make_float4(v.x, v.y, v.z, v.w);
-}
 
 constexpr int PB_ROWS = 64;         // rows of a tile
 constexpr int PB_C = 32;            // channels of a plane = input channels of the projection
@@ -81,7 +75,7 @@ __global__ __launch_bounds__(256, 2) void k_proj_bwd(ProjBwdArgs a) {
     // W_g[:32] -> LDS once: Ws[j][k] = W[j][k] (row j = input channel, k = gradient column)
     for (int e = t; e < PB_C * (PB_CO / 4); e += 256) {
         const int j = e >> 5, q = e & 31;
-        *reinterpret_cast<float4*>(&Ws[j * PB_GP + 4 * q]) = pb_gload4(W + (int64_t)j * a.ldw + 4 * q);
+        *reinterpret_cast<float4*>(&Ws[j * PB_GP + 4 * q]) = gload4(W + (int64_t)j * a.ldw + 4 * q);
     }
 
     // the tile's operands: 8 float4 of the gradient planes and 2 float4 of A per thread.  A plane's 64 rows are one contiguous 8 KB
@@ -101,16 +95,16 @@ __global__ __launch_bounds__(256, 2) void k_proj_bwd(ProjBwdArgs a) {
         live1 = tile < ntiles && row1 < rows;
         const int64_t q0 = row0 < last ? row0 : last, q1 = row1 < last ? row1 : last;
         const int64_t o0 = q0 * PB_C + c8, o1 = q1 * PB_C + c8;
-        pg[0] = pb_gload4(gP + o0);
-        pg[1] = pb_gload4(gP + o1);
-        pg[2] = pb_gload4(gP + a.psG + o0);
-        pg[3] = pb_gload4(gP + a.psG + o1);
-        pg[4] = pb_gload4(gP + 2 * a.psG + o0);
-        pg[5] = pb_gload4(gP + 2 * a.psG + o1);
-        pg[6] = pb_gload4(gP + 3 * a.psG + o0);
-        pg[7] = pb_gload4(gP + 3 * a.psG + o1);
-        pa[0] = pb_gload4(A + q0 * a.lda + c8);
-        pa[1] = pb_gload4(A + q1 * a.lda + c8);
+        pg[0] = gload4(gP + o0);
+        pg[1] = gload4(gP + o1);
+        pg[2] = gload4(gP + a.psG + o0);
+        pg[3] = gload4(gP + a.psG + o1);
+        pg[4] = gload4(gP + 2 * a.psG + o0);
+        pg[5] = gload4(gP + 2 * a.psG + o1);
+        pg[6] = gload4(gP + 3 * a.psG + o0);
+        pg[7] = gload4(gP + 3 * a.psG + o1);
+        pa[0] = gload4(A + q0 * a.lda + c8);
+        pa[1] = gload4(A + q1 * a.lda + c8);
     };
     auto stash = [&]() {
         // (values, not `cond ? pg[i] : z` on the arrays themselves: that is a select of two ADDRESSES, which keeps the arrays in
@@ -166,12 +160,7 @@ __global__ __launch_bounds__(256, 2) void k_proj_bwd(ProjBwdArgs a) {
                 }
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    accd = __builtin_amdgcn_mfma_f32_32x32x2f32(ga[cur][u].x, wb[cur][u].x, accd, 0, 0, 0);
-                    accd = __builtin_amdgcn_mfma_f32_32x32x2f32(ga[cur][u].y, wb[cur][u].y, accd, 0, 0, 0);
-                    accd = __builtin_amdgcn_mfma_f32_32x32x2f32(ga[cur][u].z, wb[cur][u].z, accd, 0, 0, 0);
-                    accd = __builtin_amdgcn_mfma_f32_32x32x2f32(ga[cur][u].w, wb[cur][u].w, accd, 0, 0, 0);
-                }
+                for (int u = 0; u < 4; ++u) mfma_quad(accd, ga[cur][u], wb[cur][u]);
                 __builtin_amdgcn_sched_barrier(0);
             }
             // register r of a lane = row (r & 3) + 8 (r >> 2) + 4 half, column l32.  Stored straight from the accumulators the tile
@@ -179,7 +168,7 @@ __global__ __launch_bounds__(256, 2) void k_proj_bwd(ProjBwdArgs a) {
             // rows leave as 4 float4 stores per lane (lane = row l >> 1 + 32 u / 8 .., half a 128-byte row each)
             float* os = Os + wave * 32 * PB_AP;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) os[((r & 3) + 8 * (r >> 2) + 4 * half) * PB_AP + l32] = accd[r];
+            for (int r = 0; r < 16; ++r) os[acc_row(r, half) * PB_AP + l32] = accd[r];
             const int64_t r0 = (int64_t)tile * PB_ROWS + wave * 32;
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
@@ -235,7 +224,7 @@ __global__ __launch_bounds__(256, 2) void k_proj_bwd(ProjBwdArgs a) {
     float ob0 = 0.0f, ob1 = 0.0f;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int f = (r & 3) + 8 * (r >> 2) + 4 * half;
+        const int f = acc_row(r, half);
         o0[r] = a.accumulate ? s0[f * ldw] : 0.0f;
         o1[r] = a.accumulate ? s0[f * ldw + 32] : 0.0f;
     }
@@ -245,7 +234,7 @@ __global__ __launch_bounds__(256, 2) void k_proj_bwd(ProjBwdArgs a) {
     }
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int f = (r & 3) + 8 * (r >> 2) + 4 * half;
+        const int f = acc_row(r, half);
         s0[f * ldw] = o0[r] + acc0[r];
         s0[f * ldw + 32] = o1[r] + acc1[r];
     }

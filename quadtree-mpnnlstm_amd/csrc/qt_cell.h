@@ -1,5 +1,8 @@
 // Device helpers of the peephole graph-LSTM cell shared by lstm.hip (stand-alone cell kernels), gemm.hip (the gate GEMM
 // with the cell fused into its epilogue) and gatecell.hip (the persistent gate-cell launches): model/model.py:394-428 + the LayerNorms of model/seq2seq.py:64-75, 140-151.
+// One copy each of what those kernels' bit-identity claims rest on: the cell arithmetic (cell_forward, cell_backward), its
+// parameters (cell_params, cell_bwd_params), the backward's operand read (cell_bwd_load), the gate quarters (ld_gates,
+// st_gates), the forward's stores (store_cell) and the fixed-order column sum of the parameter gradients (block_param_reduce).
 #pragma once
 #include "qt_common.h"
 
@@ -60,6 +63,13 @@ __device__ __forceinline__ F4 ld4(const float* p) {
 }
 __device__ __forceinline__ void st4(float* p, const F4& a) {
     *reinterpret_cast<float4*>(p) = make_float4(a.v[0], a.v[1], a.v[2], a.v[3]);
+}
+// The four h-apart quarters of a gate row (pre-activations, activations or their gradients: i, f, c, o), p = row + j0
+__device__ __forceinline__ void ld_gates(const float* p, int h, F4* a, F4* b, F4* c, F4* d) {
+    *a = ld4(p); *b = ld4(p + h); *c = ld4(p + 2 * h); *d = ld4(p + 3 * h);
+}
+__device__ __forceinline__ void st_gates(float* p, int h, const F4& a, const F4& b, const F4& c, const F4& d) {
+    st4(p, a); st4(p + h, b); st4(p + 2 * h, c); st4(p + 3 * h, d);
 }
 
 // y = gamma * xhat + beta over the group's h = 4 LPN values; returns xhat and rstd.  The means are products with the exact
@@ -168,16 +178,71 @@ __device__ __forceinline__ CellOut cell_forward(const F4& gi, const F4& gf, cons
     return cell_forward<LPN>(gi, gf, gc, go, cp, cell_params(wc, b, ln, h, j0));
 }
 
+// The forward's stores for this lane's 4 hidden units of `node`: O (the output gate once more, NULL: skipped), H', C' and the
+// gate activations the backward reads (NULL: a forward-only launch).  k_lstm_fwd, k_gemm_fwd's CELL epilogue and
+// k_gate_cell_p all store through this.
+__device__ __forceinline__ void store_cell(float* O, float* Hn, float* Cn, float* gates, int64_t node, int h, int j0,
+                                           const CellOut& r) {
+    if (O) st4(O + node * h + j0, r.Og);
+    st4(Hn + node * h + j0, r.hn);
+    st4(Cn + node * h + j0, r.cn);
+    if (gates) st_gates(gates + node * 4 * h + j0, h, r.I, r.F, r.T, r.Og);
+}
+
+// The backward's parameters for this lane's 4 hidden units (gamma = 1 without LayerNorm), as CellParams for the forward.
+struct CellBwdParams {
+    F4 wci, wcf, wco, gam_h, gam_c;
+    bool has_ln;
+};
+__device__ __forceinline__ CellBwdParams cell_bwd_params(const float* __restrict__ wc, const float* __restrict__ ln, int h, int j0) {
+    CellBwdParams p;
+    p.wci = ld4(wc + j0); p.wcf = ld4(wc + h + j0); p.wco = ld4(wc + 2 * h + j0);
+    p.has_ln = ln != nullptr;
+    const F4 one = {{1, 1, 1, 1}};
+    p.gam_h = p.gam_c = one;
+    if (ln) {
+        p.gam_h = ld4(ln + j0);
+        p.gam_c = ld4(ln + 2 * h + j0);
+    }
+    return p;
+}
+
+// The backward's operands for this lane's 4 hidden units of `node`: the saved gate activations, C, and the gradients of
+// H', C' and O.  A null pointer gives zeros (no previous state; an output nobody used has no gradient), and so does every
+// operand of a row that is not ok (past the valid count).  gHn2: an optional second gradient of H', added on load.
+struct CellBwdIn {
+    F4 I, F, T, Og, cp, gyh, gyc, go_in;
+};
+__device__ __forceinline__ CellBwdIn cell_bwd_load(bool ok, int64_t node, int h, int j0, const float* gates, const float* Cprev,
+                                                   int ld_c, const float* gHn, int ld_gh, const float* gCn, int ld_gc,
+                                                   const float* gO, int ld_go, const float* gHn2 = nullptr, int ld_gh2 = 0) {
+    const F4 z = {{0, 0, 0, 0}};
+    CellBwdIn x = {z, z, z, z, z, z, z, z};
+    if (ok) {
+        ld_gates(gates + node * 4 * h + j0, h, &x.I, &x.F, &x.T, &x.Og);
+        if (Cprev) x.cp = ld4(Cprev + node * ld_c + j0);
+        if (gHn) x.gyh = ld4(gHn + node * ld_gh + j0);
+        if (gCn) x.gyc = ld4(gCn + node * ld_gc + j0);
+        if (gO) x.go_in = ld4(gO + node * ld_go + j0);
+        if (gHn2) {
+            const F4 h2 = ld4(gHn2 + node * ld_gh2 + j0);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) x.gyh.v[k] += h2.v[k];
+        }
+    }
+    return x;
+}
+
 // Backward of one cell update for 4 hidden units of a node (lane group as in cell_forward).  acc[11][4] collects this
 // thread's parameter-gradient terms: w_c i, f, o | b i, f, c, o | LayerNorm gamma_h, beta_h, gamma_c, beta_c.
 struct CellBwdOut {
     F4 ggi, ggf, ggc, ggo, gcp;
 };
 template <int LPN>
-__device__ __forceinline__ CellBwdOut cell_backward(const F4& I, const F4& F, const F4& T, const F4& Og, const F4& cp,
-                                                    const F4& gyh, const F4& gyc, const F4& go_in, const F4& wci,
-                                                    const F4& wcf, const F4& wco, const F4& gam_h, const F4& gam_c,
-                                                    bool has_ln, float (&acc)[11][4]) {
+__device__ __forceinline__ CellBwdOut cell_backward(const CellBwdIn& x, const CellBwdParams& P, float (&acc)[11][4]) {
+    const F4 &I = x.I, &F = x.F, &T = x.T, &Og = x.Og, &cp = x.cp, &gyh = x.gyh, &gyc = x.gyc, &go_in = x.go_in;
+    const F4 &wci = P.wci, &wcf = P.wcf, &wco = P.wco, &gam_h = P.gam_h, &gam_c = P.gam_c;
+    const bool has_ln = P.has_ln;
     F4 Cr, Hr, tc;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -235,8 +300,10 @@ __device__ __forceinline__ float wave_strided_sum(float v) {
     return v;
 }
 
-// reduce NACC*4 per-thread accumulators over a 256-thread workgroup into part_row[NACC * h]; sm: 4 * LPN * NACC * 4 floats
-template <int LPN, int NACC>
+// reduce NACC*4 per-thread accumulators over a workgroup of NW waves into part_row[NACC * h]; sm: NW * LPN * NACC * 4 floats.
+// Every thread of the workgroup calls it.  The barrier waits for LDS only, which is enough for every caller: `sm` is written
+// and read nowhere else, and part_row[idx] is read and written by one thread.
+template <int LPN, int NACC, int NW = 4>
 __device__ __forceinline__ void block_param_reduce(float (&acc)[NACC][4], int h, float* sm, float* part_row, int accumulate) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
@@ -250,12 +317,12 @@ __device__ __forceinline__ void block_param_reduce(float (&acc)[NACC][4], int h,
             for (int k = 0; k < 4; ++k) sm[(wave * LPN + lane) * NACC * 4 + a * 4 + k] = acc[a][k];
     }
     qt_lds_barrier();                      // (only `sm` crosses: the rows' global stores issued before stay in flight)
-    for (int idx = threadIdx.x; idx < NACC * h; idx += 256) {
+    for (int idx = threadIdx.x; idx < NACC * h; idx += 64 * NW) {
         const int a = idx / h, j = idx % h;
         const int li = j >> 2, k = j & 3;
         float s = 0.0f;
 #pragma unroll
-        for (int w = 0; w < 4; ++w) s += sm[(w * LPN + li) * NACC * 4 + a * 4 + k];
+        for (int w = 0; w < NW; ++w) s += sm[(w * LPN + li) * NACC * 4 + a * 4 + k];
         part_row[idx] = accumulate ? part_row[idx] + s : s;
     }
 }

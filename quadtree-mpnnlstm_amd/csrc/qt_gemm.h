@@ -1,7 +1,8 @@
 // What the dense products (gemm.hip) and the gate-cell launches (gatecell.hip) both need: the node-feature operand and the
 // argument block of the GEMM kernels, the tile constants, the device helpers that address planes and rows, and the pieces the
 // dense kernels share: act_quad / relu_bwd_quad, fma_quad / post_product, store_split and stage_and_store (cheb.hip's
-// k_spmm1 takes act_quad from here too).
+// k_spmm1 takes act_quad from here too); and what every fp32 MFMA kernel of gemm.hip, gatecell.hip and projbwd.hip shares: the
+// four-MFMA step of a k-quad (mfma_quad), the accumulator row map (acc_row) and the quad table (build_quad_table).
 #pragma once
 #include "qt_common.h"
 
@@ -71,6 +72,16 @@ constexpr int BM = 128;       // block rows (4 waves x 32)
 constexpr int BN = 64;        // block columns (2 MFMA tiles per wave)
 constexpr int MAXQ = 128;     // quads (4 consecutive k) in the reduction dimension
 
+// Row of the 32 x 32 tile that accumulator register r of a lane of half (lane >> 5) holds
+__device__ __forceinline__ constexpr int acc_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
+// One k-quad of a lane on one column tile: the four MFMAs on a.x .. a.w with b.x .. b.w, in that order
+__device__ __forceinline__ void mfma_quad(f32x16& acc, const float4& a, const float4& b) {
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, acc, 0, 0, 0);
+}
+
 // Pointers that went through the LDS quad table lose their address space: hipcc then emits flat_load, and flat loads
 // force `s_waitcnt vmcnt(0) lgkmcnt(0)` at every use (they may return out of order), which serialised the whole
 // operand stream.  Loading through an explicit global (address space 1) pointer restores counted vmcnt waits.
@@ -129,14 +140,24 @@ __device__ __forceinline__ float4 post_product(const float4 (&q)[4], const float
 }
 
 // float4 v = columns j .. j + 3 of output row i: to its plane and part (out | outb; Cb, Cbb % 4 == 0: a float4 never straddles
-// two parts).  ld: the row stride of part a (g.Cb, or g.ldo for a column block of a wider matrix)
-__device__ __forceinline__ void store_split(const GemmArgs& g, int j, int64_t i, float4 v, int ld) {
-    const int ct = g.Cb + g.Cbb;
+// two parts).  ld: the row stride of part a (g.Cb, or g.ldo for a column block of a wider matrix).  add0: optional (M, Cb),
+// added to plane 0 of part a.  On plain fields for the kernels whose argument block is not a GemmArgs.
+__device__ __forceinline__ void store_split(float* out, float* outb, int Cb, int Cbb, int M, int out_sm, int j, int64_t i,
+                                            float4 v, int ld, const float* add0 = nullptr) {
+    const int ct = Cb + Cbb;
     const int pl = j / ct, ch = j - pl * ct;
-    if (ch < g.Cb)
-        *reinterpret_cast<float4*>(plane_piece(g.out, pl, i, ch, g.Cb, g.M, g.out_sm, ld)) = v;
-    else
-        *reinterpret_cast<float4*>(plane_piece(g.outb, pl, i, ch - g.Cb, g.Cbb, g.M, g.out_sm, g.Cbb)) = v;
+    if (ch < Cb) {
+        if (pl == 0 && add0) {
+            const float4 e = *reinterpret_cast<const float4*>(add0 + i * Cb + ch);
+            v.x += e.x; v.y += e.y; v.z += e.z; v.w += e.w;
+        }
+        *reinterpret_cast<float4*>(plane_piece(out, pl, i, ch, Cb, M, out_sm, ld)) = v;
+    } else {
+        *reinterpret_cast<float4*>(plane_piece(outb, pl, i, ch - Cb, Cbb, M, out_sm, Cbb)) = v;
+    }
+}
+__device__ __forceinline__ void store_split(const GemmArgs& g, int j, int64_t i, float4 v, int ld) {
+    store_split(g.out, g.outb, g.Cb, g.Cbb, g.M, g.out_sm, j, i, v, ld);
 }
 
 // The staged epilogue of the MFMA kernels (256 threads, wave w owns rows [32 w, 32 w + 32) of the 128 x 32 NT tile at (i0, j0)).
@@ -157,7 +178,7 @@ __device__ __forceinline__ void stage_and_store(f32x16 (&acc)[NT], float* Cs, co
             if (nt < NT)
 #pragma unroll
                 for (int r = 0; r < 16; ++r)
-                    Cs[(wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * half) * 64 + u * 32 + l32] = acc[nt][r];
+                    Cs[(wave * 32 + acc_row(r, half)) * 64 + u * 32 + l32] = acc[nt][r];
         }
         __syncthreads();
 #pragma unroll
@@ -176,9 +197,11 @@ __device__ __forceinline__ void stage_and_store(f32x16 (&acc)[NT], float* Cs, co
     }
 }
 
-// Quad table: quad Q of a node row lives at qptr[Q] + row * qstr[Q] (plane Q*4/Ca of the operand, or S).
+// Quad table: quad Q of a node row lives at qptr[Q] + row * qstr[Q] (plane Q*4/Ca of the operand, or S).  NTHR: the threads of
+// the calling workgroup.
+template <int NTHR = 256>
 __device__ __forceinline__ void build_quad_table(const PlaneSrc& A, const float** qptr, int* qstr, int nquad) {
-    for (int Q = threadIdx.x; Q < nquad; Q += 256) {
+    for (int Q = threadIdx.x; Q < nquad; Q += NTHR) {
         const int ct = A.Ca + A.Cab;
         const int k = 4 * Q, kc = A.Ka * ct;
         if (k < kc) {

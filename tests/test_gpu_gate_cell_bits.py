@@ -60,3 +60,98 @@ def test_fused_gate_cell_bits_and_store_range(h, Ka, rows, with_c, with_o):
     # the gate block's last quarter IS the output gate: the O output is its second copy
     if with_o:
         assert torch.equal(out['O'][:rows], out['gates'][:rows, 3 * h:])
+
+
+# ---- the backward launches against the unfused pair qt_lstm_bwd -> qt_dense2: every launch is cell_backward per node, and the
+# data gradient is the MFMA chain of k_gemm_fwd on the stored gG.  The `part` rows are summed in another order per launch shape
+# and are not compared here (tests/test_gpu_cell_oracle.py holds them).
+CB, CBB = 16, 16          # both parts of an output plane: 32 columns a plane, Kb planes = Kb 32-column MFMA tiles
+OPTS = [(True, True, True), (False, False, False), (True, False, True), (False, True, False)]     # (ln, Cprev, gO)
+
+
+def _bwd_inputs(h, rows, cap):
+    torch.manual_seed(7000 + 10 * h + rows % 89)
+    d = dev()
+    gates = torch.cat([torch.sigmoid(torch.randn(cap, 2 * h, device=d)), torch.tanh(torch.randn(cap, h, device=d)),
+                       torch.sigmoid(torch.randn(cap, h, device=d))], 1).contiguous()
+    t = dict(gates=gates, Cp=torch.randn(cap, h, device=d), gHn=torch.randn(cap, h, device=d), gCn=torch.randn(cap, h, device=d),
+             gO=torch.randn(cap, h, device=d), wc=torch.randn(3, h, device=d), ln=torch.randn(4, h, device=d),
+             Wrows=0.3 * torch.randn(4 * (CB + CBB), 4 * h, device=d), A=torch.randn(cap, 16, device=d),
+             n_dev=torch.tensor([rows], dtype=torch.int32, device=d))
+    return t
+
+
+def _reference(t, h, cap, Kb, ln, cp, go, out_sm):
+    """qt_lstm_bwd, then qt_dense2 on its stored gG: (gG, gCprev, out, outb), sentinel-filled"""
+    from qtmpnn import _lib
+    from qtmpnn._lib import ptr
+    full = lambda *s: torch.full(s, SENTINEL, device=dev())
+    gG, gCp, out, outb = full(cap, 4 * h), full(cap, h), full(Kb, cap, CB), full(Kb, cap, CBB)
+    part = torch.zeros(_lib.value('qt_lstm_bwd_blocks', cap, h), 11 * h, device=dev())
+    _lib.call('qt_lstm_bwd', ptr(t['gO']) if go else None, h, ptr(t['gHn']), h, ptr(t['gCn']), h, ptr(t['gates']),
+              ptr(t['Cp']) if cp else None, h, ptr(t['wc']), ptr(t['ln']) if ln else None, cap, ptr(t['n_dev']), h, ptr(gG),
+              ptr(gCp), ptr(part), 0)
+    _lib.call('qt_dense2', ptr(gG), 0, None, None, 0, None, 1, 4 * h, 0, None, ptr(t['Wrows']), None, 0, None, Kb, CB, CBB, cap,
+              ptr(t['n_dev']), 0, None, 0, None, ptr(out), ptr(outb), 2 * out_sm, None, None)
+    return gG, gCp, out, outb
+
+
+def _check_planes(name, got, ref, rows, cap, Kb, C, out_sm):
+    assert torch.equal(got, ref), f'{name}: differs from qt_dense2 on the stored gG'
+    assert bool((got[0, rows:] == SENTINEL).all()), f'{name}: plane 0 written past the device-side count'
+    rest = got[1:].reshape(Kb - 1, C // 4, cap, 4)[:, :, rows:] if out_sm else got[1:, rows:]
+    assert bool((rest == SENTINEL).all()), f'{name}: planes 1.. written past the device-side count'
+
+
+@pytest.mark.parametrize('rows', [1, 127, 128, 129, 300])      # the 128-row tile empty, partial, full, just over, a third tile
+@pytest.mark.parametrize('h', [8, 16])
+def test_dgrad_cell_bits_and_store_range(h, rows):
+    from qtmpnn import _lib
+    from qtmpnn._lib import ptr
+    cap = rows + 70
+    t = _bwd_inputs(h, rows, cap)
+    full = lambda *s: torch.full(s, SENTINEL, device=dev())
+    for Kb in (2, 3, 4):                  # NB = 64, 96, 128 columns: the three NT instances
+        for out_sm in (0, 1):
+            for ln, cp, go in OPTS:
+                rG, rCp, rout, routb = _reference(t, h, cap, Kb, ln, cp, go, out_sm)
+                gG, gCp, out, outb = full(cap, 4 * h), full(cap, h), full(Kb, cap, CB), full(Kb, cap, CBB)
+                part = torch.zeros(_lib.value('qt_lstm_dgrad_blocks', cap), 11 * h, device=dev())
+                _lib.call('qt_lstm_bwd_dgrad', ptr(t['gO']) if go else None, h, ptr(t['gHn']), h, ptr(t['gCn']), h, ptr(t['gates']),
+                          ptr(t['Cp']) if cp else None, h, ptr(t['wc']), ptr(t['ln']) if ln else None, cap, ptr(t['n_dev']), h,
+                          ptr(gG), ptr(gCp), ptr(part), 0, ptr(t['Wrows']), None, None, Kb, CB, CBB, ptr(out), ptr(outb), out_sm,
+                          None, 0, None)
+                torch.cuda.synchronize()
+                what = f'Kb={Kb} out_sm={out_sm} ln={ln} Cprev={cp} gO={go}'
+                assert torch.equal(gG[:rows], rG[:rows]) and torch.equal(gCp[:rows], rCp[:rows]), f'gG / gCprev differ from qt_lstm_bwd ({what})'
+                for name, a in (('gG', gG), ('gCprev', gCp), ('gG (qt_lstm_bwd)', rG), ('gCprev (qt_lstm_bwd)', rCp)):
+                    assert bool((a[rows:] == SENTINEL).all()), f'{name}: rows past the device-side count were written ({what})'
+                _check_planes(f'out ({what})', out, rout, rows, cap, Kb, CB, out_sm)
+                _check_planes(f'outb ({what})', outb, routb, rows, cap, Kb, CBB, out_sm)
+
+
+@pytest.mark.parametrize('rows', [1, 63, 64, 65, 129])         # the 64-row tile empty, partial, full, just over, a third tile
+@pytest.mark.parametrize('h', [8, 16])
+def test_fused_cell_backward_bits_and_store_range(h, rows):
+    from qtmpnn import _lib
+    from qtmpnn._lib import ptr
+    cap = rows + 70
+    t = _bwd_inputs(h, rows, cap)
+    full = lambda *s: torch.full(s, SENTINEL, device=dev())
+    nslab = _lib.value('qt_lstm_fused_blocks')
+    for Kb in ((1, 2, 3, 4) if h == 16 else (1, 2)):          # all six instances; four tiles: 128-row tiles, 512 threads
+        for ln, cp, go in OPTS:
+            _, rCp, rout, routb = _reference(t, h, cap, Kb, ln, cp, go, 0)
+            gCp, out, outb = full(cap, h), full(Kb, cap, CB), full(Kb, cap, CBB)
+            part = torch.zeros(nslab, 11 * h, device=dev())
+            slab = torch.zeros(nslab, 16, 4 * h, device=dev())
+            _lib.call('qt_lstm_bwd_fused', ptr(t['gO']) if go else None, h, ptr(t['gHn']), h, ptr(t['gCn']), h, ptr(t['gates']),
+                      ptr(t['Cp']) if cp else None, h, ptr(t['wc']), ptr(t['ln']) if ln else None, cap, ptr(t['n_dev']), h,
+                      ptr(gCp), ptr(part), 0, ptr(t['Wrows']), Kb, CB, CBB, ptr(out), ptr(outb),
+                      ptr(t['A']), 16, None, None, 0, None, 1, 16, 0, None, 0, ptr(slab), nslab)
+            torch.cuda.synchronize()
+            what = f'Kb={Kb} ln={ln} Cprev={cp} gO={go}'
+            assert torch.equal(gCp[:rows], rCp[:rows]), f'gCprev differs from qt_lstm_bwd ({what})'
+            assert bool((gCp[rows:] == SENTINEL).all()), f'gCprev: rows past the device-side count were written ({what})'
+            _check_planes(f'out ({what})', out, rout, rows, cap, Kb, CB, 0)
+            _check_planes(f'outb ({what})', outb, routb, rows, cap, Kb, CBB, 0)
