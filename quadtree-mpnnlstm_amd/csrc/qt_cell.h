@@ -13,8 +13,15 @@ constexpr float LN_EPS = 1e-5f;
 // Branch-free gate nonlinearities on the hardware exp2 / reciprocal (v_exp_f32, v_rcp_f32: 1 ulp each).  The libm forms
 // (expf + IEEE division, tanhf with its range branches) cost ~25-40 instructions per value: 80 values per node made the
 // cell ~10 us of pure VALU issue per launch at the bench shape, as much as the gate GEMM's MFMA time, and the branches
-// kept the scheduler from placing that arithmetic beside the MFMAs.  Error: sigmoid <= 3 ulp; tanh <= 2e-7 absolute
-// (<= 8 ulp; |x| < 1/8 takes the odd series, where the quotient form would lose relative accuracy by cancellation).
+// kept the scheduler from placing that arithmetic beside the MFMAs.  Error, ABSOLUTE, from the instruction sequence (derived
+// in tests/cell_f64.py: sig_own, tanh_own; u = 2^-24):
+//   sigmoid  u [s (1 - s)(2 |x| + 2) + 3 s] <= 3.3 u = 2e-7.  Relative to s this is (1 - s)(2 |x| + 2) + 3 roundings: the rounding
+//            of -log2(e) x is an absolute error of the exponent, so for negative x the relative error grows as |x| (5 ulp at
+//            x = -2.5, 13 ulp at x = -10): "3 ulp" holds for x >= 0 only, and nothing may rest on a relative reading.
+//   tanh     |x| >= 1/8: u [(1 - t^2)(2 |x| + 1) + 3 (1 - |t|) + |t|] <= 4 u = 2.4e-7, the most at |x| = 1/8, where it is
+//            16 ulp of the result; |x| < 1/8 takes the odd series (the quotient form loses relative accuracy by cancellation):
+//            (2 + x^2) u relative + 62 / 2835 |x|^9 for the series' end, under 2 ulp.
+// A saturated argument is safe: exp2 overflows to inf, rcp(inf) = 0, so sigmoid -> 0 and tanh -> +-1 without a NaN.
 // Forward and backward call the SAME functions, so recomputed values carry the same bits.
 __device__ __forceinline__ float sigmoidf_(float x) {
     return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x));

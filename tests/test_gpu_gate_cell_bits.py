@@ -2,7 +2,15 @@
 -> qt_lstm_fwd, bit for bit, at the row counts where a wave's 32-row unit is empty, partial, full and just over, and with a
 device-side row count below the buffers' capacity: rows past the count must keep the bytes they had before the launch.
 The persistent kernel loads clamped rows for the units' tails and masks only its stores, so this pins both the values of the
-valid rows and the store range."""
+valid rows and the store range.
+
+The tiled CELL epilogue of k_gemm_fwd -- qt_dense_lstm at hidden 32, and at hidden 8 / 16 when the packed gate matrix has more than
+GATE_P_MAXK = 256 rows -- is tied to the same pair in the same way.  That is the bit-for-bit route: qt_dense launches the very
+k_gemm_fwd<NT, KWT> the epilogue is compiled into (NB = 4h = 128 columns: <4, 64>; NB = 64: <2, 128>), so the accumulators hold the
+same k-ordered MFMA chain, and cell_forward is one function.  Its row tile is 128 rows: partial, full and just over.
+
+qt_lstm_fwd and qt_lstm_bwd, the anchors of every comparison here, are held to the float64 cell model by tests/test_gpu_cell_f64.py,
+and so are the `part` rows and the weight-gradient slab of the fused backward launches, accumulate = 1 included."""
 import pytest
 import torch
 
@@ -62,9 +70,25 @@ def test_fused_gate_cell_bits_and_store_range(h, Ka, rows, with_c, with_o):
         assert torch.equal(out['O'][:rows], out['gates'][:rows, 3 * h:])
 
 
+@pytest.mark.parametrize('with_o', [True, False])
+@pytest.mark.parametrize('with_c', [True, False])
+@pytest.mark.parametrize('rows', [1, 127, 128, 129])
+@pytest.mark.parametrize('h,Ka', [(32, 3), (16, 13)])    # k_gemm_fwd<4, 64, 8> (two k passes of 112); <2, 128, 4> at a reduction of 264 > GATE_P_MAXK
+def test_tiled_cell_epilogue_bits_and_store_range(h, Ka, rows, with_c, with_o):
+    assert h == 32 or Ka * (4 + h) + 4 > 256
+    out, ref = _run(h, Ka, rows, with_c, with_o)
+    for name, a in out.items():
+        if a is None:
+            continue
+        assert torch.equal(a[:rows], ref[name][:rows]), f'{name}: valid rows differ from qt_dense + qt_lstm_fwd'
+        assert bool((a[rows:] == SENTINEL).all()), f'{name}: rows past the device-side count were written'
+    if with_o:
+        assert torch.equal(out['O'][:rows], out['gates'][:rows, 3 * h:])
+
+
 # ---- the backward launches against the unfused pair qt_lstm_bwd -> qt_dense2: every launch is cell_backward per node, and the
-# data gradient is the MFMA chain of k_gemm_fwd on the stored gG.  The `part` rows are summed in another order per launch shape
-# and are not compared here (tests/test_gpu_cell_oracle.py holds them).
+# data gradient is the MFMA chain of k_gemm_fwd on the stored gG.  The `part` rows are summed in another order per launch shape:
+# tests/test_gpu_cell_f64.py compares them, and the fused launch's weight-gradient slab, with the float64 model workgroup by workgroup.
 CB, CBB = 16, 16          # both parts of an output plane: 32 columns a plane, Kb planes = Kb 32-column MFMA tiles
 OPTS = [(True, True, True), (False, False, False), (True, False, True), (False, True, False)]     # (ln, Cprev, gO)
 
