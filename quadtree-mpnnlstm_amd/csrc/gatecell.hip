@@ -204,7 +204,7 @@ struct DgradCellArgs {
 // The right operand (the weight rows, <= 32 KB, L1 / L2 resident) is read straight from global memory by the lanes that need
 // it and is not staged in LDS: the workgroup's LDS is 38 KB where the staged form took 64 KB, so more than two workgroups fit
 // a CU -- more workgroups whose load / arithmetic / MFMA / store phases overlap (the staged form's numbers: HISTORY.md, AL).
-static constexpr int QT_DGRAD_OCC = 4;      // 128 VGPRs (8-10 spilled): FOUR workgroups per CU = all 940 tiles of the bench shape resident at once
+static constexpr int QT_DGRAD_OCC = 4;      // 128 VGPRs (hidden 16: 5 spilled, 20 bytes of scratch; 9 before gG left from LDS): FOUR workgroups per CU = all 940 tiles of the bench shape resident at once
                           // (3: 138-155 VGPRs, 768 resident + a second round; 8.41 -> 8.34 ms per frozen step)
 template <int NT, int LPN>
 __global__ __launch_bounds__(256, QT_DGRAD_OCC) void k_dgrad_cell(DgradCellArgs g) {
@@ -217,6 +217,10 @@ __global__ __launch_bounds__(256, QT_DGRAD_OCC) void k_dgrad_cell(DgradCellArgs 
     const int64_t i0 = (int64_t)blockIdx.x * BM;
     const int64_t rows = qt_rows(g.n_dev, g.M);
     constexpr int h = 4 * LPN;     // (== g.h: the host picks the instance by it)
+    // gG rows leave whole, from the LDS tile behind the first barrier (below), at hidden 16 only: at hidden 8 the cell phase's
+    // stores already take 32 bytes of a 128-byte row per lane pair, and the launch was 0.7 - 1.2 us SLOWER with the row stores
+    // (27.7 -> 28.4 - 28.9 us at 120 k rows, profiles/dgrad_cell_rows.txt), so those instances keep the parent's code.
+    constexpr bool GG_ROWS = LPN == 4;
     if (i0 >= rows) return;        // past the valid rows: nothing to add to the partials (the slab rows start at zero)
     // cell backward of this workgroup's rows (rows past the valid count contribute zeros)
     {
@@ -237,13 +241,37 @@ __global__ __launch_bounds__(256, QT_DGRAD_OCC) void k_dgrad_cell(DgradCellArgs 
             const CellBwdOut o = cell_backward<LPN>(x, P, acc);
             st_gates(As + r * PITCH + j0, h, o.ggi, o.ggf, o.ggc, o.ggo);
             if (ok) {
-                st_gates(g.gG + node * 4 * h + j0, h, o.ggi, o.ggf, o.ggc, o.ggo);
+                if constexpr (!GG_ROWS) st_gates(g.gG + node * 4 * h + j0, h, o.ggi, o.ggf, o.ggc, o.ggo);
                 if (g.gCprev) st4(g.gCprev + node * h + j0, o.gcp);
             }
         }
         block_param_reduce<LPN, 11>(acc, h, sm, g.part + (int64_t)blockIdx.x * 11 * h, g.accumulate);
     }
     qt_lds_barrier();                                 // As complete
+    // Hidden 16: gG (the deferred weight gradient reads it) leaves from the finished tile, not from the cell phase.  There a lane
+    // owns the four h-apart quarters of its node's row, so a store instruction of a wave touched 16 rows and took 64 bytes of each,
+    // half a 128-byte line.  The tile's rows are one contiguous run of BM x 4h floats in gG: thread t takes the float4 pieces
+    // t, t + 256, .. of the run -- a wave 1 KB, four whole rows, per instruction -- and the stores drain under the MFMA loop.  The
+    // values are the ones the cell phase wrote to As: the same bits.  All pieces are read before the first store (a read inside the
+    // store's branch waited for LDS eight times in a row).  LDS side (ds_read_b128: four 16-lane groups, bank = word mod 64): the
+    // pitch of 68 floats shifts consecutive rows by one 16-byte slot, so two of the groups (lanes 4-11 with 16-19: pieces 4 and 3 of neighbouring rows) meet one slot
+    // twice: 6 LDS cycles where a conflict-free map takes 4, on 8 instructions a thread.  The pitch is the MFMA operand read's and stays.
+    if constexpr (GG_ROWS) {
+        constexpr int NP = BM * (K / 4) / 256;
+        const int nvalid = (int)min((int64_t)BM, rows - i0) * (K / 4);     // the float4 pieces of the valid rows: no row at or past the count is written
+        float* gq = g.gG + i0 * K;
+        float4 v[NP];
+#pragma unroll
+        for (int u = 0; u < NP; ++u) {
+            const int e = t + 256 * u;
+            v[u] = *reinterpret_cast<const float4*>(&As[(e / (K / 4)) * PITCH + (e % (K / 4)) * 4]);
+        }
+#pragma unroll
+        for (int u = 0; u < NP; ++u) {
+            const int e = t + 256 * u;
+            if (e < nvalid) *reinterpret_cast<float4*>(gq + 4 * e) = v[u];
+        }
+    }
     f32x16 acc2[NT];
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt)
