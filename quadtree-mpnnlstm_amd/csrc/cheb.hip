@@ -2,14 +2,15 @@
 //   k_spmm  -- the CSR message-aggregate  out = alpha * L^ x + beta * p + gamma * q
 //   k_spmm1 -- the same on single strided columns, with an optional output epilogue
 // The dense products that turn the aggregated planes into outputs are in gemm.hip, the gate-cell launches in gatecell.hip.
+#include "qt_aggr.h"      // the row rule: ELL head, four-edge chain
 #include "qt_gemm.h"      // (act_quad: the epilogue activation, shared with the dense kernels)
 
 namespace {
 
 // ------------------------------------------------------------------ message aggregate
-// Thread = (RPT consecutive rows) x (one VEC-wide channel chunk), chunk index fastest (RPT = 1 in every launch: two rows
-// per thread, or several 256-thread slices per workgroup, only lengthen the chain of dependent loads rowptr -> col/nrm ->
-// x rows that a thread walks -- measured 11.1 vs 10.8 us and 13.3 vs 11.0 us at N = 1.2e5, C = 20).  Measured with PMC
+// Thread = one row x one VEC-wide channel chunk, chunk index fastest (two rows per thread, or several 256-thread slices per
+// workgroup, only lengthen the chain of dependent loads rowptr -> col/nrm -> x rows that a thread walks -- measured
+// 11.1 vs 10.8 us and 13.3 vs 11.0 us at N = 1.2e5, C = 20: the rows-per-thread parameter is gone).  Measured with PMC
 // counters at the same shape: FETCH_SIZE equals the algorithmic reads once workgroups are mapped XCD-wise (below), waves
 // spend ~60 % of their cycles waiting on memory and the launch moves ~3 TB/s against the 7 TB/s a plain copy of
 // the same buffers reaches.
@@ -23,12 +24,13 @@ struct SpmmPart {
     int C, ldx, ldp, ldq, xcd_chunk;      // row strides of x / p / q in floats (out rows are dense)
 };
 static constexpr int QT_SPMM_BS = 64;      // one wave per workgroup: 11.08 ms per training step against 11.12 (128) and 11.18 (256)
-template <int VEC, int RPT, int EPT>
+template <int VEC, int EPT>
 __global__ __launch_bounds__(QT_SPMM_BS) void k_spmm(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
                                               const float* __restrict__ nrm, const int4* __restrict__ ell, int Ncap,
                                               const int32_t* __restrict__ n_dev,
                                               SpmmPart pa, SpmmPart pb, int nblk_a,     // workgroups [nblk_a, ..) do part b
                                               float alpha, float beta, float gamma) {
+    using V = fvec<VEC>;
     const bool second = (int)blockIdx.x >= nblk_a;
     const SpmmPart& P = second ? pb : pa;
     const int C = P.C, ldx = P.ldx, xcd_chunk = P.xcd_chunk;
@@ -45,87 +47,50 @@ __global__ __launch_bounds__(QT_SPMM_BS) void k_spmm(const int32_t* __restrict__
     const int rows = qt_rows(n_dev, Ncap);
     int blk = bid;
     if (xcd_chunk) {
-        const int nblk = (int)(((int64_t)((rows + RPT - 1) / RPT) * nch + QT_SPMM_BS - 1) / QT_SPMM_BS);
+        const int nblk = (int)(((int64_t)rows * nch + QT_SPMM_BS - 1) / QT_SPMM_BS);
         const int chunk = (nblk + 7) >> 3;
         if ((bid >> 3) >= chunk) return;
         blk = (bid & 7) * chunk + (bid >> 3);
     }
     const unsigned idx = (unsigned)blk * (unsigned)QT_SPMM_BS + threadIdx.x;      // N * nch < 2^31 (checked by the host entry): 32-bit
-    const int64_t rp = idx / (unsigned)nch;                        // division, a fraction of the 64-bit one's cost
-    if (rp * RPT >= rows) return;
-    const int ch = (int)(idx - (unsigned)rp * (unsigned)nch) * VEC;
-    int e0[RPT], e1[RPT];
-    int64_t row[RPT];
-#pragma unroll
-    for (int u = 0; u < RPT; ++u) {
-        row[u] = rp * RPT + u;
-        const bool ok = row[u] < rows;
-        if (!ok) row[u] = rows - 1;                // duplicate of a valid row; its result is not stored
-        e0[u] = (ok && !(VEC == 4 && ell)) ? rowptr[row[u]] : 0;
-        e1[u] = (ok && !(VEC == 4 && ell)) ? rowptr[row[u] + 1] : 0;
-    }
-    float acc[RPT][VEC];
-#pragma unroll
-    for (int u = 0; u < RPT; ++u)
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) acc[u][k] = 0.0f;
+    const int64_t row = idx / (unsigned)nch;                       // division, a fraction of the 64-bit one's cost
+    if (row >= rows) return;
+    const int ch = (int)(idx - (unsigned)row * (unsigned)nch) * VEC;
+    const bool head = VEC == 4 && ell;
+    int e0 = head ? 0 : rowptr[row], e1 = head ? 0 : rowptr[row + 1];
+    V acc = vzero<VEC>();
     // the addends are requested now, together with the index loads, not after the gather loop: one dependent memory phase
     // less at the end of every launch (each thread reads its own p / q element before it writes out: aliasing is fine)
-    float pv[RPT][VEC], qv[RPT][VEC];
-#pragma unroll
-    for (int u = 0; u < RPT; ++u) {
-        if constexpr (VEC == 4) {
-            float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
-            if (p) a = *reinterpret_cast<const float4*>(p + row[u] * P.ldp + ch);
-            if (q) b = *reinterpret_cast<const float4*>(q + row[u] * P.ldq + ch);
-            pv[u][0] = a.x; pv[u][1] = a.y; pv[u][2] = a.z; pv[u][3] = a.w;
-            qv[u][0] = b.x; qv[u][1] = b.y; qv[u][2] = b.z; qv[u][3] = b.w;
-        } else {
-            pv[u][0] = p ? p[row[u] * P.ldp + ch] : 0.0f;
-            qv[u][0] = q ? q[row[u] * P.ldq + ch] : 0.0f;
-        }
-    }
+    V pv = vzero<VEC>(), qv = vzero<VEC>();
+    if (p) pv = vload<VEC>(p + row * P.ldp + ch);
+    if (q) qv = vload<VEC>(q + row * P.ldq + ch);
     if constexpr (VEC == 4) {
         if (ell) {
             // the first four edges of a row come as two 16-byte vectors (qt_edges_norm): no row pointer on the way to the
             // gathers, fully regular index loads; only rows flagged with more than four edges go on to the CSR loop below
-#pragma unroll
-            for (int u = 0; u < RPT; ++u) {
-                int4 c4 = ell[2 * row[u]];
-                const int4 wb = ell[2 * row[u] + 1];
-                const bool more4 = c4.w < 0;
-                if (more4) c4.w = ~c4.w;
-                const float4 f0 = *reinterpret_cast<const float4*>(x + (int64_t)c4.x * ldx + ch);
-                const float4 f1 = *reinterpret_cast<const float4*>(x + (int64_t)c4.y * ldx + ch);
-                const float4 f2 = *reinterpret_cast<const float4*>(x + (int64_t)c4.z * ldx + ch);
-                const float4 f3 = *reinterpret_cast<const float4*>(x + (int64_t)c4.w * ldx + ch);
-                const float w0 = __int_as_float(wb.x), w1 = __int_as_float(wb.y), w2 = __int_as_float(wb.z), w3 = __int_as_float(wb.w);
-                acc[u][0] += w0 * f0.x; acc[u][1] += w0 * f0.y; acc[u][2] += w0 * f0.z; acc[u][3] += w0 * f0.w;
-                acc[u][0] += w1 * f1.x; acc[u][1] += w1 * f1.y; acc[u][2] += w1 * f1.z; acc[u][3] += w1 * f1.w;
-                acc[u][0] += w2 * f2.x; acc[u][1] += w2 * f2.y; acc[u][2] += w2 * f2.z; acc[u][3] += w2 * f2.w;
-                acc[u][0] += w3 * f3.x; acc[u][1] += w3 * f3.y; acc[u][2] += w3 * f3.z; acc[u][3] += w3 * f3.w;
-                if (more4 && rp * RPT + u < rows) {
-                    e0[u] = rowptr[row[u]] + 4;
-                    e1[u] = rowptr[row[u] + 1];
-                }
+            const EllHead h = ell_head(ell, row);
+            const V f[4] = {vload<4>(x + (int64_t)h.c.x * ldx + ch), vload<4>(x + (int64_t)h.c.y * ldx + ch),
+                            vload<4>(x + (int64_t)h.c.z * ldx + ch), vload<4>(x + (int64_t)h.c.w * ldx + ch)};
+            fma4<4>(acc, h.w, f);
+            if (h.more) {
+                e0 = rowptr[row] + 4;
+                e1 = rowptr[row + 1];
             }
         }
     }
-    // 4 edges per trip: the index/weight loads, then the neighbour gathers, are independent and stay in flight together
-    // (quadtree rows have ~4 neighbours, so most rows finish in the first trip, which is issued for all RPT rows at once).
+    // EPT edges per trip: the index/weight loads, then the neighbour gathers, are independent and stay in flight together
+    // (quadtree rows have ~4 neighbours, so most rows finish in the first trip).
     // Tried and rejected (round 1): staging each 64-row run of the reversed-Morton node order in LDS so that the ~87 %
     // internal neighbours are LDS reads -- 12.2 us vs 11.2 us per launch at N = 1.2e5, C = 20.
-    auto trip = [&](const int (&eb)[RPT], bool (&more)[RPT]) {
-        int cj[RPT][EPT];
-        float w[RPT][EPT];
+    auto trip = [&](int eb) -> bool {
+        int cj[EPT];
+        float w[EPT];
 #pragma unroll
-        for (int u = 0; u < RPT; ++u)
-#pragma unroll
-            for (int v = 0; v < EPT; ++v) {
-                const bool ok = eb[u] + v < e1[u];
-                cj[u][v] = ok ? col[eb[u] + v] : (int)row[u];
-                w[u][v] = ok ? nrm[eb[u] + v] : 0.0f;
-            }
+        for (int v = 0; v < EPT; ++v) {
+            const bool ok = eb + v < e1;
+            cj[v] = ok ? col[eb + v] : (int)row;
+            w[v] = ok ? nrm[eb + v] : 0.0f;
+        }
         if constexpr (VEC == 4) {
             // gathers in groups of 4 edges: the first group always (slots beyond the row's edges re-read the row itself with
             // weight 0), a further group only for the lanes whose row reaches it -- one branch per group, so a row with 4
@@ -133,67 +98,49 @@ __global__ __launch_bounds__(QT_SPMM_BS) void k_spmm(const int32_t* __restrict__
             // above) stay off the critical path of the rows with many neighbours
 #pragma unroll
             for (int v0 = 0; v0 < EPT; v0 += 4) {
+                if (v0 > 0 && eb + v0 >= e1) continue;
+                V f[4];
 #pragma unroll
-                for (int u = 0; u < RPT; ++u) {
-                    if (v0 > 0 && eb[u] + v0 >= e1[u]) continue;
-                    float4 f[4];
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) f[v] = *reinterpret_cast<const float4*>(x + (int64_t)cj[u][v0 + v] * ldx + ch);
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) {
-                        acc[u][0] += w[u][v0 + v] * f[v].x; acc[u][1] += w[u][v0 + v] * f[v].y;
-                        acc[u][2] += w[u][v0 + v] * f[v].z; acc[u][3] += w[u][v0 + v] * f[v].w;
-                    }
-                }
+                for (int v = 0; v < 4; ++v) f[v] = vload<4>(x + (int64_t)cj[v0 + v] * ldx + ch);
+                fma4<4>(acc, w + v0, f);
             }
         } else {
-            float f[RPT][EPT];
+            // (scalar rows: the compiler has always emitted these sums as separate multiplies and adds, so the intrinsic chain
+            // of fma4 would change their bits; contraction is switched off to keep them so: profiles/aggr_shared.txt)
+#pragma clang fp contract(off)
+            float f[EPT];
 #pragma unroll
-            for (int u = 0; u < RPT; ++u)
+            for (int v = 0; v < EPT; ++v) f[v] = x[(int64_t)cj[v] * ldx + ch];
 #pragma unroll
-                for (int v = 0; v < EPT; ++v) f[u][v] = x[(int64_t)cj[u][v] * ldx + ch];
-#pragma unroll
-            for (int u = 0; u < RPT; ++u)
-#pragma unroll
-                for (int v = 0; v < EPT; ++v) acc[u][0] += w[u][v] * f[u][v];
+            for (int v = 0; v < EPT; ++v) acc[0] += w[v] * f[v];
         }
-#pragma unroll
-        for (int u = 0; u < RPT; ++u) more[u] = eb[u] + EPT < e1[u];
+        return eb + EPT < e1;
     };
-    int eb[RPT];
-    bool more[RPT];
-    bool any = false;
-#pragma unroll
-    for (int u = 0; u < RPT; ++u) {
-        eb[u] = e0[u];
-        any |= e0[u] < e1[u];
-    }
+    int eb = e0;
+    bool any = e0 < e1;
     while (any) {
-        trip(eb, more);
-        any = false;
-#pragma unroll
-        for (int u = 0; u < RPT; ++u) {
-            eb[u] = more[u] ? eb[u] + EPT : e1[u];       // a finished row keeps an empty edge range
-            any |= more[u];
-        }
+        any = trip(eb);
+        eb = any ? eb + EPT : e1;       // a finished row keeps an empty edge range
     }
-#pragma unroll
-    for (int u = 0; u < RPT; ++u) {
-        if (rp * RPT + u >= rows) continue;
-        const int64_t o = row[u] * C + ch;
-        float r[VEC];
+    // The finish, spelled out as the compiler had always contracted  r = alpha acc; r += beta p; r += gamma q  (read from the
+    // listing; the intrinsic form fma(beta, p, rn(alpha acc)) in every channel would change bits): scalar rows add the
+    // separately rounded products alpha acc and beta p; a 4-channel chunk has fma(beta, p, rn(alpha acc)) in channels 0, 2, 3
+    // and fma(alpha, acc, rn(beta p)) in channel 1; gamma q is fused everywhere.  (profiles/aggr_shared.txt)
+    V r;
+    {
+#pragma clang fp contract(off)
 #pragma unroll
         for (int k = 0; k < VEC; ++k) {
-            r[k] = alpha * acc[u][k];
-            if (p) r[k] += beta * pv[u][k];
-            if (q) r[k] += gamma * qv[u][k];
-        }
-        if constexpr (VEC == 4) {
-            *reinterpret_cast<float4*>(out + o) = make_float4(r[0], r[1], r[2], r[3]);
-        } else {
-            out[o] = r[0];
+            const float aa = alpha * acc[k];
+            r[k] = aa;
+            if (p) {
+                const float bp = beta * pv[k];
+                r[k] = VEC == 1 ? aa + bp : k == 1 ? __builtin_fmaf(alpha, acc[k], bp) : __builtin_fmaf(beta, pv[k], aa);
+            }
+            if (q) r[k] = __builtin_fmaf(gamma, qv[k], r[k]);
         }
     }
+    vstore<VEC>(out + row * C + ch, r);
 }
 
 // One-column message aggregate with strided operands and an optional output epilogue: the Clenshaw recurrence of a
@@ -226,21 +173,21 @@ __global__ __launch_bounds__(64) void k_spmm1(Spmm1Args a) {
     if (row >= rows) return;
     const float pv = a.p ? a.p[row * a.ldp] : 0.0f, qv = a.q ? a.q[row * a.ldq] : 0.0f;
     const float* __restrict__ x = a.x;
+    // (the sums below mirror fma4 but are separate multiplies and adds, as the compiler has always emitted them: the
+    // intrinsic would change this kernel's bits, so contraction is switched off where they stand: profiles/aggr_shared.txt)
     float acc = 0.0f;
     int e0, e1;
     if (a.ell) {
-        int4 c4 = a.ell[2 * row];
-        const int4 wb = a.ell[2 * row + 1];
-        const bool more4 = c4.w < 0;
-        if (more4) c4.w = ~c4.w;
-        const float f0 = x[(int64_t)c4.x * a.ldx], f1 = x[(int64_t)c4.y * a.ldx], f2 = x[(int64_t)c4.z * a.ldx],
-                    f3 = x[(int64_t)c4.w * a.ldx];
-        acc += __int_as_float(wb.x) * f0;
-        acc += __int_as_float(wb.y) * f1;
-        acc += __int_as_float(wb.z) * f2;
-        acc += __int_as_float(wb.w) * f3;
+#pragma clang fp contract(off)
+        const EllHead h = ell_head(a.ell, row);
+        const float f0 = x[(int64_t)h.c.x * a.ldx], f1 = x[(int64_t)h.c.y * a.ldx], f2 = x[(int64_t)h.c.z * a.ldx],
+                    f3 = x[(int64_t)h.c.w * a.ldx];
+        acc += h.w[0] * f0;
+        acc += h.w[1] * f1;
+        acc += h.w[2] * f2;
+        acc += h.w[3] * f3;
         e0 = e1 = 0;
-        if (more4) {
+        if (h.more) {
             e0 = a.rowptr[row] + 4;
             e1 = a.rowptr[row + 1];
         }
@@ -249,6 +196,7 @@ __global__ __launch_bounds__(64) void k_spmm1(Spmm1Args a) {
         e1 = a.rowptr[row + 1];
     }
     for (int eb = e0; eb < e1; eb += 4) {
+#pragma clang fp contract(off)
         int cj[4];
         float w[4];
 #pragma unroll
@@ -263,9 +211,12 @@ __global__ __launch_bounds__(64) void k_spmm1(Spmm1Args a) {
 #pragma unroll
         for (int v = 0; v < 4; ++v) acc += w[v] * f[v];
     }
-    float v = a.alpha * acc;
-    if (a.p) v += a.beta * pv;
-    if (a.q) v += a.gamma * qv;
+    float v = a.alpha * acc;       // (the finish as k_spmm's scalar rows have it: + beta p unfused, gamma q fused)
+    {
+#pragma clang fp contract(off)
+        if (a.p) v = v + a.beta * pv;
+    }
+    if (a.q) v = __builtin_fmaf(a.gamma, qv, v);
     if (a.act == QT_ACT_TANH_RES) v = act_quad(v, QT_ACT_TANH_RES, a.drop ? a.drop[row] : 1.0f, a.res[row * a.ldr]);
     if (a.pad4)
         *reinterpret_cast<float4*>(a.out + row * a.ldo) = make_float4(v, 0.0f, 0.0f, 0.0f);
@@ -311,9 +262,9 @@ extern "C" int qt_spmm2(const int32_t* rowptr, const int32_t* col, const float* 
     if (Cb) spmm_part(&B, &nb, N, Cb, xb, ldxb, pb, ldpb, qb, ldqb, outb);
     // the wider part decides
     if (max(Ca, Cb) <= QT_EPT8_MAXC)
-        hipLaunchKernelGGL((k_spmm<4, 1, 8>), dim3(na + nb), dim3(QT_SPMM_BS), 0, (hipStream_t)stream, rowptr, col, nrm, reinterpret_cast<const int4*>(ell), N, n_dev, A, B, na, alpha, beta, gamma);
+        hipLaunchKernelGGL((k_spmm<4, 8>), dim3(na + nb), dim3(QT_SPMM_BS), 0, (hipStream_t)stream, rowptr, col, nrm, reinterpret_cast<const int4*>(ell), N, n_dev, A, B, na, alpha, beta, gamma);
     else
-        hipLaunchKernelGGL((k_spmm<4, 1, 4>), dim3(na + nb), dim3(QT_SPMM_BS), 0, (hipStream_t)stream, rowptr, col, nrm, reinterpret_cast<const int4*>(ell), N, n_dev, A, B, na, alpha, beta, gamma);
+        hipLaunchKernelGGL((k_spmm<4, 4>), dim3(na + nb), dim3(QT_SPMM_BS), 0, (hipStream_t)stream, rowptr, col, nrm, reinterpret_cast<const int4*>(ell), N, n_dev, A, B, na, alpha, beta, gamma);
     QT_LAUNCHED();
     return QT_OK;
 }
@@ -350,7 +301,7 @@ extern "C" int qt_spmm(const int32_t* rowptr, const int32_t* col, const float* n
     // Edges per trip: a trip is two dependent loads (col/nrm, then the x rows), and the few rows with many neighbours
     // (a 4x4 cell next to 1x1 cells has 16) set the length of the whole launch.  8 per trip: 6.6 -> 4.5 us at C = 4,
     // 9.3 -> 7.5 us at C = 16 (N = 1.2e5, inside a hipGraph); wider rows are bandwidth bound and prefer fewer registers.
-    hipLaunchKernelGGL((k_spmm<1, 1, 8>), dim3(grid), dim3(QT_SPMM_BS), 0, (hipStream_t)stream, rowptr, col, nrm, (const int4*)nullptr, N, n_dev, A, B, grid, alpha, beta, gamma);
+    hipLaunchKernelGGL((k_spmm<1, 8>), dim3(grid), dim3(QT_SPMM_BS), 0, (hipStream_t)stream, rowptr, col, nrm, (const int4*)nullptr, N, n_dev, A, B, grid, alpha, beta, gamma);
     QT_LAUNCHED();
     return QT_OK;
 }

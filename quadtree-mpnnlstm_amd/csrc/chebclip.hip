@@ -21,16 +21,15 @@
 // Arithmetic: the same fused multiply-adds in the same order as k_spmm (ELL slots 0..3, then the CSR tail of rows with more
 // than four edges, then alpha * acc + beta * p + gamma * q), so the planes are bit-identical to the per-hop launches
 // (tests/test_gpu_ops.py::test_clip_resident_recurrence_equals_per_hop_launches).
-#include "qt_common.h"
+#include "qt_aggr.h"      // the row rule: slice rows, the fused multiply-add, the four-edge chain
 
 namespace {
 
 // Threads per workgroup and rows gathered together, measured at the bench shape (K = 5, C = 4 + 16, forward / backward, us per
 // launch): 1024 x 1 row: 21.4 / 21.3;  1024 x 2: 22.4 / 23.8;  512 x 2: 24.9 / 26.6;  512 x 4: 25.5 / 27.3 --
 // sixteen waves that each wait on one row's five LDS reads beat eight waves with four rows in flight (per-hop launches: 29.6 / 31.4).
-static constexpr int QT_CLIP_T = 1024;
+constexpr int CL_T = 1024;                 // threads per workgroup
 constexpr int CL_ROWS = QT_TAIL_REC_CAP;   // rows of a clip that fit: 2 planes x 4096 x 16 B = 128 KB
-constexpr int CL_T = QT_CLIP_T;            // threads per workgroup
 constexpr int CL_RPT = CL_ROWS / CL_T;     // rows per thread (6 registers per row for all hops: packed ELL columns, weights; the
                                            // backward 4 more for the prefetched A_k)
 constexpr int CL_TAIL = QT_TAIL_CAP;       // LDS pool of tail edges (edges 5, 6, .. of a row) per clip: 8 B each, ~32 KB
@@ -70,48 +69,12 @@ struct ClipArgs {
     unsigned* sync;                // (2 B QT_TILE_SLICES): launch generation and arrivals per (clip, slice)
     unsigned* err;                 // the caller's persistent error word (never reset by the library): bit 0 a wait for a neighbour
                                    // tile gave up, bit 1 a tile capacity of the mesh build was exceeded
-    int T, nbj, s0, ns;            // tiles per clip, tiles per tile row; first slice and slice count of THIS launch
+    int T, s0, ns;                 // tiles per clip; first slice and slice count of THIS launch
 };
-
-// the W channels of a slice row: a plain struct (independent registers: as one ext_vector value the 4-register tuples' alignment
-// cost the W = 4 kernels ~25 more registers and spills); memory accesses go through the matching vector type
-template <int W> struct fvec {
-    float v[W];
-    __device__ __forceinline__ float& operator[](int i) { return v[i]; }
-    __device__ __forceinline__ const float& operator[](int i) const { return v[i]; }
-};
-template <int W> using fraw = float __attribute__((ext_vector_type(W)));
-template <int W> __device__ __forceinline__ fvec<W> vload(const void* p) {
-    const fraw<W> r = *reinterpret_cast<const fraw<W>*>(p);
-    fvec<W> o;
-#pragma unroll
-    for (int i = 0; i < W; ++i) o.v[i] = r[i];
-    return o;
-}
-template <int W> __device__ __forceinline__ void vstore(void* p, const fvec<W>& a) {
-    fraw<W> r;
-#pragma unroll
-    for (int i = 0; i < W; ++i) r[i] = a.v[i];
-    *reinterpret_cast<fraw<W>*>(p) = r;
-}
-template <int W> __device__ __forceinline__ fvec<W> ldg(const float* p) { return vload<W>(p); }
-template <int W> __device__ __forceinline__ fvec<W> vzero() {
-    fvec<W> z;
-#pragma unroll
-    for (int i = 0; i < W; ++i) z.v[i] = 0.0f;
-    return z;
-}
 
 // LDS rows are addressed by row * 16 (< 65536: two offsets per register); a slice row is 4 W bytes
 template <int W> __device__ __forceinline__ fvec<W> lds_row(const char* plane, unsigned off16) {
     return vload<W>(plane + off16 * (unsigned)W / 4u);
-}
-
-// acc += w f, one fused multiply-add per channel.  Spelled with the intrinsic: left to the contraction pass, the vector form of
-// w0 f0 + w1 f1 was fused the other way round in half the lanes -- 1 ulp away from k_spmm's chain ((0 + w0 f0) + w1 f1) + ...
-template <int W> __device__ __forceinline__ void vfma(fvec<W>& a, float w, const fvec<W>& f) {
-#pragma unroll
-    for (int i = 0; i < W; ++i) a[i] = __builtin_fmaf(w, f[i], a[i]);
 }
 
 // The tail of a row with more than four edges, from the LDS copy of the clip's pool.  Four pool entries and their four
@@ -175,8 +138,7 @@ __device__ __forceinline__ void gather_tail_csr(fvec<W>& a, const char* __restri
 //   between launches or hipGraph replays; the exchange buffer is zeroed once per mesh build.
 // No dependence on dispatch order beyond forward progress: spins are bounded (a timeout sets the error word and the launch
 // finishes with garbage instead of hanging) and the launches are cut so that all workgroups of one are co-resident.
-static constexpr unsigned QT_TILE_SPIN_LIMIT = 200000u;       // polls of ~1 us: ~0.2 s before a poll gives up
-constexpr unsigned TILE_SPIN_LIMIT = QT_TILE_SPIN_LIMIT;
+constexpr unsigned TILE_SPIN_LIMIT = 200000u;       // polls of ~1 us: ~0.2 s before a poll gives up
 static_assert((QT_TILE_HALO_CAP & (QT_TILE_HALO_CAP - 1)) == 0 && QT_TILE_HALO_CAP <= 256,
               "halo slots: a power of two (slot masks) of at most 256 (the boundary pool keeps a slot in 8 bits; waves 0-3 own them)");
 
@@ -286,9 +248,9 @@ __global__ __launch_bounds__(CL_T) void k_cheb_clip(ClipArgs g) {
         c4[u] = src[0];
         wb[u] = src[1];
         if constexpr (!BWD) {
-            first[u] = ldg<W>(pt.z + (rowc[u] * (unsigned)pt.ld + ch));
+            first[u] = vload<W>(pt.z + (rowc[u] * (unsigned)pt.ld + ch));
         } else {
-            first[u] = ldg<W>(pt.planes + grad_off(K - 1, rowc[u]));
+            first[u] = vload<W>(pt.planes + grad_off(K - 1, rowc[u]));
         }
     }
     {
@@ -310,7 +272,7 @@ __global__ __launch_bounds__(CL_T) void k_cheb_clip(ClipArgs g) {
             const int4 b0 = bs[0], b1 = bs[1];
             BR[2 * t] = b0;
             BR[2 * t + 1] = b1;
-            if constexpr (BWD) bnx = ldg<W>(pt.planes + grad_off(K - 2, (unsigned)r0 + ((unsigned)b1.w & (CL_ROWS - 1))));
+            if constexpr (BWD) bnx = vload<W>(pt.planes + grad_off(K - 2, (unsigned)r0 + ((unsigned)b1.w & (CL_ROWS - 1))));
         }
         if (t < nbp) BP[t] = g.tile_bpool[(int64_t)ts * QT_TILE_BPOOL_CAP + t];
         if (t < nh) {
@@ -325,8 +287,8 @@ __global__ __launch_bounds__(CL_T) void k_cheb_clip(ClipArgs g) {
             }
             HC[t] = ba < 0 ? 0 : (((ba / QT_TILE_HALO_CAP) * QT_TILE_SLICES + s) * 2 * QT_TILE_HALO_CAP + (ba & (QT_TILE_HALO_CAP - 1))) * 4;
             V hv;
-            if constexpr (!BWD) hv = ldg<W>(pt.z + ((unsigned)hc * (unsigned)pt.ld + ch));
-            else hv = ldg<W>(pt.planes + grad_off(K - 1, (unsigned)hc));
+            if constexpr (!BWD) hv = vload<W>(pt.z + ((unsigned)hc * (unsigned)pt.ld + ch));
+            else hv = vload<W>(pt.planes + grad_off(K - 1, (unsigned)hc));
             vstore<W>(HB + t * (4 * W), hv);
         }
     }
@@ -370,7 +332,7 @@ __global__ __launch_bounds__(CL_T) void k_cheb_clip(ClipArgs g) {
     }
     if constexpr (BWD) {       // A_{K-2} of the rows: needed at the end of the first hop's groups (requested here, not in the prologue:
 #pragma unroll                 // its registers would sit beside the ELL vectors' and spill)
-        for (int u = 0; u < CL_RPT; ++u) nxt[u] = ldg<W>(pt.planes + grad_off(K - 2, rowc[u]));
+        for (int u = 0; u < CL_RPT; ++u) nxt[u] = vload<W>(pt.planes + grad_off(K - 2, rowc[u]));
     }
     qt_lds_barrier();
     // One hop with the gathered plane at byte offset CO of Pl (compile-time: the hop loops below are unrolled by two, so the plane
@@ -422,11 +384,10 @@ __global__ __launch_bounds__(CL_T) void k_cheb_clip(ClipArgs g) {
                 if constexpr (OWN) own = vload<W>(slot);
                 const float bw[4] = {__int_as_float(b0.z), __int_as_float(b0.w), __int_as_float(b1.x), __int_as_float(b1.y)};
                 V acc = vzero<W>();
-#pragma unroll
-                for (int e = 0; e < 4; ++e) vfma<W>(acc, bw[e], f[e]);
+                fma4<W>(acc, bw, f);
                 const bool real = info != 0xffffffffu;          // (a NULL record: a row whose record did not fit, qt_edges_norm_tiles)
                 const unsigned pb = info & 0xffffu, pc = real ? info >> 16 : 0u;
-                for (unsigned j0 = 0; j0 < pc; j0 += 4) {
+                for (unsigned j0 = 0; j0 < pc; j0 += 4) {          // (gather_tail_lds on the boundary pool: a negative entry is a halo slot)
                     int2 e[4];
 #pragma unroll
                     for (int v = 0; v < 4; ++v) e[v] = BP[pb + min(j0 + v, pc - 1)];
@@ -466,9 +427,8 @@ __global__ __launch_bounds__(CL_T) void k_cheb_clip(ClipArgs g) {
             f[3] = lds_row<W>(Pc, lc[u][1] >> 16);
             char* slot = Pn + (rowc[u] - (unsigned)r0) * (4u * W);
             if constexpr (OWN) own = vload<W>(slot);
-            V acc = vzero<W>();                                // (the same chain of fused multiply-adds as k_spmm)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) vfma<W>(acc, w[u][e], f[e]);
+            V acc = vzero<W>();
+            fma4<W>(acc, w[u], f);
             if (tails && tinfo[u]) {
                 if ((tinfo[u] & 0xffffu) != 0xffffu)
                     gather_tail_lds<W>(acc, Pc, TE, tinfo[u]);
@@ -546,7 +506,7 @@ __global__ __launch_bounds__(CL_T) void k_cheb_clip(ClipArgs g) {
                 const V ak = nx;                              // A_k of this row; its A_{k-1} is requested as soon as A_k is consumed
 #pragma unroll
                 for (int i = 0; i < W; ++i) r[i] += 1.0f * ak[i];
-                if (k > 0) nx = ldg<W>(planes + off(k - 1, grow));
+                if (k > 0) nx = vload<W>(planes + off(k - 1, grow));
             }
         };
         auto add_ak = [&](int k) { return AddAk{pt.planes, grad_off, k}; };
@@ -573,43 +533,42 @@ __global__ __launch_bounds__(CL_T) void k_cheb_clip(ClipArgs g) {
 }  // namespace
 
 extern "C" int qt_cheb_clip_rows(void) { return CL_ROWS; }
+extern "C" int qt_num_cus(void);
 
-struct ClipMesh {       // the mesh operands both entry points share
-    const int32_t *rowptr, *col;
-    const float* nrm;
-    const int32_t *ell, *node_off, *tail_cnt, *tail_pool, *tail_rec;
-    int B;
-};
+// What the four entry points share: the CSR / ELL arrays, the sizes and the two column parts.  clip_launch and tile_launch add
+// their mesh arrays and the slice split.
+static ClipArgs clip_args(const int32_t* rowptr, const int32_t* col, const float* nrm, const int32_t* ell, int B, int Ncap, int K,
+                          int Ca, const float* za, int lda, float* Pa, int Cb, const float* zb, int ldb, float* Pb, int bwd_sm) {
+    ClipArgs g = {};
+    g.rowptr = rowptr;
+    g.col = col;
+    g.nrm = nrm;
+    g.ell = reinterpret_cast<const int4*>(ell);
+    g.B = B;
+    g.K = K;
+    g.Ncap = Ncap;
+    g.bwd_sm = bwd_sm != 0;
+    g.a = ClipPart{za, Pa, Ca, lda ? lda : Ca};
+    g.b = ClipPart{zb, Pb, Cb, ldb ? ldb : Cb};
+    return g;
+}
 
 // Slice width (the `width` argument of both entry points): 0 = automatic (2 when the launch's B * C / 2 workgroups fit the CUs in
 // one round, else 4); 2 or 4 pins it (diagnostics and the parity tests of both widths).  No library-global switch: the ABI keeps
 // no mutable state besides the thread-local error string.
-extern "C" int qt_num_cus(void);
-
-static int clip_launch(bool bwd, const ClipMesh& m, int Ncap, int K, int Ca, const float* za, int lda, float* Pa, int Cb,
-                       const float* zb, int ldb, float* Pb, void* stream, int width, int bwd_sm = 0) {
+static void clip_launch(bool bwd, ClipArgs g, const int32_t* node_off, const int32_t* tail_cnt, const int32_t* tail_pool,
+                        const int32_t* tail_rec, int width, void* stream) {
     // forward: half-width slices whenever they still fit the CUs in one round (K = 5, 16 channels, 32 clips: 16.8 -> 15.2 us);
     // backward only when even they leave half the CUs idle: its A_k loads and the final store move 8 of every 16 bytes at
     // W = 2 (the same shape backward: 19.1 us at W = 4, 21.0 at W = 2; 4 channels: 13.2 vs 11.5)
-    const int half = m.B * ((Ca + Cb) / 2);
-    const int W = width ? width : (half <= (bwd ? qt_num_cus() / 2 : qt_num_cus()) ? 2 : 4);
-    ClipArgs g;
-    g.bwd_sm = bwd_sm != 0;
-    g.rowptr = m.rowptr;
-    g.col = m.col;
-    g.nrm = m.nrm;
-    g.ell = reinterpret_cast<const int4*>(m.ell);
-    g.node_off = m.node_off;
-    g.tail_cnt = m.tail_cnt;
-    g.tail_pool = reinterpret_cast<const int2*>(m.tail_pool);
-    g.tail_rec = reinterpret_cast<const int4*>(m.tail_rec);
-    g.B = m.B;
-    g.K = K;
-    g.nsa = Ca / W;
-    g.Ncap = Ncap;
-    g.a = ClipPart{za, Pa, Ca, lda ? lda : Ca};
-    g.b = ClipPart{zb, Pb, Cb, ldb ? ldb : Cb};
-    const int grid = m.B * ((Ca + Cb) / W);
+    const int C = g.a.C + g.b.C;
+    const int W = width ? width : (g.B * (C / 2) <= (bwd ? qt_num_cus() / 2 : qt_num_cus()) ? 2 : 4);
+    g.node_off = node_off;
+    g.tail_cnt = tail_cnt;
+    g.tail_pool = reinterpret_cast<const int2*>(tail_pool);
+    g.tail_rec = reinterpret_cast<const int4*>(tail_rec);
+    g.nsa = g.a.C / W;
+    const int grid = g.B * (C / W);
     if (bwd && W == 2)
         hipLaunchKernelGGL((k_cheb_clip<true, 2>), dim3(grid), dim3(CL_T), 0, (hipStream_t)stream, g);
     else if (bwd)
@@ -618,12 +577,27 @@ static int clip_launch(bool bwd, const ClipMesh& m, int Ncap, int K, int Ca, con
         hipLaunchKernelGGL((k_cheb_clip<false, 2>), dim3(grid), dim3(CL_T), 0, (hipStream_t)stream, g);
     else
         hipLaunchKernelGGL((k_cheb_clip<false, 4>), dim3(grid), dim3(CL_T), 0, (hipStream_t)stream, g);
-    return 0;
 }
 
 #define CLIP_MESH_ARGS_OK                                                                                                        \
     QT_ARG(rowptr && col && nrm && ell && node_off && tail_cnt && tail_pool && tail_rec && B > 0 && K >= 2,                     \
            "bad arguments (the ELL side array, the tail pool and the tail-row records of qt_edges_norm are required)")
+
+// The operand, alignment and 32-bit-offset checks of the four entry points: the text of the first that fails, or NULL.  fwd: the
+// T_0 sources za / zb with their row strides exist (the backward passes NULL and 0); tile: the slice count is bounded; mesh16:
+// the mesh arrays the kernel reads as 16-byte vectors, or-ed.
+static const char* cheb_operands_bad(bool fwd, bool tile, int N, int K, int Ca, const float* za, int lda, const float* Pa, int Cb,
+                                     const float* zb, int ldb, const float* Pb, uintptr_t mesh16) {
+    if (!((!fwd || za) && Pa && Ca > 0 && Ca % 4 == 0 && Cb >= 0 && Cb % 4 == 0 && (Cb == 0 || ((!fwd || zb) && Pb)))) return "bad operands";
+    if (tile && (Ca + Cb) / 4 > QT_TILE_SLICES) return "at most QT_TILE_SLICES 4-channel slices per launch";
+    if ((lda | ldb) % 4 != 0) return "row strides must be multiples of 4";
+    if ((((uintptr_t)za | (uintptr_t)Pa | (uintptr_t)zb | (uintptr_t)Pb | mesh16) & 15) != 0) return "operands must be 16-byte aligned";
+    if (!((int64_t)K * N * max(Ca, Cb) < ((int64_t)1 << 31) && (!fwd || (int64_t)N * max(max(lda, ldb), 4) < ((int64_t)1 << 31))))
+        return "planes too large for 32-bit offsets";
+    return nullptr;
+}
+#define CLIP_MESH16 ((uintptr_t)ell | (uintptr_t)tail_pool | (uintptr_t)tail_rec)
+#define TILE_MESH16 ((uintptr_t)ell | (uintptr_t)tile_pool | (uintptr_t)tile_rec | (uintptr_t)tile_brec | (uintptr_t)tile_bpool)
 
 extern "C" int qt_cheb_clip_fwd(const int32_t* rowptr, const int32_t* col, const float* nrm, const int32_t* ell,
                                 const int32_t* node_off, const int32_t* tail_cnt, const int32_t* tail_pool,
@@ -631,13 +605,11 @@ extern "C" int qt_cheb_clip_fwd(const int32_t* rowptr, const int32_t* col, const
                                 const float* zb, int ldb, float* Tb, int width, void* stream) {
     CLIP_MESH_ARGS_OK;
     QT_ARG(width == 0 || width == 2 || width == 4, "width must be 0 (automatic), 2 or 4");
-    QT_ARG(za && Ta && Ca > 0 && Ca % 4 == 0 && Cb >= 0 && Cb % 4 == 0 && (Cb == 0 || (zb && Tb)), "bad operands");
-    QT_ARG((lda | ldb) % 4 == 0, "row strides must be multiples of 4");
-    QT_ARG((((uintptr_t)za | (uintptr_t)Ta | (uintptr_t)zb | (uintptr_t)Tb | (uintptr_t)ell | (uintptr_t)tail_pool | (uintptr_t)tail_rec) & 15) == 0, "operands must be 16-byte aligned");
-    QT_ARG((int64_t)K * N * max(Ca, Cb) < ((int64_t)1 << 31) && (int64_t)N * max(max(lda, ldb), 4) < ((int64_t)1 << 31), "planes too large for 32-bit offsets");
+    const char* bad = cheb_operands_bad(true, false, N, K, Ca, za, lda, Ta, Cb, zb, ldb, Tb, CLIP_MESH16);
+    QT_ARG(!bad, bad);
     if (N <= 0) return QT_OK;
-    const ClipMesh m = {rowptr, col, nrm, ell, node_off, tail_cnt, tail_pool, tail_rec, B};
-    clip_launch(false, m, N, K, Ca, za, lda, Ta, Cb, zb, ldb, Tb, stream, width);
+    clip_launch(false, clip_args(rowptr, col, nrm, ell, B, N, K, Ca, za, lda, Ta, Cb, zb, ldb, Tb, 0), node_off, tail_cnt, tail_pool,
+                tail_rec, width, stream);
     QT_LAUNCHED();
     return QT_OK;
 }
@@ -648,72 +620,47 @@ extern "C" int qt_cheb_clip_bwd(const int32_t* rowptr, const int32_t* col, const
                                 int width, void* stream) {
     CLIP_MESH_ARGS_OK;
     QT_ARG(width == 0 || width == 2 || width == 4, "width must be 0 (automatic), 2 or 4");
-    QT_ARG(Ga && Ca > 0 && Ca % 4 == 0 && Cb >= 0 && Cb % 4 == 0 && (Cb == 0 || Gb), "bad operands");
-    QT_ARG((((uintptr_t)Ga | (uintptr_t)Gb | (uintptr_t)ell | (uintptr_t)tail_pool | (uintptr_t)tail_rec) & 15) == 0, "operands must be 16-byte aligned");
-    QT_ARG((int64_t)K * N * max(Ca, Cb) < ((int64_t)1 << 31), "planes too large for 32-bit offsets");
+    const char* bad = cheb_operands_bad(false, false, N, K, Ca, nullptr, 0, Ga, Cb, nullptr, 0, Gb, CLIP_MESH16);
+    QT_ARG(!bad, bad);
     if (N <= 0) return QT_OK;
-    const ClipMesh m = {rowptr, col, nrm, ell, node_off, tail_cnt, tail_pool, tail_rec, B};
-    clip_launch(true, m, N, K, Ca, nullptr, 0, Ga, Cb, nullptr, 0, Gb, stream, width, planes_sm);
+    clip_launch(true, clip_args(rowptr, col, nrm, ell, B, N, K, Ca, nullptr, 0, Ga, Cb, nullptr, 0, Gb, planes_sm), node_off, tail_cnt,
+                tail_pool, tail_rec, width, stream);
     QT_LAUNCHED();
     return QT_OK;
 }
 
 // ---- frames of several 64 x 64 base cells: the same recurrences with one workgroup per (clip, TILE, slice) and a halo exchange
 // between the tiles of a clip after every hop (k_cheb_clip<.., TILE = true>)
-struct TileMesh {
-    const int32_t *rowptr, *col;
-    const float* nrm;
-    const int32_t *ell, *tile_off, *tile_cnt, *tile_pool, *tile_rec, *tile_brec, *tile_bpool, *tile_halo, *brec_addr;
-    int32_t *xbuf, *sync, *err;
-    int B, T, nbj;
-};
-
-static int tile_launch(bool bwd, const TileMesh& m, int Ncap, int K, int Ca, const float* za, int lda, float* Pa, int Cb,
-                       const float* zb, int ldb, float* Pb, void* stream, int bwd_sm) {
-    ClipArgs g;
-    g.bwd_sm = bwd_sm != 0;
-    g.rowptr = m.rowptr;
-    g.col = m.col;
-    g.nrm = m.nrm;
-    g.ell = reinterpret_cast<const int4*>(m.ell);
-    g.node_off = nullptr;
-    g.tail_cnt = nullptr;
-    g.tail_pool = nullptr;
-    g.tail_rec = nullptr;
-    g.B = m.B;
-    g.K = K;
-    g.nsa = Ca / 4;
-    g.Ncap = Ncap;
-    g.a = ClipPart{za, Pa, Ca, lda ? lda : Ca};
-    g.b = ClipPart{zb, Pb, Cb, ldb ? ldb : Cb};
-    g.tile_off = m.tile_off;
-    g.tile_cnt = m.tile_cnt;
-    g.tile_pool = reinterpret_cast<const int2*>(m.tile_pool);
-    g.tile_rec = reinterpret_cast<const int4*>(m.tile_rec);
-    g.tile_brec = reinterpret_cast<const int4*>(m.tile_brec);
-    g.tile_bpool = reinterpret_cast<const int2*>(m.tile_bpool);
-    g.tile_halo = m.tile_halo;
-    g.brec_addr = m.brec_addr;
-    g.xbuf = reinterpret_cast<unsigned long long*>(m.xbuf);
-    g.sync = reinterpret_cast<unsigned*>(m.sync);
-    g.err = reinterpret_cast<unsigned*>(m.err);
-    g.T = m.T;
-    g.nbj = m.nbj;
+static void tile_launch(bool bwd, ClipArgs g, const int32_t* tile_off, const int32_t* tile_cnt, const int32_t* tile_pool,
+                        const int32_t* tile_rec, const int32_t* tile_brec, const int32_t* tile_bpool, const int32_t* tile_halo,
+                        const int32_t* brec_addr, int32_t* xbuf, int32_t* sync, int32_t* err, int T, void* stream) {
+    g.tile_off = tile_off;
+    g.tile_cnt = tile_cnt;
+    g.tile_pool = reinterpret_cast<const int2*>(tile_pool);
+    g.tile_rec = reinterpret_cast<const int4*>(tile_rec);
+    g.tile_brec = reinterpret_cast<const int4*>(tile_brec);
+    g.tile_bpool = reinterpret_cast<const int2*>(tile_bpool);
+    g.tile_halo = tile_halo;
+    g.brec_addr = brec_addr;
+    g.xbuf = reinterpret_cast<unsigned long long*>(xbuf);
+    g.sync = reinterpret_cast<unsigned*>(sync);
+    g.err = reinterpret_cast<unsigned*>(err);
+    g.T = T;
+    g.nsa = g.a.C / 4;
     // One launch holds whole (clip, slice) groups and at most one workgroup per CU (160 KB of LDS each): all of its workgroups
     // are resident together, so a workgroup that waits for a neighbour tile never waits for one that has not been dispatched.
-    const int S = (Ca + Cb) / 4;
-    const int per = qt_num_cus() / (m.B * m.T);    // slices per launch (>= 1: the entry points refuse B T > CUs)
+    const int S = (g.a.C + g.b.C) / 4;
+    const int per = qt_num_cus() / (g.B * T);    // slices per launch (>= 1: the entry points refuse B T > CUs)
     for (int s0 = 0; s0 < S; s0 += per) {
         g.s0 = s0;
         g.ns = S - s0 < per ? S - s0 : per;
-        const int groups = m.B * g.ns;
-        const int grid = ((groups + 7) / 8) * 8 * m.T;
+        const int groups = g.B * g.ns;
+        const int grid = ((groups + 7) / 8) * 8 * T;
         if (bwd)
             hipLaunchKernelGGL((k_cheb_clip<true, 4, true>), dim3(grid), dim3(CL_T), 0, (hipStream_t)stream, g);
         else
             hipLaunchKernelGGL((k_cheb_clip<false, 4, true>), dim3(grid), dim3(CL_T), 0, (hipStream_t)stream, g);
     }
-    return 0;
 }
 
 #define TILE_MESH_ARGS_OK                                                                                                         \
@@ -747,16 +694,11 @@ extern "C" int qt_cheb_tile_fwd(const int32_t* rowptr, const int32_t* col, const
                                 int B, int T, int nbj, int N, int K, int Ca, const float* za, int lda, float* Ta, int Cb,
                                 const float* zb, int ldb, float* Tb, void* stream) {
     TILE_MESH_ARGS_OK;
-    QT_ARG(za && Ta && Ca > 0 && Ca % 4 == 0 && Cb >= 0 && Cb % 4 == 0 && (Cb == 0 || (zb && Tb)), "bad operands");
-    QT_ARG((Ca + Cb) / 4 <= QT_TILE_SLICES, "at most QT_TILE_SLICES 4-channel slices per launch");
-    QT_ARG((lda | ldb) % 4 == 0, "row strides must be multiples of 4");
-    QT_ARG((((uintptr_t)za | (uintptr_t)Ta | (uintptr_t)zb | (uintptr_t)Tb | (uintptr_t)ell | (uintptr_t)tile_pool | (uintptr_t)tile_rec |
-             (uintptr_t)tile_brec | (uintptr_t)tile_bpool) & 15) == 0, "operands must be 16-byte aligned");
-    QT_ARG((int64_t)K * N * max(Ca, Cb) < ((int64_t)1 << 31) && (int64_t)N * max(max(lda, ldb), 4) < ((int64_t)1 << 31),
-           "planes too large for 32-bit offsets");
+    const char* bad = cheb_operands_bad(true, true, N, K, Ca, za, lda, Ta, Cb, zb, ldb, Tb, TILE_MESH16);
+    QT_ARG(!bad, bad);
     if (N <= 0) return QT_OK;
-    const TileMesh m = {rowptr, col, nrm, ell, tile_off, tile_cnt, tile_pool, tile_rec, tile_brec, tile_bpool, tile_halo, brec_addr, xbuf, sync, err, B, T, nbj};
-    tile_launch(false, m, N, K, Ca, za, lda, Ta, Cb, zb, ldb, Tb, stream, 0);
+    tile_launch(false, clip_args(rowptr, col, nrm, ell, B, N, K, Ca, za, lda, Ta, Cb, zb, ldb, Tb, 0), tile_off, tile_cnt, tile_pool,
+                tile_rec, tile_brec, tile_bpool, tile_halo, brec_addr, xbuf, sync, err, T, stream);
     QT_LAUNCHED();
     return QT_OK;
 }
@@ -768,14 +710,11 @@ extern "C" int qt_cheb_tile_bwd(const int32_t* rowptr, const int32_t* col, const
                                 int B, int T, int nbj, int N, int K, int Ca, float* Ga, int Cb, float* Gb, int planes_sm,
                                 void* stream) {
     TILE_MESH_ARGS_OK;
-    QT_ARG(Ga && Ca > 0 && Ca % 4 == 0 && Cb >= 0 && Cb % 4 == 0 && (Cb == 0 || Gb), "bad operands");
-    QT_ARG((Ca + Cb) / 4 <= QT_TILE_SLICES, "at most QT_TILE_SLICES 4-channel slices per launch");
-    QT_ARG((((uintptr_t)Ga | (uintptr_t)Gb | (uintptr_t)ell | (uintptr_t)tile_pool | (uintptr_t)tile_rec | (uintptr_t)tile_brec |
-             (uintptr_t)tile_bpool) & 15) == 0, "operands must be 16-byte aligned");
-    QT_ARG((int64_t)K * N * max(Ca, Cb) < ((int64_t)1 << 31), "planes too large for 32-bit offsets");
+    const char* bad = cheb_operands_bad(false, true, N, K, Ca, nullptr, 0, Ga, Cb, nullptr, 0, Gb, TILE_MESH16);
+    QT_ARG(!bad, bad);
     if (N <= 0) return QT_OK;
-    const TileMesh m = {rowptr, col, nrm, ell, tile_off, tile_cnt, tile_pool, tile_rec, tile_brec, tile_bpool, tile_halo, brec_addr, xbuf, sync, err, B, T, nbj};
-    tile_launch(true, m, N, K, Ca, nullptr, 0, Ga, Cb, nullptr, 0, Gb, stream, planes_sm);
+    tile_launch(true, clip_args(rowptr, col, nrm, ell, B, N, K, Ca, nullptr, 0, Ga, Cb, nullptr, 0, Gb, planes_sm), tile_off, tile_cnt,
+                tile_pool, tile_rec, tile_brec, tile_bpool, tile_halo, brec_addr, xbuf, sync, err, T, stream);
     QT_LAUNCHED();
     return QT_OK;
 }

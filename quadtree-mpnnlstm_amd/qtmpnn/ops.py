@@ -380,33 +380,32 @@ def _tile_args(mesh):
             ptr(tl['err']), mesh.B, tl['T'], tl['nbj'])
 
 
+def _clip_args(mesh):
+    return (ptr(mesh.rowptr), ptr(mesh.col), ptr(mesh.nrm), ptr(mesh.ell), ptr(mesh.node_off), ptr(mesh.tail_cnt), ptr(mesh.tail_pool),
+            ptr(mesh.tail_rec), mesh.B)
+
+
+def _cheb_resident(mesh, dev, way, operands, width):
+    """qt_cheb_tile_<way> on a frame of several base cells, else qt_cheb_clip_<way> (width: 0 = the library's choice; 2 / 4 pin it)."""
+    if getattr(mesh, 'tiles', None) is not None and mesh.n * mesh.m > _CLIP_ROWS_OF():
+        _mesh._TILE_USED.add(str(dev))
+        _lib.call('qt_cheb_tile_' + way, *_tile_args(mesh), *operands)
+    else:
+        _lib.call('qt_cheb_clip_' + way, *_clip_args(mesh), *operands, int(width))
+
+
 def clip_planes(mesh, Zs, TZs, K, width=0):
     """TZs[i] <- T_1 .. T_{K-1} of the recurrence on the parts Zs, all hops in ONE launch (qt_cheb_clip_fwd).  The planes are
-    written SLICE-major: TZs[i] (allocated (K - 1, N, C_i)) then holds (K - 1, C_i / 4, N, 4).  width: channels per workgroup
-    (0 = the library's choice; 2 / 4 pin it: diagnostics and parity tests)."""
-    two = len(Zs) > 1
-    if getattr(mesh, 'tiles', None) is not None and mesh.n * mesh.m > _CLIP_ROWS_OF():
-        _mesh._TILE_USED.add(str(Zs[0].device))
-        _lib.call('qt_cheb_tile_fwd', *_tile_args(mesh), Zs[0].shape[0], K, Zs[0].shape[1], ptr(Zs[0]), _ld(Zs[0]), ptr(TZs[0]),
-                  Zs[1].shape[1] if two else 0, ptr(Zs[1]) if two else None, _ld(Zs[1]) if two else 0, ptr(TZs[1]) if two else None)
-        return
-    _lib.call('qt_cheb_clip_fwd', ptr(mesh.rowptr), ptr(mesh.col), ptr(mesh.nrm), ptr(mesh.ell), ptr(mesh.node_off),
-              ptr(mesh.tail_cnt), ptr(mesh.tail_pool), ptr(mesh.tail_rec), mesh.B, Zs[0].shape[0], K, Zs[0].shape[1], ptr(Zs[0]), _ld(Zs[0]), ptr(TZs[0]),
-              Zs[1].shape[1] if two else 0, ptr(Zs[1]) if two else None, _ld(Zs[1]) if two else 0, ptr(TZs[1]) if two else None, int(width))
+    written SLICE-major: TZs[i] (allocated (K - 1, N, C_i)) then holds (K - 1, C_i / 4, N, 4)."""
+    b = [Zs[1].shape[1], ptr(Zs[1]), _ld(Zs[1]), ptr(TZs[1])] if len(Zs) > 1 else [0, None, 0, None]
+    _cheb_resident(mesh, Zs[0].device, 'fwd', [Zs[0].shape[0], K, Zs[0].shape[1], ptr(Zs[0]), _ld(Zs[0]), ptr(TZs[0])] + b, width)
 
 
 def clip_clenshaw(mesh, Gs, K, sm=0, width=0):
     """Gs[i] (K, N, C_i) gradient planes: plane 0 <- A_0 + L^ b_1 - b_2 (Clenshaw), all hops in ONE launch (qt_cheb_clip_bwd).
     sm: planes 1 .. K-1 are stored slice-major (written so by the data-gradient kernels on request)."""
-    two = len(Gs) > 1
-    if getattr(mesh, 'tiles', None) is not None and mesh.n * mesh.m > _CLIP_ROWS_OF():
-        _mesh._TILE_USED.add(str(Gs[0].device))
-        _lib.call('qt_cheb_tile_bwd', *_tile_args(mesh), Gs[0].shape[1], K, Gs[0].shape[2], ptr(Gs[0]),
-                  Gs[1].shape[2] if two else 0, ptr(Gs[1]) if two else None, int(sm))
-        return
-    _lib.call('qt_cheb_clip_bwd', ptr(mesh.rowptr), ptr(mesh.col), ptr(mesh.nrm), ptr(mesh.ell), ptr(mesh.node_off),
-              ptr(mesh.tail_cnt), ptr(mesh.tail_pool), ptr(mesh.tail_rec), mesh.B, Gs[0].shape[1], K, Gs[0].shape[2], ptr(Gs[0]),
-              Gs[1].shape[2] if two else 0, ptr(Gs[1]) if two else None, int(sm), int(width))
+    b = [Gs[1].shape[2], ptr(Gs[1])] if len(Gs) > 1 else [0, None]
+    _cheb_resident(mesh, Gs[0].device, 'bwd', [Gs[0].shape[1], K, Gs[0].shape[2], ptr(Gs[0])] + b + [int(sm)], width)
 
 
 def _cheb_planes(Zs, mesh, K):
