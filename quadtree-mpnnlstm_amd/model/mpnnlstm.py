@@ -27,6 +27,7 @@ from qtmpnn.baselines import (check_references, default_references, forecast_sou
                               reference_fields, reference_launches, spec_name)
 from qtmpnn.dist import all_reduce_sum, allreduce_gradients
 from qtmpnn.flat import flat_params, name_table
+from qtmpnn.horizon import first_steps, resolve_schedule
 from qtmpnn._lib import on_device
 from qtmpnn.mesh import check_tile_errors, host_mask
 
@@ -104,6 +105,19 @@ class LossWeights:
             raise ValueError(f'lead_weights: the weights of the truncated chunk of steps [{steps.start}, {steps.stop}) sum to 0')
         c.lam = None if self.lam is None else self.lam[steps.start:steps.stop]
         return c
+
+
+def horizon_weights(lw, k):
+    """The LossWeights `lw` (None: unweighted, and None comes back) cut to a horizon of k steps: the same pixel weights, the first
+    k lead weights and the divisor those entries give (LossWeights.chunk) -- what train(horizon=) trains epoch by epoch with.
+    Refused under `horizon`, on the host: k above the entries there are, and first entries that sum to 0."""
+    if lw is None or k == lw.T:
+        return lw
+    if k > lw.T:
+        raise ValueError(f'horizon: lead_weights has {lw.T} entries (the built output steps), horizon={k} needs {k}')
+    if not float(lw.lam_host[:k].astype(np.float64).sum()) > 0:
+        raise ValueError(f'horizon: the first {k} lead_weights sum to 0: horizon={k} would train on no step')
+    return lw.chunk(range(k))
 
 
 def loss_weights_of(weights, lead_weights, shape, T_out, mask=None, binary=False):
@@ -779,6 +793,23 @@ def takes_ema(method):
     return wrapper
 
 
+def takes_horizon(method):
+    """Gives train() the keyword `horizon=None` (a horizon curriculum: qtmpnn.horizon.resolve_schedule has the three forms).
+    train()'s parameter list is read by signature tests and stays as it is (takes_references, takes_ema); the keyword is taken
+    here and held in self._horizon_asked while the call runs.  train() resolves and checks the whole schedule of its epochs
+    before it makes the optimiser and before any launch."""
+    import functools
+
+    @functools.wraps(method)
+    def wrapper(self, *args, horizon=None, **keywords):
+        previous, self._horizon_asked = self._horizon_asked, horizon
+        try:
+            return method(self, *args, **keywords)
+        finally:
+            self._horizon_asked = previous
+    return wrapper
+
+
 class NextFramePredictor(ABC):
     """The abstract trainer facade of the reference (model/mpnnlstm.py:34-79; moving_mnist_example.ipynb cell 2 imports it):
     it holds the decomposition settings and names the three methods a predictor offers.  `thresh` is kept as given here;
@@ -809,7 +840,8 @@ class NextFramePredictorS2S(NextFramePredictor):
                  binary=False, debug=False, model_kwargs={}):
         super().__init__(thresh=thresh, experiment_name=experiment_name, decompose=decompose, input_features=input_features,
                          transform_func=transform_func, condition=condition, device=device)
-        self.input_timesteps, self.output_timesteps = input_timesteps, output_timesteps
+        # (output_timesteps itself is the horizon in force, a property: set_horizon; this keeps what the predictor was built with)
+        self.input_timesteps, self.built_output_timesteps = input_timesteps, output_timesteps
         self.binary, self.debug = binary, debug
         self.thresh = thresh if decompose else -np.inf
         # As in the reference (:123-133) the Seq2Seq gets the RAW `thresh` (decompose=False changes self.thresh only) and
@@ -820,7 +852,8 @@ class NextFramePredictorS2S(NextFramePredictor):
                              **model_kwargs).to(device)
         self.training_initiated = False
         self.process_group = None
-        self._output_days = {}          # launch date -> its output days' indices into the daily normals (get_climatology_array)
+        self._output_days = {}          # (launch date, steps) -> the output days' indices into the normals (get_climatology_array)
+        self._horizon_asked = None      # train()'s `horizon` while it runs (takes_horizon)
         self._launch_days = {}          # launch date -> its launch-state day's index (get_launch_climatology)
         self._asked = (None, None)      # the `references` / `launch_climatology` of the call that runs (takes_references)
         # what train()'s validation keywords leave (patience, restore_best, keep_best, monitor): see train()
@@ -946,6 +979,52 @@ class NextFramePredictorS2S(NextFramePredictor):
         finally:
             self.model.set_recompute(previous)
 
+    # -- rollout horizon (beyond the reference): the setting lives on the Seq2Seq, where the rollout is ---------------------------
+    @property
+    def output_timesteps(self):
+        """The output steps every method rolls out: the horizon in force (set_horizon), else built_output_timesteps."""
+        return self.model.horizon
+
+    def set_horizon(self, k):
+        """Roll out k output steps from now on; None: the steps the predictor was built with (built_output_timesteps) again.
+        The weights do not depend on the step count, so while a horizon k is in force EVERY METHOD IS THE SAME METHOD OF A
+        PREDICTOR BUILT WITH output_timesteps=k THAT HOLDS THE SAME PARAMETERS, bit for bit: forward_loss, train_step,
+        accumulated_step, truncated_backward, make_graphed_step (accumulate=k too) and both recompute modes; predict, verify,
+        every product and its make_graphed_* maker, sensitivity and attention_weights.  `output_timesteps` reads k then.
+        k at or below the steps y holds: the first k steps of y are read in place, as a view (qtmpnn.horizon.first_steps; the
+        kernels take the clip stride).  k above the built value is allowed: the loader or the caller then supplies y with at
+        least k steps (a ClipBank made with output_timesteps=k); what reads no y (predict) needs none.  get_climatology_array
+        gives k days; lead_weights must have length k; event_dates(persist=), sensitivity(leads=) and the references are held to
+        k.  A y or a hand-made concat_layers with fewer than k steps is refused (ValueError, `horizon`) before any launch.
+        A CAPTURED STEP OR PRODUCT KEEPS THE HORIZON IT WAS CAPTURED UNDER, as it keeps its recompute mode; its replay takes y
+        with at least that many steps.  The horizon is no training state: checkpoints neither store nor restore it, and their
+        description keeps the built value.  It changes no weights, so it may be set inside averaged_weights().  Anything but
+        None or an integer >= 1 is refused by name (qtmpnn.horizon.check_horizon) before anything is launched."""
+        self.model.set_horizon(k)
+
+    @contextlib.contextmanager
+    def horizon(self, k):
+        """`with nfp.horizon(k):` -- set_horizon(k) for the block; the previous setting is back afterwards, also after an
+        exception.  Blocks nest: the inner one holds while it runs."""
+        previous = self.model.__dict__.get('_horizon')
+        self.set_horizon(k)
+        try:
+            yield self
+        finally:
+            self.model.set_horizon(previous)
+
+    def _first_steps(self, y, concat_layers=None, held=None):
+        """(y, concat_layers) held to the step count in force: the first k steps of each, as views.  While a horizon is set, fewer
+        than k steps are refused under `horizon`; with none set a short tensor goes on as it is, to the shape checks that were
+        there before.  held: the (k, whether a horizon was set) a capture was made under, `self._held()` then, in place of the
+        setting in force.  Host code: it comes before the launches of whatever calls it."""
+        k, strict = self._held() if held is None else held
+        return first_steps(y, k, 'y', strict), first_steps(concat_layers, k, 'concat_layers', strict)
+
+    def _held(self):
+        """(the step count in force, whether a horizon is set): what a capture keeps for its replays (_first_steps)."""
+        return self.output_timesteps, self.model.__dict__.get('_horizon') is not None
+
     # -- small helpers of the reference ---------------------------------------------
     def get_n_params(self):
         return get_n_params(self.model)
@@ -963,7 +1042,7 @@ class NextFramePredictorS2S(NextFramePredictor):
         m = self.model
         return {'convolution_type': m.convolution_type, 'hidden_size': int(m.hidden_size), 'n_layers': int(m.n_layers),
                 'n_conv_layers': int(m.encoder.rnns[0].n_conv_layers), 'input_features': int(self.input_features),
-                'input_timesteps': int(self.input_timesteps), 'output_timesteps': int(self.output_timesteps),
+                'input_timesteps': int(self.input_timesteps), 'output_timesteps': int(self.built_output_timesteps),
                 'binary': bool(self.binary), 'parameters': [[name, list(shape)] for name, _, shape in name_table(m)]}
 
     def save_checkpoint(self, path):
@@ -1165,6 +1244,7 @@ class NextFramePredictorS2S(NextFramePredictor):
         loss_weights / lead_weights / pos_weight (the positive-class weight) selects masked_bce, which is always fused."""
         self._check_fused(fused)
         check_concat_clips(x, concat_layers)
+        y, concat_layers = self._first_steps(y, concat_layers)
         lw = self._loss_weights(x, mask, loss_weights, lead_weights, pos_weight)
         y_hat, meshes = self.model(x, y, concat_layers, teacher_forcing_ratio=0, mask=mask,
                                    high_interest_region=high_interest_region, graph_structure=graph_structure)
@@ -1176,16 +1256,26 @@ class NextFramePredictorS2S(NextFramePredictor):
         if fused and not self.binary:
             raise ValueError('fused: fused=True selects the fused binary cross-entropy and needs a binary=True predictor')
 
-    def _loss_weights(self, x, mask, loss_weights, lead_weights, pos_weight=None, shape=None):
+    def _loss_weights(self, x, mask, loss_weights, lead_weights, pos_weight=None, shape=None, steps=None):
         """The checked, uploaded weights of this predictor's loss for batches shaped like x, or of frames of `shape` (None:
-        unweighted).  A binary=True predictor takes pos_weight beside them (masked_bce); any other refuses it by name."""
+        unweighted).  A binary=True predictor takes pos_weight beside them (masked_bce); any other refuses it by name.
+        steps: the length lead_weights must have (None: the horizon in force; train(horizon=) gives the built step count and
+        cuts the weights to every epoch's horizon, _horizon_weights)."""
         shape = tuple(x.shape[-3:-1]) if shape is None else tuple(shape)
+        if (steps is not None or self._held()[1]) and (isinstance(lead_weights, (list, tuple))
+                                                       or getattr(lead_weights, 'ndim', None) == 1):
+            want = self.output_timesteps if steps is None else steps
+            if len(lead_weights) != want:       # (said under `horizon` while one is at work; LossWeights checks everything else)
+                raise ValueError(f'horizon: lead_weights has {len(lead_weights)} entries, ' + (
+                    f'horizon={want} needs {want}' if steps is None else
+                    f'train(horizon=) takes the built length {want} and cuts it to the first entries of every epoch\'s horizon'))
+        steps = self.output_timesteps if steps is None else steps
         if self.binary:
-            lw = bce_weights_of(loss_weights, lead_weights, pos_weight, shape, self.output_timesteps, mask)
+            lw = bce_weights_of(loss_weights, lead_weights, pos_weight, shape, steps, mask)
         elif pos_weight is not None:
             raise ValueError('pos_weight: the positive-class weight belongs to the binary cross-entropy and needs a binary=True predictor')
         else:
-            lw = loss_weights_of(loss_weights, lead_weights, shape, self.output_timesteps, mask)
+            lw = loss_weights_of(loss_weights, lead_weights, shape, steps, mask)
         return lw if lw is None else lw.to(self.device if self.device is not None else ('cpu' if x is None else x.device))
 
     def _weighted_loss(self, y_hat, meshes, y, mask, lw):
@@ -1264,6 +1354,7 @@ class NextFramePredictorS2S(NextFramePredictor):
         cross-entropy of masked_mse, the loss a captured step runs.  On a binary=True predictor the weights, and pos_weight, the
         weight of the positive class, select the weighted binary cross-entropy (masked_bce)."""
         check_concat_clips(x, concat_layers)
+        y, concat_layers = self._first_steps(y, concat_layers)
         lw = self._loss_weights(x, mask, loss_weights, lead_weights, pos_weight)
         self.zero_grad()
         loss = self.forward_loss(x, y, concat_layers, mask, high_interest_region, graph_structure, fused=fused, loss_weights=lw)
@@ -1348,6 +1439,7 @@ class NextFramePredictorS2S(NextFramePredictor):
         self._check_fused(fused)
         clips = [1 if x.dim() == 4 else x.shape[0] for x, _, _ in items]
         micro_weights(clips)                # (refuses a micro-batch without clips)
+        items = [(x, *self._first_steps(y, c)) for x, y, c in items]
         lw = self._loss_weights(items[0][0], mask, loss_weights, lead_weights, pos_weight)
         return self._accumulated_backward(items, clips, lambda x, y, c: self.forward_loss(
             x, y, c, mask, high_interest_region, graph_structure, fused=fused, loss_weights=lw))
@@ -1368,6 +1460,7 @@ class NextFramePredictorS2S(NextFramePredictor):
         chunk's slice is checked before the first one runs).  pos_weight (binary=True predictors): as in train_step."""
         losses, step = [], 0
         check_concat_clips(x, concat_layers)
+        y, concat_layers = self._first_steps(y, concat_layers)
         if y.dim() == 4:
             y = y.unsqueeze(0)
         lw = self._loss_weights(x, mask, loss_weights, lead_weights, pos_weight)
@@ -1419,6 +1512,8 @@ class NextFramePredictorS2S(NextFramePredictor):
             return self._graphed_accumulation([(x, y, concat_layers)], accumulate, mask, high_interest_region, max_norm, warmup,
                                               graph_structure, force_multi, pos_weight, loss_weights, lead_weights)
         check_concat_clips(x, concat_layers)
+        held = self._held()
+        y, concat_layers = self._first_steps(y, concat_layers)
         multi, world = self._capture_setup(force_multi)
         batch = StaticBatch(x, y, concat_layers)
         lw = self._loss_weights(x, mask, loss_weights, lead_weights, pos_weight)
@@ -1461,7 +1556,7 @@ class NextFramePredictorS2S(NextFramePredictor):
         @on_device(lambda *a, **k: self.device)
         def step(x, y, concat_layers=None):
             self._ema_guard(True, ema)
-            batch.load(x, y, concat_layers)
+            batch.load(x, *self._first_steps(y, concat_layers, held))      # (the horizon of the capture, whatever is set now)
             graph.replay()
             if multi:
                 all_reduce_sum(flat, self.process_group)
@@ -1470,7 +1565,7 @@ class NextFramePredictorS2S(NextFramePredictor):
                 ema.advance()
             watch.advance()
             return static_loss
-        step.check, step.loss_weights, step.ema = watch.check, lw, ema
+        step.check, step.loss_weights, step.ema, step.horizon = watch.check, lw, ema, held[0]
         return step
 
     def _capture_setup(self, force_multi):
@@ -1506,7 +1601,8 @@ class NextFramePredictorS2S(NextFramePredictor):
         micro-batch's activations are ever live.  Stream ordering under torch.distributed as in make_graphed_step
         (warm_then_sync): the warm-up and its collectives on the caller's stream, only the captures on the side stream."""
         k = check_accumulate(accumulate)
-        items = checked_batches('make_graphed_step', batches)
+        held = self._held()
+        items = [(x, *self._first_steps(y, c)) for x, y, c in checked_batches('make_graphed_step', batches)]
         if len(items) > k or any(batch_shapes(item) != batch_shapes(items[0]) for item in items):
             raise ValueError(f'make_graphed_step: batches must be 1..{k} (accumulate) items of one shape, got {len(items)} of shapes '
                              f'{[batch_shapes(item) for item in items]}')
@@ -1550,7 +1646,7 @@ class NextFramePredictorS2S(NextFramePredictor):
         @on_device(lambda *a, **kw: self.device)
         def step(batches):
             self._ema_guard(True, ema)
-            group = checked_batches('step', batches)
+            group = [(x, *self._first_steps(y, c, held)) for x, y, c in checked_batches('step', batches)]
             j = len(group)
             if j > k or any(batch_shapes(item) != batch.shapes for item in group):
                 raise ValueError(f'step: batches must be 1..{k} items of the captured shape {batch.shapes}, got {j} of '
@@ -1570,6 +1666,7 @@ class NextFramePredictorS2S(NextFramePredictor):
             watch.advance(j)
             return static_loss
         step.check, step.loss_weights, step.accumulate, step.graphs, step.ema = watch.check, lw, k, (micro, update), ema
+        step.horizon = held[0]
         step.buffers = (*batch.tensors, acc, loss_acc, scale)       # (loss_acc is named nowhere else: StaticBatch)
         return step
 
@@ -1596,6 +1693,8 @@ class NextFramePredictorS2S(NextFramePredictor):
         climatology of the launch-state day, for the anomaly references among them -- it then follows concat in replay's
         arguments."""
         check_concat_clips(x, concat_layers)
+        held = self._held()
+        y, concat_layers = self._first_steps(y, concat_layers)
         self.model.static_shapes = True
         batch = StaticBatch(x, y, concat_layers, c0)
         sx, sy, sc, sc0 = batch.tensors + (None,) * (c0 is None)
@@ -1606,9 +1705,12 @@ class NextFramePredictorS2S(NextFramePredictor):
                 if not specs:
                     return reduce(y_hat, meshes, sx, sy, sc)
                 return reduce(y_hat, meshes, sx, sy, sc, reference_fields(sx, sc, sc0, specs))
+        # (a replay's y and concat are held to the horizon of the capture, whatever is set by then)
         if y is None:
-            return self._graphed_inference(body, lambda x, concat_layers=None, c0=None: batch.load(x, None, concat_layers, c0))
-        return self._graphed_inference(body, batch.load)
+            return self._graphed_inference(body, lambda x, concat_layers=None, c0=None: batch.load(
+                x, None, self._first_steps(None, concat_layers, held)[1], c0))
+        return self._graphed_inference(body, lambda x, y, concat_layers=None, c0=None: batch.load(
+            x, *self._first_steps(y, concat_layers, held), c0))
 
     def _graphed_one(self, who, reduce, x, y, concat_layers, **fwd):
         """_graphed_product of one product's reduce with the references the maker `who` was asked for (takes_references):
@@ -1768,6 +1870,7 @@ class NextFramePredictorS2S(NextFramePredictor):
 
     @on_device(lambda self, *a, **k: self.device)
     @takes_ema
+    @takes_horizon
     def train(self, loader_train, loader_test, climatology=None, n_epochs=200, lr=0.01, lr_decay=0.95, mask=None,
               high_interest_region=None, truncated_backprop=45, graph_structure=None, use_graph=False, accumulate=1,
               pos_weight=None, test_graph=False, patience=None, min_delta=0.0, restore_best=False, keep_best=None,
@@ -1830,7 +1933,20 @@ class NextFramePredictorS2S(NextFramePredictor):
         of the AVERAGED weights; restore_best snapshots the weights the test pass saw and writes them into the parameters after
         the last epoch; keep_best writes an ordinary checkpoint, live weights and average (format 2).  ema_eval=False only
         maintains the average.  Training itself never reads it: train_loss and the parameters after every epoch are those of the
-        run without `ema`, bit for bit.  ema_eval given without averaged weights is refused under its name."""
+        run without `ema`, bit for bit.  ema_eval given without averaged weights is refused under its name.
+        horizon=None (a keyword of this method through takes_horizon; beyond the reference): a horizon curriculum.  One integer,
+        a sequence with one entry per epoch whose last entry holds for every later epoch, or a callable epoch -> integer
+        (qtmpnn.horizon.resolve_schedule); the epoch index is len(self.train_loss) at the start of the epoch, the whole history,
+        so load_checkpoint + train(horizon=schedule) continues the schedule and ends in the bits of the run that was never
+        interrupted.  The training batches of epoch e run under set_horizon(k_e): k_e rollout steps forward and backward, the first
+        k_e steps of y, k_e climatology days.  lead_weights keeps the BUILT length and is cut to its first k_e entries, the divisor
+        being the one those entries give.  The single-chunk rule of use_graph / accumulate is judged per epoch.  THE TEST PASS
+        ALWAYS RUNS AT THE HORIZON IN FORCE WHEN train() WAS CALLED (the built one by default), so test_loss, patience, a Monitor,
+        restore_best and keep_best compare like with like across the epochs.  With use_graph=True the captured steps are kept
+        per (batch shape, horizon), and those of a horizon the schedule has left are dropped, so that their memory returns.
+        The whole schedule of this call's epochs is resolved and checked before the optimiser is made and before any launch;
+        an entry above the steps the training loader's y holds is refused on the first batch of its epoch, before its launch.
+        Every refusal names `horizon`.  With horizon=None the call is what it was, bit for bit."""
         from qtmpnn import validation
         image_shape = loader_train.dataset.image_shape
         accumulate = check_accumulate(accumulate)
@@ -1841,14 +1957,19 @@ class NextFramePredictorS2S(NextFramePredictor):
         on_loss = isinstance(monitor, str)
         selecting = patience is not None or restore_best or keep_best is not None or not on_loss
         truncate_ = truncated_backprop not in (0, None)
-        single_chunk = truncate_ and truncated_backprop >= self.output_timesteps
-        if accumulate > 1 and truncate_ and not single_chunk:
-            raise ValueError(f'accumulate: accumulate={accumulate} needs truncated_backprop=0 or >= the output steps, got '
-                             f'truncated_backprop={truncated_backprop} for {self.output_timesteps} steps (the truncated loop zeroes the '
-                             'gradients per chunk: only the last chunk of the last micro-batch would reach the optimiser)')
-        if use_graph and truncate_ and not single_chunk:
-            raise ValueError('use_graph=True needs truncated_backprop=0 or >= the output steps (the truncated loop re-runs the encoder '
-                             'per chunk)')
+        # the curriculum: the horizons of this call's epochs, by their index into the whole history (None: none asked for)
+        first_epoch = len(self.train_loss) if self.training_initiated else 0
+        schedule = None if self._horizon_asked is None else resolve_schedule(self._horizon_asked, first_epoch, n_epochs)
+        for k in dict.fromkeys([self.output_timesteps] if schedule is None else schedule):       # (every epoch's own horizon)
+            single_chunk = truncate_ and truncated_backprop >= k
+            at = '' if schedule is None else f' (horizon={k}, epoch {first_epoch + schedule.index(k)})'
+            if accumulate > 1 and truncate_ and not single_chunk:
+                raise ValueError(f'accumulate: accumulate={accumulate} needs truncated_backprop=0 or >= the output steps, got '
+                                 f'truncated_backprop={truncated_backprop} for {k} steps{at} (the truncated loop zeroes the '
+                                 'gradients per chunk: only the last chunk of the last micro-batch would reach the optimiser)')
+            if use_graph and truncate_ and not single_chunk:
+                raise ValueError('use_graph=True needs truncated_backprop=0 or >= the output steps (the truncated loop re-runs the '
+                                 f'encoder per chunk){at}')
         made = {}
         if not on_loss:
             made = make_products('train', monitor.products, ProductCall(
@@ -1863,8 +1984,15 @@ class NextFramePredictorS2S(NextFramePredictor):
         if mask is not None:
             mshape = tuple(host_mask(mask).shape) if not hasattr(mask, 'shape') else tuple(mask.shape)
             assert mshape == tuple(image_shape), f'Mask and image shapes do not match. Got {mshape} and {image_shape}'
-        truncate = truncate_ and not ((use_graph or accumulate > 1) and single_chunk)
-        lw = self._loss_weights(None, mask, loss_weights, lead_weights, pos_weight, shape=image_shape)
+        if schedule is None:
+            lw = self._loss_weights(None, mask, loss_weights, lead_weights, pos_weight, shape=image_shape)
+            weights_at = lambda k: lw
+        else:
+            # lead_weights has the built length and every pass takes its first entries (no lead_weights: ones, for every horizon)
+            full = self._loss_weights(None, mask, loss_weights, lead_weights, pos_weight, shape=image_shape, steps=max(
+                [self.built_output_timesteps] + ([] if lead_weights is not None else [self.output_timesteps, *schedule])))
+            cut = {k: horizon_weights(full, k) for k in dict.fromkeys([self.output_timesteps, *schedule])}
+            lw, weights_at = cut[self.output_timesteps], cut.__getitem__
         # the test pass: the loss of every batch (a capture holds the fused BCE, as a captured step does) and the monitor's products
         test_reduce = loss_product(mask, lw, self.binary, fused=test_graph and self.binary)
         test_graphs = {} if test_graph else None            # (the captures of the test pass, kept across the epochs)
@@ -1883,33 +2011,42 @@ class NextFramePredictorS2S(NextFramePredictor):
         batch_step = 0
         for epoch in range(n_epochs):
             running, steps = 0.0, 0
+            # the epoch's horizon (a curriculum's; else the one in force) holds for its training batches, not for its test pass
+            k_e = self.output_timesteps if schedule is None else schedule[epoch]
+            under = contextlib.nullcontext() if schedule is None else self.horizon(k_e)
+            lw_e = weights_at(k_e)
+            single_chunk = truncate_ and truncated_backprop >= k_e
+            truncate = truncate_ and not ((use_graph or accumulate > 1) and single_chunk)
+            for key in [key for key in graphed if key[1] != k_e]:
+                del graphed[key]            # (the captures of a horizon the schedule has left: their memory returns)
             # (the mode is the caller's, as in the reference: train() never calls model.train() / .eval(); ice_exp.py:181, 218 do)
-            for group in self._micro_groups(loader_train, climatology, accumulate):
-                x, y, concat = group[0]
-                if accumulate > 1:
-                    loss = self._group_step(group, accumulate, graphed if use_graph else None, mask, high_interest_region,
-                                            graph_structure, None if single_chunk else 10.0, lw)
-                elif truncate:
-                    loss = self.truncated_backward(x, y, concat, mask, high_interest_region, graph_structure,
-                                                   truncated_backprop, loss_weights=lw)[-1]
-                    # no gradient clipping in this branch (:311 is commented out)
-                    self._clip_and_step(self._grads_ready(self._world(), self.process_group), None)
-                elif use_graph:
-                    loss = self._first_sight(graphed, group[0], lambda: self.make_graphed_step(
-                        x, y, concat, mask=mask, high_interest_region=high_interest_region, warmup=1, graph_structure=graph_structure,
-                        max_norm=None if single_chunk else 10.0, loss_weights=lw), group[0])
-                else:
-                    loss = self.train_step(x, y, concat, mask, high_interest_region, graph_structure, loss_weights=lw)
-                    if self.debug:      # gradient norms of the two halves of the model (:259-276; clipped like the reference's)
-                        for part in ('encoder', 'decoder'):
-                            gs = [p.grad.detach().norm() for p in getattr(self.model, part).parameters() if p.grad is not None]
-                            self.writer.add_scalar(f'Grad/{part}/grad_norms', torch.stack(gs).norm().item(), batch_step)
-                value = loss.item()
-                for _ in group:             # (one micro-batch, unless accumulate > 1)
-                    self.writer.add_scalar('Loss/train', value, batch_step)
-                    running += value
-                    steps += 1
-                    batch_step += 1
+            with under:
+                for group in self._micro_groups(loader_train, climatology, accumulate):
+                    x, y, concat = group[0]
+                    if accumulate > 1:
+                        loss = self._group_step(group, accumulate, graphed if use_graph else None, mask, high_interest_region,
+                                                graph_structure, None if single_chunk else 10.0, lw_e)
+                    elif truncate:
+                        loss = self.truncated_backward(x, y, concat, mask, high_interest_region, graph_structure,
+                                                       truncated_backprop, loss_weights=lw_e)[-1]
+                        # no gradient clipping in this branch (:311 is commented out)
+                        self._clip_and_step(self._grads_ready(self._world(), self.process_group), None)
+                    elif use_graph:
+                        loss = self._first_sight(graphed, group[0], lambda: self.make_graphed_step(
+                            x, y, concat, mask=mask, high_interest_region=high_interest_region, warmup=1,
+                            graph_structure=graph_structure, max_norm=None if single_chunk else 10.0, loss_weights=lw_e), group[0])
+                    else:
+                        loss = self.train_step(x, y, concat, mask, high_interest_region, graph_structure, loss_weights=lw_e)
+                        if self.debug:      # gradient norms of the two halves of the model (:259-276; clipped like the reference's)
+                            for part in ('encoder', 'decoder'):
+                                gs = [p.grad.detach().norm() for p in getattr(self.model, part).parameters() if p.grad is not None]
+                                self.writer.add_scalar(f'Grad/{part}/grad_norms', torch.stack(gs).norm().item(), batch_step)
+                    value = loss.item()
+                    for _ in group:             # (one micro-batch, unless accumulate > 1)
+                        self.writer.add_scalar('Loss/train', value, batch_step)
+                        running += value
+                        steps += 1
+                        batch_step += 1
             # once per epoch: the graph-replayed steps and the test pass report their tile errors only at the end of the pass
             with averaging():
                 running_test, steps_test = self._test_pass(loader_test, climatology, test_reduce, made, test_graph, test_graphs,
@@ -2012,10 +2149,11 @@ class NextFramePredictorS2S(NextFramePredictor):
             group, accumulate, mask, high_interest_region, max_norm, 1, graph_structure, loss_weights=lw), (group,))
 
     def _first_sight(self, graphed, item, capture, args):
-        """train(use_graph=True): the step captured for batches shaped like `item` (batch_shapes), run on *args -> loss.  A shape
+        """train(use_graph=True): the step captured for batches shaped like `item` (batch_shapes) under the horizon in force -- the
+        key is the pair, a captured step keeps its horizon --, run on *args -> loss.  A key
         is captured on first sight by capture(), whose one warm-up step is that batch's own update, run eagerly just before the
         capture, and whose loss is returned; from then on the shape is replayed."""
-        key = batch_shapes(item)
+        key = (batch_shapes(item), self.output_timesteps)
         if key not in graphed:
             graphed[key] = capture()
             return self.last_warmup_loss
@@ -2030,14 +2168,15 @@ class NextFramePredictorS2S(NextFramePredictor):
         """Daily normals of the output days (mpnnlstm.py:389-400).  climatology: (Cy, 366, W, H).  launch_date (1,), as the
         reference's batch_size=1 loaders give it: (T_out, W, H, Cy), the reference's.  launch_date (B,) with B > 1 (beyond the
         reference, whose rule reads the first clip's date for a whole batch): (B, T_out, W, H, Cy), entry [c] what the call on
-        launch_date[c:c + 1] returns.  The day indices are model.utils.output_day_indices per clip, kept per distinct launch date
-        (an epoch meets the dates of the one before); they go up as ONE (B, T_out) int64 array and index the normals once."""
+        launch_date[c:c + 1] returns.  T_out is the horizon in force (set_horizon).  The day indices are
+        model.utils.output_day_indices per clip, kept per distinct (launch date, T_out) (an epoch meets the dates of the one
+        before); they go up as ONE (B, T_out) int64 array and index the normals once."""
         dates = launch_date.numpy()
         if dates.ndim != 1 or len(dates) <= 1:
             return torch.moveaxis(climatology[:, output_day_indices(dates[0], self.output_timesteps)], 0, -1)
         rows = []
         for date in dates:
-            key = date.item()
+            key = (date.item(), self.output_timesteps)       # (the steps too: the horizon may differ from call to call)
             if key not in self._output_days:
                 self._output_days[key] = output_day_indices(date, self.output_timesteps)
             rows.append(self._output_days[key])
@@ -2100,6 +2239,7 @@ class NextFramePredictorS2S(NextFramePredictor):
                 x, y = self._clip(x), self._clip(y) if reads_y else None
                 concat = self.get_climatology_array(climatology, launch_date) if climatology is not None else None
                 check_concat_clips(x, concat)
+                y = self._first_steps(y)[0]
                 if begin is not None:
                     begin(x)
                 batch = (x, concat) if y is None else (x, y, concat)
@@ -2188,6 +2328,7 @@ class NextFramePredictorS2S(NextFramePredictor):
         x = x.to(self.device)
         concat = concat_layers.to(self.device) if concat_layers is not None else None
         check_concat_clips(x, concat)
+        concat = self._first_steps(None, concat)[1]
         with torch.no_grad(), self.model.record_attention(select) as records:
             self.model(x, concat_layers=concat, teacher_forcing_ratio=0, mask=mask, high_interest_region=high_interest_region,
                        graph_structure=graph_structure)
@@ -2240,6 +2381,7 @@ class NextFramePredictorS2S(NextFramePredictor):
                              + (f'{x.dtype} {tuple(x.shape)}' if torch.is_tensor(x) else type(x).__name__))
         req = Request(x.shape, self.output_timesteps, host_mask(mask), target, leads, method, baseline, steps)
         check_concat_clips(x, concat_layers)
+        concat_layers = self._first_steps(None, concat_layers)[1]
         if self.model.remesh_input:
             raise NotImplementedError('sensitivity: remesh_input=True models are not covered (their encoder assembles the rows of '
                                       'every input frame without autograd)')

@@ -332,6 +332,7 @@ class Seq2Seq(_NoCachesInPickle, nn.Module):
         self.max_grid_size = 64                      # image_to_graph default, never overridden (graph_functions.py:590)
         self.static_shapes = False                   # True: worst-case capacities + device-side node counts (hipGraph)
         self._recompute = None                       # None | 'step' | 'stream' (set_recompute): how a rollout with autograd keeps its steps
+        self._horizon = None                         # None | k (set_horizon): the output steps forward() unrolls; None: output_timesteps
 
     # -- activation recomputation ----------------------------------------------------------
     @property
@@ -352,6 +353,21 @@ class Seq2Seq(_NoCachesInPickle, nn.Module):
         uses by one grouped launch at the end.  Another order of additions: the weight gradients equal the plain rollout's up to
         rounding; loss, outputs, meshes and dropout masks stay bit for bit, and two runs give the same bits."""
         self._recompute = recompute.check_mode(mode)
+
+    # -- rollout horizon -------------------------------------------------------------------
+    @property
+    def horizon(self):
+        """The output steps forward() unrolls: what set_horizon set, else the constructor's output_timesteps."""
+        k = self.__dict__.get('_horizon')
+        return self.output_timesteps if k is None else k
+
+    def set_horizon(self, k):
+        """forward() unrolls range(k) from now on; None: range(output_timesteps) again.  No weight depends on the step count -- the
+        decoder is autoregressive -- so any k >= 1 is a rollout of this model, above output_timesteps too; y, where teacher
+        forcing reads it, and concat_layers then need k steps.  Like the recompute mode this is no state of the model: neither
+        state_dict nor a checkpoint carries it.  Anything but None or an integer >= 1 is refused under `horizon`."""
+        from qtmpnn.horizon import check_horizon
+        self._horizon = None if k is None else check_horizon(k)
 
     def _step(self, run, *args):
         """run(*args) -- Encoder.run / Decoder.run_rows -- as the mode keeps it."""
@@ -609,7 +625,7 @@ class Seq2Seq(_NoCachesInPickle, nn.Module):
                 graph_structure=None, remesh_every=1):
         check_concat_clips(x, concat_layers)
         self.process_inputs(x, mask=mask, high_interest_region=high_interest_region, graph_structure=graph_structure)
-        return self.unroll_output(range(self.output_timesteps), y, concat_layers=concat_layers,
+        return self.unroll_output(range(self.horizon), y, concat_layers=concat_layers,
                                   teacher_forcing_ratio=teacher_forcing_ratio, mask=mask,
                                   high_interest_region=high_interest_region, remesh_every=remesh_every)
 

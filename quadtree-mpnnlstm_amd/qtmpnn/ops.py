@@ -2004,7 +2004,8 @@ def _loss_slices(T):
 class _RolloutLoss(Function):
     """_StepSSE for all output steps of a rollout in one launch per kernel (qt_{sse,bce,wsse,wbce}_rollout / _bwd): the loss
     touches every step once, after the last one, so the 3 x T_out small launches (the partial sums, per-node target sums for the
-    gradient, the gradient rows) become 3 per 16 steps.  y: (B, T, P) contiguous fp32; outs[t]: contiguous (N_t, W) matrices
+    gradient, the gradient rows) become 3 per 16 steps.  y: (B, T, P) fp32, every clip a contiguous block (_clip_rows: the clip
+    stride goes to the kernels, so the first T steps of a longer target are read in place); outs[t]: contiguous (N_t, W) matrices
     whose column 0 is the prediction.  kind: 'sse', partial sums of (out_t[label] - y)^2, or 'bce', those of torch's BCELoss
     numerator -(y max(log o, -100) + (1 - y) max(log(1 - o), -100)), o = column 0 of outs[t] (the binary head's probabilities).
     weighted: each term times lam[t] w[p], w: (P,) and lam: (T,) fp32 device tensors, no gradient; the weighted 'bce' has
@@ -2023,8 +2024,8 @@ class _RolloutLoss(Function):
         for z0, n, seg in _loss_slices(T):
             wl = (ptr(w), lam.data_ptr() + 4 * z0) if weighted else ()
             _lib.call(entry, n, seg(outs), seg(o.stride(0) for o in outs), seg(ms.labels for ms in meshes),
-                      seg(ms.level for ms in meshes), seg(ms.N for ms in meshes), seg(sums), y.data_ptr() + 4 * z0 * P, T * P, P,
-                      *wl, B, m0.n, m0.m, ptr(part[z0:]), *pw)
+                      seg(ms.level for ms in meshes), seg(ms.N for ms in meshes), seg(sums), y.data_ptr() + 4 * z0 * P,
+                      y.stride(0) if B > 1 else T * P, P, *wl, B, m0.n, m0.m, ptr(part[z0:]), *pw)
         ctx.save_for_backward(*outs, *sums, *((lam,) if weighted else ()))
         ctx.entry, ctx.meshes, ctx.pw = entry + '_bwd', meshes, pw
         return part
@@ -2050,6 +2051,19 @@ def _check_loss_weights(w, lam, mesh, T):
             raise ValueError(f'{what}: a contiguous fp32 device tensor of {count} entries is needed')
 
 
+def _clip_rows(y, B, T, P):
+    """y, the B * T * P fp32 targets of a rollout, as a (B, T, P) view whose clips are contiguous blocks of T * P values: the
+    whole of a contiguous tensor, or the first T steps of a longer (B, T', ...) one, B blocks a clip stride apart (the rollout
+    under a horizon below the steps y holds: nothing is copied).  None where y is no such view."""
+    if y.dtype != torch.float32 or y.numel() != B * T * P:
+        return None
+    if y.is_contiguous():
+        return y.view(B, T, P)
+    if y.dim() >= 2 and y.shape[0] == B and y[0].is_contiguous() and y.stride(0) >= T * P:
+        return y.as_strided((B, T, P), (y.stride(0), P, 1))
+    return None
+
+
 def _rollout_partials(kind, outputs, y, meshes, weights=None, pos_weight=None):
     """The partial sums of _RolloutLoss, or None when the steps cannot share the launches (masked-per-pixel preset meshes, odd
     layouts, N == 0).  weights: None or (w, lam), checked once the launches are known to apply."""
@@ -2060,13 +2074,14 @@ def _rollout_partials(kind, outputs, y, meshes, weights=None, pos_weight=None):
     if any(o.dtype != torch.float32 or not o.is_contiguous() or o.shape[1] != W or not o.is_cuda for o in outs):
         return None
     B, T = meshes[0].B, len(outs)
-    if y.dtype != torch.float32 or not y.is_contiguous() or y.numel() != B * T * meshes[0].P:
+    y = _clip_rows(y, B, T, meshes[0].P)
+    if y is None:
         return None
     w, lam = weights or (None, None)
     if weights is not None:
         _check_loss_weights(w, lam, meshes[0], T)
         w = w.view(-1)
-    return _RolloutLoss.apply(kind, weights is not None, y.view(B, T, meshes[0].P), tuple(meshes), w, lam, pos_weight, *outs)
+    return _RolloutLoss.apply(kind, weights is not None, y, tuple(meshes), w, lam, pos_weight, *outs)
 
 
 def rollout_sse_partials(outputs, y, meshes):
@@ -2193,8 +2208,8 @@ def with_references(rollout, references, axis, lead=1):
 
 
 def _score_args(who, outputs, meshes, y, persistence, climatology):
-    """The checked operands rollout_scores and rollout_score_maps share: (outs, y, bases, S, B, T, P), bases = two
-    (field or None, clip stride, step stride); each slot a tensor or a (name, tensor) pair (named_fields).  Refusals carry
+    """The checked operands rollout_scores and rollout_score_maps share: (outs, y, bases, S, B, T, P), y = (targets, clip stride),
+    bases = two (field or None, clip stride, step stride); each slot a tensor or a (name, tensor) pair (named_fields).  Refusals carry
     `who` and the field's name."""
     if not outputs or len(outputs) != len(meshes):
         raise ValueError(f'{who}: {len(outputs)} output steps for {len(meshes)} meshes')
@@ -2211,7 +2226,11 @@ def _score_args(who, outputs, meshes, y, persistence, climatology):
                              f'(expected {" or ".join(str(c) for c in counts)})')
         t = t.detach().to(outs[0].device, torch.float32).contiguous()
         return (t, T * P, P) if t.numel() == B * T * P else (t, P, 0)      # (field, clip stride, step stride)
-    y = dense(y, 'y', (B * T * P,))[0]
+    if y.numel() != B * T * P:
+        dense(y, 'y', (B * T * P,))
+    y = y.detach().to(outs[0].device, torch.float32)
+    rows = _clip_rows(y, B, T, P)           # (the first T steps of a longer target are read in place, through the clip stride)
+    y = (y.contiguous(), T * P) if rows is None else (rows, rows.stride(0) if B > 1 else T * P)
     bases = [dense(t, name, (B * P, B * T * P)) for name, t in named_fields(persistence, climatology)]
     S = 1 + len(bases)
     bases += [(None, 0, 0)] * (2 - len(bases))
@@ -2232,7 +2251,7 @@ def _score_chunks(entry, outs, meshes, y, bases, threshold, B, T, P, tail):
         _lib.call(entry, n, (vp * n)(*[o.data_ptr() for o in outs[sl]]),
                   (ip * n)(*[max(o.stride(0), 1) for o in outs[sl]]), (vp * n)(*[ms.labels.data_ptr() for ms in meshes[sl]]),
                   (ip * n)(*[o.shape[0] for o in outs[sl]]), (vp * n)(*[ptr(ms.n_dev) for ms in meshes[sl]]),
-                  y.data_ptr() + 4 * z0 * P, T * P, P, *base_args, ptr(m0.loss_mask), float(threshold), B, m0.n, m0.m,
+                  y[0].data_ptr() + 4 * z0 * P, y[1], P, *base_args, ptr(m0.loss_mask), float(threshold), B, m0.n, m0.m,
                   *tail(z0))
 
 
