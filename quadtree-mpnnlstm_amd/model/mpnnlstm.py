@@ -810,6 +810,34 @@ def takes_horizon(method):
     return wrapper
 
 
+_NOT_GIVEN = object()       # train(trainable=) left out: the predictor's setting stays (None asks for all parameters)
+
+
+def takes_trainable(method):
+    """Gives train() the keyword `trainable` (NextFramePredictorS2S.set_trainable: None or a sequence of fnmatch patterns over
+    the state-dict names).  train()'s parameter list is read by signature tests and stays as it is (takes_ema, takes_horizon);
+    the keyword is taken here, checked and resolved against the model's names on the host, before anything else runs, and
+    held in self._trainable_asked while the call runs.  train() applies it once the optimiser exists -- after
+    initiate_training, which returns to all-trainable, when it has to make the optimiser itself -- and the setting that was
+    in force before is back when the call ends, also after an exception.  Left out, the predictor's setting stays."""
+    import functools
+
+    @functools.wraps(method)
+    def wrapper(self, *args, trainable=_NOT_GIVEN, **keywords):
+        if trainable is _NOT_GIVEN:
+            return method(self, *args, **keywords)
+        self._check_trainable(trainable)        # (every refusal of set_trainable but the one about the optimiser, which train() makes)
+        before = self._trainable if self.training_initiated else None
+        previous, self._trainable_asked = self._trainable_asked, (True, trainable)
+        try:
+            return method(self, *args, **keywords)
+        finally:
+            self._trainable_asked = previous
+            if self.training_initiated and not self._ema_inside:
+                self.set_trainable(before)
+    return wrapper
+
+
 class NextFramePredictor(ABC):
     """The abstract trainer facade of the reference (model/mpnnlstm.py:34-79; moving_mnist_example.ipynb cell 2 imports it):
     it holds the decomposition settings and names the three methods a predictor offers.  `thresh` is kept as given here;
@@ -863,6 +891,135 @@ class NextFramePredictorS2S(NextFramePredictor):
         # is open, and train()'s (ema, ema_eval) while it runs (takes_ema)
         self.ema = self._ema_stash = None
         self._ema_inside, self._ema_asked = False, (None, True)
+        # the selection of trainable parameters (set_trainable; None: all), its 0/1 mask over the flat vector (flat-vector
+        # models with a selection; else None) and train()'s `trainable` while it runs (takes_trainable)
+        self._trainable = self._train_mask = None
+        self._trainable_asked = (False, None)
+
+    # -- trainable parameters (beyond the reference): qtmpnn.trainable has the pure parts ----------------------------------------
+    def _check_trainable(self, patterns):
+        """(patterns as a tuple or None, one flag per parameter name, whether the encoder cut applies), or the refusal: what
+        qtmpnn.trainable.resolve_trainable refuses, an open averaged_weights() block, and the cut on a remesh_input=True model.
+        Reads the predictor, changes nothing."""
+        from qtmpnn.trainable import check_patterns, encoder_frozen, resolve_trainable
+        names = [name for name, _, _ in name_table(self.model)]
+        flags = resolve_trainable(names, patterns)
+        if self._ema_inside:
+            raise RuntimeError('trainable: set_trainable() inside averaged_weights(): leave the block first')
+        cut = encoder_frozen(names, flags)
+        if cut and self.model.remesh_input:
+            raise NotImplementedError('trainable: a frozen encoder runs without autograd (the encoder cut), which does not cover '
+                                      'remesh_input=True models (their encoder re-meshes between its steps); a selection that '
+                                      'keeps one encoder parameter trainable only masks and is allowed')
+        return check_patterns(patterns), names, flags, cut
+
+    def set_trainable(self, patterns):
+        """Train only the parameters some pattern of `patterns` matches; every other one is frozen.  patterns: None -- every
+        parameter is trainable, the default, and every path is then what it was, bit for bit -- or a non-empty sequence of
+        fnmatch patterns over the state-dict names (named_parameters(), qtmpnn.flat.name_table): ('decoder.*',),
+        ('decoder.fc_out*', 'decoder.norm_o.*').  `trainable_names` lists what is trainable.
+
+        A STEP UNDER A SELECTION is torch's own rule for requires_grad=False parameters: forward, loss and backward as ever; the
+        frozen entries of the gradient are zero before the (all-reduced) gradient is used; the clipping norm is the norm of the
+        trainable gradients; Adam updates the trainable entries; frozen parameters keep their bits.  Flat-vector models: one 0/1
+        mask over the flat vector, made here, and ONE in-place multiplication of the gradient in _clip_and_step, the place every
+        optimiser step goes through (train_step, accumulated_step, the truncated loop, both recompute modes, the captured steps --
+        it sits in the graph that holds clip + Adam; under torch.distributed it follows the all-reduce, so no collective
+        changes).  qt_flat_adam is untouched: with g = m = v = 0 its update is exactly 0.  Parameter-list models (torch's Adam):
+        frozen parameters get requires_grad_(False) and grad = None, and the norm is taken over the trainable list.
+        THE MOMENTS RULE: exp_avg and exp_avg_sq of every entry that is frozen are set to zero here, in place, before the next
+        step -- Adam would otherwise go on moving a frozen entry along its old momentum.  An entry that is thawed later so
+        restarts from zero moments under the shared step count (its bias corrections are those of the run's step, not of a new
+        parameter's).
+        THE ENCODER CUT: when no parameter under `encoder.` is trainable, the encoder phase of every rollout with autograd runs
+        without it -- no activations kept, no backward launches for half of an I10O10 rollout's steps -- and loss, outputs,
+        meshes, dropout masks and the decoder's gradients stay the plain step's, bit for bit (Seq2Seq.set_encoder_cut, which
+        also says why there is no finer cut: a trainable head's gradient runs through every later decoder cell).  A partly
+        frozen encoder keeps the whole graph; only the masking applies.
+        The setting follows the optimiser, as the average does: initiate_training() returns to all-trainable.  It is no training
+        state: checkpoints neither store nor restore it (frozen moments are zero in the file, so load_checkpoint followed by the
+        same set_trainable continues bit for bit).  The average (set_ema) is untouched: the shadow of a frozen parameter is the
+        same recurrence on a constant.  A CAPTURED STEP KEEPS THE SETTING IT WAS CAPTURED UNDER and refuses to run
+        (RuntimeError, `trainable`) once the predictor's is another one.  predict, verify, the products and sensitivity do not
+        look at the setting.
+        Refusals, each under `trainable`, before any launch and before anything changes: TypeError for a plain string, for
+        what is no sequence and for a pattern that is no string; ValueError for an empty sequence, a pattern that matches no
+        name (it lists the top-level names), a selection that leaves nothing trainable, and a predictor without
+        initiate_training() / train(); RuntimeError inside averaged_weights(); NotImplementedError where the cut would apply
+        to a remesh_input=True model."""
+        from qtmpnn.trainable import flat_mask
+        patterns, names, flags, cut = self._check_trainable(patterns)
+        if patterns is not None and not self.training_initiated:
+            raise ValueError('trainable: the selection follows the optimiser: call initiate_training() first (or pass '
+                             'train(trainable=patterns))')
+        if not self.training_initiated:
+            return                          # (None on a predictor without an optimiser: all-trainable is what it is)
+        # (the same selection again keeps its mask: a captured step reads it through its pointer)
+        keep = self._train_mask if patterns == self._trainable else None
+        flat = self.flat is not None
+        if flat and not self.flat.intact(self.model):
+            raise RuntimeError('the model parameters were moved or replaced after initiate_training(): call it again')
+        with torch.no_grad():
+            if flat:
+                mask = None if patterns is None else keep if keep is not None else flat_mask(name_table(self.model), flags,
+                                                                                             self.flat.param.device)
+                st = self.optimizer.state.get(self.flat.param)
+                if st and mask is not None:
+                    frozen = mask == 0
+                    st['exp_avg'].masked_fill_(frozen, 0.0)
+                    st['exp_avg_sq'].masked_fill_(frozen, 0.0)
+                self._train_mask = mask
+            else:
+                self._share_step_count()
+                for p, f in zip(self.model.parameters(), flags, strict=True):
+                    p.requires_grad_(f)
+                    if not f:
+                        p.grad = None
+                        st = self.optimizer.state.get(p)
+                        if st:
+                            st['exp_avg'].zero_()
+                            st['exp_avg_sq'].zero_()
+                self._train_mask = None
+        self._trainable = patterns
+        self.model.set_encoder_cut(cut)
+
+    def _share_step_count(self):
+        """Parameter-list models: torch's Adam counts steps per parameter and skips one without a gradient, so a frozen
+        parameter's count stands still.  Its moments are zero, so the count means nothing until it is thawed; the largest count
+        is written into every one that exists, in place: ONE step count, what a checkpoint stores and what a thawed entry
+        continues under."""
+        states = [st for st in (self.optimizer.state.get(p) for p in self.model.parameters()) if st]
+        steps = [float(st['step']) for st in states]
+        if steps and min(steps) != max(steps):
+            for st in states:
+                st['step'].fill_(max(steps))
+
+    @property
+    def trainable_names(self):
+        """The names of the trainable parameters, a tuple in state-dict order (all of them without a selection)."""
+        from qtmpnn.trainable import resolve_trainable
+        names = [name for name, _, _ in name_table(self.model)]
+        return tuple(n for n, f in zip(names, resolve_trainable(names, self._trainable)) if f)
+
+    @contextlib.contextmanager
+    def training_only(self, patterns):
+        """`with nfp.training_only(('decoder.*',)):` -- set_trainable(patterns) for the block; the previous selection is back
+        afterwards, also after an exception (the moments of what it freezes are zeroed then, by the same rule).  Blocks nest:
+        the inner one holds while it runs."""
+        previous = self._trainable
+        self.set_trainable(patterns)
+        try:
+            yield self
+        finally:
+            self.set_trainable(previous)
+
+    def _trainable_guard(self, held):
+        """Before a replay of a step captured under the selection `held`: refused unless that still is the predictor's (the
+        mask multiplication, the list of stepped parameters and the encoder cut are part of the capture)."""
+        if held != self._trainable:
+            raise RuntimeError(f'trainable: this step was captured under trainable={held!r} and the predictor is now at '
+                               f'trainable={self._trainable!r}: a captured step keeps the setting it was captured under; capture '
+                               'a new one')
 
     # -- averaged weights (beyond the reference): qtmpnn.ema.WeightEMA, updated after every optimiser step ----------------------
     def set_ema(self, decay):
@@ -1067,6 +1224,8 @@ class NextFramePredictorS2S(NextFramePredictor):
         if not self.training_initiated:
             raise ValueError('save_checkpoint: nothing to resume yet (no initiate_training() / train()); save() stores the weights')
         from qtmpnn.optim import adam_state
+        if self.flat is None and self._trainable is not None:
+            self._share_step_count()        # (frozen parameters' counts stand still under torch's Adam; the file holds one)
         group = self.optimizer.param_groups[0]
         dev = next(self.model.parameters()).device
         host = lambda v: float(v) if torch.is_tensor(v) else [host(e) for e in v] if isinstance(v, (list, tuple)) else v
@@ -1212,6 +1371,11 @@ class NextFramePredictorS2S(NextFramePredictor):
     @on_device(lambda self, *a, **k: self.device)
     def initiate_training(self, lr, lr_decay, capturable=False):
         self.loss_func_name = 'MSE' if not self.binary else 'BCE'
+        # (the selection of trainable parameters follows the optimiser: a new one starts with all of them)
+        for p in self.model.parameters():
+            p.requires_grad_(True)
+        self._trainable = self._train_mask = None
+        self.model.set_encoder_cut(False)
         if capturable:      # optimizer.step() inside a hipGraph needs device-side step counters and lr
             lr = torch.tensor(float(lr), device=self.device)
         # fused: one multi-tensor kernel for all 238 parameter tensors (the default per-tensor path costs ~1000 tiny
@@ -1322,7 +1486,7 @@ class NextFramePredictorS2S(NextFramePredictor):
             return [self.flat.param]
         params, off = list(self.model.parameters()), 0
         for p in params:
-            p.grad = g[off:off + p.numel()].view_as(p)
+            p.grad = g[off:off + p.numel()].view_as(p) if p.requires_grad else None       # (frozen: set_trainable)
             off += p.numel()
         return params
 
@@ -1331,9 +1495,13 @@ class NextFramePredictorS2S(NextFramePredictor):
         place every optimiser step goes through: with averaged weights (set_ema) their update follows the step."""
         self._ema_guard()
         if self.flat is not None:
+            if self._train_mask is not None and self.flat.param.grad is not None:
+                self.flat.param.grad.mul_(self._train_mask)         # (set_trainable: the frozen entries are zero from here on)
             self.optimizer.step(max_norm=max_norm)
         else:
             if max_norm is not None:
+                if self._trainable is not None:
+                    clip_params = [p for p in clip_params if p.requires_grad]
                 torch.nn.utils.clip_grad_norm_(clip_params, max_norm=max_norm)
             self.optimizer.step()
         if self.ema is not None:
@@ -1534,6 +1702,7 @@ class NextFramePredictorS2S(NextFramePredictor):
         warm_then_sync(side, multi, warm)
         graph, graph2 = torch.cuda.CUDAGraph(), None
         ema, averaged = self.ema, self.ema.updates if self.ema is not None else 0
+        trainable, train_mask = self._trainable, self._train_mask
         self.zero_grad()
         # thread_local: other threads (the RCCL watchdog under torch.distributed) may issue HIP calls meanwhile
         with torch.cuda.graph(graph, stream=side, capture_error_mode='thread_local'):
@@ -1556,6 +1725,7 @@ class NextFramePredictorS2S(NextFramePredictor):
         @on_device(lambda *a, **k: self.device)
         def step(x, y, concat_layers=None):
             self._ema_guard(True, ema)
+            self._trainable_guard(trainable)
             batch.load(x, *self._first_steps(y, concat_layers, held))      # (the horizon of the capture, whatever is set now)
             graph.replay()
             if multi:
@@ -1566,6 +1736,7 @@ class NextFramePredictorS2S(NextFramePredictor):
             watch.advance()
             return static_loss
         step.check, step.loss_weights, step.ema, step.horizon = watch.check, lw, ema, held[0]
+        step.trainable, step.trainable_mask = trainable, train_mask       # (the graph reads the mask by pointer: it lives with the step)
         return step
 
     def _capture_setup(self, force_multi):
@@ -1580,9 +1751,10 @@ class NextFramePredictorS2S(NextFramePredictor):
         if not self.optimizer.defaults.get('capturable', False):
             lr = self.optimizer.param_groups[0]['lr']
             assert not self.optimizer.state, 'make_graphed_step must be called before the first optimizer step'
-            decay = None if self.ema is None else self.ema.decay
+            decay, trainable = None if self.ema is None else self.ema.decay, self._trainable
             self.initiate_training(float(lr), self.scheduler.gamma, capturable=True)
             self.set_ema(decay)         # (no step was taken: the average starts with the new optimiser, as it stood)
+            self.set_trainable(trainable)       # (and so does the selection of trainable parameters)
         return multi, world
 
     def _graphed_accumulation(self, batches, accumulate, mask=None, high_interest_region=None, max_norm=10.0, warmup=2,
@@ -1631,6 +1803,7 @@ class NextFramePredictorS2S(NextFramePredictor):
             loss_acc.add_(loss.detach())
         clip_params = self._set_grad_flat(acc)          # the optimiser reads acc from here on
         ema, averaged = self.ema, self.ema.updates if self.ema is not None else 0
+        trainable, train_mask = self._trainable, self._train_mask
         update = torch.cuda.CUDAGraph()
         with torch.cuda.graph(update, stream=side, capture_error_mode='thread_local'):
             acc.mul_(scale[0])
@@ -1646,6 +1819,7 @@ class NextFramePredictorS2S(NextFramePredictor):
         @on_device(lambda *a, **kw: self.device)
         def step(batches):
             self._ema_guard(True, ema)
+            self._trainable_guard(trainable)
             group = [(x, *self._first_steps(y, c, held)) for x, y, c in checked_batches('step', batches)]
             j = len(group)
             if j > k or any(batch_shapes(item) != batch.shapes for item in group):
@@ -1666,7 +1840,7 @@ class NextFramePredictorS2S(NextFramePredictor):
             watch.advance(j)
             return static_loss
         step.check, step.loss_weights, step.accumulate, step.graphs, step.ema = watch.check, lw, k, (micro, update), ema
-        step.horizon = held[0]
+        step.horizon, step.trainable, step.trainable_mask = held[0], trainable, train_mask
         step.buffers = (*batch.tensors, acc, loss_acc, scale)       # (loss_acc is named nowhere else: StaticBatch)
         return step
 
@@ -1871,6 +2045,7 @@ class NextFramePredictorS2S(NextFramePredictor):
     @on_device(lambda self, *a, **k: self.device)
     @takes_ema
     @takes_horizon
+    @takes_trainable
     def train(self, loader_train, loader_test, climatology=None, n_epochs=200, lr=0.01, lr_decay=0.95, mask=None,
               high_interest_region=None, truncated_backprop=45, graph_structure=None, use_graph=False, accumulate=1,
               pos_weight=None, test_graph=False, patience=None, min_delta=0.0, restore_best=False, keep_best=None,
@@ -1946,7 +2121,12 @@ class NextFramePredictorS2S(NextFramePredictor):
         per (batch shape, horizon), and those of a horizon the schedule has left are dropped, so that their memory returns.
         The whole schedule of this call's epochs is resolved and checked before the optimiser is made and before any launch;
         an entry above the steps the training loader's y holds is refused on the first batch of its epoch, before its launch.
-        Every refusal names `horizon`.  With horizon=None the call is what it was, bit for bit."""
+        Every refusal names `horizon`.  With horizon=None the call is what it was, bit for bit.
+        trainable=patterns (a keyword of this method through takes_trainable; beyond the reference): set_trainable(patterns) for
+        this call -- applied once the optimiser exists, after initiate_training when the call has to make it, and before the first
+        capture; the selection in force before is back when the call returns.  None trains every parameter; left out, the
+        predictor's selection stays.  Checked against the parameter names before anything is launched and before the optimiser
+        is made; every refusal names `trainable`."""
         from qtmpnn import validation
         image_shape = loader_train.dataset.image_shape
         accumulate = check_accumulate(accumulate)
@@ -1979,6 +2159,8 @@ class NextFramePredictorS2S(NextFramePredictor):
             self.initiate_training(lr, lr_decay, capturable=use_graph)
         if self._ema_asked[0] is not None:
             self.set_ema(self._ema_asked[0])
+        if self._trainable_asked[0]:
+            self.set_trainable(self._trainable_asked[1])
         averaging = self.averaged_weights if self.ema is not None and self._ema_asked[1] else contextlib.nullcontext
         graphed = {}
         if mask is not None:
@@ -2429,9 +2611,10 @@ class NextFramePredictorS2S(NextFramePredictor):
         if flat is not None:
             params.append(flat.param)           # (a packed model: the optimiser's one tensor over the same storage)
         required = [p.requires_grad for p in params]
-        rstate, calls, mode = random.getstate(), ops._ATTN_CALLS[0], self.model.recompute
+        rstate, calls, mode, cut = random.getstate(), ops._ATTN_CALLS[0], self.model.recompute, self.model.encoder_cut
         try:
             self.model.set_recompute(None)          # (several backward passes over one graph: the plain rollout's)
+            self.model.set_encoder_cut(False)       # (the maps are gradients THROUGH the encoder, whatever is trained)
             for p in params:
                 p.requires_grad_(False)
             self.model.to(self.device)
@@ -2469,6 +2652,7 @@ class NextFramePredictorS2S(NextFramePredictor):
             random.setstate(rstate)
             ops._ATTN_CALLS[0] = calls
             self.model.set_recompute(mode)
+            self.model.set_encoder_cut(cut)
         check_tile_errors()
         Js = host[:2 * nj].view(np.float64).reshape(-1, B, L)
         return Sensitivity(host[2 * nj:].reshape(B, L, *x5.shape[1:]).copy(), req.leads, req.method, req.target, Js[0].copy(),

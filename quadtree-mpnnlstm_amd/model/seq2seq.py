@@ -333,6 +333,7 @@ class Seq2Seq(_NoCachesInPickle, nn.Module):
         self.static_shapes = False                   # True: worst-case capacities + device-side node counts (hipGraph)
         self._recompute = None                       # None | 'step' | 'stream' (set_recompute): how a rollout with autograd keeps its steps
         self._horizon = None                         # None | k (set_horizon): the output steps forward() unrolls; None: output_timesteps
+        self._encoder_cut = False                    # set_encoder_cut: the encoder phase of a rollout with autograd runs without it
 
     # -- activation recomputation ----------------------------------------------------------
     @property
@@ -368,6 +369,33 @@ class Seq2Seq(_NoCachesInPickle, nn.Module):
         state_dict nor a checkpoint carries it.  Anything but None or an integer >= 1 is refused under `horizon`."""
         from qtmpnn.horizon import check_horizon
         self._horizon = None if k is None else check_horizon(k)
+
+    # -- frozen encoder --------------------------------------------------------------------
+    @property
+    def encoder_cut(self):
+        return bool(self.__dict__.get('_encoder_cut'))
+
+    def set_encoder_cut(self, on):
+        """True: no parameter of `encoder` is trained (NextFramePredictorS2S.set_trainable decides that), so a rollout WITH
+        autograd runs its encoder phase without it: the encoder's share of the weight packing and composition, every encoder
+        step -- plain no-grad steps in every recompute mode, the forward-only cell launch where there is one -- and nothing of
+        it is kept for a backward: no activations, Chebyshev planes or gate activations, and no data-gradient, weight-gradient
+        or compose-backward launch follows.  The state reaches the decoder detached.  Loss, every step's output, the meshes,
+        torch's generator and the attention-dropout counter are the plain rollout's bit for bit (the no-grad steps draw the same
+        masks: the seeds count calls, not graphs), and so are the decoder's gradients: hidden and cell are handed over as fresh
+        leaves that still ask for their gradient, so the first decoder step's backward issues the launches of the plain step
+        -- the same kernels over the same partial-sum slabs, hence the same bits -- and what arrives at the leaves is dropped
+        with them.
+        THERE IS NO FINER CUT.  Every decoder step's output is the next step's input, so the gradient of a trainable head runs
+        back through every later cell: cutting inside the decoder would truncate it.  A partly frozen encoder keeps the whole
+        graph as well (its trainable tensors need the steps behind them).  Rollouts without autograd (predict, verify) do not look
+        at the flag; remesh_input=True models have no such phase and refuse a rollout with autograd while it is set.  No state
+        of the model: neither state_dict nor a checkpoint carries it."""
+        self._encoder_cut = bool(on)
+
+    def _cutting(self):
+        """True while this rollout runs its encoder phase without autograd (set_encoder_cut)."""
+        return self.encoder_cut and torch.is_grad_enabled()
 
     def _step(self, run, *args):
         """run(*args) -- Encoder.run / Decoder.run_rows -- as the mode keeps it."""
@@ -408,7 +436,8 @@ class Seq2Seq(_NoCachesInPickle, nn.Module):
         (ops.PackPlan over all parameters in module order): its backward hands every parameter a view of ONE gradient
         vector, so the trainer's all-reduce, clip and Adam run on a single flat tensor (qtmpnn.flat)."""
         if not (self.encoder.plannable and self.decoder.plannable):
-            return self.encoder.pack(enc_in_pad), None          # the decoder packs itself when the rollout starts
+            with torch.no_grad() if self._cutting() else contextlib.nullcontext():
+                return self.encoder.pack(enc_in_pad), None      # the decoder packs itself when the rollout starts
         params = param_list(self)
 
         def spec():
@@ -422,8 +451,13 @@ class Seq2Seq(_NoCachesInPickle, nn.Module):
                 return out
 
             def finish(outs):
-                return (ef({k[2:]: v for k, v in outs.items() if k.startswith('e.')}),
-                        df({k[2:]: v for k, v in outs.items() if k.startswith('d.')}))
+                enc = {k[2:]: v for k, v in outs.items() if k.startswith('e.')}
+                if self._cutting():             # (the gather's backward then sees no gradient for the encoder's matrices)
+                    with torch.no_grad():
+                        enc = ef({k: tuple(t.detach() for t in v) if isinstance(v, tuple) else v.detach() for k, v in enc.items()})
+                else:
+                    enc = ef(enc)
+                return enc, df({k[2:]: v for k, v in outs.items() if k.startswith('d.')})
             return layout, finish
         return _pack_planned(self, (enc_in_pad, params[0].device), params, spec, flat_params(self) if params[0].is_cuda else None)
 
@@ -454,6 +488,10 @@ class Seq2Seq(_NoCachesInPickle, nn.Module):
         if self.remesh_input and self.recompute is not None and torch.is_grad_enabled():
             raise NotImplementedError(f"set_recompute({self.recompute!r}) does not cover remesh_input=True models (their encoder "
                                       "re-meshes between its steps): set_recompute(None) for this rollout")
+        cut = self._cutting()
+        if self.remesh_input and cut:
+            raise NotImplementedError('trainable: the encoder cut (set_encoder_cut) does not cover remesh_input=True models (their '
+                                      'encoder re-meshes between its steps)')
         self._single = x.dim() == 4
         self._deferred = None
         if self._single:
@@ -510,9 +548,12 @@ class Seq2Seq(_NoCachesInPickle, nn.Module):
         self.graph.mapping, self.graph.n_pixels_per_node, self.graph.image_shape = mesh, mesh.npix, (n, m)
         enc_pack, self._dec_pack = self._for_mode(self._packs(c + 3 + fpad))     # (the decoder pack waits for unroll_output)
         hidden = cell = None
-        for t in range(self.input_timesteps):
-            hidden, cell = self._step(self.encoder.run, feats_in[t], mesh, None if hidden is None else hidden[-1],
-                                      None if cell is None else cell[-1], enc_pack)
+        with torch.no_grad() if cut else contextlib.nullcontext():           # (without autograd _step is the plain step)
+            for t in range(self.input_timesteps):
+                hidden, cell = self._step(self.encoder.run, feats_in[t], mesh, None if hidden is None else hidden[-1],
+                                          None if cell is None else cell[-1], enc_pack)
+        if cut:         # detached, as leaves that ask for their gradient: the decoder's backward is the plain step's (set_encoder_cut)
+            hidden, cell = [h.detach().requires_grad_() for h in hidden], [c_.detach().requires_grad_() for c_ in cell]
         self.graph.hidden, self.graph.cell = hidden, cell            # per-layer lists while the rollout runs
         last = feats[-1]                                                                # x[-1, :, [0,-3,-2,-1]] (:336)
         self.graph.pyg.x = last if (c == 1 and last.is_contiguous()) else torch.cat([last[:, :1], last[:, -3:]], dim=1)
