@@ -838,6 +838,32 @@ def takes_trainable(method):
     return wrapper
 
 
+def takes_param_groups(method):
+    """Gives train() the keyword `param_groups` (NextFramePredictorS2S.set_param_groups: None or a sequence of (pattern,
+    options) pairs).  train()'s parameter list is read by signature tests and stays as it is (takes_ema, takes_horizon,
+    takes_trainable); the keyword is taken here, checked and resolved against the model's names on the host, before anything
+    else runs, and held in self._groups_asked while the call runs.  train() applies it once the optimiser exists -- after
+    initiate_training, which returns to no setting, when it has to make the optimiser itself -- and the setting that was in
+    force before is back when the call ends, also after an exception.  Left out, the predictor's setting stays."""
+    import functools
+    from qtmpnn.groups import as_pairs
+
+    @functools.wraps(method)
+    def wrapper(self, *args, param_groups=_NOT_GIVEN, **keywords):
+        if param_groups is _NOT_GIVEN:
+            return method(self, *args, **keywords)
+        self._check_param_groups(param_groups)  # (every refusal of set_param_groups but the one about the optimiser, which train() makes)
+        before = self._groups if self.training_initiated else None
+        previous, self._groups_asked = self._groups_asked, (True, param_groups)
+        try:
+            return method(self, *args, **keywords)
+        finally:
+            self._groups_asked = previous
+            if self.training_initiated and not self._ema_inside:
+                self.set_param_groups(as_pairs(before))
+    return wrapper
+
+
 class NextFramePredictor(ABC):
     """The abstract trainer facade of the reference (model/mpnnlstm.py:34-79; moving_mnist_example.ipynb cell 2 imports it):
     it holds the decomposition settings and names the three methods a predictor offers.  `thresh` is kept as given here;
@@ -895,6 +921,10 @@ class NextFramePredictorS2S(NextFramePredictor):
         # models with a selection; else None) and train()'s `trainable` while it runs (takes_trainable)
         self._trainable = self._train_mask = None
         self._trainable_asked = (False, None)
+        # the parameter groups (set_param_groups; None: no setting) in check_groups' form, their vectors and launches
+        # (qtmpnn.groups.GroupedStep, made on first use and kept with the optimiser) and train()'s `param_groups` while it runs
+        self._groups = self._grouped = None
+        self._groups_asked = (False, None)
 
     # -- trainable parameters (beyond the reference): qtmpnn.trainable has the pure parts ----------------------------------------
     def _check_trainable(self, patterns):
@@ -982,6 +1012,7 @@ class NextFramePredictorS2S(NextFramePredictor):
                 self._train_mask = None
         self._trainable = patterns
         self.model.set_encoder_cut(cut)
+        self._refresh_groups()              # (set_param_groups: a frozen entry gets neither decay nor blend)
 
     def _share_step_count(self):
         """Parameter-list models: torch's Adam counts steps per parameter and skips one without a gradient, so a frozen
@@ -1020,6 +1051,86 @@ class NextFramePredictorS2S(NextFramePredictor):
             raise RuntimeError(f'trainable: this step was captured under trainable={held!r} and the predictor is now at '
                                f'trainable={self._trainable!r}: a captured step keeps the setting it was captured under; capture '
                                'a new one')
+
+    # -- parameter groups (beyond the reference): qtmpnn.groups has the pure parts and the launches ------------------------------
+    def _check_param_groups(self, groups):
+        """(the setting in check_groups' form or None, {name: (lr_scale, weight_decay)}), or the refusal: what
+        qtmpnn.groups.resolve_groups refuses, and an open averaged_weights() block.  Reads the predictor, changes nothing."""
+        from qtmpnn.groups import check_groups, resolve_groups
+        resolved = resolve_groups([name for name, _, _ in name_table(self.model)], groups)
+        if self._ema_inside:
+            raise RuntimeError('param_groups: set_param_groups() inside averaged_weights(): leave the block first')
+        return check_groups(groups), resolved
+
+    def set_param_groups(self, groups):
+        """A learning-rate scale and a decoupled weight decay per parameter.  groups: None -- no setting, the default, and every
+        path is then what it was, bit for bit -- or a non-empty sequence of (pattern, options) pairs (a dict pattern -> options
+        is read in its insertion order): `pattern` an fnmatch pattern over the state-dict names, the names set_trainable
+        matches; `options` a dict with keys from {'lr_scale', 'weight_decay'}, finite numbers >= 0.  The FIRST matching pair
+        decides a parameter; one that nothing matches has lr_scale 1 and weight_decay 0.  `param_group_table` lists the result.
+            [('*norm*', {}), ('*bias*', {}), ('encoder.*', dict(lr_scale=0.1, weight_decay=1e-2)), ('*', dict(weight_decay=1e-2))]
+        A STEP UNDER A SETTING is torch's AdamW with the learning rate lr * s_i and the decay lam_i per entry, lr the optimiser's
+        current learning rate (the device tensor when capturable: StepLR is followed by replays); after the all-reduce, after
+        the trainable mask and after clipping with the GLOBAL norm, which is unchanged:
+            p_i <- p_i * (1 - lr * s_i * lam_i);    p_i <- p_i - lr * s_i * mhat_i / (sqrt(vhat_i) + eps)
+        with the moments and the one step count updated exactly as without a setting, for every entry, also where s_i = 0.
+        qtmpnn.groups.GroupedStep has the mechanism, ONE for both optimiser forms, in _clip_and_step, the place every optimiser
+        step goes through: multiply by the decay vector, stash the parameters in a buffer allocated once, run the existing step
+        untouched (qt_flat_adam, torch's fused Adam; optimizer.param_groups stays ONE group), blend p <- p0 + s (p - p0) on the
+        entries with s != 1.  No host read, no allocation per step; the launches sit in the graph that holds clip + Adam.
+        WHAT HOLDS: entries with (s, lam) = (1, 0) have the plain step's bits in one step from equal state (the decay
+        multiplies by exactly 1.0f and the blend skips them); a setting that is (1, 0) everywhere issues no launch at all;
+        entries with s = 0 keep their bits while their moments advance and the clipping norm still sees them (this is not
+        set_trainable); entries frozen by set_trainable get neither decay nor update; the average (set_ema) is updated after
+        the blend, so the shadow averages what the step wrote.
+        The setting follows the optimiser: initiate_training() returns to None.  It is no training state: checkpoints neither
+        store nor restore it.  A CAPTURED STEP KEEPS THE SETTING IT WAS CAPTURED UNDER and refuses to run (RuntimeError,
+        `param_groups`) once the predictor's is another one.  predict, verify, the products and sensitivity do not look at it.
+        Refusals, each under `param_groups`, before any launch and before anything changes: TypeError for a plain string, for
+        what is no sequence, for a pair that is no (str, dict) and for an option that is no number (True included); ValueError
+        for an empty sequence, an unknown option key, a negative or non-finite number, a pattern that is the first match of no
+        parameter (it lists the top-level names and says when an earlier pattern shadows it), and a predictor without
+        initiate_training() / train(); RuntimeError inside averaged_weights()."""
+        from qtmpnn.groups import GroupedStep
+        setting, _ = self._check_param_groups(groups)
+        if setting is not None and not self.training_initiated:
+            raise ValueError('param_groups: the setting follows the optimiser: call initiate_training() first (or pass '
+                             'train(param_groups=groups))')
+        if not self.training_initiated:
+            return                          # (None on a predictor without an optimiser: no setting is what it has)
+        if setting is not None and self._grouped is None:
+            if self.flat is not None and not self.flat.intact(self.model):
+                raise RuntimeError('the model parameters were moved or replaced after initiate_training(): call it again')
+            # (made once per optimiser and filled in place from then on: a captured step reads the vectors by pointer)
+            self._grouped = GroupedStep(self.flat.param if self.flat is not None else list(self.model.parameters()),
+                                        name_table(self.model))
+        self._groups = setting
+        self._refresh_groups()
+
+    def _refresh_groups(self):
+        """Fill the vectors of the setting in force under the trainable selection in force (set_param_groups and set_trainable
+        end here: a frozen entry gets neither decay nor blend)."""
+        if self._groups is None or self._grouped is None:
+            return
+        from qtmpnn.groups import as_pairs, resolve_groups
+        from qtmpnn.trainable import resolve_trainable
+        names = [name for name, _, _ in name_table(self.model)]
+        self._grouped.set(resolve_groups(names, as_pairs(self._groups)), resolve_trainable(names, self._trainable))
+
+    @property
+    def param_group_table(self):
+        """{state-dict name: (lr_scale, weight_decay)} of the setting in force, in state-dict order ((1.0, 0.0) without one)."""
+        from qtmpnn.groups import as_pairs, resolve_groups
+        return resolve_groups([name for name, _, _ in name_table(self.model)], as_pairs(self._groups))
+
+    def _groups_guard(self, held):
+        """Before a replay of a step captured under the setting `held`: refused unless that still is the predictor's (the
+        decay, stash and blend launches are part of the capture)."""
+        if held != self._groups:
+            from qtmpnn.groups import as_pairs
+            raise RuntimeError(f'param_groups: this step was captured under param_groups={as_pairs(held)!r} and the predictor is '
+                               f'now at param_groups={as_pairs(self._groups)!r}: a captured step keeps the setting it was '
+                               'captured under; capture a new one')
 
     # -- averaged weights (beyond the reference): qtmpnn.ema.WeightEMA, updated after every optimiser step ----------------------
     def set_ema(self, decay):
@@ -1376,6 +1487,7 @@ class NextFramePredictorS2S(NextFramePredictor):
             p.requires_grad_(True)
         self._trainable = self._train_mask = None
         self.model.set_encoder_cut(False)
+        self._groups = self._grouped = None     # (and so do the parameter groups: set_param_groups)
         if capturable:      # optimizer.step() inside a hipGraph needs device-side step counters and lr
             lr = torch.tensor(float(lr), device=self.device)
         # fused: one multi-tensor kernel for all 238 parameter tensors (the default per-tensor path costs ~1000 tiny
@@ -1494,16 +1606,25 @@ class NextFramePredictorS2S(NextFramePredictor):
         """clip_grad_norm_(max_norm) + optimizer.step() (mpnnlstm.py:251, 257); max_norm None: no clipping (:311).  The one
         place every optimiser step goes through: with averaged weights (set_ema) their update follows the step."""
         self._ema_guard()
+        grouped = self._grouped if self._groups is not None else None       # (set_param_groups: decay and stash, step, blend)
         if self.flat is not None:
-            if self._train_mask is not None and self.flat.param.grad is not None:
+            if self.flat.param.grad is None:
+                grouped = None              # (FlatAdam takes no step without a gradient)
+            elif self._train_mask is not None:
                 self.flat.param.grad.mul_(self._train_mask)         # (set_trainable: the frozen entries are zero from here on)
+            if grouped is not None:
+                grouped.before(self.optimizer.param_groups[0]['lr'])
             self.optimizer.step(max_norm=max_norm)
         else:
             if max_norm is not None:
                 if self._trainable is not None:
                     clip_params = [p for p in clip_params if p.requires_grad]
                 torch.nn.utils.clip_grad_norm_(clip_params, max_norm=max_norm)
+            if grouped is not None:
+                grouped.before(self.optimizer.param_groups[0]['lr'])
             self.optimizer.step()
+        if grouped is not None:
+            grouped.after()
         if self.ema is not None:
             self.ema.update()
 
@@ -1703,6 +1824,7 @@ class NextFramePredictorS2S(NextFramePredictor):
         graph, graph2 = torch.cuda.CUDAGraph(), None
         ema, averaged = self.ema, self.ema.updates if self.ema is not None else 0
         trainable, train_mask = self._trainable, self._train_mask
+        groups, grouped = self._groups, self._grouped if self._groups is not None else None
         self.zero_grad()
         # thread_local: other threads (the RCCL watchdog under torch.distributed) may issue HIP calls meanwhile
         with torch.cuda.graph(graph, stream=side, capture_error_mode='thread_local'):
@@ -1726,6 +1848,7 @@ class NextFramePredictorS2S(NextFramePredictor):
         def step(x, y, concat_layers=None):
             self._ema_guard(True, ema)
             self._trainable_guard(trainable)
+            self._groups_guard(groups)
             batch.load(x, *self._first_steps(y, concat_layers, held))      # (the horizon of the capture, whatever is set now)
             graph.replay()
             if multi:
@@ -1737,6 +1860,7 @@ class NextFramePredictorS2S(NextFramePredictor):
             return static_loss
         step.check, step.loss_weights, step.ema, step.horizon = watch.check, lw, ema, held[0]
         step.trainable, step.trainable_mask = trainable, train_mask       # (the graph reads the mask by pointer: it lives with the step)
+        step.param_groups, step.grouped = groups, grouped         # (and so do the vectors of the parameter groups)
         return step
 
     def _capture_setup(self, force_multi):
@@ -1751,10 +1875,12 @@ class NextFramePredictorS2S(NextFramePredictor):
         if not self.optimizer.defaults.get('capturable', False):
             lr = self.optimizer.param_groups[0]['lr']
             assert not self.optimizer.state, 'make_graphed_step must be called before the first optimizer step'
-            decay, trainable = None if self.ema is None else self.ema.decay, self._trainable
+            decay, trainable, groups = None if self.ema is None else self.ema.decay, self._trainable, self._groups
             self.initiate_training(float(lr), self.scheduler.gamma, capturable=True)
             self.set_ema(decay)         # (no step was taken: the average starts with the new optimiser, as it stood)
             self.set_trainable(trainable)       # (and so does the selection of trainable parameters)
+            from qtmpnn.groups import as_pairs
+            self.set_param_groups(as_pairs(groups))     # (and the parameter groups)
         return multi, world
 
     def _graphed_accumulation(self, batches, accumulate, mask=None, high_interest_region=None, max_norm=10.0, warmup=2,
@@ -1804,6 +1930,7 @@ class NextFramePredictorS2S(NextFramePredictor):
         clip_params = self._set_grad_flat(acc)          # the optimiser reads acc from here on
         ema, averaged = self.ema, self.ema.updates if self.ema is not None else 0
         trainable, train_mask = self._trainable, self._train_mask
+        groups, grouped = self._groups, self._grouped if self._groups is not None else None
         update = torch.cuda.CUDAGraph()
         with torch.cuda.graph(update, stream=side, capture_error_mode='thread_local'):
             acc.mul_(scale[0])
@@ -1820,6 +1947,7 @@ class NextFramePredictorS2S(NextFramePredictor):
         def step(batches):
             self._ema_guard(True, ema)
             self._trainable_guard(trainable)
+            self._groups_guard(groups)
             group = [(x, *self._first_steps(y, c, held)) for x, y, c in checked_batches('step', batches)]
             j = len(group)
             if j > k or any(batch_shapes(item) != batch.shapes for item in group):
@@ -1841,6 +1969,7 @@ class NextFramePredictorS2S(NextFramePredictor):
             return static_loss
         step.check, step.loss_weights, step.accumulate, step.graphs, step.ema = watch.check, lw, k, (micro, update), ema
         step.horizon, step.trainable, step.trainable_mask = held[0], trainable, train_mask
+        step.param_groups, step.grouped = groups, grouped
         step.buffers = (*batch.tensors, acc, loss_acc, scale)       # (loss_acc is named nowhere else: StaticBatch)
         return step
 
@@ -2046,6 +2175,7 @@ class NextFramePredictorS2S(NextFramePredictor):
     @takes_ema
     @takes_horizon
     @takes_trainable
+    @takes_param_groups
     def train(self, loader_train, loader_test, climatology=None, n_epochs=200, lr=0.01, lr_decay=0.95, mask=None,
               high_interest_region=None, truncated_backprop=45, graph_structure=None, use_graph=False, accumulate=1,
               pos_weight=None, test_graph=False, patience=None, min_delta=0.0, restore_best=False, keep_best=None,
@@ -2126,7 +2256,10 @@ class NextFramePredictorS2S(NextFramePredictor):
         this call -- applied once the optimiser exists, after initiate_training when the call has to make it, and before the first
         capture; the selection in force before is back when the call returns.  None trains every parameter; left out, the
         predictor's selection stays.  Checked against the parameter names before anything is launched and before the optimiser
-        is made; every refusal names `trainable`."""
+        is made; every refusal names `trainable`.
+        param_groups=groups (a keyword of this method through takes_param_groups; beyond the reference):
+        set_param_groups(groups) for this call, applied and restored as `trainable` is.  None is no setting; left out, the
+        predictor's setting stays.  Every refusal names `param_groups`."""
         from qtmpnn import validation
         image_shape = loader_train.dataset.image_shape
         accumulate = check_accumulate(accumulate)
@@ -2161,6 +2294,8 @@ class NextFramePredictorS2S(NextFramePredictor):
             self.set_ema(self._ema_asked[0])
         if self._trainable_asked[0]:
             self.set_trainable(self._trainable_asked[1])
+        if self._groups_asked[0]:
+            self.set_param_groups(self._groups_asked[1])
         averaging = self.averaged_weights if self.ema is not None and self._ema_asked[1] else contextlib.nullcontext
         graphed = {}
         if mask is not None:
